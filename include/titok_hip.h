@@ -505,6 +505,18 @@ int ttv_clip_from_u8(const void* frames_thwc, int T, int H, int W, void* clip_ct
 int ttv_sq_err_accumulate(void* const* recon, void* const* target, const int32_t* sizes, int n_clips, int dtype, int clamp, double* acc,
                           void* stream);
 
+/* SSIM statistic of the evaluation loop (model/metrics/eval_metrics.py:20-21,32-37: x.clamp(-1, 1), CTHW -> TCHW, torchmetrics
+ * StructuralSimilarityIndexMeasure(data_range=2) = running sum of per-frame SSIM + frame count): for up to
+ * TTV_MAX_CLIPS_PER_LAUNCH contiguous clip pairs [C,T,H,W] (host arrays of device pointers, `dtype`; dims = n_clips x (C,T,H,W),
+ * host), acc[0] += sum over frames of mean_{C x (H-10) x (W-10)} ssim (the windows wholly inside the frame, which is what the
+ * reference's reflect-pad + crop keeps), acc[1] += number of frames, both double, device memory.  `clamp` clamps the
+ * reconstruction only.  fp32 arithmetic for both dtypes; H and W must be >= 11.  The workspace (ttv_ssim_workspace_bytes(dims,
+ * n_clips) bytes, 8-byte aligned, caller-owned) holds the per-tile partial sums, reduced by a second launch in a fixed order:
+ * identical inputs give identical bits.  SSIM = acc[0] / acc[1] is finished on the host. */
+int64_t ttv_ssim_workspace_bytes(const int32_t* dims, int n_clips);
+int ttv_ssim_accumulate(void* const* recon, void* const* target, const int32_t* dims, int n_clips, int dtype, int clamp, double* acc,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- measurement hook (bench.py roofline leg) ---------------------------------------------------------- */
 /* Kernel classes whose launches can be bracketed by HIP events on the stream they are launched on. */
 #define TTV_KC_ATTENTION 1

@@ -729,6 +729,13 @@ int ttv_sq_err_accumulate(void* const* recon, void* const* target, const int32_t
   return TTV_OK;
 }
 
+int64_t ttv_ssim_workspace_bytes(const int32_t* dims, int n_clips) { return ttvk_ssim_workspace_bytes(dims, n_clips); }
+
+int ttv_ssim_accumulate(void* const* recon, void* const* target, const int32_t* dims, int n_clips, int dtype, int clamp, double* acc,
+                        void* workspace, int64_t workspace_bytes, void* stream) {
+  return ttvk_ssim(recon, target, dims, n_clips, dtype, clamp, acc, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int ttv_debug_set(int flags) {
   g_ttv_debug = flags;
   return TTV_OK;

@@ -188,3 +188,9 @@ int ttvk_const_rows_bwd(const float* colsum, const float* mask_token, const floa
                         int d, hipStream_t s);
 int ttvk_rope_build(const float* base_cos, const float* base_sin, int n_ids, int F, const int* clip_desc, const int* cu, const int* row_seq,
                     float* out, int total_rows, hipStream_t s);
+
+// ---- ttv_metrics.hip ----
+// dims: n_clips x (C, T, H, W); -1 (error set) on a bad shape
+int64_t ttvk_ssim_workspace_bytes(const int32_t* dims, int n_clips);
+int ttvk_ssim(void* const* recon, void* const* target, const int32_t* dims, int n_clips, int dtype, int clamp, double* acc2, void* workspace,
+              int64_t workspace_bytes, hipStream_t s);

@@ -1,9 +1,17 @@
-"""PSNR of the evaluation loop on the GPU (reference model/metrics/eval_metrics.py:11-51, the 'psnr' entry).
+"""PSNR and SSIM of the evaluation loop on the GPU (reference model/metrics/eval_metrics.py:11-51, the 'psnr' and 'ssim' entries).
 
-The reference builds torchmetrics' PeakSignalNoiseRatio(data_range=2) and feeds it `x.clamp(-1, 1)` per clip (eval_metrics.py:19,
-32-36): a running sum of squared errors and an element count, `10 * log10(data_range^2 / mse)` at compute().  Here both sums live in
-one device buffer filled by `ttv_sq_err_accumulate` (one launch per update, no host sync until compute()).  SSIM / FVD / JEDi are
-out of scope (remote weights).
+The reference builds torchmetrics' PeakSignalNoiseRatio(data_range=2) and StructuralSimilarityIndexMeasure(data_range=2) and feeds
+them `x.clamp(-1, 1)` per clip, CTHW -> TCHW (eval_metrics.py:19-21, 32-37).
+- PSNR: a running sum of squared errors and an element count, `10 * log10(data_range^2 / mse)` at compute().  Both sums live in one
+  device buffer filled by `ttv_sq_err_accumulate` (one launch per update).
+- SSIM: 11-tap Gaussian window (sigma 1.5), C1 = (0.01 * 2)^2, C2 = (0.03 * 2)^2, per frame the mean over C x (H-10) x (W-10) (the
+  windows wholly inside the frame: exactly what torchmetrics' reflect-pad + crop keeps); a running sum of per-frame values and a
+  frame count, so compute() is a mean of per-frame means, not a pixel-weighted mean.  Filled by `ttv_ssim_accumulate` (two launches
+  per call of up to 64 clips; per-tile partials in a workspace this module owns, reduced in a fixed order: bit-reproducible).
+  Deliberate deviations from torchmetrics: fp32 arithmetic for bf16 and fp32 inputs (under bf16 autocast torchmetrics convolves
+  in bf16); frames with H < 11 or W < 11 are refused (torchmetrics gives NaN for 6-10 and raises for <= 5); no cross-rank sum
+  in compute() (torchmetrics sums its state over ranks; PSNR here does not either).
+No host sync until compute().  FVD / JEDi need network-fetched weights (I3D, V-JEPA) and are out of scope.
 """
 from __future__ import annotations
 
@@ -16,6 +24,8 @@ import torch.nn as nn
 
 from ... import _lib
 
+AVAILABLE = ("psnr", "ssim")
+
 
 class EvalMetrics(nn.Module):
     def __init__(self, config=None, eval_prefix: str = "eval"):
@@ -25,32 +35,67 @@ class EvalMetrics(nn.Module):
         if config is not None:
             names = [m for m in config.training.eval.log_metrics]
             for m in names:
-                if m != "psnr":
-                    raise NotImplementedError(f"metric '{m}' needs weights fetched over the network (reference model/metrics/); only 'psnr' is built")
+                if m not in AVAILABLE:
+                    raise NotImplementedError(f"metric '{m}' is not built: FVD / JEDi need weights fetched over the network "
+                                              f"(reference model/metrics/); the available metrics are {', '.join(AVAILABLE)}")
         self.names = names
-        self._acc = None
+        self._acc = None         # psnr: (sum of squared errors, element count), double
+        self._ssim_acc = None    # ssim: (sum of per-frame SSIM, frame count), double
+        self._ssim_ws = None     # ssim: per-tile partial sums, grown as needed
+
+    def _ssim_groups(self, rs, ts):
+        """Host-side shapes and workspace sizes of every call of up to TTV_MAX_CLIPS_PER_LAUNCH clips (raises before any launch)."""
+        groups = []
+        for c0 in range(0, len(rs), _lib.TTV_MAX_CLIPS_PER_LAUNCH):
+            r, t = rs[c0:c0 + _lib.TTV_MAX_CLIPS_PER_LAUNCH], ts[c0:c0 + _lib.TTV_MAX_CLIPS_PER_LAUNCH]
+            for a, b in zip(r, t):
+                if a.dim() != 4 or a.shape != b.shape:
+                    raise ValueError(f"EvalMetrics ssim: clips must be [C,T,H,W] pairs of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+            dims = (C.c_int32 * (4 * len(r)))(*[int(d) for a in r for d in a.shape])
+            nbytes = _lib.lib().ttv_ssim_workspace_bytes(dims, len(r))
+            if nbytes < 0:
+                _lib.check(1, "ttv_ssim_workspace_bytes")
+            groups.append((r, t, dims, nbytes))
+        return groups
 
     def update(self, recon: Sequence[torch.Tensor], target: Sequence[torch.Tensor]) -> None:
         if not self.names:
             return
         r0 = recon[0]
         _lib.require_gpu(r0, "EvalMetrics.update")
-        if self._acc is None or self._acc.device != r0.device:
-            self._acc = torch.zeros(2, dtype=torch.float64, device=r0.device)
         rs = [t.contiguous() for t in recon]
         ts = [t.to(r0.dtype).contiguous() for t in target]
-        sizes = (C.c_int32 * len(rs))(*[int(t.numel()) for t in rs])
-        rc = _lib.lib().ttv_sq_err_accumulate(_lib.ptr_array(rs), _lib.ptr_array(ts), sizes, len(rs), _lib.dtype_code(r0.dtype), 1,
-                                              self._acc.data_ptr(), _lib.stream_ptr(r0.device))
-        _lib.check(rc, "ttv_sq_err_accumulate")
+        dt, stream = _lib.dtype_code(r0.dtype), _lib.stream_ptr(r0.device)
+        groups = self._ssim_groups(rs, ts) if "ssim" in self.names else []
+        if "psnr" in self.names:
+            if self._acc is None or self._acc.device != r0.device:
+                self._acc = torch.zeros(2, dtype=torch.float64, device=r0.device)
+            sizes = (C.c_int32 * len(rs))(*[int(t.numel()) for t in rs])
+            rc = _lib.lib().ttv_sq_err_accumulate(_lib.ptr_array(rs), _lib.ptr_array(ts), sizes, len(rs), dt, 1, self._acc.data_ptr(), stream)
+            _lib.check(rc, "ttv_sq_err_accumulate")
+        if groups:
+            if self._ssim_acc is None or self._ssim_acc.device != r0.device:
+                self._ssim_acc = torch.zeros(2, dtype=torch.float64, device=r0.device)
+            need = max(g[3] for g in groups)
+            if self._ssim_ws is None or self._ssim_ws.device != r0.device or self._ssim_ws.numel() < need:
+                self._ssim_ws = torch.empty(need, dtype=torch.uint8, device=r0.device)
+            for r, t, dims, nbytes in groups:
+                rc = _lib.lib().ttv_ssim_accumulate(_lib.ptr_array(r), _lib.ptr_array(t), dims, len(r), dt, 1, self._ssim_acc.data_ptr(),
+                                                    self._ssim_ws.data_ptr(), self._ssim_ws.numel(), stream)
+                _lib.check(rc, "ttv_ssim_accumulate")
 
     def compute(self) -> dict:
-        if not self.names or self._acc is None:
-            return {}
-        sq, n = (float(v) for v in self._acc.cpu())
-        psnr = 10.0 * math.log10(4.0 * n / sq) if sq > 0 else float("inf")
-        return {f"{self.eval_prefix}/psnr": psnr}
+        out = {}
+        for name in self.names:
+            if name == "psnr" and self._acc is not None:
+                sq, n = (float(v) for v in self._acc.cpu())
+                out[f"{self.eval_prefix}/psnr"] = 10.0 * math.log10(4.0 * n / sq) if sq > 0 else float("inf")
+            elif name == "ssim" and self._ssim_acc is not None:
+                s, n = (float(v) for v in self._ssim_acc.cpu())
+                out[f"{self.eval_prefix}/ssim"] = s / n if n > 0 else float("nan")
+        return out
 
     def reset(self) -> None:
-        if self._acc is not None:
-            self._acc.zero_()
+        for acc in (self._acc, self._ssim_acc):
+            if acc is not None:
+                acc.zero_()
