@@ -444,7 +444,8 @@ int ttv_fsq_backward(const ttv_fsq_params* p, const float* z, const void* dcodes
  * chunks : device int32 [n_chunks][2] = (entry index, first element): one block per chunk of up to 8192 elements.
  * ttv_opt_grad_sumsq writes partials[c] = sum of grad^2 over chunk c.  ttv_opt_adamw_step sums partials[0 .. n_partials) in a fixed order
  * (all chunks of ALL tensor lists of the step: the global gradient norm, written to out_norm when not NULL), scales the gradients by
- * min(1, max_norm / (norm + 1e-6)) in registers (max_norm <= 0 or n_partials == 0: no clipping; p.grad is NOT rewritten) and applies
+ * min(1, max_norm / (norm + 1e-6)) in registers (NaN when the norm is NaN, as torch's clamp: every updated element becomes NaN;
+ * max_norm <= 0 or n_partials == 0: no clipping; p.grad is NOT rewritten) and applies
  * AdamW with the given bias corrections 1 - beta1^t and sqrt(1 - beta2^t). */
 int ttv_opt_grad_sumsq(const void* table, const int32_t* chunks, int n_chunks, int dtype, float* partials, void* stream);
 int ttv_opt_adamw_step(const void* table, const int32_t* chunks, int n_chunks, int dtype, const float* partials, int n_partials, float lr,

@@ -1,0 +1,90 @@
+"""Block-wise error measure and float64 attention reference for the attention tests (no GPU needed; imported by
+tests/test_hip_backward_shapes.py and checked by tests/test_blockwise_cpu.py).
+
+A global relative Frobenius error hides one wrong tile: among the 36 864 rows of a 32-clip batch a single 64-row block of one head
+carries ~4 % of the norm, so a block that is off by 5 % moves the global figure by 0.2 %.  `block_errors` measures every
+(sequence, head, 64-row block) on its own - the granularity at which the attention kernels tile the rows of a sequence (64-row
+backward blocks, half of a 128-row query block) - and `check_blockwise` asserts both figures."""
+import torch
+
+
+def row_blocks(cu_seqlens, block: int = 64):
+    """Block id of every packed row (blocks restart at each sequence start; a sequence's last block may be short) and the count."""
+    ids, n = [], 0
+    for b in range(len(cu_seqlens) - 1):
+        s = int(cu_seqlens[b + 1]) - int(cu_seqlens[b])
+        ids.append(n + torch.arange(s) // block)
+        n += -(-s // block)
+    return (torch.cat(ids) if ids else torch.zeros(0, dtype=torch.long)), n
+
+
+def block_errors(x, ref, cu_seqlens, heads: int, block: int = 64):
+    """[n_blocks, heads] relative Frobenius error ||x - ref|| / ||ref|| per (sequence, head, `block`-row block).  x, ref: [L, heads * w]
+    (any dtype, compared in float64).  A reference block whose norm is far below the typical block's (< 1e-2 of the root-mean-square
+    block norm) is measured against that floor instead: such a block is a cancellation (dQ of a one-row sequence is exactly zero: its
+    softmax is 1 and dS = dP - delta), where the kernel's rounding residue has no meaningful relative size.  An all-zero reference
+    block with an O(1) result is still an error far beyond any bound."""
+    x, ref = x.double().cpu(), ref.double().cpu()
+    L = ref.shape[0]
+    assert x.shape == ref.shape and ref.shape[1] % heads == 0, (tuple(x.shape), tuple(ref.shape), heads)
+    ids, n = row_blocks(cu_seqlens, block)
+    assert ids.numel() == L, (ids.numel(), L)
+    d2 = (x - ref).pow(2).view(L, heads, -1).sum(-1)
+    r2 = ref.pow(2).view(L, heads, -1).sum(-1)
+    num = torch.zeros(n, heads, dtype=torch.float64).index_add_(0, ids, d2)
+    den = torch.zeros(n, heads, dtype=torch.float64).index_add_(0, ids, r2)
+    floor = 1e-4 * float(den.mean()) + 1e-300
+    return (num / den.clamp_min(floor)).sqrt()
+
+
+def global_error(x, ref) -> float:
+    x, ref = x.double().cpu(), ref.double().cpu()
+    return float((x - ref).norm() / (ref.norm() + 1e-30))
+
+
+def check_blockwise(x, ref, cu_seqlens, heads: int, block_tol: float, global_tol: float, what: str = ""):
+    """Assert that x is finite, within `global_tol` of ref as a whole and within `block_tol` in every (sequence, head, block).
+    Returns (worst block error, global error) for the report."""
+    assert bool(torch.isfinite(x.double()).all()), f"{what}: non-finite values"
+    glob = global_error(x, ref)
+    err = block_errors(x, ref, cu_seqlens, heads)
+    worst = float(err.max()) if err.numel() else 0.0
+    assert glob < global_tol, f"{what}: global relative error {glob:.3e} >= {global_tol:.1e}"
+    if err.numel():
+        blk, head = divmod(int(err.argmax()), err.shape[1])
+        assert worst < block_tol, f"{what}: block {blk} head {head}: relative error {worst:.3e} >= {block_tol:.1e} (global {glob:.3e})"
+    return worst, glob
+
+
+def attention_reference(qkvg, dout, cu_seqlens, hq: int, hkv: int):
+    """float64 per-sequence softmax attention (non-causal, scale 1/8, GQA: q-head h reads kv-head h // (hq / hkv)) on the packed
+    [L, 2d + 2g] rows q | gate | k | v of the attention kernels, and its autograd backward for the upstream gradient `dout` [L, d].
+    Returns out [L, d] (ungated), gated = out * sigmoid(gate), lse [L, hq] (natural log of the row sums of exp(scores)) and
+    grad [L, 2d + 2g] (gradient of <out, dout> w.r.t. q, k, v; zero in the gate columns).  Autograd runs per (sequence, kv-head) so a
+    1152-row sequence costs a few 10 MB.  (The oracle's attention_varlen computes in float32 whatever its inputs.)"""
+    x, do = qkvg.detach().double().cpu(), dout.detach().double().cpu()
+    L, d, g, rep = x.shape[0], hq * 64, hkv * 64, hq // hkv
+    out = torch.zeros(L, d, dtype=torch.float64)
+    lse = torch.zeros(L, hq, dtype=torch.float64)
+    grad = torch.zeros_like(x)
+    for b in range(len(cu_seqlens) - 1):
+        s, e = int(cu_seqlens[b]), int(cu_seqlens[b + 1])
+        n = e - s
+        for kh in range(hkv):
+            qc = slice(kh * rep * 64, (kh + 1) * rep * 64)
+            kc = slice(2 * d + kh * 64, 2 * d + (kh + 1) * 64)
+            vc = slice(2 * d + g + kh * 64, 2 * d + g + (kh + 1) * 64)
+            q = x[s:e, qc].reshape(n, rep, 64).transpose(0, 1).clone().requires_grad_(True)      # [rep, n, 64]
+            k = x[s:e, kc].clone().requires_grad_(True)
+            v = x[s:e, vc].clone().requires_grad_(True)
+            sc = q @ k.T * 0.125
+            o = torch.softmax(sc, -1) @ v
+            o.backward(do[s:e, qc].reshape(n, rep, 64).transpose(0, 1))
+            with torch.no_grad():
+                out[s:e, qc] = o.transpose(0, 1).reshape(n, rep * 64)
+                lse[s:e, kh * rep:(kh + 1) * rep] = torch.logsumexp(sc, -1).T
+            grad[s:e, qc] = q.grad.transpose(0, 1).reshape(n, rep * 64)
+            grad[s:e, kc] = k.grad
+            grad[s:e, vc] = v.grad
+    gated = out * torch.sigmoid(x[:, d:2 * d])
+    return out, gated, lse, grad

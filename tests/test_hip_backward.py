@@ -399,23 +399,25 @@ def test_mixed_precision_training_step_fp32_master_weights_bf16_compute():
     ref = TiTok(config())
     ref.load_state_dict(seeded_titok_state(0), strict=True)
     ref = ref.to(DEV, torch.bfloat16).train()
-    idx = []
+    # per tower with the token indices held fixed (as in the per-tower tests above): a token whose index flips between the two runs would
+    # legitimately change the decoder's input and with it part of the encoder's gradient.  Encoder: smooth loss on z; decoder: the
+    # training step's L1 loss on fixed codes.
+    from titok_video_amd.train import l1_reconstruction_loss
+    g = torch.Generator().manual_seed(4)
+    wz = torch.randn(sum(counts), 5, generator=g).to(DEV)
+    codes = O.fsq_indices_to_codes(torch.randint(0, 4375, (sum(counts),), generator=g, dtype=torch.int32), LEVELS).to(DEV, torch.bfloat16)
     for m in (model, ref):
-        recon, out = m(clips, counts)
-        idx.append(out["indices"].clone())
+        zz = m.encoder.forward_z(clips, counts)
+        ((zz * wz).sum() + 0.1 * zz.pow(2).sum()).backward()
+        recon = m.decode(codes, counts, shapes)
         assert recon[0].dtype == torch.bfloat16
-        from titok_video_amd.train import l1_reconstruction_loss
         l1_reconstruction_loss(recon, [c * 0.5 for c in clips]).backward()
-    same_indices = torch.equal(idx[0], idx[1])
     for (n, p), (_, q) in zip(model.named_parameters(), ref.named_parameters()):
         assert p.grad is not None and p.grad.dtype == torch.float32 and torch.isfinite(p.grad).all(), n
         g, h = p.grad.double().flatten(), q.grad.double().flatten()
         if float(h.norm()) > 0 and p.numel() >= 4096:
-            # not bit-equal by construction: the bf16 model rounds norm gains, biases and the gradients themselves to bf16.  A token
-            # whose index flips between the two runs (one of ten here; seen when the attention kernels' row maximum was fixed in round 5:
-            # 3570 vs 3605) legitimately changes the decoder's input and with it a tenth of the encoder's gradient: then the
-            # directions only have to stay related (cf. the per-tower tests above, which hold the indices fixed)
-            assert float((g @ h) / (g.norm() * h.norm() + 1e-30)) > (0.9 if same_indices else 0.6), (n, same_indices)
+            # not bit-equal by construction: the bf16 model rounds norm gains, biases and the gradients themselves to bf16
+            assert float((g @ h) / (g.norm() * h.norm() + 1e-30)) > 0.9, n
     # one optimizer step with a learning rate whose update (~1e-7 relative) a bf16 parameter could not represent
     for m in (model, ref):
         m.zero_grad(set_to_none=True)

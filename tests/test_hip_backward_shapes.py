@@ -1,0 +1,351 @@
+"""The training backward at the sequence lengths training runs (`-m gpu`).
+
+The training step of the benchmark runs 5 or 32 clips of 16x128x128: 1152 rows per sequence, 18 backward blocks of 64 rows, 9 query
+blocks of 128, GQA 2 (tiny), 4 (small) or 3 (base).  tests/test_hip_backward.py checks the backward on sequences of at most 102 rows.
+
+  * single kernels: ttv_attention_lse (flags 0 and TTV_ATTN_GATE; default, all-half and all-full work tables) and
+    ttv_attention_backward (bf16 k_attn_bwd, fp32 k_attn_bwd_f32; with and without rotary) against a float64 autograd reference on
+    the same bf16-rounded operands, per (sequence, head, 64-row block) as well as globally (tests/blockwise.py), LSE of every row,
+    nothing written to the gate columns or past the last row.
+  * towers: encoder (smooth loss on z) and decoder (fixed codes, smooth loss on the pixels) gradients against the oracle's autograd at
+    full-size clips, with latent-only query rows skipped in the encoder's last layer (K = 128 of 1152 rows, K = 200: two latent
+    query blocks), at the tiny and the small size; the bf16 encoder with and without that shortcut.
+"""
+import functools
+import os
+import subprocess
+import sys
+from types import SimpleNamespace
+
+import pytest
+import torch
+
+from oracle import titok_oracle as O
+from tests.blockwise import attention_reference, check_blockwise
+from titok_video_amd import _lib
+from titok_video_amd.plan import BatchPlan
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+LEVELS = [7, 5, 5, 5, 5]
+DT = {"bf16": torch.bfloat16, "f32": torch.float32}
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TTV_ATTN_GATE = 1
+
+
+def L():
+    return _lib.lib()
+
+
+def S():
+    return _lib.stream_ptr(torch.device(DEV))
+
+
+def report(*parts):
+    print("MEASURED", *parts, flush=True)
+
+
+# ---------------------------------------------------------------------------------------------- attention kernels
+BATCHES = {
+    "one": ([(16, 128, 128)], [128]),                                               # 1152 rows
+    "five": ([(16, 128, 128)] * 5, [128] * 5),                                      # the reference's 5-clip batch: half items by default
+    "ragged": ([(16, 128, 128), (16, 64, 64), (8, 32, 48), (4, 8, 8)], [1, 61, 5, 0]),   # 1025, 317, 53, 1 rows
+    "far": ([(16, 128, 128), (16, 64, 64), (8, 32, 48), (4, 8, 8)], [1, 61, 5, 0]),      # the same with rows of far-off scores
+}
+# rows of the "far" batch whose every score sits `level` log2-units from zero (sequences 0, 1 and 2; first, middle and last blocks)
+FAR_ROWS = {5: -100.0, 700: 90.0, 1024: -40.0, 1025 + 64: 90.0, 1025 + 316: -100.0, 1025 + 317 + 52: -40.0}
+# bounds (relative Frobenius error per (sequence, head, 64-row block), global): forward output, backward dq / dk / dv; LSE: max abs.
+# Measured on MI355X, worst over all cases (block, global): forward bf16 3.2e-3, 2.4e-3; fp32 2.7e-6, 6.4e-7; backward bf16 9.2e-3
+# (far rows; 3.3e-3 otherwise), 3.7e-3; fp32 5.1e-5 (far rows: dK sums dS q over rows whose |q| is ~30x the others'; 2.4e-5
+# otherwise), 2.9e-6; LSE 6e-6 (|LSE| up to ~60 on far rows: a few fp32 ulps).  The bounds keep a margin of about 2.
+FWD_TOL = {"bf16": (6e-3, 4e-3), "f32": (1e-5, 2e-6)}
+BWD_TOL = {"bf16": (2e-2, 8e-3), "f32": (1e-4, 1e-5)}
+LSE_TOL = {"bf16": 3e-5, "f32": 3e-5}
+
+
+@functools.lru_cache(maxsize=None)
+def _case(batch, hq, hkv):
+    """bf16-rounded operands (the fp32 kernels get the same values) and the float64 reference for them."""
+    shapes, counts = BATCHES[batch]
+    plan = BatchPlan(shapes, counts, (4, 8, 8), DEV)
+    d, gq = hq * 64, hkv * 64
+    ld = 2 * d + 2 * gq
+    Lr = plan.total_rows
+    g = torch.Generator().manual_seed(100 * hq + hkv + len(batch))
+    x = torch.randn(Lr, ld, generator=g)
+    if batch == "far":      # built like tests/test_hip_ops.py test_attention_swp_rows_whose_scores_all_sit_far_from_zero
+        x *= 0.5
+        u = torch.randn(64, generator=g)
+        u = u / u.norm() * 4.0                                          # |u| = 4; every key of every kv-head carries u
+        # ... exactly: the keys' own noise is made orthogonal to u, so a far row's scores are `level` plus ordinary O(1) noise (its
+        # softmax is as spread as any other row's).  With noise along u the huge q of a far row turns that noise into a one-hot
+        # softmax, where dS = P (dP - delta) is the cancellation of two O(1) numbers and delta = rowsum(dO * O) comes from the
+        # bf16-stored O (as in FlashAttention-2): its 2^-9 rounding, times the row's |q| ~ 30x the others', then dominates a block of dK.
+        kk = x[:, 2 * d:2 * d + gq].view(-1, hkv, 64)
+        kk -= (kk @ u / 16.0).unsqueeze(-1) * u
+        x[:, 2 * d:2 * d + gq] += u.repeat(hkv)
+        c_exp = 0.125 * 1.4426950408889634
+        for row, level in FAR_ROWS.items():
+            x[row, :d] += (level / (c_exp * 16.0)) * u.repeat(hq)        # q . u * scale * log2(e) = level, every q-head
+    x = x.to(torch.bfloat16)
+    dout = torch.randn(Lr, d, generator=g).to(torch.bfloat16)
+    out, gated, lse, grad = attention_reference(x, dout, plan.cu_seqlens, hq, hkv)
+    return plan, x, dout, out, gated, lse, grad
+
+
+def _unrotate(gpart, cs):
+    """Gradient w.r.t. the q / k before the rotary embedding: the transposed rotation (tests/test_hip_backward.py)."""
+    cos, sin = cs[:, :32].unsqueeze(1), cs[:, 32:].unsqueeze(1)
+    gh = gpart.unflatten(-1, (-1, 32, 2))
+    return torch.stack((gh[..., 0] * cos + gh[..., 1] * sin, gh[..., 1] * cos - gh[..., 0] * sin), -1).flatten(-3)
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f32"])
+@pytest.mark.parametrize("table", [None, True, False], ids=["default", "halves", "full"])
+@pytest.mark.parametrize("heads", [(4, 2), (8, 2), (12, 4)], ids=["rep2", "rep4", "rep3"])
+@pytest.mark.parametrize("batch", list(BATCHES))
+def test_attention_forward_lse_and_backward_at_training_lengths(batch, heads, table, dt):
+    hq, hkv = heads
+    plan, x, dout, ref_out, ref_gated, ref_lse, ref_grad = _case(batch, hq, hkv)
+    d, gq = hq * 64, hkv * 64
+    ld = 2 * d + 2 * gq
+    Lr, cu = plan.total_rows, plan.cu_seqlens
+    code = _lib.dtype_code(DT[dt])
+    xd, dod = x.to(DEV, DT[dt]), dout.to(DEV, DT[dt])
+    tab = plan.attention_table(hq, hkv, table)
+    if batch == "five" and table is None:
+        assert bool((tab[:, 3] == 1).any()), "the 5-clip batch is expected to carry half items under the default rule"
+    fb, fg = FWD_TOL[dt]
+    tag = f"{batch} {hq}/{hkv} {['default', 'halves', 'full'][[None, True, False].index(table)]} {dt}"
+    for flags in (TTV_ATTN_GATE, 0):                                  # the ungated output of the second call feeds the backward
+        o = torch.full((Lr + 1, d), float("nan"), dtype=DT[dt], device=DEV)
+        lse = torch.full((Lr + 1, hq), float("nan"), device=DEV)
+        _lib.check(L().ttv_attention_lse(xd.data_ptr(), ld, o.data_ptr(), d, plan.cu_dev.data_ptr(), tab.data_ptr(), tab.shape[0], hq, hkv,
+                                         64, flags, code, lse.data_ptr(), S()), "attention_lse")
+        torch.cuda.synchronize()
+        oc, lc = o.cpu(), lse.cpu()
+        assert bool(torch.isnan(oc[Lr]).all()) and bool(torch.isnan(lc[Lr]).all()), "written past the last row"
+        wo, go = check_blockwise(oc[:Lr], ref_gated if flags else ref_out, cu, hq, fb, fg, f"{tag} flags {flags}: output")
+        assert bool(torch.isfinite(lc[:Lr]).all())
+        lerr = float((lc[:Lr].double() - ref_lse).abs().max())
+        assert lerr < LSE_TOL[dt], (tag, flags, lerr)
+        report(f"{tag} fwd flags {flags}: output worst block {wo:.2e} global {go:.2e}; lse max abs {lerr:.2e}")
+    bb, bg = BWD_TOL[dt]
+    cs = plan.rope_cs.cpu().double()
+    for rope in (False, True):
+        dq = torch.full((Lr + 1, ld), float("nan"), dtype=DT[dt], device=DEV)
+        delta = torch.empty(Lr, hq, device=DEV)
+        scratch = torch.empty(Lr, 2 * gq, device=DEV)
+        bt = plan.table(4, 2 * plan.n_blocks64)
+        rs = plan.table(5, Lr)
+        _lib.check(L().ttv_attention_backward(xd.data_ptr(), ld, o.data_ptr(), d, dod.data_ptr(), d, lse.data_ptr(), delta.data_ptr(),
+                                              plan.cu_dev.data_ptr(), bt.data_ptr(), plan.n_blocks64, rs.data_ptr(), dq.data_ptr(), ld,
+                                              scratch.data_ptr(), Lr, hq, hkv, code, plan.rope_cs.data_ptr() if rope else None, S()),
+                   "attention_backward")
+        torch.cuda.synchronize()
+        got = dq.cpu()
+        assert bool(torch.isnan(got[Lr]).all()), "written past the last row"
+        assert bool(torch.isnan(got[:, d:2 * d]).all()), "written into the gate columns"
+        gref = ref_grad.clone()
+        if rope:
+            gref[:, :d] = _unrotate(gref[:, :d], cs)
+            gref[:, 2 * d:2 * d + gq] = _unrotate(gref[:, 2 * d:2 * d + gq], cs)
+        res = []
+        for name, c0, c1, nh in (("dq", 0, d, hq), ("dk", 2 * d, 2 * d + gq, hkv), ("dv", 2 * d + gq, ld, hkv)):
+            res.append((name,) + check_blockwise(got[:Lr, c0:c1], gref[:, c0:c1], cu, nh, bb, bg, f"{tag} rope {rope}: {name}"))
+        report(f"{tag} bwd rope {int(rope)}: " + "; ".join(f"{n} worst block {w:.2e} global {gl:.2e}" for n, w, gl in res))
+
+
+# ---------------------------------------------------------------------------------------------- towers at full-size clips
+def config(size="tiny"):
+    return SimpleNamespace(tokenizer=SimpleNamespace(model=SimpleNamespace(
+        patch_size=[4, 8, 8], fsq_levels=LEVELS, encoder_size=size, decoder_size=size)))
+
+
+# 1152 rows with K = 128 (latent limit 128), 456 rows with K = 200 (two latent query blocks, limit 256), 53 rows with K = 5
+FULL = ([(16, 128, 128), (16, 64, 64), (8, 32, 48)], [128, 200, 5])
+# small size: one sequence longer than 128 rows (168, latent limit 128), one short
+SMALL = ([(8, 64, 64), (4, 16, 16)], [40, 3])
+
+
+def _state(size):
+    from titok_video_amd.synthetic import seeded_titok_state
+    if size == "tiny":
+        return seeded_titok_state(0)
+    return seeded_titok_state(3, encoder_size=size, decoder_size=size, gain=3.0)
+
+
+def _model(size, dtype):
+    from titok_video_amd.model.titok import TiTok
+    m = TiTok(config(size))
+    m.load_state_dict(_state(size), strict=True)
+    return m.to(DEV, dtype).train()
+
+
+def _weights(n_rows, n_pix, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(n_rows, 5, generator=g), [torch.randn(s, generator=g) for s in n_pix]
+
+
+@functools.lru_cache(maxsize=None)
+def _encoder_reference(size, shapes, counts):
+    from titok_video_amd.synthetic import synthetic_clips
+    sd = {k: v.clone().requires_grad_(True) for k, v in _state(size).items()}
+    clips = [c.requires_grad_(True) for c in synthetic_clips(shapes, seed=8)]
+    wz, _ = _weights(sum(counts), [], 4)
+    z = O.encoder_forward(clips, list(counts), sd, size, (4, 8, 8), prefix="encoder.")
+    ((z * wz).sum() + 0.1 * z.pow(2).sum()).backward()
+    return {k: v.grad for k, v in sd.items() if k.startswith("encoder.")}, [c.grad for c in clips]
+
+
+def _encoder_grads(size, dtype, shapes, counts):
+    from titok_video_amd.synthetic import synthetic_clips
+    model = _model(size, dtype)
+    clips = [c.requires_grad_(True) for c in synthetic_clips(shapes, seed=8, dtype=dtype, device=DEV)]
+    wz, _ = _weights(sum(counts), [], 4)
+    z = model.encoder.forward_z(clips, list(counts))
+    ((z * wz.to(DEV)).sum() + 0.1 * z.pow(2).sum()).backward()
+    torch.cuda.synchronize()
+    return {"encoder." + n: p.grad for n, p in model.encoder.named_parameters()}, [c.grad for c in clips]
+
+
+def _decoder_target(shapes, counts, seed):
+    from titok_video_amd.synthetic import synthetic_clips
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randint(0, 4375, (sum(counts),), generator=g, dtype=torch.int32)
+    codes = O.fsq_indices_to_codes(idx, LEVELS)                       # exactly representable in bf16
+    target = [c * 0.5 for c in synthetic_clips(shapes, seed=9)]
+    return codes, target
+
+
+def _decoder_loss(recon, target):
+    # smooth: no sign(recon - target) that flips for pixels within rounding noise of the target (the L1 loss of the training step)
+    return sum(0.5 * (r.float() - t).pow(2).mean() for r, t in zip(recon, target))
+
+
+@functools.lru_cache(maxsize=None)
+def _decoder_reference(size, shapes, counts):
+    codes, target = _decoder_target(shapes, counts, 3)
+    sd = {k: v.clone().requires_grad_(True) for k, v in _state(size).items()}
+    cr = codes.clone().requires_grad_(True)
+    _decoder_loss(O.titok_decode(cr, list(counts), list(shapes), sd, size), target).backward()
+    return {k: v.grad for k, v in sd.items() if k.startswith("decoder.")}, cr.grad
+
+
+def _decoder_grads(size, dtype, shapes, counts):
+    codes, target = _decoder_target(shapes, counts, 3)
+    model = _model(size, dtype)
+    cd = codes.to(DEV, dtype).requires_grad_(True)
+    rec = model.decode(cd, list(counts), list(shapes))
+    _decoder_loss(rec, [t.to(DEV) for t in target]).backward()
+    torch.cuda.synchronize()
+    return {"decoder." + n: p.grad for n, p in model.decoder.named_parameters()}, cd.grad
+
+
+def _rel(a, b):
+    a, b = a.double().cpu(), b.double().cpu()
+    return float((a - b).norm() / (b.norm() + 1e-30))
+
+
+def _check_fp32(got, ref, what):
+    assert set(got) == set(ref), what
+    worst = max((_rel(got[n], ref[n]), n) for n in ref)
+    report(f"{what}: worst parameter gradient error {worst[0]:.2e} ({worst[1]})")
+    for n in ref:
+        assert got[n] is not None, n
+        assert _rel(got[n], ref[n]) < 2e-3, (what, n, _rel(got[n], ref[n]))
+
+
+def _check_bf16(got, ref, what):
+    """The per-tower bounds of tests/test_hip_backward.py: cosine >= 0.97 (>= 4096 elements) / 0.90, global relative error < 0.12."""
+    tot_d = tot_b = 0.0
+    low = (2.0, "")
+    for n, r in ref.items():
+        g, r = got[n].double().cpu().flatten(), r.double().flatten()
+        cos = float((g @ r) / (g.norm() * r.norm() + 1e-30))
+        low = min(low, (cos, n))
+        assert cos > (0.97 if r.numel() >= 4096 else 0.90), (what, n, cos)
+        tot_d += float((g - r).pow(2).sum()); tot_b += float(r.pow(2).sum())
+    glob = (tot_d / tot_b) ** 0.5
+    report(f"{what}: global gradient error {glob:.4f}, lowest cosine {low[0]:.4f} ({low[1]})")
+    assert glob < 0.12, (what, glob)
+
+
+@pytest.mark.parametrize("size,batch", [("tiny", FULL), ("small", SMALL)], ids=["tiny-full", "small"])
+def test_encoder_gradients_fp32_at_full_size(size, batch):
+    """fp32 encoder (k_attn_bwd_f32 with the latent query-row limit, the compact latent_tail backward with patch rows present) against
+    the oracle's autograd: every parameter and the input clips within 2e-3."""
+    shapes, counts = batch
+    ref, ref_clips = _encoder_reference(size, tuple(shapes), tuple(counts))
+    got, clips = _encoder_grads(size, torch.float32, shapes, counts)
+    _check_fp32(got, ref, f"fp32 encoder {size}")
+    for c, rc in zip(clips, ref_clips):
+        assert _rel(c, rc) < 2e-3
+
+
+@pytest.mark.parametrize("size,batch", [("tiny", FULL), ("small", SMALL)], ids=["tiny-full", "small"])
+def test_decoder_gradients_fp32_at_full_size(size, batch):
+    shapes, counts = batch
+    ref, ref_codes = _decoder_reference(size, tuple(shapes), tuple(counts))
+    got, codes = _decoder_grads(size, torch.float32, shapes, counts)
+    _check_fp32(got, ref, f"fp32 decoder {size}")
+    assert _rel(codes, ref_codes) < 2e-3
+
+
+@pytest.mark.parametrize("size,batch", [("tiny", FULL), ("small", SMALL)], ids=["tiny-full", "small"])
+def test_tower_gradients_bf16_at_full_size(size, batch):
+    shapes, counts = batch
+    ref, ref_clips = _encoder_reference(size, tuple(shapes), tuple(counts))
+    got, clips = _encoder_grads(size, torch.bfloat16, shapes, counts)
+    _check_bf16(got, ref, f"bf16 encoder {size}")
+    for c, rc in zip(clips, ref_clips):
+        assert _rel(c.float(), rc) < 0.10
+    ref, ref_codes = _decoder_reference(size, tuple(shapes), tuple(counts))
+    got, codes = _decoder_grads(size, torch.bfloat16, shapes, counts)
+    _check_bf16(got, ref, f"bf16 decoder {size}")
+    assert _rel(codes.float(), ref_codes) < 0.2
+
+
+_ENCODER_STEP = r"""
+import sys, torch
+sys.path.insert(0, sys.argv[1])
+from tests.test_hip_backward_shapes import FULL, _encoder_grads
+shapes, counts = FULL
+grads, clips = _encoder_grads("tiny", torch.bfloat16, shapes, counts)
+torch.save({"params": {n: g.float().cpu() for n, g in grads.items()}, "clips": [c.float().cpu() for c in clips]}, sys.argv[2])
+"""
+
+
+def test_encoder_latent_shortcut_changes_only_summation_order_bf16(tmp_path):
+    """The bf16 encoder step with the latent-only last layer (latent_tail: compact rows behind the attention; attention forward for the
+    latent query blocks only, backward skipping the rows behind them) against the same step on every row (TTV_ENC_LATENT_LAST=0).
+    The skipped rows carry exact zeros, so only summation order may differ.  The switch is an environment variable read once per
+    process, so each setting runs in a child process: ttv_debug_set bit 19 is per host thread, and autograd runs the backward on a
+    thread of its own, which would see the shortcut on after a forward without it."""
+    outs = []
+    for flag in ("1", "0"):
+        path = str(tmp_path / f"grads_{flag}.pt")
+        env = dict(os.environ, TTV_ENC_LATENT_LAST=flag)
+        r = subprocess.run([sys.executable, "-c", _ENCODER_STEP, ROOT, path], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        outs.append(torch.load(path))
+    a, b = outs
+    worst = max((_rel(a["params"][n], b["params"][n]), n) for n in b["params"])
+    wclip = max(_rel(x, y) for x, y in zip(a["clips"], b["clips"]))
+    report(f"bf16 encoder shortcut vs all rows: worst parameter gradient difference {worst[0]:.2e} ({worst[1]}), clips {wclip:.2e}")
+    for n in b["params"]:      # measured on MI355X: 7.6e-6 (an out_proj weight), clips bit-identical
+        assert _rel(a["params"][n], b["params"][n]) < 3e-5, (n, _rel(a["params"][n], b["params"][n]))
+    assert wclip < 3e-5
+
+
+def test_tower_gradients_fp32_with_an_empty_latent_clip():
+    """A clip with K = 0 next to full-size ones (the latent query-row limit is 0 for it: no latent query block, dQ = 0 for every row)."""
+    shapes, counts = [(16, 128, 128), (4, 16, 16), (8, 32, 48)], [128, 0, 5]
+    ref, ref_clips = _encoder_reference("tiny", tuple(shapes), tuple(counts))
+    got, clips = _encoder_grads("tiny", torch.float32, shapes, counts)
+    _check_fp32(got, ref, "fp32 encoder with K = 0")
+    for c, rc in zip(clips, ref_clips):
+        assert _rel(c, rc) < 2e-3
+    ref, ref_codes = _decoder_reference("tiny", tuple(shapes), tuple(counts))
+    got, codes = _decoder_grads("tiny", torch.float32, shapes, counts)
+    _check_fp32(got, ref, "fp32 decoder with K = 0")

@@ -126,3 +126,53 @@ def test_make_optimizer_picks_the_hip_step_and_training_step_uses_it():
         for p, r in zip(params, ref):
             assert (p.detach() - r.detach()).abs().max().item() <= 2e-6 * max(1.0, r.detach().abs().max().item()), step
             r.data.copy_(p.detach())          # same starting point for the next step
+
+
+def _assert_same_with_nans(a, r, tol, what):
+    """NaN where the reference has NaN (and nowhere else), the finite values within tol."""
+    a, r = a.detach().float().cpu(), r.detach().float().cpu()
+    assert torch.equal(torch.isnan(a), torch.isnan(r)), (what, int(torch.isnan(a).sum()), int(torch.isnan(r).sum()))
+    fin = ~torch.isnan(r)
+    assert torch.equal(a[fin].isinf(), r[fin].isinf()), what
+    ok = fin & torch.isfinite(r)
+    if bool(ok.any()):
+        d = (a[ok] - r[ok]).abs().max().item()
+        assert d <= tol(r[ok]), (what, d)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("bad", [float("nan"), float("inf")])
+def test_non_finite_gradient_clips_and_steps_like_torch(dtype, bad):
+    """One gradient element NaN or +inf, max_norm set: torch's clip_grad_norm_ returns a NaN / inf norm and scales every gradient by
+    clamp(max_norm / (norm + 1e-6), max=1) - NaN for a NaN norm (every parameter with a gradient is poisoned), 0 for an infinite one
+    (inf * 0 = NaN at the inf element only) - and AdamW applies that.  The second step gives a finite gradient to the already-NaN state."""
+    from titok_video_amd.optim import HipAdamW
+    ours, ref = _params(dtype, 0), _params(dtype, 0)
+    opt = HipAdamW(ours, **HYPER)
+    opt_ref = torch.optim.AdamW(ref, foreach=False, fused=False, **HYPER)
+    for step in range(2):
+        gs = _grads(dtype, step, 0.02 * (step + 1))
+        if step == 0:
+            gs[3].view(-1)[1000] = bad                       # the (64, 129) tensor, element in its first chunk
+        for p, r, g in zip(ours, ref, gs):
+            p.grad, r.grad = g.clone(), g.clone()
+        norm = opt.clip_and_step(1.0)
+        norm_ref = torch.nn.utils.clip_grad_norm_(ref, 1.0)
+        opt_ref.step()
+        n, nr = float(norm), float(norm_ref)
+        if step == 0:
+            assert (n != n and nr != nr) if bad != bad else (n == nr == float("inf")), (step, n, nr)
+        else:
+            assert abs(n - nr) <= (1e-5 if dtype == torch.float32 else 1e-2) * nr, (step, n, nr)
+        # tolerances of test_matches_torch_adamw_over_several_steps
+        ptol = (lambda r: 2e-6) if dtype == torch.float32 else (lambda r: 2.0 ** -7 * max(1e-3, r.abs().max().item()))
+        stol = lambda r: (1e-6 if dtype == torch.float32 else 2e-2) * max(r.abs().max().item(), 1e-12)
+        for i, (p, r) in enumerate(zip(ours, ref)):
+            _assert_same_with_nans(p, r, ptol, (step, i, "param"))
+            so, sr = opt.state[p], opt_ref.state[r]
+            _assert_same_with_nans(so["exp_avg"], sr["exp_avg"], stol, (step, i, "exp_avg"))
+            _assert_same_with_nans(so["exp_avg_sq"], sr["exp_avg_sq"], stol, (step, i, "exp_avg_sq"))
+        if bad != bad:
+            assert all(bool(torch.isnan(p.detach()).all()) for p in ours)           # the NaN coefficient reached every parameter
+        else:
+            assert sum(int(torch.isnan(p.detach()).sum()) for p in ours) == 1     # only the inf element

@@ -410,7 +410,7 @@ static int layers_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, 
 // step for the 7 M parameters of the tiny tokenizer (98 MB of traffic in bf16: 0.4 TB/s); these two move the same bytes once:
 //   k_opt_gradsq: one block per 8 192-element chunk of a tensor -> partial[chunk] = sum g^2 (fixed order inside the block)
 //   k_opt_adamw : every block first sums ALL partials in one fixed order (the same value in every block, bit-reproducible run to run -
-//                 no atomics), derives the clip factor min(1, max_norm / (norm + 1e-6)), then updates its chunk; the gradient is scaled in
+//                 no atomics), derives the clip factor min(1, max_norm / (norm + 1e-6)) (NaN for a NaN norm, as torch), then updates its chunk; the gradient is scaled in
 //                 registers and NOT rewritten (clip_grad_norm_ scales p.grad in place: the only difference a caller could see).
 // fp32 arithmetic whatever the tensors' dtype (fp32 or bf16; state in the parameter's dtype), operation order of torch's fused kernel:
 //   p -= lr wd p ; m = lerp(m, g, 1 - b1) ; v = b2 v + (1 - b2) g g ; p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps).
@@ -492,7 +492,11 @@ __global__ __launch_bounds__(256) void k_opt_adamw(const OptEntry* __restrict__ 
     for (int i = threadIdx.x; i < n_partial; i += 256) acc += partial[i];
     const float norm = sqrtf(opt_block_sum(acc, red));
     if (out_norm && blockIdx.x == 0 && threadIdx.x == 0) out_norm[0] = norm;
-    if (h.max_norm > 0.f) coef = fminf(1.0f, h.max_norm / (norm + 1e-6f));
+    if (h.max_norm > 0.f) {
+      // torch.clamp(max_norm / (norm + 1e-6), max=1): a NaN norm gives a NaN factor that reaches every gradient (fminf would return 1)
+      const float r = h.max_norm / (norm + 1e-6f);
+      coef = r >= 1.0f ? 1.0f : r;
+    }
   }
   const int2 c = chunks[blockIdx.x];
   const OptEntry e = tab[c.x];
