@@ -4,7 +4,8 @@ tests/test_hip_backward_shapes.py and checked by tests/test_blockwise_cpu.py).
 A global relative Frobenius error hides one wrong tile: among the 36 864 rows of a 32-clip batch a single 64-row block of one head
 carries ~4 % of the norm, so a block that is off by 5 % moves the global figure by 0.2 %.  `block_errors` measures every
 (sequence, head, 64-row block) on its own - the granularity at which the attention kernels tile the rows of a sequence (64-row
-backward blocks, half of a 128-row query block) - and `check_blockwise` asserts both figures."""
+backward blocks, half of a 128-row query block) - and `check_blockwise` asserts both figures.  `tile_errors` / `check_tiles` do the
+same per 128 x 128 tile of a weight gradient (tests/test_hip_backward_bf16.py)."""
 import torch
 
 
@@ -88,3 +89,34 @@ def attention_reference(qkvg, dout, cu_seqlens, hq: int, hkv: int):
             grad[s:e, vc] = v.grad
     gated = out * torch.sigmoid(x[:, d:2 * d])
     return out, gated, lse, grad
+
+
+def tile_errors(x, ref, tile: int = 128):
+    """[ceil(N / tile), ceil(K / tile)] relative Frobenius error per `tile` x `tile` tile of 2-D [N, K] matrices - the output tile of
+    the weight-gradient GEMM (k_wgrad128_bf16): one wrong tile or split of it shows here and nowhere in a global figure.  Edge tiles
+    are short.  Same floor as block_errors: a tile whose reference norm is below 1e-2 of the root-mean-square tile norm is measured
+    against that floor."""
+    x, ref = x.double().cpu(), ref.double().cpu()
+    assert x.shape == ref.shape and ref.dim() == 2, (tuple(x.shape), tuple(ref.shape))
+    N, K = ref.shape
+    tn, tk = -(-N // tile), -(-K // tile)
+
+    def sums(v):
+        v = torch.nn.functional.pad(v.pow(2), (0, tk * tile - K, 0, tn * tile - N))
+        return v.view(tn, tile, tk, tile).sum((1, 3))
+    num, den = sums(x - ref), sums(ref)
+    floor = 1e-4 * float(den.mean()) + 1e-300
+    return (num / den.clamp_min(floor)).sqrt()
+
+
+def check_tiles(x, ref, tile_tol: float, global_tol: float, what: str = "", tile: int = 128):
+    """Assert that the matrix x is finite, within `global_tol` of ref as a whole and within `tile_tol` in every tile.  Returns
+    (worst tile error, global error)."""
+    assert bool(torch.isfinite(x.double()).all()), f"{what}: non-finite values"
+    glob = global_error(x, ref)
+    err = tile_errors(x, ref, tile)
+    worst = float(err.max())
+    assert glob < global_tol, f"{what}: global relative error {glob:.3e} >= {global_tol:.1e}"
+    tn, tk = divmod(int(err.argmax()), err.shape[1])
+    assert worst < tile_tol, f"{what}: tile ({tn}, {tk}): relative error {worst:.3e} >= {tile_tol:.1e} (global {glob:.3e})"
+    return worst, glob

@@ -71,6 +71,65 @@ def test_wgrad(dt, shape, workspace):
         assert torch.equal(outs[0], outs[1])
 
 
+def _wgrad_call(dy, lddy, x, ldx, dw, lddw, Lr, N, K, dt, workspace):
+    nbytes = int(L().ttv_linear_wgrad_workspace_bytes(Lr, N, K)) if workspace else 0
+    ws = torch.full((max(nbytes, 4) // 4,), float("nan"), device=DEV)
+    return L().ttv_linear_wgrad(dy, lddy, x, ldx, dw.data_ptr(), lddw, Lr, N, K, _lib.dtype_code(DT[dt]), ws.data_ptr() if workspace else None,
+                                nbytes, S())
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f32"])
+@pytest.mark.parametrize("shape", [(1000, 256, 768), (130, 256, 704), (4097, 136, 120), (1090, 128, 128)])
+@pytest.mark.parametrize("workspace", [False, True])
+def test_wgrad_strided_operands(dt, shape, workspace):
+    """Operands with leading dimensions past their widths (lddy > N, ldx > K: rows of a wider buffer, as the tower's qkvg / u slices)
+    and a dW with lddw > K whose padding columns hold NaN: they must stay NaN, and the padding of dY / X must not reach dW."""
+    Lr, N, K = shape
+    lddy, ldx, lddw = N + 24, K + 40, K + 5
+    g = torch.Generator().manual_seed(Lr + 1)
+    dyb = torch.randn(Lr, lddy, generator=g).to(DT[dt])
+    xb = torch.randn(Lr, ldx, generator=g).to(DT[dt])
+    dyb[:, N:] = float("nan")
+    xb[:, K:] = float("nan")
+    dyd, xd = dyb.to(DEV), xb.to(DEV)
+    dw = torch.full((N, lddw), float("nan"), device=DEV)
+    dw[:, :K] = 0
+    _lib.check(_wgrad_call(dyd.data_ptr(), lddy, xd.data_ptr(), ldx, dw, lddw, Lr, N, K, dt, workspace), "wgrad strided")
+    out = dw.cpu()
+    assert bool(torch.isnan(out[:, K:]).all()), "wrote into the padding columns of dW"
+    ref = dyb[:, :N].double().T @ xb[:, :K].double()
+    assert rel(out[:, :K], ref) < (2e-3 if dt == "bf16" else 2e-5)
+
+
+@pytest.mark.parametrize("shape", [(1000, 256, 768), (333, 768, 256), (70, 8, 264), (1090, 128, 128)])
+def test_wgrad_bf16_operands_not_16_byte_aligned(shape):
+    """dY and X 8 bytes past a 16-byte boundary: the 64 x 64 fallback k_wgrad_bf16 (the tiled kernel's DMA needs 16-byte rows), same
+    bound as the aligned path."""
+    Lr, N, K = shape
+    g = torch.Generator().manual_seed(Lr + 2)
+    dy = torch.randn(Lr, N, generator=g).to(torch.bfloat16)
+    x = torch.randn(Lr, K, generator=g).to(torch.bfloat16)
+    dyb = torch.zeros(Lr * N + 8, dtype=torch.bfloat16, device=DEV)
+    xb = torch.zeros(Lr * K + 8, dtype=torch.bfloat16, device=DEV)
+    dyb[4:4 + Lr * N] = dy.flatten().to(DEV)
+    xb[4:4 + Lr * K] = x.flatten().to(DEV)
+    assert (dyb.data_ptr() + 8) % 16 == 8 and (xb.data_ptr() + 8) % 16 == 8
+    dw = torch.zeros(N, K, device=DEV)
+    _lib.check(_wgrad_call(dyb.data_ptr() + 8, N, xb.data_ptr() + 8, K, dw, K, Lr, N, K, "bf16", True), "wgrad unaligned")
+    assert rel(dw, dy.double().T @ x.double()) < 2e-3
+
+
+@pytest.mark.parametrize("shape", [(64, 260, 256), (64, 256, 132), (64, 12, 12)])
+def test_wgrad_bf16_rejects_widths_not_a_multiple_of_8(shape):
+    Lr, N, K = shape
+    dy = torch.zeros(Lr, N, dtype=torch.bfloat16, device=DEV)
+    x = torch.zeros(Lr, K, dtype=torch.bfloat16, device=DEV)
+    dw = torch.full((N, K), 7.0, device=DEV)
+    rc = _wgrad_call(dy.data_ptr(), N, x.data_ptr(), K, dw, K, Lr, N, K, "bf16", False)
+    assert rc == 1, rc                                                 # TTV_ERR_INVALID
+    assert bool((dw == 7.0).all())
+
+
 def _rms_bwd_ref(x, gain, dy):
     xr = x.double().requires_grad_(True)
     gr = gain.double().requires_grad_(True)
