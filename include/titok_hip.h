@@ -518,6 +518,56 @@ int64_t ttv_ssim_workspace_bytes(const int32_t* dims, int n_clips);
 int ttv_ssim_accumulate(void* const* recon, void* const* target, const int32_t* dims, int n_clips, int dtype, int clamp, double* acc,
                         void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- LPIPS / Gram perceptual terms (model/metrics/lpips_gram.py LPIPS.forward, model/losses/loss_module.py:121-138) ----------
+ * VGG16 features[0:30] (13 3x3 convolutions with bias + ReLU, 4 2x2 max-pools) on n reconstruction and n target crops, the LPIPS
+ * head on the taps relu1_2 .. relu5_3 (lin weights applied with eval semantics: no dropout) and the optional Gram term; the
+ * input-gradient backward into the reconstruction crops.  Weights are frozen (no weight gradients).  Activations NHWC in the
+ * compute dtype (TTV_BF16: MFMA implicit GEMM with fp32 accumulation; TTV_F32: exact fp32); head, Gram and losses in fp32.
+ *
+ * Weight images (built once per weight version by the caller from W[co][ci][kh][kw], tap t = 3 kh + kw), compute dtype:
+ *   direct image  [9][Cin][Cout]            = W[co][ci][kh][kw]
+ *   dgrad direct  [9][Cout][Cin]            = W[co][ci][2-kh][2-kw]
+ *   MFMA image    [Cin/32][9][Cout][32]     (the direct image with Cin split into 32-channel chunks, innermost)
+ *   dgrad MFMA    [Cout/32][9][Cin][32]
+ * A convolution takes the MFMA images when dtype == TTV_BF16, Cin % 32 == 0 and Cout % 64 == 0, the direct images otherwise (so
+ * every fp32 layer, and conv1_1 plus its dgrad in bf16).  b[l]: fp32 bias [Cout]; lin[k]: fp32 [C_k] (lin{k}.model.1.weight). */
+typedef struct {
+  const void* w[13];     /* forward image of conv layer l (features index 0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28) */
+  const void* wd[13];    /* dgrad image of conv layer l */
+  const float* b[13];
+  const float* lin[5];
+} ttv_lpips_weights;
+
+/* Sizes for n image pairs of H x W (multiples of 16, 16 .. 2048), -1 on a bad shape or dtype.  The tape holds every activation of
+ * the 2n-image stack (reconstruction images first); the workspace holds partial sums, head gradients and dgrad buffers. */
+int64_t ttv_lpips_tape_bytes(int n, int H, int W, int dtype);
+int64_t ttv_lpips_workspace_bytes(int n, int H, int W, int dtype);
+
+/* recon, target: [n][3][H][W] (dtype, contiguous).  lpips[n] (fp32, device) = per-image LPIPS (sum over taps of the spatial mean of
+ * sum_c lin_c (n0 - n1)^2); gram[n] (fp32, device, or NULL to skip the Gram term) = mean over taps of mse(G0, G1), G = F F^T / hw on
+ * the un-normalised features.  tape and workspace: caller-owned, 256-byte aligned; the tape is kept for ttv_lpips_backward.
+ * Partial sums are reduced in a fixed order: identical inputs give identical bits. */
+int ttv_lpips_forward(const ttv_lpips_weights* w, const void* recon, const void* target, int n, int H, int W, int dtype, float* lpips,
+                      float* gram, void* tape, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* d recon [n][3][H][W] (dtype) from the upstream gradients glpips[n] and ggram[n] (fp32, device; ggram NULL = Gram term off), using
+ * the tape of the forward call with the same n, H, W, dtype and weights.  Max-pool gradients go to the first maximum of each window
+ * in row-major order (torch max_pool2d). */
+int ttv_lpips_backward(const ttv_lpips_weights* w, const void* tape, int n, int H, int W, int dtype, const float* glpips,
+                       const float* ggram, void* drecon, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Single operations (tests).  ttv_lpips_conv3x3: x [N][H][W][Cin] -> y [N][H][W][Cout], 3x3, stride 1, zero pad 1 per image, with
+ * the weight image the dtype / shape rule above selects.  mode 0: y = relu(conv + bias); 1: y = conv * (h > 0), h [N][H][W][Cout];
+ * 2: y = conv.  Workspace: ttv_lpips_conv_workspace_bytes (split-K partials; 0 when none).  ttv_lpips_maxpool: 2x2 / 2 max-pool of
+ * NHWC x.  ttv_lpips_maxpool_backward: dx = (route(dy) + add) * (h > 0) over h [N][H][W][C], dy [N][H/2][W/2][C] (or NULL), add fp32
+ * (or NULL); route sends each dy element to the first maximum of its window of h in row-major order. */
+int64_t ttv_lpips_conv_workspace_bytes(int N, int H, int W, int Cin, int Cout, int dtype);
+int ttv_lpips_conv3x3(const void* x, int N, int H, int W, int Cin, int Cout, const void* w, const float* bias, int mode, const void* h,
+                      void* y, int dtype, void* workspace, int64_t workspace_bytes, void* stream);
+int ttv_lpips_maxpool(const void* x, int N, int H, int W, int C, void* y, int dtype, void* stream);
+int ttv_lpips_maxpool_backward(const void* dy, const float* add, const void* h, int N, int H, int W, int C, void* dx, int dtype,
+                               void* stream);
+
 /* ---- measurement hook (bench.py roofline leg) ---------------------------------------------------------- */
 /* Kernel classes whose launches can be bracketed by HIP events on the stream they are launched on. */
 #define TTV_KC_ATTENTION 1

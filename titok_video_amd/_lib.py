@@ -81,6 +81,10 @@ class TowerGrads(C.Structure):
                 ("proj_out_w", vp), ("proj_out_b", vp), ("layers", C.POINTER(LayerGrads)), ("layer_done_events", C.POINTER(vp))]
 
 
+class LpipsWeights(C.Structure):
+    _fields_ = [("w", vp * 13), ("wd", vp * 13), ("b", vp * 13), ("lin", vp * 5)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -158,6 +162,14 @@ SYMBOLS = {
     "ttv_sq_err_accumulate": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "ttv_ssim_workspace_bytes": (C.c_int64, [vp, C.c_int]),
     "ttv_ssim_accumulate": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int64, vp]),
+    "ttv_lpips_tape_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ttv_lpips_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ttv_lpips_forward": (C.c_int, [C.POINTER(LpipsWeights), vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int64, vp]),
+    "ttv_lpips_backward": (C.c_int, [C.POINTER(LpipsWeights), vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int64, vp]),
+    "ttv_lpips_conv_workspace_bytes": (C.c_int64, [C.c_int] * 6),
+    "ttv_lpips_conv3x3": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int64, vp]),
+    "ttv_lpips_maxpool": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
+    "ttv_lpips_maxpool_backward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "ttv_debug_set": (C.c_int, [C.c_int]),
     "ttv_debug_stamps": (C.c_int, [vp]),
     "ttv_prof_begin": (C.c_int, [C.c_int, C.c_int]),

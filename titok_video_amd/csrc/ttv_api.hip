@@ -736,6 +736,38 @@ int ttv_ssim_accumulate(void* const* recon, void* const* target, const int32_t* 
   return ttvk_ssim(recon, target, dims, n_clips, dtype, clamp, acc, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+int64_t ttv_lpips_tape_bytes(int n, int H, int W, int dtype) { return ttvk_lpips_tape_bytes(n, H, W, dtype); }
+
+int64_t ttv_lpips_workspace_bytes(int n, int H, int W, int dtype) { return ttvk_lpips_workspace_bytes(n, H, W, dtype); }
+
+int ttv_lpips_forward(const ttv_lpips_weights* w, const void* recon, const void* target, int n, int H, int W, int dtype, float* lpips,
+                      float* gram, void* tape, void* workspace, int64_t workspace_bytes, void* stream) {
+  return ttvk_lpips_forward(w, recon, target, n, H, W, dtype, lpips, gram, tape, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ttv_lpips_backward(const ttv_lpips_weights* w, const void* tape, int n, int H, int W, int dtype, const float* glpips,
+                       const float* ggram, void* drecon, void* workspace, int64_t workspace_bytes, void* stream) {
+  return ttvk_lpips_backward(w, tape, n, H, W, dtype, glpips, ggram, drecon, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int64_t ttv_lpips_conv_workspace_bytes(int N, int H, int W, int Cin, int Cout, int dtype) {
+  return ttvk_lpips_conv_workspace_bytes(N, H, W, Cin, Cout, dtype);
+}
+
+int ttv_lpips_conv3x3(const void* x, int N, int H, int W, int Cin, int Cout, const void* w, const float* bias, int mode, const void* h,
+                      void* y, int dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+  return ttvk_lpips_conv3x3(x, N, H, W, Cin, Cout, w, bias, mode, h, y, dtype, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ttv_lpips_maxpool(const void* x, int N, int H, int W, int C, void* y, int dtype, void* stream) {
+  return ttvk_lpips_maxpool(x, N, H, W, C, y, dtype, (hipStream_t)stream);
+}
+
+int ttv_lpips_maxpool_backward(const void* dy, const float* add, const void* h, int N, int H, int W, int C, void* dx, int dtype,
+                               void* stream) {
+  return ttvk_lpips_maxpool_backward(dy, add, h, N, H, W, C, dx, dtype, (hipStream_t)stream);
+}
+
 int ttv_debug_set(int flags) {
   g_ttv_debug = flags;
   return TTV_OK;

@@ -194,3 +194,16 @@ int ttvk_rope_build(const float* base_cos, const float* base_sin, int n_ids, int
 int64_t ttvk_ssim_workspace_bytes(const int32_t* dims, int n_clips);
 int ttvk_ssim(void* const* recon, void* const* target, const int32_t* dims, int n_clips, int dtype, int clamp, double* acc2, void* workspace,
               int64_t workspace_bytes, hipStream_t s);
+
+// ---- ttv_lpips.hip ----
+int64_t ttvk_lpips_tape_bytes(int n, int H, int W, int dtype);
+int64_t ttvk_lpips_workspace_bytes(int n, int H, int W, int dtype);
+int ttvk_lpips_forward(const ttv_lpips_weights* w, const void* recon, const void* target, int n, int H, int W, int dtype, float* lpips,
+                       float* gram, void* tape, void* ws, int64_t ws_bytes, hipStream_t s);
+int ttvk_lpips_backward(const ttv_lpips_weights* w, const void* tape, int n, int H, int W, int dtype, const float* glpips, const float* ggram,
+                        void* drecon, void* ws, int64_t ws_bytes, hipStream_t s);
+int64_t ttvk_lpips_conv_workspace_bytes(int N, int H, int W, int Cin, int Cout, int dtype);
+int ttvk_lpips_conv3x3(const void* x, int N, int H, int W, int Cin, int Cout, const void* w, const float* bias, int mode, const void* h,
+                       void* y, int dtype, void* ws, int64_t ws_bytes, hipStream_t s);
+int ttvk_lpips_maxpool(const void* x, int N, int H, int W, int C, void* y, int dtype, hipStream_t s);
+int ttvk_lpips_maxpool_backward(const void* dy, const float* add, const void* h, int N, int H, int W, int C, void* dx, int dtype, hipStream_t s);

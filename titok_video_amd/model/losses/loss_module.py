@@ -7,11 +7,14 @@ path (tape forward + hand-written backward, input-clip gradients included).  Sam
 same `forward(target, recon, disc_forward=False)` signature, same return value `(total_loss, {'gen/..' | 'disc/..': scalar})`
 and the same state-dict keys (`disc_model.*`).
 
-Not built: the LPIPS / Gram terms (loss_module.py:28-36,61-94,121-138).  Their VGG weights are fetched from the network by the
-reference, so `perceptual_weight` and `gram_weight` must be 0 here; anything else raises.
+The LPIPS / Gram terms (loss_module.py:28-36,59-93,121-138) run on the HIP path too (model/metrics/lpips_gram.py).  Their weights
+never come from the network: pass `perceptual_weights=` (a path or a state dict with the reference LPIPS keys) or set the config key
+`tokenizer.losses.perceptual_weights` to a path; with neither, a non-zero `perceptual_weight` or `gram_weight` raises.  The module
+sits under `perceptual_model` (never saved in trainer checkpoints, checkpoint.py).
 """
 from __future__ import annotations
 
+import random
 from typing import List, Optional, Sequence
 
 import torch
@@ -20,6 +23,7 @@ import torch.nn.functional as F
 
 from ..base.blocks import TiTokEncoder
 from ..base.utils import init_weights
+from ..metrics.lpips_gram import LPIPS
 from ...train import l1_reconstruction_loss
 
 
@@ -29,8 +33,15 @@ _F32_HEAD = os.environ.get("TTV_DISC_F32_HEAD", "0") == "1"
 _TWO_CALLS = os.environ.get("TTV_DISC_TWO_CALLS", "0") == "1"
 
 
+def _resized_hw(H: int, W: int, size: int):
+    """torchvision resize(size=int) output size: the short edge becomes `size`, the long edge int(size * long / short)."""
+    short, long = (W, H) if W <= H else (H, W)
+    new_short, new_long = size, int(size * long / short)
+    return (new_long, new_short) if W <= H else (new_short, new_long)
+
+
 class ReconstructionLoss(nn.Module):
-    def __init__(self, config):
+    def __init__(self, config, perceptual_weights=None):
         super().__init__()
         self.config = config
         loss_c = config.tokenizer.losses
@@ -38,8 +49,21 @@ class ReconstructionLoss(nn.Module):
         self.perceptual_weight = float(loss_c.perceptual_weight)
         self.gram_weight = float(loss_c.gram_weight)
         if self.perceptual_weight > 0.0 or self.gram_weight > 0.0:
-            raise NotImplementedError("the LPIPS / Gram terms need network-fetched VGG weights (reference lpips_gram.py:10-48); "
-                                      "set tokenizer.losses.perceptual_weight = gram_weight = 0 on this path")
+            source = perceptual_weights if perceptual_weights is not None else getattr(loss_c, "perceptual_weights", None)
+            if source is None:
+                raise NotImplementedError(
+                    "the LPIPS / Gram terms need the VGG16 + LPIPS weights, which the reference fetches from the network "
+                    "(lpips_gram.py:10-48): pass ReconstructionLoss(config, perceptual_weights=...) or set "
+                    "tokenizer.losses.perceptual_weights to a state-dict file (see INTEGRATION.md), or set "
+                    "tokenizer.losses.perceptual_weight = gram_weight = 0")
+            if isinstance(source, (str, bytes, os.PathLike)):
+                self.perceptual_model = LPIPS.from_file(source)
+            else:
+                self.perceptual_model = LPIPS()
+                self.perceptual_model.load_state_dict(source, strict=True)
+            self.perceptual_model.eval()
+            for p in self.perceptual_model.parameters():
+                p.requires_grad = False
         model_d = config.discriminator.model
         self.disc_weight = float(loss_c.disc_weight)
         if self.disc_weight > 0.0:
@@ -50,6 +74,35 @@ class ReconstructionLoss(nn.Module):
         self.gp_noise = float(loss_d.gp_noise)
         self.centering_weight = float(loss_d.centering_weight)
         self.total_steps = config.training.main.max_steps
+
+    # ---- perceptual crops (loss_module.py:59-93) ----------------------------------------------------------------------------
+    def perceptual_preprocess(self, target, recon, resize_prob: float = 0.25):
+        """Random crops of the frames, consuming Python's `random` exactly as the reference does, so the same `random.seed` picks
+        the same frames and offsets: one random() per frame for the shuffle (sorted(..., key=random.random())), then per taken frame
+        a random() for the resize only when the frame is at least the crop size on both edges, then randrange for the row and the
+        column offsets.  The loop stops AFTER appending once i >= perceptual_samples_per_step (24 -> 25 crops; -1 -> all frames).
+        The reconstruction is clamped to [-1, 1]; the resize is torchvision's resize(size=s) on a tensor (short edge -> s, long
+        edge int(s * long / short), bicubic, align_corners=False, no antialias).  Returns (recon [F,C,s,s], target [F,C,s,s])."""
+        target_out, recon_out = [], []
+        size = int(self.config.tokenizer.losses.perceptual_sampling_size)
+        samples = int(self.config.tokenizer.losses.perceptual_samples_per_step)
+        if samples == -1:
+            samples = len(target)
+        for i, (trg, rec) in enumerate(sorted(zip(target, recon), key=lambda k: random.random())):
+            rec = rec.clamp(-1, 1)
+            H, W = trg.shape[1:]
+            if (H < size or W < size) or random.random() < resize_prob:
+                new_h, new_w = _resized_hw(H, W, size)
+                trg = F.interpolate(trg[None], size=(new_h, new_w), mode="bicubic", align_corners=False)[0]
+                rec = F.interpolate(rec[None], size=(new_h, new_w), mode="bicubic", align_corners=False)[0]
+            H, W = trg.shape[1:]
+            dy = random.randrange(0, (H - size) + 1)
+            dx = random.randrange(0, (W - size) + 1)
+            target_out.append(trg[:, dy:dy + size, dx:dx + size])
+            recon_out.append(rec[:, dy:dy + size, dx:dx + size])
+            if i >= samples:
+                break
+        return torch.stack(recon_out, dim=0).contiguous(), torch.stack(target_out, dim=0).contiguous()
 
     # ---- discriminator access -------------------------------------------------------------------------------------------
     def disc_wrapper(self, x: Sequence[torch.Tensor]) -> torch.Tensor:
@@ -78,7 +131,7 @@ class ReconstructionLoss(nn.Module):
             return self._discriminator_step_loss(target, recon, gp_noise_tensors)
         return self._generator_step_loss(target, recon)
 
-    # ---- generator step (loss_module.py:110-162, perceptual terms off) ----------------------------------------------------
+    # ---- generator step (loss_module.py:110-162) -------------------------------------------------------------------------
     def _generator_step_loss(self, target, recon):
         real = [t.contiguous() for t in target]
         fake = [r.contiguous() for r in recon]
@@ -86,6 +139,22 @@ class ReconstructionLoss(nn.Module):
         # the [B] vector until the final .mean(); mean(a + w b) = mean(a) + w mean(b), so the scalar is carried instead.
         terms = {"recon_loss": l1_reconstruction_loss(fake, real)}
         total = terms["recon_loss"]
+        if self.perceptual_weight > 0.0 or self.gram_weight > 0.0:              # (:123-137)
+            target_frames, recon_frames = [], []
+            for t, r in zip(real, fake):
+                target_frames += t.unbind(1)
+                recon_frames += r.unbind(1)
+            # The reference unpacks preprocess's (recon, target) as (target, recon) and calls LPIPS(target crops, recon crops); both
+            # terms are symmetric in their two arguments, so the crops go in as (recon, target) here and the gradient is taken
+            # with respect to the HIP module's input.
+            rec_crops, trg_crops = self.perceptual_preprocess(target_frames, recon_frames)
+            lp, gr = self.perceptual_model(rec_crops, trg_crops.detach(), compute_gram=self.gram_weight > 0.0)
+            if self.perceptual_weight > 0.0:
+                terms["perceptual_loss"] = lp.mean()
+                total = total + self.perceptual_weight * terms["perceptual_loss"]
+            if self.gram_weight > 0.0:
+                terms["gram_loss"] = gr.mean()
+                total = total + self.gram_weight * terms["gram_loss"]
         if self.disc_weight > 0.0:
             self._set_disc_trainable(False)                                   # the generator sees a frozen critic (:144-146)
             score_real = self.disc_wrapper([t.detach() for t in real])        # no gradient path: runs the fused inference towers

@@ -95,6 +95,26 @@ def seeded_titok_state(seed: int = 0, encoder_size: str = "tiny", decoder_size: 
     return sd
 
 
+def seeded_lpips_state(seed: int = 0) -> Dict[str, torch.Tensor]:
+    """fp32 CPU state dict with the reference LPIPS keys (model/metrics/lpips_gram.py) from `seed`: He-normal 3x3 convolutions
+    (std sqrt(2 / (9 Cin))), biases N(0, 0.05^2), lin weights |N(0, 1)| / C (trained LPIPS lin weights are non-negative).
+    Drawn in key order from one CPU generator."""
+    from .model.metrics.lpips_gram import CHNS, CONV_INDICES, VGG_FEATURES, _slice_of
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(int(seed))
+    out: Dict[str, torch.Tensor] = OrderedDict()
+    out["scaling_layer.shift"] = torch.tensor([-0.030, -0.088, -0.188])[None, :, None, None]
+    out["scaling_layer.scale"] = torch.tensor([0.458, 0.448, 0.450])[None, :, None, None]
+    dims = {f[0]: (f[2], f[3]) for f in VGG_FEATURES if f[1] == "conv"}
+    for i in CONV_INDICES:
+        cin, cout = dims[i]
+        out[f"net.slice{_slice_of(i)}.{i}.weight"] = torch.randn((cout, cin, 3, 3), generator=gen) * math.sqrt(2.0 / (9 * cin))
+        out[f"net.slice{_slice_of(i)}.{i}.bias"] = 0.05 * torch.randn((cout,), generator=gen)
+    for k, c in enumerate(CHNS):
+        out[f"lin{k}.model.1.weight"] = torch.randn((1, c, 1, 1), generator=gen).abs() / c
+    return out
+
+
 def synthetic_clips(shapes: Sequence[Sequence[int]], seed: int = 1234,
                     dtype: torch.dtype = torch.float32, device="cpu") -> List[torch.Tensor]:
     """List of `[3,T,H,W]` clips, U(-1,1), generated on CPU from `seed` then moved/cast."""
