@@ -568,6 +568,44 @@ int ttv_lpips_maxpool(const void* x, int N, int H, int W, int C, void* y, int dt
 int ttv_lpips_maxpool_backward(const void* dy, const float* add, const void* h, int N, int H, int W, int C, void* dx, int dtype,
                                void* stream);
 
+/* ---- FVD: clip preprocessing and the I3D feature extractor (model/metrics/fvd.py FVDCalculator.update) ----------------------
+ * I3D (Inception-v1 inflated, Kinetics-400 RGB) up to the 400 logits before the softmax, averaged over time, in fp32 with
+ * activations channels-last.  58 convolutions in this order: 0 Conv3d_1a_7x7, 1 Conv3d_2b_1x1, 2 Conv3d_2c_3x3, then for the
+ * Inception blocks Mixed_3b, 3c, 4b, 4c, 4d, 4e, 4f, 5b, 5c (b = 0 .. 8) 3 + 6 b + (b0, b1a, b1b, b2a, b2b, b3b), and 57 the logits.
+ * w[i]: fp32 weight image [K][Cout], K = ((dt kH + dh) kW + dw) Cin + ci, i.e. W[co][ci][dt][dh][dw] -> [dt][dh][dw][ci][co].
+ * scale[i], shift[i]: fp32 [Cout], the folded eval BatchNorm (y = conv * scale + shift, then ReLU).  The logits take shift[57] as
+ * their bias and no scale (scale[57] may be NULL).  Every output is a fixed-order fp32 chain: a clip's features are
+ * bit-identical whatever other clips share the launch. */
+#define TTV_I3D_CONVS 58
+#define TTV_I3D_FEATURES 400
+typedef struct {
+  const float* w[TTV_I3D_CONVS];
+  const float* scale[TTV_I3D_CONVS];
+  const float* shift[TTV_I3D_CONVS];
+} ttv_i3d_weights;
+
+/* Workspace of ttv_i3d_features for n clips (1 .. TTV_MAX_CLIPS_PER_LAUNCH), -1 on a bad n. */
+int64_t ttv_i3d_workspace_bytes(int n);
+
+/* Up to TTV_MAX_CLIPS_PER_LAUNCH contiguous clips [3][T][H][W] (host array of device pointers, `dtype`; dims = n_clips x
+ * (C, T, H, W), host) -> out [n_clips][10][224][224][3] fp32: the clip clamped to [-1, 1] when `clamp` is set (the reference clamps
+ * the reconstruction only), resampled trilinearly to 3 x 224 x 224 (torch align_corners=False; the reference's F.interpolate
+ * asks for size (C, 224, 224), so the time axis always goes to C = 3 frames), frame 2 repeated into frames 3 .. 9. */
+int ttv_fvd_preprocess(void* const* clips, const int32_t* dims, int n_clips, int dtype, int clamp, float* out, void* stream);
+
+/* x: [n][10][224][224][3] fp32 (ttv_fvd_preprocess), feats: [n][400] fp32.  x and the workspace are 256-byte aligned. */
+int ttv_i3d_features(const ttv_i3d_weights* w, const float* x, int n, float* feats, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+
+/* Single operations (tests).  ttv_i3d_conv3d: x [N][T][H][W][Cin] -> channels [c_off, c_off + Cout) of y [N][To][Ho][Wo][ldc],
+ * a k x k x k convolution (k = 1, 3, 7) with stride 1 or 2 in every dimension and TF-SAME padding, y = conv * scale + shift
+ * (scale / shift NULL: 1 / 0), ReLU when `relu`; w is the weight image above.  ttv_i3d_maxpool3d: kt x kh x kw max-pool with
+ * strides st x sh x sw and TF-SAME padding (padded cells never win) of x [N][T][H][W][C] -> y [N][To][Ho][Wo][C]. */
+int ttv_i3d_conv3d(const float* x, int N, int T, int H, int W, int Cin, int k, int stride, const float* w, const float* scale,
+                   const float* shift, int Cout, int relu, float* y, int ldc, int c_off, void* stream);
+int ttv_i3d_maxpool3d(const float* x, int N, int T, int H, int W, int C, int kt, int kh, int kw, int st, int sh, int sw, float* y,
+                      void* stream);
+
 /* ---- measurement hook (bench.py roofline leg) ---------------------------------------------------------- */
 /* Kernel classes whose launches can be bracketed by HIP events on the stream they are launched on. */
 #define TTV_KC_ATTENTION 1

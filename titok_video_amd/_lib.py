@@ -85,6 +85,14 @@ class LpipsWeights(C.Structure):
     _fields_ = [("w", vp * 13), ("wd", vp * 13), ("b", vp * 13), ("lin", vp * 5)]
 
 
+TTV_I3D_CONVS = 58
+TTV_I3D_FEATURES = 400
+
+
+class I3dWeights(C.Structure):
+    _fields_ = [("w", vp * TTV_I3D_CONVS), ("scale", vp * TTV_I3D_CONVS), ("shift", vp * TTV_I3D_CONVS)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -170,6 +178,11 @@ SYMBOLS = {
     "ttv_lpips_conv3x3": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int64, vp]),
     "ttv_lpips_maxpool": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "ttv_lpips_maxpool_backward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
+    "ttv_i3d_workspace_bytes": (C.c_int64, [C.c_int]),
+    "ttv_fvd_preprocess": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "ttv_i3d_features": (C.c_int, [C.POINTER(I3dWeights), vp, C.c_int, vp, vp, C.c_int64, vp]),
+    "ttv_i3d_conv3d": (C.c_int, [vp] + [C.c_int] * 7 + [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]),
+    "ttv_i3d_maxpool3d": (C.c_int, [vp] + [C.c_int] * 11 + [vp, vp]),
     "ttv_debug_set": (C.c_int, [C.c_int]),
     "ttv_debug_stamps": (C.c_int, [vp]),
     "ttv_prof_begin": (C.c_int, [C.c_int, C.c_int]),

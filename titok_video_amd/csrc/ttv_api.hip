@@ -768,6 +768,27 @@ int ttv_lpips_maxpool_backward(const void* dy, const float* add, const void* h, 
   return ttvk_lpips_maxpool_backward(dy, add, h, N, H, W, C, dx, dtype, (hipStream_t)stream);
 }
 
+int64_t ttv_i3d_workspace_bytes(int n) { return ttvk_i3d_workspace_bytes(n); }
+
+int ttv_fvd_preprocess(void* const* clips, const int32_t* dims, int n_clips, int dtype, int clamp, float* out, void* stream) {
+  return ttvk_fvd_preprocess(clips, dims, n_clips, dtype, clamp, out, (hipStream_t)stream);
+}
+
+int ttv_i3d_features(const ttv_i3d_weights* w, const float* x, int n, float* feats, void* workspace, int64_t workspace_bytes,
+                     void* stream) {
+  return ttvk_i3d_features(w, x, n, feats, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ttv_i3d_conv3d(const float* x, int N, int T, int H, int W, int Cin, int k, int stride, const float* w, const float* scale,
+                   const float* shift, int Cout, int relu, float* y, int ldc, int c_off, void* stream) {
+  return ttvk_i3d_conv3d(x, N, T, H, W, Cin, k, stride, w, scale, shift, Cout, relu, y, ldc, c_off, (hipStream_t)stream);
+}
+
+int ttv_i3d_maxpool3d(const float* x, int N, int T, int H, int W, int C, int kt, int kh, int kw, int st, int sh, int sw, float* y,
+                      void* stream) {
+  return ttvk_i3d_maxpool3d(x, N, T, H, W, C, kt, kh, kw, st, sh, sw, y, (hipStream_t)stream);
+}
+
 int ttv_debug_set(int flags) {
   g_ttv_debug = flags;
   return TTV_OK;

@@ -207,3 +207,12 @@ int ttvk_lpips_conv3x3(const void* x, int N, int H, int W, int Cin, int Cout, co
                        void* y, int dtype, void* ws, int64_t ws_bytes, hipStream_t s);
 int ttvk_lpips_maxpool(const void* x, int N, int H, int W, int C, void* y, int dtype, hipStream_t s);
 int ttvk_lpips_maxpool_backward(const void* dy, const float* add, const void* h, int N, int H, int W, int C, void* dx, int dtype, hipStream_t s);
+
+// ---- ttv_i3d.hip ----
+int64_t ttvk_i3d_workspace_bytes(int n);
+int ttvk_fvd_preprocess(void* const* clips, const int32_t* dims, int n_clips, int dtype, int clamp, float* out, hipStream_t s);
+int ttvk_i3d_features(const ttv_i3d_weights* w, const float* x, int n, float* feats, void* ws, int64_t ws_bytes, hipStream_t s);
+int ttvk_i3d_conv3d(const float* x, int N, int T, int H, int W, int Cin, int k, int stride, const float* w, const float* scale,
+                    const float* shift, int Cout, int relu, float* y, int ldc, int c_off, hipStream_t s);
+int ttvk_i3d_maxpool3d(const float* x, int N, int T, int H, int W, int C, int kt, int kh, int kw, int st, int sh, int sw, float* y,
+                       hipStream_t s);

@@ -11,7 +11,11 @@ them `x.clamp(-1, 1)` per clip, CTHW -> TCHW (eval_metrics.py:19-21, 32-37).
   Deliberate deviations from torchmetrics: fp32 arithmetic for bf16 and fp32 inputs (under bf16 autocast torchmetrics convolves
   in bf16); frames with H < 11 or W < 11 are refused (torchmetrics gives NaN for 6-10 and raises for <= 5); no cross-rank sum
   in compute() (torchmetrics sums its state over ranks; PSNR here does not either).
-No host sync until compute().  FVD / JEDi need network-fetched weights (I3D, V-JEPA) and are out of scope.
+- FVD (the 'fvd' entry, reference fvd.FVDCalculator): needs the I3D detector's weights from a local file, given as
+  `EvalMetrics(config, fvd_detector=path)` or the optional config key `training.eval.fvd_detector`; without one 'fvd' raises as
+  before.  The reconstruction is clamped, the target is not (eval_metrics.py:33), each clip goes in as a batch of one; see
+  fvd.py for the preprocessing and the detector.  The detector's weights are not part of state_dict().
+No host sync until compute().  JEDi needs V-JEPA weights and a `jepa/` checkout and is out of scope.
 """
 from __future__ import annotations
 
@@ -28,14 +32,20 @@ AVAILABLE = ("psnr", "ssim")
 
 
 class EvalMetrics(nn.Module):
-    def __init__(self, config=None, eval_prefix: str = "eval"):
+    def __init__(self, config=None, eval_prefix: str = "eval", fvd_detector=None):
         super().__init__()
         self.eval_prefix = eval_prefix
         names = ["psnr"]
+        self._fvd = None
         if config is not None:
             names = [m for m in config.training.eval.log_metrics]
+            if fvd_detector is None:
+                fvd_detector = getattr(config.training.eval, "fvd_detector", None)
             for m in names:
-                if m not in AVAILABLE:
+                if m == "fvd" and fvd_detector is not None:
+                    from .fvd import FVDCalculator
+                    self.__dict__["_fvd"] = FVDCalculator(detector=fvd_detector)
+                elif m not in AVAILABLE:
                     raise NotImplementedError(f"metric '{m}' is not built: FVD / JEDi need weights fetched over the network "
                                               f"(reference model/metrics/); the available metrics are {', '.join(AVAILABLE)}")
         self.names = names
@@ -83,6 +93,8 @@ class EvalMetrics(nn.Module):
                 rc = _lib.lib().ttv_ssim_accumulate(_lib.ptr_array(r), _lib.ptr_array(t), dims, len(r), dt, 1, self._ssim_acc.data_ptr(),
                                                     self._ssim_ws.data_ptr(), self._ssim_ws.numel(), stream)
                 _lib.check(rc, "ttv_ssim_accumulate")
+        if self._fvd is not None:
+            self._fvd.update_clips(recon, target, clamp_recon=True)
 
     def compute(self) -> dict:
         out = {}
@@ -93,9 +105,13 @@ class EvalMetrics(nn.Module):
             elif name == "ssim" and self._ssim_acc is not None:
                 s, n = (float(v) for v in self._ssim_acc.cpu())
                 out[f"{self.eval_prefix}/ssim"] = s / n if n > 0 else float("nan")
+            elif name == "fvd" and self._fvd is not None:
+                out[f"{self.eval_prefix}/fvd"] = self._fvd.compute()
         return out
 
     def reset(self) -> None:
         for acc in (self._acc, self._ssim_acc):
             if acc is not None:
                 acc.zero_()
+        if self._fvd is not None:
+            self._fvd.reset()

@@ -115,6 +115,26 @@ def seeded_lpips_state(seed: int = 0) -> Dict[str, torch.Tensor]:
     return out
 
 
+def seeded_i3d_state(seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Canonical I3D state dict (model/metrics/fvd.py canonical_shapes) of seeded values: He-normal convolutions, BatchNorm with no
+    scale (as TF's I3D), small means and shifts, running_var in [0.5, 1.5]; logits He-normal with a small bias."""
+    from .model.metrics.fvd import canonical_shapes
+
+    g = torch.Generator().manual_seed(seed)
+    out = OrderedDict()
+    for key, shape in canonical_shapes().items():
+        if key.endswith(".bn.weight"):
+            continue
+        if len(shape) == 5:
+            fan_in = shape[1] * shape[2] * shape[3] * shape[4]
+            out[key] = torch.randn(shape, generator=g) * math.sqrt(2.0 / fan_in)
+        elif key.endswith("running_var"):
+            out[key] = 0.5 + torch.rand(shape, generator=g)
+        else:   # bn.bias, bn.running_mean, logits.conv3d.bias
+            out[key] = 0.1 * torch.randn(shape, generator=g)
+    return out
+
+
 def synthetic_clips(shapes: Sequence[Sequence[int]], seed: int = 1234,
                     dtype: torch.dtype = torch.float32, device="cpu") -> List[torch.Tensor]:
     """List of `[3,T,H,W]` clips, U(-1,1), generated on CPU from `seed` then moved/cast."""
