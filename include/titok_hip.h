@@ -606,6 +606,67 @@ int ttv_i3d_conv3d(const float* x, int N, int T, int H, int W, int Cin, int k, i
 int ttv_i3d_maxpool3d(const float* x, int N, int T, int H, int W, int C, int kt, int kh, int kw, int st, int sh, int sw, float* y,
                       void* stream);
 
+/* ---- JEDi: clip preprocessing and the V-JEPA ViT-L/16 feature extractor (model/metrics/jedi.py JEDiMetric.get_feats) ------------
+ * V-JEPA ViT-L/16 (patch 16, tubelet 2, 16 frames at 224^2 = 1568 tokens in (t, h, w) order, width 1024, 16 heads of 64, MLP 4096,
+ * LayerNorm eps 1e-6) and the SSv2 probe's AttentivePooler (one query, one CrossAttentionBlock, LayerNorm eps 1e-5), with the
+ * precision of bf16 autocast: linear / attention operands bf16, fp32 accumulation, softmax and LayerNorm statistics, an fp32
+ * residual stream.  Every Linear's output is rounded to bf16 before its bias-free consumers (GELU, the residual add, pos_embed).
+ * Linear weights are bf16 images [out][in] (patch_w: the Conv3d weight [1024][3][2][16][16] flattened to [1024][1536]); their biases
+ * bf16 (autocast casts them too); LayerNorm weights / biases, pos_embed [1568][1024] and query_tokens [1024] fp32.
+ * pool_q: bf16 [1024], xattn.q(query_tokens) as autocast computes it (the query is a constant: formed once per weight load). */
+#define TTV_VJEPA_WIDTH 1024
+#define TTV_VJEPA_TOKENS 1568
+#define TTV_VJEPA_PATCH_K 1536
+typedef struct ttv_vjepa_layer {
+  const float* norm1_w; const float* norm1_b;
+  const void* qkv_w; const void* qkv_b;       /* [3072][1024], [3072]: q | k | v (attn.qkv) */
+  const void* proj_w; const void* proj_b;     /* [1024][1024] */
+  const float* norm2_w; const float* norm2_b;
+  const void* fc1_w; const void* fc1_b;       /* [4096][1024] */
+  const void* fc2_w; const void* fc2_b;       /* [1024][4096] */
+} ttv_vjepa_layer;
+typedef struct ttv_vjepa_weights {
+  int32_t width, heads, depth;                /* 1024, 16 (ViT-L only), blocks to run (24 for the checkpoint; fewer for tests) */
+  const void* patch_w; const void* patch_b; const float* pos_embed;
+  const ttv_vjepa_layer* layers;              /* HOST array [depth] */
+  const float* norm_w; const float* norm_b;   /* the encoder's final norm */
+  /* the pooler (classifier.pooler.*), needed for finetuned features only */
+  const float* query_tokens; const void* pool_q;
+  const float* pool_norm1_w; const float* pool_norm1_b;
+  const void* pool_kv_w; const void* pool_kv_b;       /* [2048][1024]: k | v */
+  const void* pool_proj_w; const void* pool_proj_b;
+  const float* pool_norm2_w; const float* pool_norm2_b;
+  const void* pool_fc1_w; const void* pool_fc1_b;
+  const void* pool_fc2_w; const void* pool_fc2_b;
+} ttv_vjepa_weights;
+
+/* Up to TTV_MAX_CLIPS_PER_LAUNCH clips [3][T][S][S] (host array of device pointers, `dtype`; dims = n_clips x (C, T, H, W), host;
+ * H == W, 1 <= T <= 16) -> out bf16 [n_clips * 1568][1536], the tubelet patch rows of the Conv3d in (c, kt, kh, kw) order: clamp to
+ * [-1, 1], (v + 1) / 2, bicubic to 224 x 224 (F.interpolate, align_corners=False, antialias=False), (v - mean) / std with ImageNet's
+ * mean / std, the last frame repeated up to 16 frames; fp32 arithmetic, one rounding.  16-byte aligned out. */
+int ttv_jedi_preprocess(void* const* clips, const int32_t* dims, int n_clips, int dtype, void* out, void* stream);
+/* Workspace of ttv_vjepa_features for n clips (1 .. TTV_MAX_CLIPS_PER_LAUNCH), -1 on a bad n. */
+int64_t ttv_vjepa_workspace_bytes(int n);
+/* x: ttv_jedi_preprocess's rows for n clips -> feats fp32 [n][1024]: the pooler's output (finetuned != 0) or the mean of the final
+ * norm's output over the 1568 tokens.  Nothing sums across clips: a clip's features do not depend on the others.  Workspace 256-byte
+ * aligned. */
+int ttv_vjepa_features(const ttv_vjepa_weights* w, const void* x, int n, float* feats, int finetuned, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+
+/* Single operations (tests).  ttv_vjepa_layernorm: y = LN2(LN1(x)) or LN1(x) (w2 NULL) of fp32 rows of width 1024; y32 (optional) the
+ * first norm's fp32 output (may alias x), y16 (optional) the last norm's bf16 output.  ttv_vjepa_linear: y = x w^T + bias on bf16
+ * operands with epilogue TTV_VJEPA_EPI_STORE (bf16 y), _GELU (bf16 y = gelu_erf(bf16(acc + bias))) or _RESID (fp32 y = resid[r] +
+ * bf16(acc + bias), r = row % resid_rows or row when resid_rows == 0; y may alias resid); N % 128 == 0, K % 64 == 0.
+ * ttv_vjepa_pool_attention: out bf16 [n][1024] = per head softmax(q k^T / 8) v with q bf16 [1024] and kv bf16 [n * rows][2048] (k | v). */
+#define TTV_VJEPA_EPI_STORE 0
+#define TTV_VJEPA_EPI_GELU 1
+#define TTV_VJEPA_EPI_RESID 2
+int ttv_vjepa_layernorm(const float* x, int ldx, int rows, int width, const float* w1, const float* b1, float eps1, const float* w2,
+                        const float* b2, float eps2, float* y32, int ld32, void* y16, int ld16, void* stream);
+int ttv_vjepa_linear(const void* x, int ldx, const void* w, int ldw, const void* bias, int M, int N, int K, int epilogue,
+                     const float* resid, int ldr, int resid_rows, void* y, int ldy, void* stream);
+int ttv_vjepa_pool_attention(const void* q, const void* kv, int n, int rows, void* out, void* stream);
+
 /* ---- measurement hook (bench.py roofline leg) ---------------------------------------------------------- */
 /* Kernel classes whose launches can be bracketed by HIP events on the stream they are launched on. */
 #define TTV_KC_ATTENTION 1

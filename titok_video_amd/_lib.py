@@ -93,6 +93,25 @@ class I3dWeights(C.Structure):
     _fields_ = [("w", vp * TTV_I3D_CONVS), ("scale", vp * TTV_I3D_CONVS), ("shift", vp * TTV_I3D_CONVS)]
 
 
+TTV_VJEPA_WIDTH = 1024
+TTV_VJEPA_TOKENS = 1568
+TTV_VJEPA_PATCH_K = 1536
+TTV_VJEPA_EPI_STORE, TTV_VJEPA_EPI_GELU, TTV_VJEPA_EPI_RESID = 0, 1, 2
+
+
+class VjepaLayer(C.Structure):
+    _fields_ = [("norm1_w", vp), ("norm1_b", vp), ("qkv_w", vp), ("qkv_b", vp), ("proj_w", vp), ("proj_b", vp), ("norm2_w", vp),
+                ("norm2_b", vp), ("fc1_w", vp), ("fc1_b", vp), ("fc2_w", vp), ("fc2_b", vp)]
+
+
+class VjepaWeights(C.Structure):
+    _fields_ = [("width", i32), ("heads", i32), ("depth", i32), ("patch_w", vp), ("patch_b", vp), ("pos_embed", vp),
+                ("layers", C.POINTER(VjepaLayer)), ("norm_w", vp), ("norm_b", vp), ("query_tokens", vp), ("pool_q", vp),
+                ("pool_norm1_w", vp), ("pool_norm1_b", vp), ("pool_kv_w", vp), ("pool_kv_b", vp), ("pool_proj_w", vp),
+                ("pool_proj_b", vp), ("pool_norm2_w", vp), ("pool_norm2_b", vp), ("pool_fc1_w", vp), ("pool_fc1_b", vp),
+                ("pool_fc2_w", vp), ("pool_fc2_b", vp)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -183,6 +202,12 @@ SYMBOLS = {
     "ttv_i3d_features": (C.c_int, [C.POINTER(I3dWeights), vp, C.c_int, vp, vp, C.c_int64, vp]),
     "ttv_i3d_conv3d": (C.c_int, [vp] + [C.c_int] * 7 + [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]),
     "ttv_i3d_maxpool3d": (C.c_int, [vp] + [C.c_int] * 11 + [vp, vp]),
+    "ttv_jedi_preprocess": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
+    "ttv_vjepa_workspace_bytes": (C.c_int64, [C.c_int]),
+    "ttv_vjepa_features": (C.c_int, [C.POINTER(VjepaWeights), vp, C.c_int, vp, C.c_int, vp, C.c_int64, vp]),
+    "ttv_vjepa_layernorm": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_float, vp, vp, C.c_float, vp, C.c_int, vp, C.c_int, vp]),
+    "ttv_vjepa_linear": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp]),
+    "ttv_vjepa_pool_attention": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
     "ttv_debug_set": (C.c_int, [C.c_int]),
     "ttv_debug_stamps": (C.c_int, [vp]),
     "ttv_prof_begin": (C.c_int, [C.c_int, C.c_int]),

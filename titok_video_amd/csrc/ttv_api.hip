@@ -789,6 +789,31 @@ int ttv_i3d_maxpool3d(const float* x, int N, int T, int H, int W, int C, int kt,
   return ttvk_i3d_maxpool3d(x, N, T, H, W, C, kt, kh, kw, st, sh, sw, y, (hipStream_t)stream);
 }
 
+int ttv_jedi_preprocess(void* const* clips, const int32_t* dims, int n_clips, int dtype, void* out, void* stream) {
+  return ttvk_jedi_preprocess(clips, dims, n_clips, dtype, out, (hipStream_t)stream);
+}
+
+int64_t ttv_vjepa_workspace_bytes(int n) { return ttvk_vjepa_workspace_bytes(n); }
+
+int ttv_vjepa_features(const ttv_vjepa_weights* w, const void* x, int n, float* feats, int finetuned, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+  return ttvk_vjepa_features(w, x, n, feats, finetuned, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ttv_vjepa_layernorm(const float* x, int ldx, int rows, int width, const float* w1, const float* b1, float eps1, const float* w2,
+                        const float* b2, float eps2, float* y32, int ld32, void* y16, int ld16, void* stream) {
+  return ttvk_vjepa_layernorm(x, ldx, rows, width, w1, b1, eps1, w2, b2, eps2, y32, ld32, y16, ld16, (hipStream_t)stream);
+}
+
+int ttv_vjepa_linear(const void* x, int ldx, const void* w, int ldw, const void* bias, int M, int N, int K, int epilogue,
+                     const float* resid, int ldr, int resid_rows, void* y, int ldy, void* stream) {
+  return ttvk_vjepa_linear(x, ldx, w, ldw, bias, M, N, K, epilogue, resid, ldr, resid_rows, y, ldy, (hipStream_t)stream);
+}
+
+int ttv_vjepa_pool_attention(const void* q, const void* kv, int n, int rows, void* out, void* stream) {
+  return ttvk_vjepa_pool_attention(q, kv, n, rows, out, (hipStream_t)stream);
+}
+
 int ttv_debug_set(int flags) {
   g_ttv_debug = flags;
   return TTV_OK;

@@ -53,6 +53,7 @@ struct GemmDev {
   uint8_t* yq; uint8_t* yq_mx; int ld_yq_mx, yq_nkp;   // EPI_GEGLU of the MX kernel: h leaves as block-scaled e4m3 [M, N] + scales instead of bf16
   int clip0, pt_shift, ph_shift;   // log2(patch_t), log2(patch_h); patch_w == 8
   long long* stamps;               // diagnostic builds only (-DQKV_STAMPS): g_ttv_stamps
+  int resid_rows;                  // EPI_BIAS_RESID_F32R: residual row = token % resid_rows (0: token)
 };
 
 // per-token part of a patch destination (EPI_STORE_PATCH), computed once per token tile
@@ -123,7 +124,7 @@ __device__ __forceinline__ void epilogue_tile(const GemmDev& p, const int (&tok)
     }
   }
 
-  if (EPI == EPI_STORE || EPI == EPI_STORE_PATCH) {
+  if (EPI == EPI_STORE || EPI == EPI_STORE_PATCH || EPI == EPI_BIAS_PLAIN) {
     if (p.bias) {
       f32x4 b[NI];
 #pragma unroll
@@ -221,6 +222,32 @@ __device__ __forceinline__ void epilogue_tile(const GemmDev& p, const int (&tok)
 #pragma unroll
           for (int e = 0; e < 4; ++e) acc[i][j][e] = gelu_erf(acc2[i][j][e]) * acc[i][j][e];
         }
+  } else if (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESID_F32R) {
+    f32x4 b[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) b[i] = Vec4<T>::load((const T*)p.bias + fc[i]);
+    if (EPI == EPI_BIAS_RESID_F32R) {
+      f32x4 r[NI][NJ];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int rr = p.resid_rows ? tc[j] % p.resid_rows : tc[j];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) r[i][j] = *reinterpret_cast<const f32x4*>((const float*)p.resid + (size_t)rr * p.ldr + fc[i]);
+      }
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[i][j][e] = r[i][j][e] + round_to<T>(acc[i][j][e] + b[i][e]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[i][j][e] = gelu_erf(round_to<T>(acc[i][j][e] + b[i][e]));
+    }
   } else {  // EPI_RESID_T / EPI_RESID_F32
     f32x4 r[NI][NJ];
 #pragma unroll
@@ -234,7 +261,7 @@ __device__ __forceinline__ void epilogue_tile(const GemmDev& p, const int (&tok)
   }
 
   // ---- stores ----
-  if (EPI == EPI_RESID_F32) {
+  if (EPI == EPI_RESID_F32 || EPI == EPI_BIAS_RESID_F32R) {
 #pragma unroll
     for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -2231,6 +2258,7 @@ int ttvk_gemm(GemmEpilogue epi, const GemmArgs& a, hipStream_t s) {
   d.x_scale = nullptr; d.w_scale = nullptr;
   d.row_scale = a.row_scale;
   d.stamps = g_ttv_stamps;
+  d.resid_rows = a.resid_rows;
   TTV_CHECK_ARG(!a.row_scale || ((a.dtype == TTV_BF16 || a.split3) && (epi == EPI_STORE || epi == EPI_QKV_ROPE || epi == EPI_GEGLU)),
                 "gemm: row_scale is a STORE / QKV_ROPE / GEGLU option of the bf16 and the split-bf16 kernels");
   TTV_CHECK_ARG(!a.x_rows || (a.dtype == TTV_BF16 && a.K == 256 && a.N % 8 == 0 && epi != EPI_RESID_NORM), "gemm: x_rows needs the bf16 K=256 kernel");
@@ -2273,6 +2301,32 @@ int ttvk_gemm(GemmEpilogue epi, const GemmArgs& a, hipStream_t s) {
     case EPI_RESID_F32:
       TTV_CHECK_ARG(a.resid && a.ldr % 4 == 0, "gemm: residual missing");
       return launch<EPI_RESID_F32>(d, a.dtype, pn, s);
+    case EPI_BIAS_PLAIN:
+    case EPI_BIAS_GELU:
+    case EPI_BIAS_RESID_F32R: {
+      // V-JEPA linears (ttv_vjepa.hip): bf16, whole 64-wide k tiles.  The kernel is chosen by N and K alone (256 x 256 tiles when N % 256
+      // == 0, else the 128 x 128 LDS-DMA kernel), never by M, so that a row's value does not depend on what else is in the launch
+      TTV_CHECK_ARG(a.dtype == TTV_BF16 && a.K % BK == 0 && a.bias && (uintptr_t)a.bias % 8 == 0, "gemm: V-JEPA epilogues need bf16, K %% 64 == 0 and a bias");
+      TTV_CHECK_ARG(!a.add_scalar && !a.row_scale, "gemm: V-JEPA epilogues take no scalar / row scale");
+      TTV_CHECK_ARG(epi != EPI_BIAS_RESID_F32R || (a.resid && a.ldr % 4 == 0 && (uintptr_t)a.resid % 16 == 0 && a.resid_rows >= 0),
+                    "gemm: fp32 residual missing or unaligned");
+      TTV_CHECK_ARG((uint64_t)a.M * (uint64_t)a.ldx * 2u < (1ull << 32) && (uint64_t)a.N * (uint64_t)a.ldw * 2u < (1ull << 32),
+                    "gemm: operand too large for 32-bit byte offsets");
+      if (d.N % T256_F == 0 && d.K >= 2 * BK) {
+        const int nf = d.N / T256_F, nt = ttv_cdiv(d.M, T256_T);
+        if (epi == EPI_BIAS_PLAIN) hipLaunchKernelGGL((k_gemm_bf16_t256<EPI_BIAS_PLAIN>), dim3(nf * nt), dim3(512), 0, s, d, nf);
+        else if (epi == EPI_BIAS_GELU) hipLaunchKernelGGL((k_gemm_bf16_t256<EPI_BIAS_GELU>), dim3(nf * nt), dim3(512), 0, s, d, nf);
+        else hipLaunchKernelGGL((k_gemm_bf16_t256<EPI_BIAS_RESID_F32R>), dim3(nf * nt), dim3(512), 0, s, d, nf);
+        TTV_CHECK_LAUNCH("gemm_vjepa_t256");
+        return TTV_OK;
+      }
+      const int nf = ttv_cdiv(d.N, TF), nt = ttv_cdiv(d.M, TT);
+      if (epi == EPI_BIAS_PLAIN) hipLaunchKernelGGL((k_gemm_bf16_dma<EPI_BIAS_PLAIN, 4>), dim3(nf * nt), dim3(256), 0, s, d, nf);
+      else if (epi == EPI_BIAS_GELU) hipLaunchKernelGGL((k_gemm_bf16_dma<EPI_BIAS_GELU, 4>), dim3(nf * nt), dim3(256), 0, s, d, nf);
+      else hipLaunchKernelGGL((k_gemm_bf16_dma<EPI_BIAS_RESID_F32R, 4>), dim3(nf * nt), dim3(256), 0, s, d, nf);
+      TTV_CHECK_LAUNCH("gemm_vjepa");
+      return TTV_OK;
+    }
     case EPI_RESID_NORM: {
       TTV_CHECK_ARG(ttvk_gemm_supports_resid_norm(a.dtype, a.N, a.K), "gemm: fused residual+norm needs bf16 and N == 256");
       TTV_CHECK_ARG(a.resid && a.norm_gain && a.ldr % 4 == 0 && a.ldw >= 256, "gemm: residual / gain missing");

@@ -49,6 +49,11 @@ enum GemmEpilogue {
   EPI_RESID_NORM,  // y = RMSNorm(alpha*resid + acc) * norm_gain, stored in dtype (whole KEEL step, transformer.py:141-145);
                    // needs a kernel whose waves own full rows: bf16, K == 256, N == 256 (ttvk_gemm_supports_resid_norm)
   EPI_STORE_PATCH, // y = acc + bias written straight into the clips as patches (blocks.py:173-176 + utils.py:37-51; bf16, K = 256)
+  // V-JEPA linears under bf16 autocast (model/metrics/jedi.py; ttv_vjepa.hip).  bias is dtype; the Linear's output is rounded to dtype
+  // before anything else is applied to it, as autocast's bf16 F.linear output is
+  EPI_BIAS_PLAIN,  // y = acc + bias, stored in dtype (EPI_STORE's arithmetic on the fixed kernel below)   (attn.qkv, pooler kv)
+  EPI_BIAS_GELU,   // y = gelu_erf(round(acc + bias)), stored in dtype                                         (mlp.fc1 + GELU)
+  EPI_BIAS_RESID_F32R,  // y = resid[r] + round(acc + bias), fp32 resid / y, r = row % resid_rows (0: row); y may alias resid
 };
 
 struct GemmArgs {
@@ -90,6 +95,7 @@ struct GemmArgs {
   const int* patch_rows;           // device [M]
   const int* row_seq;              // device [L]
   int patch_t, patch_h, patch_w;   // powers of two; patch_w * sizeof(bf16) == 16
+  int resid_rows;                  // EPI_BIAS_RESID_F32R: the residual row of GEMM row t is t % resid_rows (0: t)
 };
 struct ClipPtrs { void* p[TTV_MAX_CLIPS_PER_LAUNCH]; };
 int ttvk_gemm(GemmEpilogue epi, const GemmArgs& a, hipStream_t s);
@@ -216,3 +222,14 @@ int ttvk_i3d_conv3d(const float* x, int N, int T, int H, int W, int Cin, int k, 
                     const float* shift, int Cout, int relu, float* y, int ldc, int c_off, hipStream_t s);
 int ttvk_i3d_maxpool3d(const float* x, int N, int T, int H, int W, int C, int kt, int kh, int kw, int st, int sh, int sw, float* y,
                        hipStream_t s);
+
+// ---- ttv_vjepa.hip ----
+int ttvk_jedi_preprocess(void* const* clips, const int32_t* dims, int n_clips, int dtype, void* out, hipStream_t s);
+int64_t ttvk_vjepa_workspace_bytes(int n);
+int ttvk_vjepa_features(const ttv_vjepa_weights* w, const void* x, int n, float* feats, int finetuned, void* ws, int64_t ws_bytes,
+                        hipStream_t s);
+int ttvk_vjepa_layernorm(const float* x, int ldx, int rows, int width, const float* w1, const float* b1, float eps1, const float* w2,
+                         const float* b2, float eps2, float* y32, int ld32, void* y16, int ld16, hipStream_t s);
+int ttvk_vjepa_linear(const void* x, int ldx, const void* w, int ldw, const void* bias, int M, int N, int K, int epilogue,
+                      const float* resid, int ldr, int resid_rows, void* y, int ldy, hipStream_t s);
+int ttvk_vjepa_pool_attention(const void* q, const void* kv, int n, int rows, void* out, hipStream_t s);

@@ -15,7 +15,12 @@ them `x.clamp(-1, 1)` per clip, CTHW -> TCHW (eval_metrics.py:19-21, 32-37).
   `EvalMetrics(config, fvd_detector=path)` or the optional config key `training.eval.fvd_detector`; without one 'fvd' raises as
   before.  The reconstruction is clamped, the target is not (eval_metrics.py:33), each clip goes in as a batch of one; see
   fvd.py for the preprocessing and the detector.  The detector's weights are not part of state_dict().
-No host sync until compute().  JEDi needs V-JEPA weights and a `jepa/` checkout and is out of scope.
+- JEDi (the 'jedi' entry, reference jedi.JEDiMetric): needs the V-JEPA encoder's and the SSv2 probe's weights from local files,
+  given as `EvalMetrics(config, jedi_weights=..., jedi_probe=...)` or the optional config keys `training.eval.jedi_weights` /
+  `training.eval.jedi_probe`; without them 'jedi' raises as before.  `training.eval.jedi_jepa_model` is honoured (vit_large only).
+  Both clips are clamped (get_feats clamps again), each goes in as a batch of one; see jedi.py.  The weights are not part of
+  state_dict().
+No host sync until compute().
 """
 from __future__ import annotations
 
@@ -32,19 +37,28 @@ AVAILABLE = ("psnr", "ssim")
 
 
 class EvalMetrics(nn.Module):
-    def __init__(self, config=None, eval_prefix: str = "eval", fvd_detector=None):
+    def __init__(self, config=None, eval_prefix: str = "eval", fvd_detector=None, jedi_weights=None, jedi_probe=None):
         super().__init__()
         self.eval_prefix = eval_prefix
         names = ["psnr"]
         self._fvd = None
+        self._jedi = None
         if config is not None:
             names = [m for m in config.training.eval.log_metrics]
             if fvd_detector is None:
                 fvd_detector = getattr(config.training.eval, "fvd_detector", None)
+            if jedi_weights is None:
+                jedi_weights = getattr(config.training.eval, "jedi_weights", None)
+            if jedi_probe is None:
+                jedi_probe = getattr(config.training.eval, "jedi_probe", None)
             for m in names:
                 if m == "fvd" and fvd_detector is not None:
                     from .fvd import FVDCalculator
                     self.__dict__["_fvd"] = FVDCalculator(detector=fvd_detector)
+                elif m == "jedi" and jedi_weights is not None:
+                    from .jedi import JEDiMetric
+                    model_name = getattr(config.training.eval, "jedi_jepa_model", "vit_large")
+                    self.__dict__["_jedi"] = JEDiMetric(model_name=model_name, weights=jedi_weights, probe=jedi_probe)
                 elif m not in AVAILABLE:
                     raise NotImplementedError(f"metric '{m}' is not built: FVD / JEDi need weights fetched over the network "
                                               f"(reference model/metrics/); the available metrics are {', '.join(AVAILABLE)}")
@@ -95,6 +109,8 @@ class EvalMetrics(nn.Module):
                 _lib.check(rc, "ttv_ssim_accumulate")
         if self._fvd is not None:
             self._fvd.update_clips(recon, target, clamp_recon=True)
+        if self._jedi is not None:
+            self._jedi.update_clips(recon, target)
 
     def compute(self) -> dict:
         out = {}
@@ -107,6 +123,8 @@ class EvalMetrics(nn.Module):
                 out[f"{self.eval_prefix}/ssim"] = s / n if n > 0 else float("nan")
             elif name == "fvd" and self._fvd is not None:
                 out[f"{self.eval_prefix}/fvd"] = self._fvd.compute()
+            elif name == "jedi" and self._jedi is not None:
+                out[f"{self.eval_prefix}/jedi"] = self._jedi.compute()
         return out
 
     def reset(self) -> None:
@@ -115,3 +133,5 @@ class EvalMetrics(nn.Module):
                 acc.zero_()
         if self._fvd is not None:
             self._fvd.reset()
+        if self._jedi is not None:
+            self._jedi.reset()

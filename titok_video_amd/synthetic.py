@@ -135,6 +135,37 @@ def seeded_i3d_state(seed: int = 0) -> Dict[str, torch.Tensor]:
     return out
 
 
+def _vjepa_values(shapes, g: torch.Generator) -> Dict[str, torch.Tensor]:
+    out = OrderedDict()
+    for key, shape in shapes.items():
+        if key == "pos_embed":      # a sincos table of token index, |values| <= 1, like upstream's uniform-power table
+            pos = torch.arange(shape[1], dtype=torch.float64)[:, None]
+            freq = 1.0 / 10000.0 ** (torch.arange(shape[2] // 2, dtype=torch.float64) / (shape[2] // 2))
+            out[key] = torch.cat([torch.sin(pos * freq), torch.cos(pos * freq)], 1).float()[None]
+        elif "norm" in key and key.endswith(".weight"):
+            out[key] = 1.0 + 0.05 * torch.randn(shape, generator=g)
+        elif key.endswith(".bias"):
+            out[key] = 0.02 * torch.randn(shape, generator=g)
+        else:                       # linears, the patch Conv3d, query_tokens: trunc-normal std 0.02 (upstream's init)
+            out[key] = torch.nn.init.trunc_normal_(torch.empty(shape), std=0.02, a=-0.04, b=0.04, generator=g)
+    return out
+
+
+def seeded_vjepa_state(depth: int = 24, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Canonical V-JEPA ViT-L/16 encoder state dict (model/metrics/jedi.py encoder_shapes) of `depth` blocks with seeded values:
+    trunc-normal std 0.02 linears, LayerNorm weights 1 + N(0, 0.05^2), biases N(0, 0.02^2), a sincos pos_embed."""
+    from .model.metrics.jedi import encoder_shapes
+
+    return _vjepa_values(encoder_shapes(depth), torch.Generator().manual_seed(seed))
+
+
+def seeded_probe_state(seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Canonical pooler state dict of the SSv2 probe (model/metrics/jedi.py probe_shapes), seeded as seeded_vjepa_state."""
+    from .model.metrics.jedi import probe_shapes
+
+    return _vjepa_values(probe_shapes(), torch.Generator().manual_seed(seed))
+
+
 def synthetic_clips(shapes: Sequence[Sequence[int]], seed: int = 1234,
                     dtype: torch.dtype = torch.float32, device="cpu") -> List[torch.Tensor]:
     """List of `[3,T,H,W]` clips, U(-1,1), generated on CPU from `seed` then moved/cast."""
