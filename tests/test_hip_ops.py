@@ -5,6 +5,15 @@ All tests need the MI355X (`-m gpu`).  Tolerances are written next to each compa
   * fp32 kernels: differences come from summation order / libm only;
   * bf16 kernels: inputs are bf16-rounded once for both sides; the kernel accumulates in fp32 and rounds its
     output to bf16 once, so the bound is a few bf16 ulps (2^-8 relative) of the output magnitude.
+
+`assert_close` asserts that GLOBALLY: one relative Frobenius error over the whole output and a max-abs bound that is a fraction of
+the global maximum (among 36 864 rows one wrong 64-row block of one head moves the first by 0.2 %: tests/test_blockwise_cpu.py).
+Asserted per 16-row x 64-column tile as well, with a bound from a reference-only rounding model (`assert_tiles` below), in
+test_mlp_fused, test_layer_tail_fused and test_linear_256x256_tiles; asserted per (sequence, head, 64-row block), per tile and per
+planted row at the benchmark's shapes in tests/test_hip_forward_shapes.py (every route of ttv_attention / ttv_attention64 against a
+float64 reference, to_qkv + rotary, the fused MLP and the fused layer tail at width 256).  Every other test of this file - the
+norms, rotary, the general-K linears, GEGLU, the residual linears, and the attention tests below, whose reference
+(oracle.attention_varlen) computes in float32 - still asserts it globally only.
 """
 import ctypes as C
 import os
@@ -49,6 +58,23 @@ def assert_close(out, ref, dt, scale=1.0):
     assert torch.isfinite(out).all()
     assert rel_err(out, ref) < r * scale, rel_err(out, ref)
     assert float((out - ref).abs().max()) <= m * scale * float(ref.abs().max() + 1e-30)
+
+
+def assert_tiles(out, ref, exact=None, f32_terms=0):
+    """Beside assert_close: the relative Frobenius error of every 16-row x 64-column tile (one MFMA row group of one wave; tests/blockwise.py).
+    `ref` carries the roundings the kernel is known to make inside; the bound is 2 x what a reference-only rounding model - `ref` stored
+    once to bf16 - costs in its worst tile against `exact`, the same definition without any rounding (`ref` itself where there is
+    none inside).  f32_terms = K for an output stored in fp32: no store to model, the bound is 2 x sqrt(K) x 2^-24 (K fp32 additions)."""
+    from tests.blockwise import bf16_store, check_row_tiles, global_error, row_tile_errors
+    ref = ref.double().cpu()
+    exact = ref if exact is None else exact.double().cpu()
+    if f32_terms:
+        tile = glob = 2.0 * f32_terms ** 0.5 * 2.0 ** -24
+    else:
+        model = bf16_store(ref)
+        tile, glob = 2.0 * float(row_tile_errors(model, exact).max()), 2.0 * global_error(model, exact)
+    worst, g = check_row_tiles(out.cpu(), ref, 16, 64, tile, glob, "tiles")
+    print(f"MEASURED tiles {tuple(ref.shape)}: worst 16 x 64 tile {worst:.2e} (bound {tile:.2e}), global {g:.2e} (bound {glob:.2e})")
 
 
 # ---------------------------------------------------------------------------------------------- FSQ
@@ -253,6 +279,7 @@ def test_linear_256x256_tiles(case, M):
         finally:
             L().ttv_debug_set(0)
         assert_close(y.float(), ref, "bf16")
+        assert_tiles(y.float(), ref, f32_terms=K if case == "resid_f32" else 0)
         outs.append(y.clone())
     assert torch.equal(outs[0], outs[1])     # same products in the same k order, same epilogue: bit-equal to the 128 x 128 kernel
 
@@ -444,10 +471,13 @@ def test_mlp_fused(M, keel, I, deal9):
     xn = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + 1e-5)
     hh = xn @ w12f.double().T
     a, gate = hh.chunk(2, -1)
-    h = (torch.nn.functional.gelu(gate) * a).to(torch.bfloat16).double()      # the kernel rounds h to bf16 (MFMA operand)
+    h0 = torch.nn.functional.gelu(gate) * a
+    h = h0.to(torch.bfloat16).double()                                        # the kernel rounds h to bf16 (MFMA operand)
     y = alpha * xf + h @ w3.double().T
     ref = y * torch.rsqrt(y.pow(2).mean(-1, keepdim=True) + 1e-5) * pg.double() if keel else y
     assert_close(xd.float(), ref, "bf16", scale=1.5)
+    y0 = alpha * xf + h0 @ w3.double().T                                      # the same without that rounding: the rounding model's baseline
+    assert_tiles(xd.float(), ref, exact=y0 * torch.rsqrt(y0.pow(2).mean(-1, keepdim=True) + 1e-5) * pg.double() if keel else y0)
     assert L().ttv_mlp_fused(xd.data_ptr(), d, pack.data_ptr(), I, xd.data_ptr(), d, None, 1.0, 1e-5, M, 512,
                              _lib.TTV_BF16, S()) == 3
 
@@ -493,15 +523,18 @@ def test_layer_tail_fused(M, keel, back):
         torch.cuda.synchronize()
     finally:
         L().ttv_debug_set(0)
-    y1 = alpha * x.double() + ao.double() @ wo.double().T
-    x1 = y1 * torch.rsqrt(y1.pow(2).mean(-1, keepdim=True) + 1e-5) * ag.double() if keel else y1
-    x1 = x1.to(torch.bfloat16).double()                                      # the kernel rounds x1 to bf16 (residual stream dtype)
-    xn = x1 * torch.rsqrt(x1.pow(2).mean(-1, keepdim=True) + 1e-5)
-    a, gate = (xn @ w12f.double().T).chunk(2, -1)
-    h = (torch.nn.functional.gelu(gate) * a).to(torch.bfloat16).double()
-    y = alpha * x1 + h @ w3.double().T
-    ref = y * torch.rsqrt(y.pow(2).mean(-1, keepdim=True) + 1e-5) * pg.double() if keel else y
+    def definition(rnd):
+        y1 = alpha * x.double() + ao.double() @ wo.double().T
+        x1 = y1 * torch.rsqrt(y1.pow(2).mean(-1, keepdim=True) + 1e-5) * ag.double() if keel else y1
+        x1 = rnd(x1)                                                         # the kernel rounds x1 to bf16 (residual stream dtype)
+        xn = x1 * torch.rsqrt(x1.pow(2).mean(-1, keepdim=True) + 1e-5)
+        a, gate = (xn @ w12f.double().T).chunk(2, -1)
+        h = rnd(torch.nn.functional.gelu(gate) * a)
+        y = alpha * x1 + h @ w3.double().T
+        return y * torch.rsqrt(y.pow(2).mean(-1, keepdim=True) + 1e-5) * pg.double() if keel else y
+    ref = definition(lambda t: t.to(torch.bfloat16).double())
     assert_close(xd.float(), ref, "bf16", scale=2.0)
+    assert_tiles(xd.float(), ref, exact=definition(lambda t: t))
     if back:
         x2 = xd.double().cpu()                                               # the projection reads the stored (bf16) rows
         q = (x2 * torch.rsqrt(x2.pow(2).mean(-1, keepdim=True) + 1e-5)) @ wqf.double().T
@@ -512,6 +545,7 @@ def test_layer_tail_fused(M, keel, back):
             return torch.stack([th[..., 0] * c - th[..., 1] * sn, th[..., 0] * sn + th[..., 1] * c], -1).reshape(M, -1)
         qref = torch.cat([rot(q[:, :d]), q[:, d:2 * d], rot(q[:, 2 * d:2 * d + gq]), q[:, 2 * d + gq:]], 1)
         assert_close(qkv.float(), qref, "bf16", scale=2.0)
+        assert_tiles(qkv.float(), qref)
 
 
 # ---------------------------------------------------------------------------------------------- attention
