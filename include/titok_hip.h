@@ -499,6 +499,22 @@ int ttv_l1_loss(void* const* recon, void* const* target, void* const* grad, cons
  * value u8 / 127.5 - 1 evaluated in fp32 and rounded once.  T*H*W % 4 == 0 (patch-aligned clips always are). */
 int ttv_clip_from_u8(const void* frames_thwc, int T, int H, int W, void* clip_cthw, int dtype, void* stream);
 
+/* The loader's front on the device (dataset/video_dataset.py:96-119: v2.RandomResizedCrop / v2.Resize + CenterCrop with BICUBIC and
+ * antialias=True, RandomHorizontalFlip, then the tail above), up to TTV_MAX_CLIPS_PER_LAUNCH clips in ONE launch.  Host arrays:
+ * frames_thwc[i] uint8 [T][Hs][Ws][3] (device, contiguous, any alignment; the whole array is the resampling domain - a crop is made
+ * by handing over the crop box only), clips_cthw[i] [3][T][Ho][Wo] in `dtype` (device, 16-byte aligned), geom = n_clips x
+ * (T, Hs, Ws, Hr, Wr, oy, ox, Ho, Wo, flip): the frame is resampled to the virtual size Hr x Wr, of which the window of Ho x Wo at
+ * (oy, ox) is produced (oy + Ho <= Hr, ox + Wo <= Wr), mirrored along W when flip = 1.
+ * Value, per channel and frame (aten's _upsample_bicubic2d_aa, the float path of torchvision's resize): along an axis n_in -> n_out,
+ * scale = n_in / n_out, support = 2 scale if scale >= 1 else 2, inv = 1 / scale if scale >= 1 else 1; output i has the centre
+ * c = scale (i + 0.5) and the taps lo = max(0, int(c - support + 0.5)) <= j < hi = min(int(c + support + 0.5), n_in) with weights
+ * cubic((j - c + 0.5) inv) (Keys, a = -0.5) divided by their sum.  Width pass, then height pass, fp32, no rounding in between;
+ * level = clamp(round_half_even(v), 0, 255); stored value level / 127.5 - 1 as ttv_clip_from_u8 forms it, rounded once to `dtype`.
+ * (aten's native uint8 kernel, which torchvision picks for uint8 input on an AVX2 host, rounds and clamps between the passes and
+ * uses fixed-point weights; this is the float path.)  A scale above 8 on an axis, a window outside the resized frame, a
+ * misaligned destination, more clips than the limit or a bad dtype return TTV_ERR_INVALID and launch nothing. */
+int ttv_clip_resample_u8(void* const* frames_thwc, void* const* clips_cthw, const int32_t* geom, int n_clips, int dtype, void* stream);
+
 /* PSNR statistic of the evaluation loop (model/metrics/eval_metrics.py:19,32-36: x.clamp(-1, 1), torchmetrics
  * PeakSignalNoiseRatio(data_range=2) = running sum of squared errors + element count): acc[0] += sum (clamp(recon) - target)^2,
  * acc[1] += number of elements, both double, device memory, over the clips of the call (host arrays of device pointers, `dtype`).

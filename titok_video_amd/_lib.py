@@ -186,6 +186,7 @@ SYMBOLS = {
     "ttv_rope_table_build": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp]),
     "ttv_l1_loss": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp]),
     "ttv_clip_from_u8": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
+    "ttv_clip_resample_u8": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
     "ttv_sq_err_accumulate": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "ttv_ssim_workspace_bytes": (C.c_int64, [vp, C.c_int]),
     "ttv_ssim_accumulate": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int64, vp]),

@@ -720,6 +720,10 @@ int ttv_clip_from_u8(const void* frames_thwc, int T, int H, int W, void* clip_ct
   return ttvk_clip_from_u8(frames_thwc, (long long)T * H * W, clip_cthw, dtype, (hipStream_t)stream);
 }
 
+int ttv_clip_resample_u8(void* const* frames_thwc, void* const* clips_cthw, const int32_t* geom, int n_clips, int dtype, void* stream) {
+  return ttvk_clip_resample_u8(frames_thwc, clips_cthw, geom, n_clips, dtype, (hipStream_t)stream);
+}
+
 int ttv_sq_err_accumulate(void* const* recon, void* const* target, const int32_t* sizes, int n_clips, int dtype, int clamp, double* acc,
                           void* stream) {
   for (int c0 = 0; c0 < n_clips; c0 += TTV_MAX_CLIPS_PER_LAUNCH) {

@@ -37,6 +37,10 @@ int ttvk_quant_mx_fp8(const void* in, int in_dtype, int ld_in, void* out, int ld
 
 int ttvk_clip_from_u8(const void* frames, long long n_pix, void* clip, int dtype, hipStream_t s);
 
+// ---- ttv_resample.hip ----
+// geom: n_clips x (T, Hs, Ws, Hr, Wr, oy, ox, Ho, Wo, flip), host
+int ttvk_clip_resample_u8(void* const* src, void* const* dst, const int32_t* geom, int n_clips, int dtype, hipStream_t s);
+
 // ---- ttv_gemm.hip ----
 // out^T-oriented GEMM: the MFMA "row" side is the output feature (W rows), the "column" side the token (X rows),
 // so every lane owns 4 consecutive output features of one token and the epilogues below are lane-local.

@@ -8,13 +8,19 @@ configs/tiny.yaml:65-66); the batch is then emitted as
     {'video': [C,T,H,W tensors], 'fps': [...], '__key__': [...], 'token_counts': int32 tensor [B]}.
 This module produces the same dicts from seeded synthetic clips, with rank-disjoint sharding for data parallelism
 (the reference has no node split - SURVEY.md R4).
+
+It also restates the front of the reference's loader, `_video_process` (video_dataset.py:38-127): `ClipSampling` holds the keys of
+`training.sampling` it reads, `sample_chunks` makes its draws (chunk length, frame rate, output grid, crop box, flip) and returns the
+geometry that `ttv_clip_resample_u8` executes on the device, and `resample_clip` is that call for one clip.
 """
 from __future__ import annotations
 
 import math
 import random
+from dataclasses import dataclass
 from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 
@@ -47,6 +53,153 @@ class SyntheticClipStream:
             video = torch.rand((3, *shape), generator=g, dtype=torch.float32) * 2.0 - 1.0     # [-1, 1] (video_dataset.py:118-119)
             yield {"video": video.to(device=self.device, dtype=self.dtype), "fps": rng.uniform(*self.fps_range), "__key__": f"synthetic_{i:08d}"}
             i += self.world_size
+
+
+@dataclass(frozen=True)
+class ClipSampling:
+    """The keys of `training.sampling` that `_video_process` reads, plus the tokenizer's `patch_size` (all grids are (T, H, W)).
+    `min_scale` is the least share of the frame's area a training crop sees; upstream only configs/tiny_csv.yaml sets it (0.25)
+    although both dataset files read it, so `from_config` falls back to that value when the key is absent."""
+    min_grid: Tuple[int, int, int] = (8, 128, 128)
+    max_grid: Tuple[int, int, int] = (16, 168, 168)
+    fps_range: Tuple[int, int] = (3, 5)
+    max_aspect_ratio: float = 2.0
+    min_scale: float = 0.25
+    patch_size: Tuple[int, int, int] = (4, 8, 8)
+
+    def __post_init__(self):
+        for name in ("min_grid", "max_grid", "fps_range", "patch_size"):
+            object.__setattr__(self, name, tuple(int(v) for v in getattr(self, name)))
+        if not (all(d % p == 0 for d, p in zip(self.min_grid, self.patch_size)) and all(d % p == 0 for d, p in zip(self.max_grid, self.patch_size))):
+            raise ValueError("dimensions in min_grid and max_grid must be evenly divisible by their respective patch size")
+        if not 0.0 < self.min_scale <= 1.0:
+            raise ValueError(f"min_scale = {self.min_scale} must lie in (0, 1]")
+
+    @classmethod
+    def from_config(cls, config) -> "ClipSampling":
+        cs = config.training.sampling
+        return cls(min_grid=tuple(cs.min_grid), max_grid=tuple(cs.max_grid), fps_range=tuple(cs.fps_range),
+                   max_aspect_ratio=float(cs.max_aspect_ratio), min_scale=float(getattr(cs, "min_scale", 0.25)),
+                   patch_size=tuple(config.tokenizer.model.patch_size))
+
+
+def resized_hw(h: int, w: int, size: int) -> Tuple[int, int]:
+    """torchvision Resize(size=int): the short edge becomes `size`, the long edge int(size * long / short) (the rule
+    model/losses/loss_module.py `_resized_hw` also restates)."""
+    if w <= h:
+        return int(size * h / w), size
+    return size, int(size * w / h)
+
+
+def random_resized_crop_box(rng: random.Random, height: int, width: int, scale: Tuple[float, float], ratio: float) -> Tuple[int, int, int, int]:
+    """(top, left, h, w) as torchvision's RandomResizedCrop.get_params draws it at a FIXED aspect ratio (ratio = (r, r), what the
+    reference passes): ten attempts of an area share uniform in `scale`, w = round(sqrt(area * r)), h = round(sqrt(area / r)), accepted
+    when the box fits, with uniform integer offsets; then the central fallback (the largest box of that ratio)."""
+    area = height * width
+    for _ in range(10):
+        target = area * rng.uniform(scale[0], scale[1])
+        w = int(round(math.sqrt(target * ratio)))
+        h = int(round(math.sqrt(target / ratio)))
+        if 0 < w <= width and 0 < h <= height:
+            return rng.randrange(0, height - h + 1), rng.randrange(0, width - w + 1), h, w
+    in_ratio = float(width) / float(height)
+    if in_ratio < ratio:
+        w, h = width, int(round(width / ratio))
+    elif in_ratio > ratio:
+        h, w = height, int(round(height * ratio))
+    else:
+        w, h = width, height
+    return (height - h) // 2, (width - w) // 2, h, w
+
+
+def sample_chunks(rng: random.Random, in_grid: Sequence[int], in_fps: int, sampling: ClipSampling, eval: bool = False) -> Iterator[Dict]:
+    """The chunks `_video_process` cuts out of one decoded video of `in_grid` = (frames, H, W) at `in_fps` (video_dataset.py:66-125).
+
+    Same accept test (every dimension >= min_grid, in_fps >= min_fps), same `while` loop, the same four `randrange` draws in the same
+    order from `rng` (chunk frames, chunk fps, chunk height, chunk width), `np.linspace(start, end - 1, n, dtype=int)` frame indices and
+    `start = end + 1`.  Then the transform's own draws, from the same `rng`: training = RandomResizedCrop.get_params
+    (`random_resized_crop_box`) and the flip coin; evaluation draws nothing.  torchvision draws those from torch's global generator
+    and is not installed here: this matches its DISTRIBUTION, not its draws.  A `randrange` over an empty range (a grid the source
+    cannot satisfy) ends the video, as the reference's `except` does.
+
+    Yields {'indices': frame indices, 'fps', 'span': (start, end), 'out': (T, Ho, Wo), 'box': (top, left, h, w) of the source region
+    to hand to the kernel (the crop in training, the whole frame in evaluation), 'geom': (T, h, w, Hr, Wr, oy, ox, Ho, Wo, flip) as
+    ttv_clip_resample_u8 takes it for that region}."""
+    min_grid, max_grid, patch = sampling.min_grid, sampling.max_grid, sampling.patch_size
+    min_fps, max_fps = sampling.fps_range
+    mar = sampling.max_aspect_ratio
+    in_grid = [int(v) for v in in_grid]
+    in_fps = int(in_fps)
+    if not (all(x >= y for x, y in zip(in_grid, min_grid)) and in_fps >= min_fps):
+        return
+    start = 0
+    while True:
+        try:
+            n = rng.randrange(min_grid[0], max_grid[0] + 1, patch[0])
+            fps = rng.randrange(min_fps, min(max_fps, in_fps) + 1, 1)
+            end = start + int(n * (in_fps / fps))
+            if in_grid[0] < end:
+                return
+            ho = rng.randrange(min_grid[1], min(max_grid[1], in_grid[1]) + 1, patch[1])
+            width_error = int(ho / mar) % patch[2]
+            min_w = max(min_grid[2], int(ho / mar) - width_error)
+            max_w = min(max_grid[2], in_grid[2], int(ho * mar))
+            wo = rng.randrange(min_w, max_w + 1, patch[2])
+        except ValueError:
+            return
+        indices = np.linspace(start, end - 1, n, dtype=int).tolist()
+        if eval:
+            hr, wr = resized_hw(in_grid[1], in_grid[2], max(ho, wo))
+            box = (0, 0, in_grid[1], in_grid[2])
+            geom = (n, in_grid[1], in_grid[2], hr, wr, int(round((hr - ho) / 2.0)), int(round((wr - wo) / 2.0)), ho, wo, 0)
+        else:
+            box = random_resized_crop_box(rng, in_grid[1], in_grid[2], (sampling.min_scale, 1.0), wo / ho)
+            flip = 1 if rng.random() < 0.5 else 0
+            geom = (n, box[2], box[3], ho, wo, 0, 0, ho, wo, flip)
+        yield {"indices": indices, "fps": fps, "span": (start, end), "out": (n, ho, wo), "box": box, "geom": geom}
+        start = end + 1
+
+
+def resample_geoms(frames: Sequence[torch.Tensor], geoms: Sequence[Sequence[int]], dtype: torch.dtype, stream: int) -> List[torch.Tensor]:
+    """ttv_clip_resample_u8 on device uint8 arrays [T,h,w,3] (contiguous) with their geometries, TTV_MAX_CLIPS_PER_LAUNCH clips per
+    call: the clips [3,T,Ho,Wo] in `dtype`, allocated on the current stream's device."""
+    from . import _lib
+    code = _lib.dtype_code(dtype)
+    clips = [torch.empty((3, int(g[0]), int(g[7]), int(g[8])), dtype=dtype, device=f.device) for f, g in zip(frames, geoms)]
+    step = _lib.TTV_MAX_CLIPS_PER_LAUNCH
+    for c0 in range(0, len(clips), step):
+        flat = [int(v) for g in geoms[c0:c0 + step] for v in g]
+        arr = (_lib.i32 * len(flat))(*flat)
+        n = len(clips[c0:c0 + step])
+        _lib.check(_lib.lib().ttv_clip_resample_u8(_lib.ptr_array(frames[c0:c0 + step]), _lib.ptr_array(clips[c0:c0 + step]), arr, n, code, stream), "ttv_clip_resample_u8")
+    return clips
+
+
+def resample_clip(frames_u8: torch.Tensor, out_hw: Tuple[int, int], box: Optional[Tuple[int, int, int, int]] = None, flip: bool = False,
+                  eval: bool = False, dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """One clip through ttv_clip_resample_u8, for users with their own loader: decoded frames uint8 [T,H,W,3] on the GPU -> [3,T,Ho,Wo] in
+    `dtype`, [-1, 1].  Training form (default): the `box` = (top, left, h, w) of the frame (the whole frame when None) is resized to
+    `out_hw` with the antialiased bicubic filter and mirrored when `flip`.  eval=True: Resize(max(out_hw)) + CenterCrop(out_hw) of the
+    whole frame.  Runs on the current stream; there is no CPU path."""
+    from . import _lib
+    _lib.require_gpu(frames_u8, "resample_clip")
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError(f"resample_clip: frames must be uint8 [T,H,W,3], got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+    t, h, w, _ = frames_u8.shape
+    ho, wo = int(out_hw[0]), int(out_hw[1])
+    if eval:
+        if box is not None or flip:
+            raise ValueError("resample_clip: the evaluation form takes neither a crop box nor a flip")
+        hr, wr = resized_hw(h, w, max(ho, wo))
+        src, geom = frames_u8, (t, h, w, hr, wr, int(round((hr - ho) / 2.0)), int(round((wr - wo) / 2.0)), ho, wo, 0)
+    else:
+        top, left, bh, bw = (0, 0, h, w) if box is None else (int(v) for v in box)
+        if not (0 <= top and 0 <= left and bh > 0 and bw > 0 and top + bh <= h and left + bw <= w):
+            raise ValueError(f"resample_clip: box {box} lies outside the {h} x {w} frame")
+        src, geom = frames_u8[:, top:top + bh, left:left + bw], (t, bh, bw, ho, wo, 0, 0, ho, wo, int(bool(flip)))
+    src = src.contiguous()
+    with torch.cuda.device(frames_u8.device):
+        return resample_geoms([src], [geom], dtype, _lib.stream_ptr(frames_u8.device))[0]
 
 
 def dynamic_batches(samples, patch: Sequence[int], token_range: Sequence[int], max_seq_len: int, seed: int = 0,

@@ -18,6 +18,13 @@ thread of the training process and was the whole step: 45 ms per step against 3.
 
 Batches are dealt round-robin over the workers in a fixed order, so a (paths, rank, world, seed, workers) tuple always yields the
 same batch sequence.
+
+With `sampling=` (data.ClipSampling) the shards may hold decoded video of ANY size: a worker runs the reference's `_video_process`
+draws on each sample (data.sample_chunks: chunk of frames at a drawn frame rate, output grid on the patch lattice, and in training
+the RandomResizedCrop box and the flip coin), copies only the selected frames - in training only the crop box of them - into its ring
+slot, and sizes the batch by the OUTPUT grid.  The upload thread copies the slot's bytes in one transfer and makes ONE
+ttv_clip_resample_u8 call per batch (64 clips per call): antialiased bicubic resize, centre-crop window (evaluation), flip and
+normalisation on the device.  Without `sampling=` nothing changes.
 """
 from __future__ import annotations
 
@@ -35,7 +42,7 @@ import torch
 import torch.multiprocessing as mp
 
 from . import _lib
-from .data import dynamic_batches
+from .data import ClipSampling, dynamic_batches, resample_geoms, sample_chunks
 
 
 def raw_shard_samples(paths: Sequence[str], epochs: Optional[int] = 1) -> Iterator[Dict]:
@@ -69,19 +76,58 @@ class _Failure:
         self.where, self.text = where, text
 
 
-def _worker_main(paths, patch, token_range, seq_len, seed, epochs, drop_last, ring, free_q, out_q, release):
+class _Chunk:
+    """One chunk of data.sample_chunks as data.dynamic_batches sees it: `shape` is the OUTPUT clip's, so the batch is sized by what
+    the model gets; the frames stay in the decoded video until the batch is written into a ring slot."""
+
+    def __init__(self, frames, chunk):
+        self.frames, self.indices, self.box, self.geom = frames, chunk["indices"], chunk["box"], chunk["geom"]
+        self.shape = (3, *chunk["out"])
+
+
+def _sampled_chunks(samples, sampling, eval_mode, seed, max_source_hw, skipped):
+    """The reference's `_video_process` over raw shard samples: one {'video': _Chunk, 'fps', '__key__'} per chunk.  A source frame
+    above `max_source_hw` is skipped and counted (the slot size follows from that bound), like a sample the reference fails to decode."""
+    import random
+    rng = random.Random(seed ^ 0x5EED)
+    for smp in samples:
+        frames = smp["video"].permute(1, 2, 3, 0)                  # back to the decoder's [T,H,W,3]
+        t, h, w, _c = frames.shape
+        if h > max_source_hw[0] or w > max_source_hw[1]:
+            skipped[0] += 1
+            continue
+        for ch in sample_chunks(rng, (t, h, w), int(smp["fps"]), sampling, eval=eval_mode):
+            yield {"video": _Chunk(frames, ch), "fps": ch["fps"], "__key__": smp["__key__"] + f"_{ch['span'][0]}-{ch['span'][1]}"}
+
+
+def _worker_main(paths, patch, token_range, seq_len, seed, epochs, drop_last, sampling, eval_mode, max_source_hw, ring, free_q, out_q, release):
     torch.set_num_threads(1)
     try:
-        for b in dynamic_batches(raw_shard_samples(paths, epochs), patch, token_range, seq_len, seed=seed, drop_last=drop_last):
+        skipped = [0]
+        samples = raw_shard_samples(paths, epochs)
+        if sampling is not None:
+            samples = _sampled_chunks(samples, sampling, eval_mode, seed, max_source_hw, skipped)
+        for b in dynamic_batches(samples, patch, token_range, seq_len, seed=seed, drop_last=drop_last):
             slot = free_q.get()                    # flow control: a slot the consumer has finished uploading from
             buf, off, clips = ring[slot], 0, []
-            for v in b["video"]:                   # channel-first view of [T,H,W,3] frames: write them back as the decoder's layout
-                t, h, w = v.shape[1:]
-                n = 3 * t * h * w
-                buf[off:off + n].view(t, h, w, 3).copy_(v.permute(1, 2, 3, 0))
+            for v in b["video"]:
+                if sampling is None:               # channel-first view of [T,H,W,3] frames: write them back as the decoder's layout
+                    t, h, w = v.shape[1:]
+                    n = 3 * t * h * w
+                    buf[off:off + n].view(t, h, w, 3).copy_(v.permute(1, 2, 3, 0))
+                else:                              # the selected frames, and of them the box the kernel resamples
+                    top, left, h, w = v.box
+                    t = len(v.indices)
+                    n = 3 * t * h * w
+                    dst = buf[off:off + n].view(t, h, w, 3)
+                    for k, fi in enumerate(v.indices):
+                        dst[k].copy_(v.frames[fi, top:top + h, left:left + w])
                 clips.append((off, t, h, w))
                 off += (n + 15) // 16 * 16
-            out_q.put({"slot": slot, "clips": clips, "fps": b["fps"], "__key__": b["__key__"], "token_counts": b["token_counts"].tolist()})
+            msg = {"slot": slot, "clips": clips, "fps": b["fps"], "__key__": b["__key__"], "token_counts": b["token_counts"].tolist()}
+            if sampling is not None:
+                msg["geom"], msg["skipped"] = [v.geom for v in b["video"]], skipped[0]
+            out_q.put(msg)
         out_q.put(None)                            # end of data: only a worker that finished its shards says so
     except BaseException:                          # corrupt shard, a clip that does not fit its ring slot, ...: the consumer re-raises
         out_q.put(_Failure(f"loader worker (shards {list(paths)})", traceback.format_exc()))
@@ -94,17 +140,31 @@ class ShardBatchLoader:
 
         loader = ShardBatchLoader(paths, rank, world, workers=2); loader.start()     # BEFORE the first GPU call of the process
         for batch in loader.batches(device, torch.bfloat16): ...                    # {'video': [C,T,H,W tensors], 'fps', '__key__', 'token_counts'}
+
+    sampling=ClipSampling(...): the shards hold decoded video of any size up to `max_source_hw` (larger sources are skipped and
+    counted in `loader.skipped`); clips are cut, cropped, resized and flipped as the reference's `_video_process` does (`eval=True`:
+    Resize + CenterCrop, no random crop or flip), batches also carry 'geom' (the ttv_clip_resample_u8 geometry of each clip).
     """
 
     def __init__(self, paths: Sequence[str], rank: int = 0, world_size: int = 1, patch=(4, 8, 8), token_range=(1, 128), seq_len: int = 6144,
-                 seed: int = 0, workers: int = 2, epochs: Optional[int] = None, drop_last: bool = True, prefetch: int = 4):
+                 seed: int = 0, workers: int = 2, epochs: Optional[int] = None, drop_last: bool = True, prefetch: int = 4,
+                 sampling: Optional[ClipSampling] = None, eval: bool = False, max_source_hw=(288, 384)):
         mine = [p for i, p in enumerate(sorted(paths)) if i % world_size == rank]
         self.workers = max(1, min(workers, len(mine)))
         self._args = [([p for j, p in enumerate(mine) if j % self.workers == w], tuple(patch), tuple(token_range), seq_len, seed + 1009 * w,
-                       epochs, drop_last) for w in range(self.workers)]
+                       epochs, drop_last, sampling, bool(eval), tuple(max_source_hw)) for w in range(self.workers)]
         self.prefetch = max(2, prefetch)
         # a batch holds at most seq_len patch rows of prod(patch) * 3 bytes each (+ 16-byte alignment per clip)
         self.slot_bytes = int(seq_len) * int(np.prod(patch)) * 3 + 4096
+        self.sampling, self.skipped = sampling, 0
+        self._skipped = [0] * self.workers
+        if sampling is not None:
+            if tuple(patch) != sampling.patch_size:
+                raise ValueError(f"ShardBatchLoader: patch {tuple(patch)} differs from sampling.patch_size {sampling.patch_size}")
+            # a slot holds SOURCE pixels: per output patch row at most prod(patch) * (source area / output area) of them, and the
+            # smallest output a source region can go to is min_grid's (+ 16-byte alignment per clip, at most seq_len clips)
+            area = -(-(int(max_source_hw[0]) * int(max_source_hw[1])) // (sampling.min_grid[1] * sampling.min_grid[2]))
+            self.slot_bytes = int(seq_len) * int(np.prod(patch)) * 3 * max(1, area) + 16 * int(seq_len) + 4096
         self._procs, self._queues, self._free, self._rings = [], [], [], []
         self._registered = False
         self._pinned = False
@@ -140,6 +200,9 @@ class ShardBatchLoader:
                     live.remove(w)
                     continue
                 b["worker"] = w
+                if "skipped" in b:
+                    self._skipped[w] = b.pop("skipped")
+                    self.skipped = sum(self._skipped)
                 b["frames"] = [self._rings[w][b["slot"]][off:off + 3 * t * h * wd].view(t, h, wd, 3) for off, t, h, wd in b["clips"]]
                 yield b
 
@@ -203,10 +266,10 @@ class ShardBatchLoader:
                         ev0.synchronize()
                         self.release(b0)
                     frames = b["frames"]
+                    used = b["clips"][-1][0] + frames[-1].numel()          # bytes of the slot this batch occupies
                     if not self._pinned:           # registration refused: one staging copy through ordinary pinned memory
-                        n_bytes = sum(f.numel() for f in frames)
-                        if staging is None or staging.numel() < n_bytes:
-                            staging = torch.empty(max(n_bytes, self.slot_bytes), dtype=torch.uint8).pin_memory()
+                        if staging is None or staging.numel() < used:
+                            staging = torch.empty(max(used, self.slot_bytes), dtype=torch.uint8).pin_memory()
                         off, views = 0, []
                         for f in frames:
                             v = staging[off:off + f.numel()].view(f.shape)
@@ -215,14 +278,21 @@ class ShardBatchLoader:
                             off += (f.numel() + 15) // 16 * 16
                         frames = views
                     with torch.cuda.stream(up):
-                        clips = []
-                        for v in frames:
-                            t, h, w, _c = v.shape
-                            d8 = torch.empty(v.shape, dtype=torch.uint8, device=device)
-                            d8.copy_(v, non_blocking=True)
-                            clip = torch.empty((3, t, h, w), dtype=dtype, device=device)
-                            _lib.check(lib.ttv_clip_from_u8(d8.data_ptr(), t, h, w, clip.data_ptr(), code, up.cuda_stream), "ttv_clip_from_u8")
-                            clips.append(clip)
+                        if self.sampling is not None:      # the slot's bytes in one transfer, the whole batch in one launch per 64 clips
+                            host = staging if not self._pinned else self._rings[b["worker"]][b["slot"]]
+                            d8 = torch.empty(used, dtype=torch.uint8, device=device)
+                            d8.copy_(host[:used], non_blocking=True)
+                            srcs = [d8[off:off + 3 * t * h * w] for off, t, h, w in b["clips"]]
+                            clips = resample_geoms(srcs, b["geom"], dtype, up.cuda_stream)
+                        else:
+                            clips = []
+                            for v in frames:
+                                t, h, w, _c = v.shape
+                                d8 = torch.empty(v.shape, dtype=torch.uint8, device=device)
+                                d8.copy_(v, non_blocking=True)
+                                clip = torch.empty((3, t, h, w), dtype=dtype, device=device)
+                                _lib.check(lib.ttv_clip_from_u8(d8.data_ptr(), t, h, w, clip.data_ptr(), code, up.cuda_stream), "ttv_clip_from_u8")
+                                clips.append(clip)
                         ev = torch.cuda.Event()
                         ev.record(up)
                     if not self._pinned:
@@ -230,6 +300,8 @@ class ShardBatchLoader:
                     in_flight.append((ev, b))
                     item = ({"video": clips, "fps": b["fps"], "__key__": b["__key__"],
                              "token_counts": torch.tensor(b["token_counts"], dtype=torch.int32)}, ev)
+                    if self.sampling is not None:
+                        item[0]["geom"] = b["geom"]
                     while not self._stop.is_set():  # a consumer that stopped early must not leave this thread blocked in put()
                         try:
                             out_q.put(item, timeout=0.2)

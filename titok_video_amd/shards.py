@@ -47,6 +47,39 @@ def write_synthetic_shards(out_dir: str, n_shards: int, clips_per_shard: int, mi
     return paths
 
 
+def write_synthetic_video_shards(out_dir: str, n_shards: int, clips_per_shard: int, frames=(24, 48), fps=(6, 12), height=(160, 288),
+                                 width=(200, 384), noise: int = 12, seed: int = 0) -> List[str]:
+    """Shards of decoded video that is NOT on the patch lattice, for the resampling path of the loader (`sampling=`): per sample a
+    seeded number of frames, an integer frame rate and a frame size drawn from the given inclusive ranges; content = a few drifting
+    sinusoids per channel (smooth, like video) plus uniform noise of +-`noise` levels.  Same member format as write_synthetic_shards."""
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    for s in range(n_shards):
+        path = os.path.join(out_dir, f"shard-{s:05d}.tar")
+        with tarfile.open(path, "w") as tar:
+            for j in range(clips_per_shard):
+                i = s * clips_per_shard + j
+                rng = random.Random((seed << 20) + i)
+                t, h, w = rng.randrange(frames[0], frames[1] + 1), rng.randrange(height[0], height[1] + 1), rng.randrange(width[0], width[1] + 1)
+                g = np.random.default_rng((seed << 20) + i)
+                yy, xx = np.meshgrid(np.arange(h, dtype=np.float32) / h, np.arange(w, dtype=np.float32) / w, indexing="ij")
+                tt = np.arange(t, dtype=np.float32)[:, None, None]
+                img = np.zeros((t, h, w, 3), dtype=np.float32)
+                for c in range(3):
+                    for _ in range(3):
+                        fy, fx, ph, dr = g.uniform(0.5, 4.0), g.uniform(0.5, 4.0), g.uniform(0.0, 6.2831853), g.uniform(0.0, 0.3)
+                        img[..., c] += np.sin(6.2831853 * (fy * yy + fx * xx)[None] + ph + dr * tt)
+                img = (img / 3.0 * 0.4 + 0.5) * 255.0 + g.integers(-noise, noise + 1, size=img.shape)
+                vid = np.clip(np.rint(img), 0, 255).astype(np.uint8)
+                key = f"video_{i:08d}"
+                for name, payload in ((key + ".npy", _npy_bytes(vid)), (key + ".json", json.dumps({"fps": rng.randrange(fps[0], fps[1] + 1)}).encode())):
+                    info = tarfile.TarInfo(name)
+                    info.size = len(payload)
+                    tar.addfile(info, io.BytesIO(payload))
+        paths.append(path)
+    return paths
+
+
 def _npy_bytes(a: np.ndarray) -> bytes:
     buf = io.BytesIO()
     np.save(buf, a, allow_pickle=False)

@@ -44,6 +44,8 @@ def main():
     ap.add_argument("--clips-per-shard", type=int, default=64)
     ap.add_argument("--seq-len", type=int, default=6144)
     ap.add_argument("--no-overlap", action="store_true")
+    ap.add_argument("--sampling", action="store_true", help="decoded-video shards (160..288 x 200..384) through the reference's crop / antialiased "
+                    "resize / flip on the device (ShardBatchLoader(sampling=...)); a different workload: more bytes uploaded per batch")
     ap.add_argument("--workers", type=int, default=2, help="loader worker processes per rank (the reference uses 3, video_dataset.py:211)")
     ap.add_argument("--backend", default="nccl")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
@@ -77,7 +79,7 @@ def main():
     from titok_video_amd.model.losses import ReconstructionLoss
     from titok_video_amd.model.titok import TiTok
     from titok_video_amd.loader import ShardBatchLoader
-    from titok_video_amd.shards import write_synthetic_shards
+    from titok_video_amd.shards import write_synthetic_shards, write_synthetic_video_shards
     from titok_video_amd.synthetic import seeded_titok_state, seeded_tower_state
     from titok_video_amd.train import freeze_python_gc, gan_training_step, limit_host_threads, make_discriminator_optimizer, make_optimizer
 
@@ -107,7 +109,10 @@ def main():
             shutil.rmtree(shard_dir, ignore_errors=True)            # a stale directory of the same name (token reuse): marker goes first
             staging = shard_dir + ".writing.%d" % os.getpid()
             shutil.rmtree(staging, ignore_errors=True)
-            write_synthetic_shards(staging, n_shards, args.clips_per_shard, seed=11)
+            if args.sampling:
+                write_synthetic_video_shards(staging, n_shards, args.clips_per_shard, seed=11)
+            else:
+                write_synthetic_shards(staging, n_shards, args.clips_per_shard, seed=11)
             with open(os.path.join(staging, ".written"), "w") as f:
                 f.write(token)
             os.rename(staging, shard_dir)
@@ -124,8 +129,12 @@ def main():
                     raise SystemExit("train_dp.py: rank 0 never finished writing the shards (waited 120 s for %s to hold this run's token)" % marker)
                 time.sleep(0.05)
     paths = sorted(os.path.join(shard_dir, f) for f in os.listdir(shard_dir) if f.endswith(".tar"))[:n_shards]
+    sampling = None
+    if args.sampling:                                      # configs/tiny.yaml sampling keys, min_scale of tiny_csv.yaml
+        from titok_video_amd.data import ClipSampling
+        sampling = ClipSampling(min_grid=(8, 128, 128), max_grid=(16, 168, 168), fps_range=(3, 5), max_aspect_ratio=2.0, min_scale=0.25)
     loader = ShardBatchLoader(paths, rank, world, patch=(4, 8, 8), token_range=(1, 128), seq_len=args.seq_len, seed=100 + rank,
-                              workers=args.workers, epochs=None, drop_last=True).start()
+                              workers=args.workers, epochs=None, drop_last=True, sampling=sampling).start()
 
     if not rehearsal and torch.cuda.device_count() <= dev_index:
         raise SystemExit(f"rank {rank}: LOCAL_RANK {local_rank} but only {torch.cuda.device_count()} GPU(s) visible")
