@@ -572,6 +572,37 @@ int ttv_lpips_forward(const ttv_lpips_weights* w, const void* recon, const void*
 int ttv_lpips_backward(const ttv_lpips_weights* w, const void* tape, int n, int H, int W, int dtype, const float* glpips,
                        const float* ggram, void* drecon, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The perceptual crops of the generator step (model/losses/loss_module.py:59-93) and their backward: what lies between the towers
+ * and ttv_lpips_forward / ttv_lpips_backward.  Host arrays: recon_clips[i], target_clips[i] = contiguous clips [3][T][H][W] in `dtype`
+ * (device), clip_dims = n_clips x (T, H, W), crops = n_crops x (clip, frame, H, W, Hr, Wr, oy, ox): the crop is cut from that frame
+ * of that clip ((H, W) repeats the clip's size), Hr x Wr is the virtual resized frame - equal to H x W when the frame is not resized
+ * (a resize that keeps the size, e.g. of a 128 x 128 frame at size 128, has the weights (0, 1, 0, 0) exactly and is taken as a copy too:
+ * the same values for finite pixels; -0.0 stays -0.0 and an Inf / NaN does not spread to its neighbours as 0 * Inf would),
+ * otherwise the short edge becomes `size` and the long edge int(size * long / short) (torchvision's resize(size)) - and (oy, ox) is the
+ * origin of the size x size window in it.  n_clips and n_crops are any counts >= 1 (tables are split into launches inside), `size` a
+ * multiple of 16 (16 .. 2048).  Outputs recon_crops, target_crops [n_crops][3][size][size] in `dtype`, 16-byte aligned.
+ * Value of output element (c, i, j) of a crop, with v = min(max(x, -1), 1) for the reconstruction and v = x for the target:
+ *   not resized: v at (oy + i, ox + j) of the frame, a copy;
+ *   resized: torch's upsample_bicubic2d(align_corners=False), no antialiasing, at (oy + i, ox + j) of the resized frame.  Per axis
+ *     n_in -> n_out: scale = (float)n_in / (float)n_out, src = fmaf(scale, dst + 0.5f, -0.5f), i0 = floor(src), t = src - i0, taps
+ *     i0 - 1 .. i0 + 2 clamped to [0, n_in - 1], weights (Keys, A = -0.75, fp32) c2(t + 1), c1(t), c1(1 - t), c2(2 - t) with
+ *     c1(x) = ((A + 2) x - (A + 3)) x x + 1 and c2(x) = ((A x - 5 A) x + 8 A) x - 4 A.  Rows are the outer loop and columns the
+ *     inner: h_r = sum_k wx_k v[iy_r][ix_k], out = sum_r wy_r h_r, each sum an fmaf chain in ascending tap order from 0, fp32,
+ *     rounded once to `dtype`.
+ * ttv_lpips_crops_backward: from g [n_crops][3][size][size] (`dtype`, the gradient of recon_crops) the whole gradient of every
+ * reconstruction clip, grad_clips[i] [3][T][H][W] in `dtype` (16-byte aligned), written once, with no memset: frames no crop names
+ * are zeros; a sampled frame gets 1[-1 <= x <= 1] (R^T g), R the forward operator of its crop (pixels outside the window's
+ * footprint: zeros; the mask is inclusive, torch's clamp backward).  R^T g is formed as a gather: an input pixel sums over the
+ * output pixels whose clamped taps touch it - output rows ascending, per row columns ascending, taps ascending, fmaf in fp32, one
+ * rounding - so there are no atomics and identical calls give identical bits.  A frame is sampled at most once.
+ * TTV_ERR_INVALID with nothing launched: a bad dtype or size, a clip / frame index or (H, W) that does not match clip_dims, Hr x Wr
+ * that is neither H x W nor the resize rule's, a window outside the virtual frame, a frame named twice, a misaligned destination.
+ * Work is enqueued on `stream` only; no synchronisation, no library state. */
+int ttv_lpips_crops_forward(void* const* recon_clips, void* const* target_clips, const int32_t* clip_dims, int n_clips, const int32_t* crops,
+                            int n_crops, int size, void* recon_crops, void* target_crops, int dtype, void* stream);
+int ttv_lpips_crops_backward(void* const* recon_clips, void* const* grad_clips, const int32_t* clip_dims, int n_clips, const int32_t* crops,
+                             int n_crops, int size, const void* g, int dtype, void* stream);
+
 /* Single operations (tests).  ttv_lpips_conv3x3: x [N][H][W][Cin] -> y [N][H][W][Cout], 3x3, stride 1, zero pad 1 per image, with
  * the weight image the dtype / shape rule above selects.  mode 0: y = relu(conv + bias); 1: y = conv * (h > 0), h [N][H][W][Cout];
  * 2: y = conv.  Workspace: ttv_lpips_conv_workspace_bytes (split-K partials; 0 when none).  ttv_lpips_maxpool: 2x2 / 2 max-pool of

@@ -198,6 +198,8 @@ SYMBOLS = {
     "ttv_lpips_conv3x3": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int64, vp]),
     "ttv_lpips_maxpool": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "ttv_lpips_maxpool_backward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
+    "ttv_lpips_crops_forward": (C.c_int, [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
+    "ttv_lpips_crops_backward": (C.c_int, [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp]),
     "ttv_i3d_workspace_bytes": (C.c_int64, [C.c_int]),
     "ttv_fvd_preprocess": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "ttv_i3d_features": (C.c_int, [C.POINTER(I3dWeights), vp, C.c_int, vp, vp, C.c_int64, vp]),

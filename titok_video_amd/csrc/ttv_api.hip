@@ -754,6 +754,17 @@ int ttv_lpips_backward(const ttv_lpips_weights* w, const void* tape, int n, int 
   return ttvk_lpips_backward(w, tape, n, H, W, dtype, glpips, ggram, drecon, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+int ttv_lpips_crops_forward(void* const* recon_clips, void* const* target_clips, const int32_t* clip_dims, int n_clips, const int32_t* crops,
+                            int n_crops, int size, void* recon_crops, void* target_crops, int dtype, void* stream) {
+  return ttvk_lpips_crops_forward(recon_clips, target_clips, clip_dims, n_clips, crops, n_crops, size, recon_crops, target_crops, dtype,
+                                  (hipStream_t)stream);
+}
+
+int ttv_lpips_crops_backward(void* const* recon_clips, void* const* grad_clips, const int32_t* clip_dims, int n_clips, const int32_t* crops,
+                             int n_crops, int size, const void* g, int dtype, void* stream) {
+  return ttvk_lpips_crops_backward(recon_clips, grad_clips, clip_dims, n_clips, crops, n_crops, size, g, dtype, (hipStream_t)stream);
+}
+
 int64_t ttv_lpips_conv_workspace_bytes(int N, int H, int W, int Cin, int Cout, int dtype) {
   return ttvk_lpips_conv_workspace_bytes(N, H, W, Cin, Cout, dtype);
 }

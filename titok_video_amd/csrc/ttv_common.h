@@ -180,6 +180,29 @@ struct TtvProfScope {
 };
 
 static inline int ttv_cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// ---- torch's bicubic taps without antialiasing (aten/src/ATen/native/UpSample.h, upsample_bicubic2d, align_corners=False) ----------
+// Along one axis n_in -> n_out: src = scale * (dst + 0.5) - 0.5 with no clamp at 0 for cubic, i = floor(src), t = src - i, taps
+// i - 1 .. i + 2 clamped to [0, n_in - 1], Keys weights with A = -0.75.  ttv_cubic_floor is the i of an output index on its own
+// (the transpose in ttv_crops.hip inverts it); the fmaf and the rounding of its operands are the same in both.
+__device__ __forceinline__ float ttv_cubic_src(int dst, float scale) { return fmaf(scale, (float)dst + 0.5f, -0.5f); }
+__device__ __forceinline__ int ttv_cubic_floor(int dst, float scale) { return (int)floorf(ttv_cubic_src(dst, scale)); }
+__device__ __forceinline__ void cubic_taps(int dst, int n_in, int n_out, int (&idx)[4], float (&w)[4]) {
+  const float scale = (float)n_in / (float)n_out;
+  const float src = ttv_cubic_src(dst, scale);
+  const float fl = floorf(src);
+  const float t = src - fl;
+  const int i0 = (int)fl;
+  constexpr float A = -0.75f;
+  auto c1 = [](float x) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; };
+  auto c2 = [](float x) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; };
+  w[0] = c2(t + 1.f); w[1] = c1(t); w[2] = c1(1.f - t); w[3] = c2(2.f - t);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int j = i0 - 1 + k;
+    idx[k] = j < 0 ? 0 : (j > n_in - 1 ? n_in - 1 : j);
+  }
+}
 // bf16 path: gelu(g) * x without erff().  Phi(g) = sigmoid(p(g)), p odd of degree 5 (minimax fit, g clamped to +-8 so the
 // negative g^5 coefficient never takes over): max |g*Phi - gelu_erf(g)| = 2.6e-5 over all g - 1/10 of a bf16 half-ulp at
 // 0.06 - and 12 VALU issue slots per element (v_exp_f32 / v_rcp_f32 count 2 each) against 18 for an erf polynomial of

@@ -205,6 +205,12 @@ int64_t ttvk_ssim_workspace_bytes(const int32_t* dims, int n_clips);
 int ttvk_ssim(void* const* recon, void* const* target, const int32_t* dims, int n_clips, int dtype, int clamp, double* acc2, void* workspace,
               int64_t workspace_bytes, hipStream_t s);
 
+// ---- ttv_crops.hip ----
+int ttvk_lpips_crops_forward(void* const* recon, void* const* target, const int32_t* clip_dims, int n_clips, const int32_t* crops, int n_crops,
+                             int size, void* recon_crops, void* target_crops, int dtype, hipStream_t s);
+int ttvk_lpips_crops_backward(void* const* recon, void* const* grad, const int32_t* clip_dims, int n_clips, const int32_t* crops, int n_crops,
+                              int size, const void* g, int dtype, hipStream_t s);
+
 // ---- ttv_lpips.hip ----
 int64_t ttvk_lpips_tape_bytes(int n, int H, int W, int dtype);
 int64_t ttvk_lpips_workspace_bytes(int n, int H, int W, int dtype);

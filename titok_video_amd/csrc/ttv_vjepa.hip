@@ -40,25 +40,6 @@ struct JediClips {
   int T[TTV_MAX_CLIPS_PER_LAUNCH], S[TTV_MAX_CLIPS_PER_LAUNCH];
 };
 
-// torch's bicubic taps (aten/src/ATen/native/UpSample.h): src = scale * (dst + 0.5) - 0.5 with no clamp at 0 for cubic,
-// i = floor(src), t = src - i, taps i - 1 .. i + 2 clamped to [0, in - 1]
-__device__ __forceinline__ void cubic_taps(int dst, int in, int (&idx)[4], float (&w)[4]) {
-  const float scale = (float)in / (float)VJ_S;
-  const float src = fmaf(scale, (float)dst + 0.5f, -0.5f);
-  const float fl = floorf(src);
-  const float t = src - fl;
-  const int i0 = (int)fl;
-  constexpr float A = -0.75f;
-  auto c1 = [](float x) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; };
-  auto c2 = [](float x) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; };
-  w[0] = c2(t + 1.f); w[1] = c1(t); w[2] = c1(1.f - t); w[3] = c2(2.f - t);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int j = i0 - 1 + k;
-    idx[k] = j < 0 ? 0 : (j > in - 1 ? in - 1 : j);
-  }
-}
-
 template <typename T>
 __device__ __forceinline__ float rescaled(const T* p) {
   float v = Cvt<T>::to_f(*p);
@@ -81,7 +62,7 @@ __global__ __launch_bounds__(256) void k_jedi_prep(JediClips a, bf16_t* __restri
   const T* frame = reinterpret_cast<const T*>(a.x[clip]) + ((size_t)c * Tn + f) * S * S;
   int iy[4];
   float wy[4];
-  cubic_taps(hp * VJ_P + kh, S, iy, wy);
+  cubic_taps(hp * VJ_P + kh, S, VJ_S, iy, wy);   // torch's bicubic taps, shared with ttv_crops.hip (ttv_common.h)
   const float mean = c == 0 ? 0.485f : c == 1 ? 0.456f : 0.406f;
   const float stdv = c == 0 ? 0.229f : c == 1 ? 0.224f : 0.225f;
   bf16x8 o;
@@ -89,7 +70,7 @@ __global__ __launch_bounds__(256) void k_jedi_prep(JediClips a, bf16_t* __restri
   for (int e = 0; e < 8; ++e) {
     int ix[4];
     float wx[4];
-    cubic_taps(wp * VJ_P + half * 8 + e, S, ix, wx);
+    cubic_taps(wp * VJ_P + half * 8 + e, S, VJ_S, ix, wx);
     float acc = 0.f;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {   // rows outer, columns inner, products and sums rounded one by one (torch's CPU order)

@@ -1,1 +1,1 @@
-from .loss_module import ReconstructionLoss  # noqa: F401
+from .loss_module import PerceptualCrops, ReconstructionLoss, perceptual_crop_plan  # noqa: F401

@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ... import _lib
 from ..base.blocks import TiTokEncoder
 from ..base.utils import init_weights
 from ..metrics.lpips_gram import LPIPS
@@ -38,6 +39,71 @@ def _resized_hw(H: int, W: int, size: int):
     short, long = (W, H) if W <= H else (H, W)
     new_short, new_long = size, int(size * long / short)
     return (new_long, new_short) if W <= H else (new_short, new_long)
+
+
+def _fused_crops() -> bool:
+    """TTV_LPIPS_CROPS=0 selects the eager crop path of `perceptual_preprocess` on GPU tensors too (A/B and tests)."""
+    return os.environ.get("TTV_LPIPS_CROPS", "1") != "0"
+
+
+def perceptual_crop_plan(frame_shapes, size: int, samples: int, resize_prob: float = 0.25):
+    """The draws of the reference's perceptual_preprocess (loss_module.py:59-93) for frames of the given (H, W), consuming Python's
+    `random` exactly as it does: one random() per frame for the shuffle (sorted(..., key=random.random())), then per taken frame a
+    random() for the resize only when the frame is at least `size` on both edges, then randrange for the row and the column origin.
+    The loop stops AFTER appending once i >= samples (24 -> 25 crops; -1 -> every frame).  Returns, in the order the crops are
+    stacked, (frame index, H, W, Hr, Wr, oy, ox, resized): Hr x Wr is the frame the window is cut from (torchvision's resize(size):
+    short edge -> size, long edge int(size * long / short)) and equals H x W when `resized` is False."""
+    if samples == -1:
+        samples = len(frame_shapes)
+    plan = []
+    for i, k in enumerate(sorted(range(len(frame_shapes)), key=lambda _k: random.random())):
+        H, W = frame_shapes[k]
+        resized = (H < size or W < size) or random.random() < resize_prob
+        Hr, Wr = _resized_hw(H, W, size) if resized else (H, W)
+        oy = random.randrange(0, (Hr - size) + 1)
+        ox = random.randrange(0, (Wr - size) + 1)
+        plan.append((k, H, W, Hr, Wr, oy, ox, resized))
+        if i >= samples:
+            break
+    return plan
+
+
+class PerceptualCrops(torch.autograd.Function):
+    """The crops of a plan in one HIP launch (csrc/ttv_crops.hip) and their backward in one more.  `table` holds one
+    (clip, frame, H, W, Hr, Wr, oy, ox) per crop; `clips` are the n reconstruction clips followed by the n target clips [3,T,H,W].
+    Returns (recon crops, target crops) [F,3,size,size]; gradients flow into the reconstruction clips only."""
+
+    @staticmethod
+    def forward(ctx, table, size, n, *clips):
+        recon, target = clips[:n], clips[n:]
+        dev, dtype = recon[0].device, recon[0].dtype
+        for c in clips:
+            _lib.require_gpu(c, "PerceptualCrops")
+            if c.dtype != dtype or c.dim() != 4 or c.shape[0] != 3 or not c.is_contiguous():
+                raise ValueError(f"PerceptualCrops: clips must be contiguous [3,T,H,W] of one dtype, got {tuple(c.shape)} {c.dtype}")
+        dt = _lib.dtype_code(dtype)
+        dims = (_lib.i32 * (3 * n))(*[int(v) for c in recon for v in c.shape[1:]])
+        crops = (_lib.i32 * (8 * len(table)))(*[int(v) for row in table for v in row])
+        rec = torch.empty((len(table), 3, size, size), dtype=dtype, device=dev)
+        trg = torch.empty_like(rec)
+        _lib.check(_lib.lib().ttv_lpips_crops_forward(_lib.ptr_array(recon), _lib.ptr_array(target), dims, n, crops, len(table), size,
+                                                      rec.data_ptr(), trg.data_ptr(), dt, _lib.stream_ptr(dev)), "ttv_lpips_crops_forward")
+        ctx.mark_non_differentiable(trg)
+        if any(ctx.needs_input_grad[3:3 + n]):
+            ctx.save_for_backward(*recon)
+            ctx.call = (dims, n, crops, len(table), size, dt)
+        return rec, trg
+
+    @staticmethod
+    def backward(ctx, g, _g_target):
+        dims, n, crops, n_crops, size, dt = ctx.call
+        recon = ctx.saved_tensors
+        dev = recon[0].device
+        g = (torch.zeros((n_crops, 3, size, size), dtype=recon[0].dtype, device=dev) if g is None else g.to(recon[0].dtype)).contiguous()
+        grads = [torch.empty_like(r) for r in recon]
+        _lib.check(_lib.lib().ttv_lpips_crops_backward(_lib.ptr_array(recon), _lib.ptr_array(grads), dims, n, crops, n_crops, size,
+                                                       g.data_ptr(), dt, _lib.stream_ptr(dev)), "ttv_lpips_crops_backward")
+        return (None, None, None) + tuple(grads) + (None,) * n
 
 
 class ReconstructionLoss(nn.Module):
@@ -86,23 +152,35 @@ class ReconstructionLoss(nn.Module):
         target_out, recon_out = [], []
         size = int(self.config.tokenizer.losses.perceptual_sampling_size)
         samples = int(self.config.tokenizer.losses.perceptual_samples_per_step)
-        if samples == -1:
-            samples = len(target)
-        for i, (trg, rec) in enumerate(sorted(zip(target, recon), key=lambda k: random.random())):
-            rec = rec.clamp(-1, 1)
-            H, W = trg.shape[1:]
-            if (H < size or W < size) or random.random() < resize_prob:
-                new_h, new_w = _resized_hw(H, W, size)
+        plan = perceptual_crop_plan([tuple(t.shape[1:]) for t in target], size, samples, resize_prob)
+        for k, _H, _W, new_h, new_w, dy, dx, resized in plan:
+            trg, rec = target[k], recon[k].clamp(-1, 1)
+            if resized:
                 trg = F.interpolate(trg[None], size=(new_h, new_w), mode="bicubic", align_corners=False)[0]
                 rec = F.interpolate(rec[None], size=(new_h, new_w), mode="bicubic", align_corners=False)[0]
-            H, W = trg.shape[1:]
-            dy = random.randrange(0, (H - size) + 1)
-            dx = random.randrange(0, (W - size) + 1)
             target_out.append(trg[:, dy:dy + size, dx:dx + size])
             recon_out.append(rec[:, dy:dy + size, dx:dx + size])
-            if i >= samples:
-                break
         return torch.stack(recon_out, dim=0).contiguous(), torch.stack(target_out, dim=0).contiguous()
+
+    def perceptual_crops(self, target, recon, resize_prob: float = 0.25):
+        """`perceptual_preprocess` of the clips' frames on the HIP path: the same draws (perceptual_crop_plan over the frames of clip 0,
+        then clip 1, ...), the crops in one launch, their backward in one more; the per-frame views are never built.  `target` and
+        `recon` are lists of GPU clips [3,T,H,W], bf16 or fp32 (what the kernels take: `_generator_step_loss` sends anything else down
+        the eager path); clips that are not contiguous are made so and the target is cast to the reconstruction's dtype, as stacking
+        the eager crops into one LPIPS batch does.  A frame that draws the resize but keeps its size is cut as a copy (the identity
+        resize has the weights (0, 1, 0, 0) exactly).  Returns (recon [F,3,s,s], target [F,3,s,s])."""
+        recon = [r.contiguous() for r in recon]
+        target = [t.to(r.dtype).contiguous() for t, r in zip(target, recon)]
+        size = int(self.config.tokenizer.losses.perceptual_sampling_size)
+        samples = int(self.config.tokenizer.losses.perceptual_samples_per_step)
+        shapes, owner = [], []
+        for c, t in enumerate(target):
+            T, H, W = t.shape[1:]
+            shapes += [(H, W)] * T
+            owner += [(c, f) for f in range(T)]
+        plan = perceptual_crop_plan(shapes, size, samples, resize_prob)
+        table = [owner[k] + (H, W, Hr, Wr, oy, ox) for k, H, W, Hr, Wr, oy, ox, _resized in plan]
+        return PerceptualCrops.apply(table, size, len(recon), *recon, *target)
 
     # ---- discriminator access -------------------------------------------------------------------------------------------
     def disc_wrapper(self, x: Sequence[torch.Tensor]) -> torch.Tensor:
@@ -140,14 +218,17 @@ class ReconstructionLoss(nn.Module):
         terms = {"recon_loss": l1_reconstruction_loss(fake, real)}
         total = terms["recon_loss"]
         if self.perceptual_weight > 0.0 or self.gram_weight > 0.0:              # (:123-137)
-            target_frames, recon_frames = [], []
-            for t, r in zip(real, fake):
-                target_frames += t.unbind(1)
-                recon_frames += r.unbind(1)
             # The reference unpacks preprocess's (recon, target) as (target, recon) and calls LPIPS(target crops, recon crops); both
             # terms are symmetric in their two arguments, so the crops go in as (recon, target) here and the gradient is taken
             # with respect to the HIP module's input.
-            rec_crops, trg_crops = self.perceptual_preprocess(target_frames, recon_frames)
+            if _fused_crops() and all(c.is_cuda and c.dtype in (torch.bfloat16, torch.float32) for c in real + fake):
+                rec_crops, trg_crops = self.perceptual_crops(real, fake)
+            else:                                      # CPU tensors, other dtypes, or TTV_LPIPS_CROPS=0: the eager definition
+                target_frames, recon_frames = [], []
+                for t, r in zip(real, fake):
+                    target_frames += t.unbind(1)
+                    recon_frames += r.unbind(1)
+                rec_crops, trg_crops = self.perceptual_preprocess(target_frames, recon_frames)
             lp, gr = self.perceptual_model(rec_crops, trg_crops.detach(), compute_gram=self.gram_weight > 0.0)
             if self.perceptual_weight > 0.0:
                 terms["perceptual_loss"] = lp.mean()
