@@ -727,9 +727,37 @@ int ttv_vjepa_pool_attention(const void* q, const void* kv, int n, int rows, voi
 /* Start recording launches of `kernel_class` (up to max_records; events are created here, outside any launch path).
  * This is the only process-global state in the library and it is off by default. */
 int ttv_prof_begin(int kernel_class, int max_records);
-/* Diagnostics for kernel ablation timing / tests (never set in product use): bit0 = GEMM epilogues skip their stores;
- * bit7 (128) / bit8 (256) = force the 160- / 128-token tile of the general-K GEMM instead of the grid-balance choice.
- * The flags belong to the CALLING HOST THREAD (thread-local): launches made by other threads are unaffected. */
+/* Diagnostics for kernel ablation timing / tests (never set in product use): an OR of the TTV_DBG_* bits below.
+ * The flags belong to the CALLING HOST THREAD (thread-local): launches made by other threads are unaffected.
+ * The values are cited by number in tools/, profiles/ and DESIGN.md and never change.  Where a value is read by two kernels' worth of
+ * code with two meanings it has two names (marked "same value as"); tools/README.md lists every bit beside the environment switches,
+ * titok_video_amd/_lib.py mirrors the table as DBG_* (tests/test_cabi_cpu.py holds the two equal). */
+enum {
+  TTV_DBG_NO_STORES = 1,               /* GEMM, k_qkv256(ws) and k_mlp256 epilogues store nothing; k_gemm_k256 also skips the rotary (ttv_gemm.hip, ttv_qkv256*.inc, ttv_mlp.hip) */
+  TTV_DBG_K256_NO_PANEL_DMA = 2,       /* k_gemm_k256: no weight-panel DMA after the first (ttv_gemm.hip) */
+  TTV_DBG_MLP_NO_WEIGHT_DMA = 2,       /* k_mlp256: no w12 / w3 panel DMA after the first; same value as K256_NO_PANEL_DMA (ttv_mlp.hip) */
+  TTV_DBG_K256_NO_TILE_RELOAD = 4,     /* k_gemm_k256: token rows are not reloaded when a block's range enters the next tile (ttv_gemm.hip) */
+  TTV_DBG_MLP_NO_GEGLU = 4,            /* k_mlp256: no GEGLU arithmetic, garbage results; same value as K256_NO_TILE_RELOAD (ttv_mlp.hip) */
+  TTV_DBG_K256_NO_EPILOGUE_MATH = 8,   /* k_gemm_k256: no folded pre-norm / rotary arithmetic in the epilogue, garbage results (ttv_gemm.hip) */
+  TTV_DBG_MLP_TILES8 = 8,              /* ttvk_mlp_fused: force the 2-tile pair variant; same value as K256_NO_EPILOGUE_MATH (ttv_mlp.hip) */
+  TTV_DBG_MLP_NO_P2 = 16,              /* k_mlp256: no w3 (P2) MFMAs, garbage results (ttv_mlp.hip) */
+  TTV_DBG_MLP_PAIRS_ONLY = 32,         /* ttvk_mlp_fused: never choose the 9-tile deal (ttv_mlp.hip) */
+  TTV_DBG_MLP_TILES4 = 64,             /* ttvk_mlp_fused: force the 1-tile pair variant (ttv_mlp.hip) */
+  TTV_DBG_GEMM_TILE160 = 128,          /* general-K bf16 / fp32 / gather GEMM: force the 160-token tile (ttv_gemm.hip) */
+  TTV_DBG_GEMM_TILE128 = 256,          /* general-K bf16 / fp32 / gather GEMM: force the 128-token tile; TILE160 wins when both are set (ttv_gemm.hip) */
+  TTV_DBG_GEMM_T256 = 512,             /* bf16 GEMM: force k_gemm_bf16_t256 (256 x 256 tiles) wherever it applies (ttv_gemm.hip) */
+  TTV_DBG_MLP_TILES9 = 512,            /* ttvk_mlp_fused: force the 9-tile eight-wave deal; same value as GEMM_T256 (ttv_mlp.hip) */
+  TTV_DBG_GEMM_NO_T256 = 1024,         /* bf16 GEMM: never k_gemm_bf16_t256 (ttv_gemm.hip) */
+  TTV_DBG_MX_UNFUSED_QUANT = 2048,     /* block-scaled fp8 layers: every operand quantised by a pass of its own, as TTV_MX_FUSED_QUANT=0 (ttv_api.hip) */
+  TTV_DBG_SPLIT3_NO_IMAGES = 4096,     /* split-bf16 towers: fp32 activations, split inside the GEMMs, as TTV_SPLIT3_IMAGES=0 (ttv_api.hip) */
+  TTV_DBG_SPLIT3_NO_DMA = 8192,        /* fp32 GEMM: the register-staged kernel instead of k_gemm_split_dma, as TTV_SPLIT3_DMA=0 (ttv_gemm.hip) */
+  TTV_DBG_K256_GENERAL = 16384,        /* bf16 K = 256 GEMM without folded pre-norm or patch scatter: through the general-K kernels (ttv_gemm.hip) */
+  TTV_DBG_QKV256_OFF = 32768,          /* to_qkv at K = 256: k_gemm_k256<EPI_QKV_ROPE> instead of k_qkv256, as TTV_QKV256=0 (ttv_gemm.hip) */
+  TTV_DBG_QKV256_WS = 131072,          /* to_qkv at K = 256: the weight-stationary k_qkv256ws, as TTV_QKV256=2 (ttv_gemm.hip) */
+  TTV_DBG_ENC_ALL_ROWS = 524288,       /* encoder's last layer on every row, as TTV_ENC_LATENT_LAST=0 (ttv_api.hip, ttv_train.hip) */
+  TTV_DBG_ATTN_NO_SWP = 1048576,       /* ttvk_attention keeps k_attn_bf16 where it would take k_attn_swp, as TTV_ATTN_SWP=0 (ttv_attn.hip) */
+  TTV_DBG_DEC_ALL_BLOCKS = 2097152     /* decoder's last attention on every query block, as TTV_DEC_PATCH_LAST=0 (ttv_api.hip) */
+};
 int ttv_debug_set(int flags);
 /* Diagnostics: device buffer (>= 256 int64) that instrumented kernels fill with s_memtime stamps of block 0; NULL = off. */
 int ttv_debug_stamps(void* device_buffer);

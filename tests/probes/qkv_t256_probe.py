@@ -11,7 +11,7 @@ g=torch.Generator().manual_seed(0)
 x=(torch.randn(M,d,generator=g)).to(bf).to(DEV); w=(torch.randn(2*d+2*gq,d,generator=g)*d**-0.5).to(bf).to(DEV)
 y=torch.empty(M,2*d+2*gq,dtype=bf,device=DEV)
 flops=2*M*(2*d+2*gq)*d
-for bit,tag in ((0,"default (k_qkv256)"),(32768,"k_gemm_k256"),(16384|512,"general-K 256x256"),(16384|1024,"general-K 128/160-token tiles")):
+for bit,tag in ((0,"default (k_qkv256)"),(_lib.DBG_QKV256_OFF,"k_gemm_k256"),(_lib.DBG_K256_GENERAL|_lib.DBG_GEMM_T256,"general-K 256x256"),(_lib.DBG_K256_GENERAL|_lib.DBG_GEMM_NO_T256,"general-K 128/160-token tiles")):
     lib.ttv_debug_set(bit)
     call=lambda: lib.ttv_linear_qkv_rope(x.data_ptr(),d,w.data_ptr(),d,y.data_ptr(),2*d+2*gq,M,d,gq,plan.rope_cs.data_ptr(),code,ST)
     for _ in range(3): _lib.check(call(),"qkv")

@@ -67,6 +67,18 @@ def test_struct_layouts_match_header():
         assert fields == [f[0] for f in cls._fields_], struct
 
 
+def test_debug_bits_match_header():
+    # the TTV_DBG_* enum beside ttv_debug_set and _lib.DBG_*: the same names with the same values, in the same order
+    src = open(HEADER).read()
+    body = re.search(r"enum \{([^}]*TTV_DBG_[^}]*)\};", src).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    header = [(n, int(v)) for n, v in re.findall(r"\bTTV_DBG_([A-Z0-9_]+)\s*=\s*(\d+)", body)]
+    assert len(header) >= 20 and len(header) == body.count("TTV_DBG_")
+    mirror = [(k[4:], v) for k, v in vars(_lib).items() if k.startswith("DBG_")]
+    assert mirror == header
+    assert all(v > 0 and v & (v - 1) == 0 for _, v in header), "every name is one bit"
+
+
 def test_invalid_arguments_return_codes_without_touching_the_gpu(handle):
     d = _lib.TowerDims(kind=0, dtype=7)
     b = _lib.Batch()

@@ -71,7 +71,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 BF = torch.bfloat16
 GATE, PAIRED, QSCALED, ALLFULL, PIPE, SPLIT3 = 1, 2, 4, 8, 16, 32
-NO_SWP = 1048576                    # ttv_debug_set bit 20: ttvk_attention keeps k_attn_bf16 where it would take k_attn_swp
+NO_SWP = _lib.DBG_ATTN_NO_SWP      # ttv_debug_set bit 20: ttvk_attention keeps k_attn_bf16 where it would take k_attn_swp
 TOL = dict(FWD_TOL, split3=(FWD_TOL["f32"][0] * 2.0 ** 7, FWD_TOL["f32"][1] * 2.0 ** 7))
 HEADS = [(4, 2), (8, 2), (12, 4)]
 
@@ -366,7 +366,7 @@ def test_to_qkv_rope_width_256_per_tile(M):
     xd, wd = x.to(DEV), w.to(DEV)
     outs = []
     try:
-        for bits in (0, 1 << 15):
+        for bits in (0, _lib.DBG_QKV256_OFF):
             y = torch.full((M + 1, NQ), float("nan"), dtype=BF, device=DEV)
             L().ttv_debug_set(bits)
             _lib.check(L().ttv_linear_qkv_rope(xd.data_ptr(), D, wd.data_ptr(), D, y.data_ptr(), NQ, M, D, GQ, plan.rope_cs.data_ptr(),
@@ -392,7 +392,7 @@ def test_mlp_fused_width_256_per_tile(M, keel, deal9):
     y[:M] = x.to(DEV)
     pack = torch.empty(L().ttv_mlp_pack_bytes(INNER, 0), dtype=torch.uint8, device=DEV)
     _lib.check(L().ttv_mlp_pack(w12d.data_ptr(), w3d.data_ptr(), None, None, 0, INNER, D, _lib.TTV_BF16, pack.data_ptr(), S()), "mlp_pack")
-    L().ttv_debug_set(512 if deal9 else 0)
+    L().ttv_debug_set(_lib.DBG_MLP_TILES9 if deal9 else 0)
     try:
         _lib.check(L().ttv_mlp_fused(y.data_ptr(), D, pack.data_ptr(), INNER, y.data_ptr(), D, pgd.data_ptr() if keel else None,
                                      8.0 if keel else 1.0, EPS, M, D, _lib.TTV_BF16, S()), "mlp_fused")
@@ -426,7 +426,7 @@ def test_layer_tail_fused_width_256_per_tile(M, keel, back, deal9):
     qkv = torch.full((M + 1, NQ), float("nan"), dtype=BF, device=DEV)
     nx = _lib.NextQkv(qkv=qkv.data_ptr(), ld=NQ, rope_cs=csd.data_ptr(), rows=NQ, rope_q_end=D, rope_k_begin=2 * D, rope_k_end=2 * D + GQ)
     alpha = 8.0 if keel else 1.0
-    L().ttv_debug_set(512 if deal9 else 0)
+    L().ttv_debug_set(_lib.DBG_MLP_TILES9 if deal9 else 0)
     try:
         _lib.check(L().ttv_layer_tail_fused(aod.data_ptr(), D, agd.data_ptr() if keel else None, alpha, y.data_ptr(), D, pack.data_ptr(), INNER,
                                             y.data_ptr(), D, pgd.data_ptr() if keel else None, alpha, EPS, M, D, _lib.TTV_BF16,

@@ -316,7 +316,7 @@ def test_mx_quantisation_fused_into_the_producers_is_bit_identical():
     m = m.to(DEV, torch.bfloat16).eval()
     m.encoder.fp8_linears = m.decoder.fp8_linears = "mx"
     outs = []
-    for bit in (0, 2048):
+    for bit in (0, _lib.DBG_MX_UNFUSED_QUANT):
         _lib.lib().ttv_debug_set(bit)
         try:
             with torch.no_grad():
@@ -359,7 +359,7 @@ def test_mx_tower_layer_off_the_mx_path_reads_the_folded_bf16_weights_not_the_mx
     m.encoder.fp8_linears = m.decoder.fp8_linears = "mx"
     clips = [c.to(DEV, torch.bfloat16) for c in clips_cpu]
     outs = {}
-    for bits in (0, 1 << 19):
+    for bits in (0, 1 << 19):      # _lib.DBG_ENC_ALL_ROWS (the results below are keyed by the value)
         _lib.lib().ttv_debug_set(bits)
         try:
             with torch.no_grad():

@@ -215,7 +215,7 @@ def test_linear_general_k_tile_heights(shape, tile):
     x, w, g = _lin_inputs(M, N, K, "bf16", M + N)
     y = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=DEV)
     xd, wd = x.to(DEV), w.to(DEV)
-    L().ttv_debug_set(128 if tile == 160 else 256)
+    L().ttv_debug_set(_lib.DBG_GEMM_TILE160 if tile == 160 else _lib.DBG_GEMM_TILE128)
     try:
         _lib.check(L().ttv_linear(xd.data_ptr(), K, wd.data_ptr(), K, None, None, y.data_ptr(), N, M, N, K, _lib.dtype_code(torch.bfloat16), S()), "linear")
         torch.cuda.synchronize()
@@ -233,7 +233,7 @@ def test_linear_256x256_tiles(case, M):
     bf = torch.bfloat16
     code = _lib.dtype_code(bf)
     outs = []
-    for bit in (512, 1024):
+    for bit in (_lib.DBG_GEMM_T256, _lib.DBG_GEMM_NO_T256):
         L().ttv_debug_set(bit)
         try:
             if case == "store":
@@ -294,7 +294,7 @@ def test_linear_256x256_tiles_short_k(K, M):
     xd, wd = x.to(DEV), w.to(DEV)
     code = _lib.dtype_code(torch.bfloat16)
     outs = []
-    for bit in (512, 1024):
+    for bit in (_lib.DBG_GEMM_T256, _lib.DBG_GEMM_NO_T256):
         y = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=DEV)
         L().ttv_debug_set(bit)
         try:
@@ -317,9 +317,9 @@ def test_linear_256x256_tiles_repeatable():
     y0 = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
     y1 = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
     try:
-        L().ttv_debug_set(1024)
+        L().ttv_debug_set(_lib.DBG_GEMM_NO_T256)
         _lib.check(L().ttv_linear(xd.data_ptr(), K, wd.data_ptr(), K, None, None, y0.data_ptr(), N, M, N, K, code, S()), "linear")
-        L().ttv_debug_set(512)
+        L().ttv_debug_set(_lib.DBG_GEMM_T256)
         for _ in range(40):
             y1.fill_(float("nan"))
             _lib.check(L().ttv_linear(xd.data_ptr(), K, wd.data_ptr(), K, None, None, y1.data_ptr(), N, M, N, K, code, S()), "linear")
@@ -374,7 +374,7 @@ def test_to_qkv_width256_kernels_give_the_same_bits(shape):
     xd, wd = x.to(DEV), w.to(DEV)
     outs = []
     try:
-        for bits in (0, 1 << 15, 1 << 17):
+        for bits in (0, _lib.DBG_QKV256_OFF, _lib.DBG_QKV256_WS):
             y = torch.full((M, 2 * d + 2 * gq), float("nan"), dtype=torch.bfloat16, device=DEV)
             L().ttv_debug_set(bits)
             _lib.check(L().ttv_linear_qkv_rope(xd.data_ptr(), d, wd.data_ptr(), d, y.data_ptr(), 2 * d + 2 * gq, M, d, gq,
@@ -460,7 +460,7 @@ def test_mlp_fused(M, keel, I, deal9):
     assert pack.numel() == (I // 32) * 48 * 1024 + 128 * 1024
     _lib.check(L().ttv_mlp_pack(w12d.data_ptr(), w3d.data_ptr(), None, None, 0, I, d, _lib.TTV_BF16, pack.data_ptr(), S()), "mlp_pack")
     alpha = 8.0 if keel else 1.0
-    L().ttv_debug_set(512 if deal9 else 0)
+    L().ttv_debug_set(_lib.DBG_MLP_TILES9 if deal9 else 0)
     try:
         _lib.check(L().ttv_mlp_fused(xd.data_ptr(), d, pack.data_ptr(), I, xd.data_ptr(), d,
                                      pgd.data_ptr() if keel else None, alpha, 1e-5, M, d, _lib.TTV_BF16, S()), "mlp_fused")
@@ -515,7 +515,7 @@ def test_layer_tail_fused(M, keel, back):
     qkv = torch.zeros(M, nq, dtype=torch.bfloat16, device=DEV)
     nx = _lib.NextQkv(qkv=qkv.data_ptr(), ld=nq, rope_cs=csd.data_ptr(), rows=nq, rope_q_end=d, rope_k_begin=2 * d, rope_k_end=2 * d + gq)
     alpha = 8.0 if keel else 1.0
-    L().ttv_debug_set(512 if deal9 else 0)
+    L().ttv_debug_set(_lib.DBG_MLP_TILES9 if deal9 else 0)
     try:
         _lib.check(L().ttv_layer_tail_fused(aod.data_ptr(), d, agd.data_ptr() if keel else None, alpha, xd.data_ptr(), d, pack.data_ptr(), I,
                                             xd.data_ptr(), d, pgd.data_ptr() if keel else None, alpha, 1e-5, M, d, _lib.TTV_BF16,
@@ -860,7 +860,7 @@ def test_linear_f32_lds_dma_staging_is_bit_identical(shape):
     b = (torch.randn(N, generator=g) * 0.1)
     xd, wd, bd = x.to(DEV), w.to(DEV), b.to(DEV)
     outs = []
-    for bit in (0, 8192):
+    for bit in (0, _lib.DBG_SPLIT3_NO_DMA):
         y = torch.full((M, N), float("nan"), device=DEV)
         L().ttv_debug_set(bit)
         try:

@@ -237,7 +237,7 @@ def test_to_qkv_kernels_agree_inside_the_towers():
     lib = _lib.lib()
     outs = []
     try:
-        for bits in (0, 1 << 15, 1 << 17):
+        for bits in (0, _lib.DBG_QKV256_OFF, _lib.DBG_QKV256_WS):
             lib.ttv_debug_set(bits)
             with torch.no_grad():
                 recon, out = model(clips, counts)
@@ -276,7 +276,7 @@ def test_encoder_last_layer_on_latent_rows_only_changes_no_bit(mode):
     lib = _lib.lib()
     outs = []
     try:
-        for bits in (0, 1 << 19):
+        for bits in (0, _lib.DBG_ENC_ALL_ROWS):
             lib.ttv_debug_set(bits)
             with torch.no_grad():
                 codes, info = model.encode(clips, counts, want_bounded=True)
@@ -311,7 +311,7 @@ def test_decoder_last_layer_without_latent_only_query_blocks_changes_no_bit(monk
         codes, info = model.encode(clips, counts)
     outs = []
     try:
-        for bits in (0, 1 << 21):
+        for bits in (0, _lib.DBG_DEC_ALL_BLOCKS):
             lib.ttv_debug_set(bits)
             with torch.no_grad():
                 recon = model.decode(codes, counts, shapes)

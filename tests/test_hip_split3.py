@@ -188,7 +188,7 @@ def test_split_images_written_by_the_producers_change_no_bit():
     model.load_state_dict(sd, strict=True)
     model = model.to(DEV, torch.float32).eval().set_index_exact("split3")
     outs = []
-    for bit in (0, 8192, 4096):      # default (images + LDS-DMA GEMM) | images, register-staged GEMM | fp32 activations, split in the GEMM
+    for bit in (0, _lib.DBG_SPLIT3_NO_DMA, _lib.DBG_SPLIT3_NO_IMAGES):      # default (images + LDS-DMA GEMM) | images, register-staged GEMM | fp32 activations, split in the GEMM
         L().ttv_debug_set(bit)
         try:
             with torch.no_grad():

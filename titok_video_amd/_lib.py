@@ -11,15 +11,44 @@ import threading
 
 import torch
 
+from . import switches
+
 TTV_BF16, TTV_F32 = 0, 1
 TTV_ENCODER, TTV_DECODER = 0, 1
 TTV_MAX_FSQ = 8
 TTV_MAX_TOKEN = 64
 TTV_MAX_CLIPS_PER_LAUNCH = 64
 
+# ttv_debug_set bits: the TTV_DBG_* enum of include/titok_hip.h under the same names (tests/test_cabi_cpu.py holds the two equal).
+# A value with two names is read by two kernels with two meanings; tools/README.md says what each bit forces.
+DBG_NO_STORES = 1
+DBG_K256_NO_PANEL_DMA = 2
+DBG_MLP_NO_WEIGHT_DMA = 2
+DBG_K256_NO_TILE_RELOAD = 4
+DBG_MLP_NO_GEGLU = 4
+DBG_K256_NO_EPILOGUE_MATH = 8
+DBG_MLP_TILES8 = 8
+DBG_MLP_NO_P2 = 16
+DBG_MLP_PAIRS_ONLY = 32
+DBG_MLP_TILES4 = 64
+DBG_GEMM_TILE160 = 128
+DBG_GEMM_TILE128 = 256
+DBG_GEMM_T256 = 512
+DBG_MLP_TILES9 = 512
+DBG_GEMM_NO_T256 = 1024
+DBG_MX_UNFUSED_QUANT = 2048
+DBG_SPLIT3_NO_IMAGES = 4096
+DBG_SPLIT3_NO_DMA = 8192
+DBG_K256_GENERAL = 16384
+DBG_QKV256_OFF = 32768
+DBG_QKV256_WS = 131072
+DBG_ENC_ALL_ROWS = 524288
+DBG_ATTN_NO_SWP = 1048576
+DBG_DEC_ALL_BLOCKS = 2097152
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # TTV_LIB_PATH: diagnostics only (an instrumented build of the same sources, tools/attn_stamps.py)
-LIB_PATH = os.environ.get("TTV_LIB_PATH") or os.path.join(_HERE, "libtitok_hip.so")
+LIB_PATH = switches.text("TTV_LIB_PATH") or os.path.join(_HERE, "libtitok_hip.so")
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 

@@ -19,6 +19,12 @@ void ttv_set_error(const char* fmt, ...) {
 
 // ---- measurement hook ----
 int g_ttv_prof_class = 0;
+// The switches that more than one site reads (declared in ttv_common.h): name and default live here, the sites cache the value.
+bool ttv_sw_enc_latent_last() { static const bool v = ttv_env_flag("TTV_ENC_LATENT_LAST", true); return v; }
+bool ttv_sw_keel_f32sum() { static const bool v = ttv_env_flag("TTV_KEEL_F32SUM", false); return v; }
+bool ttv_sw_fused_patch() { static const bool v = ttv_env_flag("TTV_FUSED_PATCH", true); return v; }
+bool ttv_sw_attn_pipe() { static const bool v = ttv_env_flag("TTV_ATTN_PIPE", false); return v; }
+float ttv_sw_attn_thr() { static const float v = ttv_env_float("TTV_ATTN_THR", 8.0f); return v; }   // log2 units; 0 = exact running maximum
 thread_local int g_ttv_debug = 0;     // per host thread: a thread that forces a kernel variant (tests, A/B tools) does not change what another thread launches
 long long* g_ttv_stamps = nullptr;   // diagnostics: device buffer for in-kernel clock stamps (ttv_debug_stamps)
 static hipEvent_t* g_prof_start = nullptr;
@@ -104,8 +110,8 @@ static int run_layer_mx(const ttv_tower_dims* d, const ttv_layer_weights& lw, co
   // pass of its own, A/B): the KEEL post-norm kernel writes x also as its block-scaled image (ws.f8 / ws.f8mx), the w12 GEMM's GEGLU
   // epilogue writes h only as its image (into the bf16 h buffer and the xn buffer, both unused in this mode).  Left as passes: the
   // attention output (its kernel is untouched) and layer 0's two inputs (no norm kernel in front of them).
-  static const bool fused_env = !(getenv("TTV_MX_FUSED_QUANT") && getenv("TTV_MX_FUSED_QUANT")[0] == '0');
-  const bool fused_q = fused_env && !(g_ttv_debug & 2048);      // ttv_debug_set bit 11: the unfused sequence (tests: both must agree bit for bit)
+  static const bool fused_env = ttv_env_flag("TTV_MX_FUSED_QUANT", true);
+  const bool fused_q = fused_env && !(g_ttv_debug & TTV_DBG_MX_UNFUSED_QUANT);      // ttv_debug_set bit 11: the unfused sequence (tests: both must agree bit for bit)
   if (!rstd_valid) TTV_TRY(ttvk_row_rstd(ws.x, dt, dm, ws.rstd, L, dm, d->eps, s));
   if (!xq_valid) TTV_TRY(ttvk_quant_mx_fp8(ws.x, dt, dm, ws.f8, dm, ws.f8mx, nullptr, L, dm, s));
   xq_valid = false;
@@ -173,6 +179,84 @@ static bool rows_f8(int dt, int dm, const void* img, const void* row_scale, cons
   return dt == TTV_BF16 && img && row_scale && !mx && dm % 128 == 0 && !(dm == 256 && folded);
 }
 
+// What run_layers decides once per call and its two helpers below read.
+struct LayerCtx {
+  const ttv_tower_dims* d; const ttv_batch* b; const TowerWs& ws; hipStream_t s;
+  int split3, s3img;   // fp32 tower on the three-pass bf16 kernels / its activations travel as split images
+  bool gen_ok;         // a folded pre-norm may take its row statistic as the GEMM's row scale (wide bf16 towers, split-bf16 towers)
+};
+
+// A pre-normed projection's weight in every form a tower may carry: plain, with the pre-norm gain folded in (NULL: not packed),
+// and the row-scaled e4m3 image (f8: use it, see rows_f8).
+struct PreNormW { const float* gain; const void *w, *w_pn, *w_f8; const float* w_f8_scale; bool f8; };
+
+// y[rows, N] = epilogue(RMSNorm(x) * gain @ W^T): to_qkv (EPI_QKV_ROPE) and w12 (EPI_GEGLU).  Routes: the row-scaled fp8 image (mixed
+// bf16 / fp8, config #5: the pre-norm output is quantised to e4m3 per token into the xn buffer - L x dm bytes of values, then L fp32
+// scales - and the projection runs on the fp8 MFMA); the width-256 kernel's folded pre-norm; other widths with the gain folded into
+// the weight as well (w_pn) and the row statistic - from the kernel that produced x (rstd_valid) or from one light pass - multiplying
+// the GEMM's output rows, so no stand-alone RMSNorm launch and no normalised copy of x; else RMSNorm into xn, then the plain weight.
+// Split-bf16 towers: the normalised row is written as the projection's split image (its producer splits it once, the GEMM's staging
+// threads copy bytes); TTV_SPLIT3_IMAGES=0 keeps fp32 activations and the split in the GEMM (A/B).
+static int prenorm_proj(const LayerCtx& c, GemmEpilogue epi, const char* x, int rows, const PreNormW& p, int N, char* y, int y_image,
+                        bool rstd_valid) {
+  const ttv_tower_dims* d = c.d;
+  const TowerWs& ws = c.ws;
+  const int dm = d->width, dt = d->dtype;
+  GemmArgs a = {};
+  a.dtype = dt; a.ldx = dm; a.ldw = dm; a.M = rows; a.N = N; a.K = dm; a.y = y; a.ldy = N;
+  if (epi == EPI_QKV_ROPE) {
+    a.rope_cs = c.b->rope_cs; a.rope_q_end = dm; a.rope_k_begin = 2 * dm; a.rope_k_end = 2 * dm + d->kv_heads * d->head_dim;
+  }
+  if (p.f8) {
+    float* const f8_scales = reinterpret_cast<float*>(ws.xn + (((size_t)c.b->total_rows * dm + 255) & ~(size_t)255));
+    TTV_TRY(ttvk_quant_rows_fp8(x, dt, dm, p.gain, d->eps, ws.xn, dm, f8_scales, rows, dm, c.s));
+    a.x = ws.xn; a.w = p.w_f8;
+    return ttvk_gemm_fp8(epi, a, f8_scales, p.w_f8_scale, c.s);
+  }
+  const bool fold256 = dt == TTV_BF16 && dm == 256 && p.w_pn;
+  const bool fold_gen = c.gen_ok && p.w_pn;
+  const bool fold = fold256 || fold_gen;
+  if (fold_gen && !rstd_valid) TTV_TRY(ttvk_row_rstd(x, dt, dm, ws.rstd, rows, dm, d->eps, c.s));
+  if (!fold) TTV_TRY(ttvk_rmsnorm(x, dt, dm, nullptr, ws.xn, dt, dm, nullptr, p.gain, rows, dm, d->eps, c.s, nullptr, nullptr, nullptr, c.s3img));
+  a.split3 = c.split3; a.x_image = c.s3img && !fold; a.y_image = y_image;
+  a.prenorm = fold256; a.eps = d->eps;
+  a.row_scale = fold_gen ? ws.rstd : nullptr;
+  a.x = fold ? x : ws.xn; a.w = fold ? p.w_pn : p.w;
+  if (epi == EPI_QKV_ROPE) { a.rope_ids = c.b->rope_ids; a.rope_base = c.b->rope_ids ? c.b->rope_base : nullptr; }
+  return ttvk_gemm(epi, a, c.s);
+}
+
+// The tail of a KEEL sub-layer (out_proj and w3): x <- RMSNorm(alpha * x + in @ W^T) * gain, in place on the rows of cx; layer 0 has
+// no norm and alpha = 1.  `o` arrives with operand, weight, shapes and the residual set.  Width 256 does it in one kernel
+// (EPI_RESID_NORM; in place is safe: a token row is read as residual and written by the same wave only).  Wide towers: the sum leaves
+// the GEMM through HBM and a row kernel normalises it.  bf16 towers store it in the compute dtype, in place on x (a token row element
+// is read as residual and written by the same lane) - the reference's autocast rounds that sum to bf16 as well (transformer.py:141:
+// bf16 * alpha + bf16) -: half the bytes of the fp32 buffer on both kernels.  fp32 towers, and TTV_KEEL_F32SUM=1 (A/B), keep the fp32
+// buffer.  want_rstd: the row kernel also leaves the statistic of the row it wrote in ws.rstd, for a folded pre-norm behind it;
+// rstd_valid is set to it on that route and left alone on the others.
+static int keel_tail(const LayerCtx& c, GemmArgs o, int layer, const float* post_gain, char* cx, bool want_rstd, bool& rstd_valid) {
+  const ttv_tower_dims* d = c.d;
+  const int dm = d->width, dt = d->dtype;
+  static const bool keel_f32sum = ttv_sw_keel_f32sum();
+  o.alpha = layer == 0 ? 1.f : d->alpha; o.y = cx; o.ldy = dm;
+  if (layer == 0) return ttvk_gemm(EPI_RESID_T, o, c.s);
+  if (ttvk_gemm_supports_resid_norm(dt, dm, o.K)) {
+    o.norm_gain = post_gain; o.eps = d->eps;
+    return ttvk_gemm(EPI_RESID_NORM, o, c.s);
+  }
+  float* const next_rstd = want_rstd ? c.ws.rstd : nullptr;
+  if (dt == TTV_BF16 && !keel_f32sum) {
+    TTV_TRY(ttvk_gemm(EPI_RESID_T, o, c.s));
+    TTV_TRY(ttvk_rmsnorm(cx, dt, dm, nullptr, cx, dt, dm, nullptr, post_gain, o.M, dm, d->eps, c.s, next_rstd));
+  } else {
+    o.y = c.ws.y32;
+    TTV_TRY(ttvk_gemm(EPI_RESID_F32, o, c.s));
+    TTV_TRY(ttvk_rmsnorm(c.ws.y32, TTV_F32, dm, nullptr, cx, dt, dm, nullptr, post_gain, o.M, dm, d->eps, c.s, next_rstd));
+  }
+  rstd_valid = want_rstd;
+  return TTV_OK;
+}
+
 // One ResidualAttentionBlock stack (reference transformer.py:126-146) on ws.x in place.
 static int run_layers(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_batch* b, const TowerWs& ws, hipStream_t s) {
   const int L = b->total_rows, dm = d->width, g = d->kv_heads * d->head_dim, dt = d->dtype;
@@ -180,30 +264,31 @@ static int run_layers(const ttv_tower_dims* d, const ttv_tower_weights* w, const
   // pre-norm gains folded into the weight (to_qkv_pn / w12_pn) with the row statistic applied to the GEMM's output rows: the wide bf16
   // towers, and the split-bf16 towers of any width (their weights are repacked anyway; the exact-fp32 towers keep the reference's order)
   const bool gen_ok = (dt == TTV_BF16 && dm != 256) || split3;
-  static const bool s3img_env = !(getenv("TTV_SPLIT3_IMAGES") && getenv("TTV_SPLIT3_IMAGES")[0] == '0');
-  const int s3img = (split3 && s3img_env && !(g_ttv_debug & 4096)) ? 1 : 0;     // ttv_debug_set bit 12: fp32 activations, split inside the GEMMs (tests)
+  static const bool s3img_env = ttv_env_flag("TTV_SPLIT3_IMAGES", true);
+  const int s3img = (split3 && s3img_env && !(g_ttv_debug & TTV_DBG_SPLIT3_NO_IMAGES)) ? 1 : 0;     // ttv_debug_set bit 12: fp32 activations, split inside the GEMMs (tests)
   const int nq = 2 * dm + 2 * g;
   bool qkv_ready = false;   // the previous layer's tail kernel already produced this layer's rotated qkv
   bool rstd_valid = false;  // ws.rstd holds rsqrt(mean(x^2) + eps) of the current ws.x (written by the kernel that produced x)
   bool xq_valid = false;    // ws.f8 / ws.f8mx hold the block-scaled e4m3 image of the current ws.x (run_layer_mx)
-  static const bool attn_pipe = getenv("TTV_ATTN_PIPE") && getenv("TTV_ATTN_PIPE")[0] == '1';   // opt-in pipelined attention kernel
+  static const bool attn_pipe = ttv_sw_attn_pipe();   // opt-in pipelined attention kernel
   // The encoder's output is its latent rows (blocks.py:101-103): with the batch's latent-query table the LAST layer runs its attention for
   // those query rows only and everything behind the attention on the sum K_b latent rows, gathered into compact buffers (ws.xl, ws.aol) and
   // scattered back into ws.x at the end.  Row-wise kernels on other rows: the values of the rows that are read are the same bits.
   // TTV_ENC_LATENT_LAST=0: every row, as the reference computes it (A/B, tests).  Not for the block-scaled fp8 layers (run_layer_mx).
-  static const bool lat_env = !(getenv("TTV_ENC_LATENT_LAST") && getenv("TTV_ENC_LATENT_LAST")[0] == '0');
-  const bool lat_last = lat_env && !(g_ttv_debug & 524288) && d->kind == TTV_ENCODER && b->qblocks_latent && b->n_qblocks_latent > 0 &&
+  static const bool lat_env = ttv_sw_enc_latent_last();
+  const bool lat_last = lat_env && !(g_ttv_debug & TTV_DBG_ENC_ALL_ROWS) && d->kind == TTV_ENCODER && b->qblocks_latent && b->n_qblocks_latent > 0 &&
                         b->latent_rows && b->sum_tokens > 0 && b->sum_tokens < L;
   // The decoder's output is its patch rows (blocks.py:171): with the batch's patch-query table the LAST layer's attention skips the query
   // blocks that hold latent rows only.  Their rows of ws.ao keep the previous layer's values (finite), everything behind the attention
   // is row-wise, the tail gathers patch rows: no patch row changes a bit.  TTV_DEC_PATCH_LAST=0 / debug bit 21: every block (A/B, tests).
-  static const bool pat_env = !(getenv("TTV_DEC_PATCH_LAST") && getenv("TTV_DEC_PATCH_LAST")[0] == '0');
-  const bool pat_last = pat_env && !(g_ttv_debug & 2097152) && d->kind == TTV_DECODER && d->layers >= 2 && b->qblocks_patch &&
+  static const bool pat_env = ttv_env_flag("TTV_DEC_PATCH_LAST", true);
+  const bool pat_last = pat_env && !(g_ttv_debug & TTV_DBG_DEC_ALL_BLOCKS) && d->kind == TTV_DECODER && d->layers >= 2 && b->qblocks_patch &&
                         b->n_qblocks_patch > 0 && !split3 && !b->qblocks_paired;
   bool compacted = false;
+  const LayerCtx ctx = {d, b, ws, s, split3, s3img, gen_ok};
   for (int i = 0; i < d->layers; ++i) {
     const ttv_layer_weights& lw = w->layers[i];
-    static const bool keel_f32 = getenv("TTV_KEEL_F32SUM") && getenv("TTV_KEEL_F32SUM")[0] == '1';
+    static const bool keel_f32 = ttv_sw_keel_f32sum();
     if (dt == TTV_BF16 && dm != 256 && dm % 128 == 0 && d->inner % 128 == 0 && !keel_f32 && lw.to_qkv_f8 && lw.to_qkv_mx && lw.w12_f8 && lw.w12_mx &&
         lw.out_proj_f8 && lw.out_proj_mx && lw.w3_f8 && lw.w3_mx &&
         !(lat_last && i == d->layers - 1)) {    // the encoder's last layer: its latent rows on the bf16 kernels instead (a ninth of the rows)
@@ -213,39 +298,16 @@ static int run_layers(const ttv_tower_dims* d, const ttv_tower_weights* w, const
     }
     xq_valid = false;
     // ---- attention sub-layer (transformer.py:85-104) ----
-    // mixed bf16 / fp8 (config #5): the pre-norm output is quantised to e4m3 per token (into the xn buffer: L x dm bytes of values,
-    // then L fp32 scales) and the projection runs on the fp8 MFMA; everything downstream is unchanged
+    // mixed bf16 / fp8 (config #5): to_qkv and w12 run on the row-scaled fp8 image (prenorm_proj); everything downstream is unchanged.
     // NOT when the images are the block-scaled ones (to_qkv_mx / w12_mx set: e4m3 of W * gain divided by the row factor AND the per-32
     // E8M0 scales, which only run_layer_mx's GEMMs undo): a layer of an MX tower that lands here - the encoder's latent-only last layer,
     // every layer under TTV_KEEL_F32SUM=1 - runs its projections on the bf16 kernels from the folded weights
     const bool f8_qkv = rows_f8(dt, dm, lw.to_qkv_f8, lw.to_qkv_f8_scale, lw.to_qkv_mx, lw.to_qkv_pn);
     const bool f8_w12 = rows_f8(dt, dm, lw.w12_f8, lw.w12_f8_scale, lw.w12_mx, lw.w12_pn);
-    float* const f8_scales = reinterpret_cast<float*>(ws.xn + (((size_t)L * dm + 255) & ~(size_t)255));
-    if (!qkv_ready && f8_qkv) {
-      TTV_TRY(ttvk_quant_rows_fp8(ws.x, dt, dm, lw.pre_ln, d->eps, ws.xn, dm, f8_scales, L, dm, s));
-      GemmArgs a = {};
-      a.dtype = dt; a.x = ws.xn; a.ldx = dm; a.w = lw.to_qkv_f8; a.ldw = dm; a.M = L; a.N = nq; a.K = dm; a.y = ws.qkv; a.ldy = nq;
-      a.rope_cs = b->rope_cs; a.rope_q_end = dm; a.rope_k_begin = 2 * dm; a.rope_k_end = 2 * dm + g;
-      TTV_TRY(ttvk_gemm_fp8(EPI_QKV_ROPE, a, f8_scales, lw.to_qkv_f8_scale, s));
-    } else if (!qkv_ready) {
-      const bool fold_qkv = dt == TTV_BF16 && dm == 256 && lw.to_qkv_pn;
-      // other widths: the gain is folded into the weight as well (to_qkv_pn), the row statistic comes from the kernel that
-      // produced x (the KEEL post-norm below writes it) or from one light pass, and multiplies the GEMM's output rows - no
-      // stand-alone RMSNorm launch, no normalised copy of x
-      const bool fold_gen = gen_ok && lw.to_qkv_pn;
-      if (fold_gen && !rstd_valid) TTV_TRY(ttvk_row_rstd(ws.x, dt, dm, ws.rstd, L, dm, d->eps, s));
-      // split-bf16 towers: the normalised row is written as the projection's split image (its producer splits it once, the GEMM's
-      // staging threads copy bytes); TTV_SPLIT3_IMAGES=0 keeps fp32 activations and the split in the GEMM (A/B)
-      if (!fold_qkv && !fold_gen) TTV_TRY(ttvk_rmsnorm(ws.x, dt, dm, nullptr, ws.xn, dt, dm, nullptr, lw.pre_ln, L, dm, d->eps, s, nullptr, nullptr, nullptr, s3img));
-      GemmArgs a = {};
-      a.dtype = dt; a.split3 = split3; a.x_image = s3img && !fold_qkv && !fold_gen; a.y_image = s3img ? 2 : 0;
-      a.prenorm = fold_qkv; a.eps = d->eps;
-      a.row_scale = fold_gen ? ws.rstd : nullptr;
+    if (!qkv_ready) {
       const void* w_plain = (dt == TTV_BF16 && lw.to_qkv_qs) ? lw.to_qkv_qs : lw.to_qkv;   // inference copy with scaled q rows, if packed
-      a.x = (fold_qkv || fold_gen) ? ws.x : ws.xn; a.ldx = dm; a.w = (fold_qkv || fold_gen) ? lw.to_qkv_pn : w_plain; a.ldw = dm; a.M = L; a.N = nq; a.K = dm; a.y = ws.qkv; a.ldy = nq;
-      a.rope_cs = b->rope_cs; a.rope_q_end = dm; a.rope_k_begin = 2 * dm; a.rope_k_end = 2 * dm + g;
-      a.rope_ids = b->rope_ids; a.rope_base = b->rope_ids ? b->rope_base : nullptr;
-      TTV_TRY(ttvk_gemm(EPI_QKV_ROPE, a, s));
+      const PreNormW qw = {lw.pre_ln, w_plain, lw.to_qkv_pn, lw.to_qkv_f8, lw.to_qkv_f8_scale, f8_qkv};
+      TTV_TRY(prenorm_proj(ctx, EPI_QKV_ROPE, ws.x, L, qw, nq, ws.qkv, s3img ? 2 : 0, rstd_valid));
     }
     // q arrives pre-scaled when the projection used the folded weight whose q rows carry scale * log2(e)
     const bool q_scaled = dt == TTV_BF16 && (lw.to_qkv_pn ? lw.qkv_q_prescaled != 0 : lw.to_qkv_qs != nullptr);
@@ -284,9 +346,8 @@ static int run_layers(const ttv_tower_dims* d, const ttv_tower_weights* w, const
     // TTV_FUSED_QKV=1 additionally folds the NEXT layer's QKV projection + rotary into the tail kernel: correct and tested,
     // but measured 3 % slower end to end than the stand-alone QKV kernel (the phase runs on the 192 CUs / uneven wave pairs
     // of the tail kernel: 31 us against 35 us stand-alone in isolation, worse in the pipeline), so it is opt-in.
-    static const bool keel_f32sum = getenv("TTV_KEEL_F32SUM") && getenv("TTV_KEEL_F32SUM")[0] == '1';
-    static const bool use_fused_mlp = !(getenv("TTV_FUSED_MLP") && getenv("TTV_FUSED_MLP")[0] == '0');
-    static const bool use_fused_qkv = getenv("TTV_FUSED_QKV") && getenv("TTV_FUSED_QKV")[0] == '1';
+    static const bool use_fused_mlp = ttv_env_flag("TTV_FUSED_MLP", true);
+    static const bool use_fused_qkv = ttv_env_flag("TTV_FUSED_QKV", false);
     if (use_fused_mlp && ttvk_mlp_fused_supported(dt, dm, d->inner) && lw.mlp_pack) {
       // one kernel for the rest of the layer: out_proj + residual/KEEL norm, then pre-norm + w12 + GEGLU + w3 +
       // residual/KEEL norm, in place on x, and (when the pack carries it) the NEXT layer's pre_ln + to_qkv + rotary
@@ -301,74 +362,18 @@ static int run_layers(const ttv_tower_dims* d, const ttv_tower_weights* w, const
     GemmArgs o = {};
     o.dtype = dt; o.split3 = split3; o.x_image = s3img;
     o.x = cao; o.ldx = dm; o.w = lw.out_proj; o.ldw = dm; o.M = Lc; o.N = dm; o.K = dm; o.resid = cx; o.ldr = dm;
-    if (i == 0) {
-      o.alpha = 1.f; o.y = cx; o.ldy = dm;
-      TTV_TRY(ttvk_gemm(EPI_RESID_T, o, s));
-    } else if (ttvk_gemm_supports_resid_norm(dt, dm, dm)) {
-      // x <- RMSNorm(alpha*x + ao@Wo^T) * gain in one kernel; in place on x is safe: a token row is read (as residual)
-      // and written by the same wave only
-      o.alpha = d->alpha; o.y = cx; o.ldy = dm; o.norm_gain = lw.attn_post_ln; o.eps = d->eps;
-      TTV_TRY(ttvk_gemm(EPI_RESID_NORM, o, s));
-    } else {
-      // wide towers: the KEEL sum alpha * x + f(x) leaves the GEMM through HBM and a row kernel normalises it.  bf16 towers store it
-      // in the compute dtype, in place on x (a token row element is read as residual and written by the same lane) - the reference's
-      // autocast rounds that sum to bf16 as well (transformer.py:141: bf16 * alpha + bf16) -: half the bytes of the fp32 buffer on
-      // both kernels.  fp32 towers, and TTV_KEEL_F32SUM=1 (A/B), keep the fp32 buffer.
-      const bool want = gen_ok && lw.w12_pn && !f8_w12;
-      if (dt == TTV_BF16 && !keel_f32sum) {
-        o.alpha = d->alpha; o.y = cx; o.ldy = dm;
-        TTV_TRY(ttvk_gemm(EPI_RESID_T, o, s));
-        TTV_TRY(ttvk_rmsnorm(cx, dt, dm, nullptr, cx, dt, dm, nullptr, lw.attn_post_ln  , Lc, dm, d->eps, s, want ? ws.rstd : nullptr));
-      } else {
-        o.alpha = d->alpha; o.y = ws.y32; o.ldy = dm;
-        TTV_TRY(ttvk_gemm(EPI_RESID_F32, o, s));
-        TTV_TRY(ttvk_rmsnorm(ws.y32, TTV_F32, dm, nullptr, cx, dt, dm, nullptr, lw.attn_post_ln  , Lc, dm, d->eps, s, want ? ws.rstd : nullptr));
-      }
-      rstd_valid = want;
-    }
+    TTV_TRY(keel_tail(ctx, o, i, lw.attn_post_ln, cx, gen_ok && lw.w12_pn && !f8_w12, rstd_valid));
     // ---- GEGLU sub-layer (transformer.py:47-56) ----
-    const bool fold_ffd = dt == TTV_BF16 && dm == 256 && lw.w12_pn;
-    const bool fold_ffd_gen = gen_ok && lw.w12_pn && !f8_w12;
-    if (f8_w12) {
-      TTV_TRY(ttvk_quant_rows_fp8(cx, dt, dm, lw.ffd_norm, d->eps, ws.xn, dm, f8_scales, Lc, dm, s));
-      GemmArgs f = {};
-      f.dtype = dt; f.x = ws.xn; f.ldx = dm; f.w = lw.w12_f8; f.ldw = dm; f.M = Lc; f.N = d->inner; f.K = dm; f.y = ws.h; f.ldy = d->inner;
-      TTV_TRY(ttvk_gemm_fp8(EPI_GEGLU, f, f8_scales, lw.w12_f8_scale, s));
-    } else {
-    if (fold_ffd_gen && !rstd_valid) TTV_TRY(ttvk_row_rstd(cx, dt, dm, ws.rstd  , Lc, dm, d->eps, s));
-    if (!fold_ffd && !fold_ffd_gen) TTV_TRY(ttvk_rmsnorm(cx, dt, dm, nullptr, ws.xn, dt, dm, nullptr, lw.ffd_norm  , Lc, dm, d->eps, s, nullptr, nullptr, nullptr, s3img));
-    GemmArgs f = {};
-    f.dtype = dt; f.split3 = split3; f.x_image = s3img && !fold_ffd && !fold_ffd_gen; f.y_image = s3img;
-    f.prenorm = fold_ffd; f.eps = d->eps;
-    f.row_scale = fold_ffd_gen ? ws.rstd : nullptr;
-    f.x = (fold_ffd || fold_ffd_gen) ? cx : ws.xn; f.ldx = dm; f.w = (fold_ffd || fold_ffd_gen) ? lw.w12_pn : lw.w12; f.ldw = dm; f.M = Lc; f.N = d->inner; f.K = dm; f.y = ws.h; f.ldy = d->inner;
-    TTV_TRY(ttvk_gemm(EPI_GEGLU, f, s));
-    }
+    const PreNormW fw = {lw.ffd_norm, lw.w12, lw.w12_pn, lw.w12_f8, lw.w12_f8_scale, f8_w12};
+    TTV_TRY(prenorm_proj(ctx, EPI_GEGLU, cx, Lc, fw, d->inner, ws.h, s3img, rstd_valid));
     rstd_valid = false;
     GemmArgs f3 = {};
     f3.dtype = dt; f3.split3 = split3; f3.x_image = s3img;
     f3.x = ws.h; f3.ldx = d->inner; f3.w = lw.w3; f3.ldw = d->inner; f3.M = Lc; f3.N = dm; f3.K = d->inner; f3.resid = cx; f3.ldr = dm;
-    if (i == 0) {
-      f3.alpha = 1.f; f3.y = cx; f3.ldy = dm;
-      TTV_TRY(ttvk_gemm(EPI_RESID_T, f3, s));
-    } else if (ttvk_gemm_supports_resid_norm(dt, dm, d->inner)) {
-      // x <- RMSNorm(alpha*x + h@W3^T) * gain in one full-row kernel (in place: a token row is read and written by one block)
-      f3.alpha = d->alpha; f3.y = cx; f3.ldy = dm; f3.norm_gain = lw.ffd_post_ln; f3.eps = d->eps;
-      TTV_TRY(ttvk_gemm(EPI_RESID_NORM, f3, s));
-    } else {
-      const bool want = gen_ok && i + 1 < d->layers && w->layers[i + 1].to_qkv_pn &&
-                        !rows_f8(dt, dm, w->layers[i + 1].to_qkv_f8, w->layers[i + 1].to_qkv_f8_scale, w->layers[i + 1].to_qkv_mx, w->layers[i + 1].to_qkv_pn);
-      if (dt == TTV_BF16 && !keel_f32sum) {      // see the attention sub-layer above
-        f3.alpha = d->alpha; f3.y = cx; f3.ldy = dm;
-        TTV_TRY(ttvk_gemm(EPI_RESID_T, f3, s));
-        TTV_TRY(ttvk_rmsnorm(cx, dt, dm, nullptr, cx, dt, dm, nullptr, lw.ffd_post_ln  , Lc, dm, d->eps, s, want ? ws.rstd : nullptr));
-      } else {
-        f3.alpha = d->alpha; f3.y = ws.y32; f3.ldy = dm;
-        TTV_TRY(ttvk_gemm(EPI_RESID_F32, f3, s));
-        TTV_TRY(ttvk_rmsnorm(ws.y32, TTV_F32, dm, nullptr, cx, dt, dm, nullptr, lw.ffd_post_ln  , Lc, dm, d->eps, s, want ? ws.rstd : nullptr));
-      }
-      rstd_valid = want;
-    }
+    // the next layer's to_qkv takes the row statistic when it runs with the folded weight on the bf16 kernels
+    const bool next_rstd = gen_ok && i + 1 < d->layers && w->layers[i + 1].to_qkv_pn &&
+                           !rows_f8(dt, dm, w->layers[i + 1].to_qkv_f8, w->layers[i + 1].to_qkv_f8_scale, w->layers[i + 1].to_qkv_mx, w->layers[i + 1].to_qkv_pn);
+    TTV_TRY(keel_tail(ctx, f3, i, lw.ffd_post_ln, cx, next_rstd, rstd_valid));
   }
   if (compacted)     // the latent rows back where the encoder's tail (and anybody else) reads them
     TTV_TRY(ttvk_copy_rows(ws.xl, (int64_t)dm * esize(dt), nullptr, ws.x, (int64_t)dm * esize(dt), b->latent_rows, b->sum_tokens, dm * (int)esize(dt), s));
@@ -621,7 +626,7 @@ int ttv_encoder_forward(const ttv_tower_dims* d, const ttv_tower_weights* w, con
 
   // patchify (utils.py:26-34) + proj_in (blocks.py:91-93); when the shapes allow it the GEMM reads its K = (c, pt, ph, pw)
   // operand straight from the clips (16-byte pixel-row segments) instead of from a gathered [P, pd] copy
-  static const bool use_fused_patch = !(getenv("TTV_FUSED_PATCH") && getenv("TTV_FUSED_PATCH")[0] == '0');
+  static const bool use_fused_patch = ttv_sw_fused_patch();
   auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
   const bool gather = use_fused_patch && dt == TTV_BF16 && d->patch_w == 8 && pow2(d->patch_t) && pow2(d->patch_h) &&
                       b->n_clips <= TTV_MAX_CLIPS_PER_LAUNCH && b->row_seq && pd % 64 == 0 && pd != 256;
@@ -682,7 +687,7 @@ int ttv_decoder_forward(const ttv_tower_dims* d, const ttv_tower_weights* w, con
   }
   // unpatchify inside the GEMM epilogue (8 consecutive output features = one 16-byte pixel row segment of a patch) when the
   // shapes allow it: saves the [P, pd] round trip and the copy kernel.  TTV_FUSED_PATCH=0 keeps the two-kernel sequence.
-  static const bool use_fused_patch = !(getenv("TTV_FUSED_PATCH") && getenv("TTV_FUSED_PATCH")[0] == '0');
+  static const bool use_fused_patch = ttv_sw_fused_patch();
   auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
   if (use_fused_patch && dt == TTV_BF16 && dm == 256 && d->patch_w == 8 && pow2(d->patch_t) && pow2(d->patch_h) &&
       b->n_clips <= TTV_MAX_CLIPS_PER_LAUNCH && b->row_seq && pd % 64 == 0) {

@@ -20,8 +20,8 @@
 
 #define QB 128
 #define KB 64
-// online softmax: the running reference of a query row moves only when a score exceeds it by more than this (log2 units)
-#define ATTN_DEFER_THR 8.0f
+// online softmax: the running reference of a query row moves only when a score exceeds it by more than the kernels' defer_thr argument
+// (log2 units; ttv_sw_attn_thr(): 8 unless TTV_ATTN_THR says otherwise)
 // pre-scaled-q kernel: the row maximum is taken only when a tile's row sums say the running reference is stale (see LAZY in k_attn_bf16)
 #ifndef ATTN_LAZY
 #define ATTN_LAZY 1
@@ -1638,7 +1638,7 @@ int ttvk_attention_mxout(const void* qkvg, int ld, void* out_q, void* out_mx, in
   TTV_CHECK_ARG(ld >= 2 * d_model + 2 * gqa && ld % 8 == 0 && d_model % 128 == 0 && ld_mx == (int)(4 * ((d_model / 128 + 3) / 4 * 4)),
                 "attention_mxout: bad leading dims (d_model %% 128, ld_mx = 4 * round_up(d_model / 128, 4))");
   TTV_CHECK_ARG(qkvg && out_q && out_mx && (uintptr_t)qkvg % 16 == 0 && (uintptr_t)out_q % 8 == 0, "attention_mxout: null / unaligned pointers");
-  static const float defer_thr = getenv("TTV_ATTN_THR") ? (float)atof(getenv("TTV_ATTN_THR")) : ATTN_DEFER_THR;
+  static const float defer_thr = ttv_sw_attn_thr();
   TtvProfScope prof(TTV_KC_ATTENTION, s);
   hipLaunchKernelGGL((k_attn_bf16<true, 1, true, false, true>), dim3(n_qblocks), dim3(256), 0, s, (const bf16_t*)qkvg, ld, (bf16_t*)nullptr, ld_mx,
                      cu_seqlens, qblocks, n_qblocks, d_model, gqa, rep, 1.0f, (float*)out_mx, (bf16_t*)out_q, defer_thr, g_ttv_stamps);
@@ -1667,7 +1667,7 @@ int ttvk_attention(const void* qkvg, int ld, void* out, int ldo, const int* cu_s
     // pre-scaled q: the exponent factor is 1; the accumulator-carried maximum (PRE) is built for the 4-wave kernel only - the paired
     // kernel is held to 128 VGPRs and would spill its start vector - so paired launches run the generic softmax with factor 1
     const float c_eff = prescaled ? 1.0f : c_exp;
-    static const float defer_thr = getenv("TTV_ATTN_THR") ? (float)atof(getenv("TTV_ATTN_THR")) : ATTN_DEFER_THR;   // diagnostics: 0 = exact running maximum
+    static const float defer_thr = ttv_sw_attn_thr();   // diagnostics: 0 = exact running maximum
 #define ATTN_LAUNCH(G_, NE_, P_, T_, grid_, threads_)                                                                                   \
   hipLaunchKernelGGL((k_attn_bf16<G_, NE_, (P_) && (NE_) == 1, T_>), grid_, dim3(threads_), 0, s, (const bf16_t*)qkvg, ld, (bf16_t*)out, ldo, \
                      cu_seqlens, qblocks, n_qblocks, d_model, gqa, rep, c_eff, lse_out, (bf16_t*)out_raw, defer_thr, g_ttv_stamps)
@@ -1682,14 +1682,14 @@ int ttvk_attention(const void* qkvg, int ld, void* out, int ldo, const int* cu_s
     // tables of full items only with pre-scaled q, no tape: the software-pipelined kernel on request (flag TTV_ATTN_PIPE; slower
     // than the plain loop, see its header)
     // round 5: the in-wave software pipeline of ttv_attn_swp.hip is the default for such tables (TTV_ATTN_SWP=0: k_attn_bf16, A/B)
-    static const bool swp_env = !(getenv("TTV_ATTN_SWP") && getenv("TTV_ATTN_SWP")[0] == '0');
-    if (swp_env && !(flags & TTV_ATTN_PIPE) && (flags & TTV_ATTN_ALLFULL) && prescaled && !paired && !tape && !(g_ttv_debug & 1048576)) {
+    static const bool swp_env = ttv_env_flag("TTV_ATTN_SWP", true);
+    if (swp_env && !(flags & TTV_ATTN_PIPE) && (flags & TTV_ATTN_ALLFULL) && prescaled && !paired && !tape && !(g_ttv_debug & TTV_DBG_ATTN_NO_SWP)) {
       return ttvk_attention_swp(qkvg, ld, out, ldo, cu_seqlens, qblocks, n_qblocks, q_heads, kv_heads, gate_mul, s);
     }
     if ((flags & TTV_ATTN_PIPE) && (flags & TTV_ATTN_ALLFULL) && prescaled && !paired && !tape) {
       // the reference moves when a lane's 16-key sum of p exceeds 2^pipe_thr: bf16 P and fp32 sums have the range for it, and
       // with 40 the rare branch is rare for any score distribution (8, k_attn_bf16's value: every few tiles at a spread of 6)
-      static const float pipe_thr = getenv("TTV_ATTN_PIPE_THR") ? (float)atof(getenv("TTV_ATTN_PIPE_THR")) : ATTN_PIPE_THR;
+      static const float pipe_thr = ttv_env_float("TTV_ATTN_PIPE_THR", ATTN_PIPE_THR);
       if (gate_mul) hipLaunchKernelGGL((k_attn_pipe<true>), grid, dim3(256), 0, s, (const bf16_t*)qkvg, ld, (bf16_t*)out, ldo, cu_seqlens, qblocks, d_model, gqa, rep, pipe_thr, g_ttv_stamps);
       else hipLaunchKernelGGL((k_attn_pipe<false>), grid, dim3(256), 0, s, (const bf16_t*)qkvg, ld, (bf16_t*)out, ldo, cu_seqlens, qblocks, d_model, gqa, rep, pipe_thr, g_ttv_stamps);
     } else if (paired) {

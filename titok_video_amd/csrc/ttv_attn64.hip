@@ -610,7 +610,7 @@ int ttvk_attention64(const void* qkvg, int ld, void* out, int ldo, const int* cu
   TTV_CHECK_ARG(ld >= 2 * d_model + 2 * gqa && ld % 8 == 0 && ldo % 8 == 0, "attention64: bad leading dims");
   TTV_CHECK_ARG((uintptr_t)qkvg % 16 == 0 && (uintptr_t)out % 16 == 0, "attention64: unaligned pointers");
   TTV_CHECK_ARG(flags & TTV_ATTN_QSCALED, "attention64: needs pre-scaled q (TTV_ATTN_QSCALED)");
-  static const float defer_thr = getenv("TTV_ATTN_THR") ? (float)atof(getenv("TTV_ATTN_THR")) : 8.0f;
+  static const float defer_thr = ttv_sw_attn_thr();
   TtvProfScope prof(TTV_KC_ATTENTION, s);
   if (flags & TTV_ATTN_GATE)
     hipLaunchKernelGGL((k_attn_w64<true>), dim3(n_items), dim3(256), 0, s, (const bf16_t*)qkvg, ld, (bf16_t*)out, ldo, cu_seqlens, items, d_model, gqa,

@@ -588,7 +588,7 @@ int ttvk_geglu_fwd(const void* u, int ldu, void* h, int ldh, int rows, int I, in
 int ttvk_geglu_bwd(const void* u, int ldu, const void* dh, int lddh, void* du, int lddu, int rows, int I, int dt, hipStream_t s) {
   if (rows == 0) return TTV_OK;
   const int nb = ew_blocks((long)rows * I / 4);
-  static const bool exact = getenv("TTV_GEGLU_BWD_ERF") && getenv("TTV_GEGLU_BWD_ERF")[0] == '1';      // A/B: the erff() form
+  static const bool exact = ttv_env_flag("TTV_GEGLU_BWD_ERF", false);      // A/B: the erff() form
   const bool v8 = !exact && I % 8 == 0 && ldu % 8 == 0 && lddh % 8 == 0 && lddu % 8 == 0 && ((uintptr_t)u % 16 == 0) && ((uintptr_t)dh % 16 == 0) && ((uintptr_t)du % 16 == 0);
   if (dt == TTV_BF16 && v8) hipLaunchKernelGGL(k_geglu_bwd_bf16, dim3(ew_blocks((long)rows * I / 8)), dim3(256), 0, s, (const bf16_t*)u, ldu, (const bf16_t*)dh, lddh, (bf16_t*)du, lddu, rows, I);
   else if (dt == TTV_BF16) hipLaunchKernelGGL((k_geglu_bwd<bf16_t>), dim3(nb), dim3(256), 0, s, (const bf16_t*)u, ldu, (const bf16_t*)dh, lddh, (bf16_t*)du, lddu, rows, I);
@@ -1143,11 +1143,11 @@ __global__ __launch_bounds__(256) void k_wgrad_f32(const float* __restrict__ dy,
 }
 
 static int wgrad_target_blocks() {
-  static const int v = getenv("TTV_WGRAD_BLOCKS") ? atoi(getenv("TTV_WGRAD_BLOCKS")) : 200;
+  static const int v = ttv_env_int("TTV_WGRAD_BLOCKS", 200);
   return v < 1 ? 1 : v;
 }
 static int wgrad_min_steps() {
-  static const int v = getenv("TTV_WGRAD_MIN_STEPS") ? atoi(getenv("TTV_WGRAD_MIN_STEPS")) : 16;
+  static const int v = ttv_env_int("TTV_WGRAD_MIN_STEPS", 16);
   return v < 1 ? 1 : v;
 }
 static void wgrad_plan(int L, int N, int K, int* splits, int* tpb) {
@@ -1176,10 +1176,11 @@ int64_t ttvk_wgrad_ws_bytes(int L, int N, int K) {
 int ttvk_wgrad(const void* dy, int lddy, const void* x, int ldx, float* dw, int lddw, int L, int N, int K, int dt, float* part,
                int64_t part_bytes, hipStream_t s, WgradBatch* batch) {
   if (L == 0 || N == 0 || K == 0 || !dw) return TTV_OK;   // dw == NULL: frozen weight
-  static const bool batch_env = !(getenv("TTV_WGRAD_BATCHED") && getenv("TTV_WGRAD_BATCHED")[0] == '0');   // A/B
+  static const bool batch_env = ttv_env_flag("TTV_WGRAD_BATCHED", true);   // A/B
   if (!batch_env && batch) { BW_TRY(ttvk_wgrad_flush(batch, s)); batch = nullptr; }
   if (dt == TTV_BF16 && N % 8 == 0 && K % 8 == 0 && lddy % 8 == 0 && ldx % 8 == 0) {
-    static const int wg_tile64 = getenv("TTV_WGRAD_TILE64") ? 1 : 0;
+    // TTV_WGRAD_TILE64 is on when merely present, whatever its value: only a set variable reads the same under two defaults
+    static const int wg_tile64 = ttv_env_int("TTV_WGRAD_TILE64", 0) == ttv_env_int("TTV_WGRAD_TILE64", 1) ? 1 : 0;
     if (!wg_tile64 && ((uintptr_t)dy % 16 == 0) && ((uintptr_t)x % 16 == 0)) {
       int splits, tpb;
       wgrad_plan(L, N, K, &splits, &tpb);

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/titok_hip.h"
 
@@ -180,6 +181,28 @@ struct TtvProfScope {
 };
 
 static inline int ttv_cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// ---- environment switches (host; A/B diagnostics, every one listed in tools/README.md) ------------------------------------------------
+// The library reads its environment through these three and nowhere else.  A call site keeps the value in a function-local `static const` (one read per process).
+// Flags look at the first character only: a default-on flag is off only for '0...', a default-off flag on only for '1...'.
+static inline bool ttv_env_flag(const char* name, bool default_on) {
+  const char* v = getenv(name);
+  return default_on ? !(v && v[0] == '0') : (v && v[0] == '1');
+}
+static inline int ttv_env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
+static inline float ttv_env_float(const char* name, float dflt) {
+  const char* v = getenv(name);
+  return v ? (float)atof(v) : dflt;
+}
+// Switches that more than one site reads: one accessor each (ttv_api.hip), so that the name and the default are written once.
+bool ttv_sw_enc_latent_last();       // TTV_ENC_LATENT_LAST (default on): run_layers, the training forward
+bool ttv_sw_keel_f32sum();           // TTV_KEEL_F32SUM (default off): run_layers' path choice and its KEEL tails
+bool ttv_sw_fused_patch();           // TTV_FUSED_PATCH (default on): the encoder's and the decoder's patch kernels
+bool ttv_sw_attn_pipe();             // TTV_ATTN_PIPE (default off): the opt-in pipelined attention kernel
+float ttv_sw_attn_thr();            // TTV_ATTN_THR (default 8): deferred-rescale threshold of k_attn_bf16 / k_attn64 (0 = exact running maximum)
 
 // ---- torch's bicubic taps without antialiasing (aten/src/ATen/native/UpSample.h, upsample_bicubic2d, align_corners=False) ----------
 // Along one axis n_in -> n_out: src = scale * (dst + 0.5) - 0.5 with no clamp at 0 for cubic, i = floor(src), t = src - i, taps

@@ -215,7 +215,7 @@ int ttvk_rmsnorm(const void* in, int in_dtype, int ld_in, const int* src_rows, v
   TTV_CHECK_ARG(d % 4 == 0 && d <= 64 * 4 * MAX_ITERS, "rmsnorm: width %d must be a multiple of 4 and <= 1024", d);
   TTV_CHECK_ARG(ld_in % 4 == 0 && ld_out % 4 == 0, "rmsnorm: leading dims must be multiples of 4");
   TTV_CHECK_ARG(!mx_q || (mx_s && d % 128 == 0 && (uintptr_t)mx_q % 4 == 0), "rmsnorm: the block-scaled fp8 side output needs its scale buffer and width %% 128 == 0");
-  static const bool fast256 = !(getenv("TTV_RMSNORM256") && getenv("TTV_RMSNORM256")[0] == '0');      // A/B
+  static const bool fast256 = ttv_env_flag("TTV_RMSNORM256", true);      // A/B
   if (fast256 && rows > 0 && d == 256 && in_dtype == TTV_BF16 && out_dtype == TTV_BF16 && !src_rows && !dst_rows && !next_rstd && !mx_q && !split_image &&
       ld_in % 8 == 0 && ld_out % 8 == 0 && ((uintptr_t)in % 16 == 0) && ((uintptr_t)out % 16 == 0) && ((uintptr_t)gain % 16 == 0)) {
     hipLaunchKernelGGL(k_rmsnorm256_bf16, dim3(ttv_cdiv(rows, 32)), dim3(256), 0, s, (const bf16_t*)in, ld_in, (bf16_t*)out, ld_out, gain, rows, eps);

@@ -98,7 +98,7 @@ __device__ __forceinline__ uint4 split4_bf16(uint4 v) {
 template <int EPI, typename T, int NI, int NJ>
 __device__ __forceinline__ void epilogue_tile(const GemmDev& p, const int (&tok)[NJ], const int (&feat)[NI],
                                               f32x4 (&acc)[NI][NJ], f32x4 (&acc2)[NI][NJ], int kq, const PatchDst* pd = nullptr) {
-  if (p.debug & 1) {  // timing-only path: keep the values alive, store nothing
+  if (p.debug & TTV_DBG_NO_STORES) {  // timing-only path: keep the values alive, store nothing
 #pragma unroll
     for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -847,7 +847,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm_bf16_t256(GemmDev p, int n_ftil
     // inside its head): loaded once - the 8-byte loads of the [L,64] table are what this epilogue costs - and applied to both
     // halves, then stored by the plain epilogue.  Arithmetic and order as in epilogue_tile (row scale first, then the rotation).
     const int f_first = __builtin_amdgcn_readfirstlane(fbase + wr * 128);
-    if (!(p.debug & 1) && (f_first < p.rope_q_end || (f_first >= p.rope_k_begin && f_first < p.rope_k_end))) {
+    if (!(p.debug & TTV_DBG_NO_STORES) && (f_first < p.rope_q_end || (f_first >= p.rope_k_begin && f_first < p.rope_k_end))) {
       float2 c[4][4], sn[4][4];
       float rs[4];
 #pragma unroll
@@ -1109,7 +1109,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_fp8_dma(GemmDev p, int n_ftiles
       // 32-element MX block of h - spread over the four lane groups kq -, so the block maximum is two xor shuffles away, and the
       // bf16 copy of h (151 MB at the base shape) and its quantisation pass disappear.  Values are rounded to bf16 first: the image is
       // bit for bit what k_quant_mx_fp8 makes of the bf16 h the plain epilogue stores.
-      if (p.debug & 1) return;
+      if (p.debug & TTV_DBG_NO_STORES) return;
       const int blk = (fbase + wf * 32) >> 5;
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
@@ -1255,7 +1255,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_k256(GemmDev p, int n_panels, i
   for (int it = it0; it < it1; ++it) {
     const int buf = (it - it0) & 1;
     const int tile = it / n_panels, panel = it - tile * n_panels;
-    if (tile != cur_tile && !((p.debug & 4) && cur_tile >= 0)) {
+    if (tile != cur_tile && !((p.debug & TTV_DBG_K256_NO_TILE_RELOAD) && cur_tile >= 0)) {
       cur_tile = tile;
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
@@ -1337,7 +1337,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_k256(GemmDev p, int n_panels, i
     }
     // next panel -> other buffer, in flight behind the whole MFMA phase (every wave left that buffer before the
     // previous item's barrier)
-    if (it + 1 < it1 && !(p.debug & 2)) GLDS_PANEL((it + 1) % n_panels, buf ^ 1);
+    if (it + 1 < it1 && !(p.debug & TTV_DBG_K256_NO_PANEL_DMA)) GLDS_PANEL((it + 1) % n_panels, buf ^ 1);
 
     f32x4 acc[4][2];
 #pragma unroll
@@ -1377,7 +1377,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_k256(GemmDev p, int n_panels, i
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       tok[j] = tile * K256_TT + wave * 32 + j * 16 + l15;
-      if (PRENORM && !(p.debug & 8)) {     // debug bit 8 (tools/qkv_ablate.py): no epilogue arithmetic - timing only, garbage results
+      if (PRENORM && !(p.debug & TTV_DBG_K256_NO_EPILOGUE_MATH)) {     // debug bit 8 (tools/qkv_ablate.py): no epilogue arithmetic - timing only, garbage results
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[i][j] *= rstd[j];
       }
@@ -1392,7 +1392,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_k256(GemmDev p, int n_panels, i
 #pragma unroll
       for (int i = 0; i < 4; ++i) feat[i] = panel * FO + i * 16 + kq * 4;
       const int f_first = panel * FO;
-      if (!(p.debug & 8) && (f_first < p.rope_q_end || (f_first >= p.rope_k_begin && f_first < p.rope_k_end))) {
+      if (!(p.debug & TTV_DBG_K256_NO_EPILOGUE_MATH) && (f_first < p.rope_q_end || (f_first >= p.rope_k_begin && f_first < p.rope_k_end))) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -1525,7 +1525,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_k256_rownorm(GemmDev p, int n_t
       const uint2 p0 = pack_bf16x4(acc[i0]), p1 = pack_bf16x4(acc[i1]);
       const uint4 out = xchg16_pair(p0, p1);     // v_permlane16_swap: even kq (own p0, partner's p0), odd kq (partner's p1, own p1)
       const int start = odd ? i1 * 16 + kq * 4 - 4 : i0 * 16 + kq * 4;
-      if (tvalid && !(p.debug & 1)) *reinterpret_cast<uint4*>(yrow + start) = out;
+      if (tvalid && !(p.debug & TTV_DBG_NO_STORES)) *reinterpret_cast<uint4*>(yrow + start) = out;
     }
     if (p.y2) {                         // the NEXT pre-norm of the row just written (training tape: xn of the following sub-layer)
       ss2 = quad16_sum(ss2);
@@ -1542,7 +1542,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_k256_rownorm(GemmDev p, int n_t
         const uint2 p0 = pack_bf16x4(y0), p1 = pack_bf16x4(y1);
         const uint4 out = xchg16_pair(p0, p1);     // v_permlane16_swap: even kq (own p0, partner's p0), odd kq (partner's p1, own p1)
         const int start = odd ? i1 * 16 + kq * 4 - 4 : i0 * 16 + kq * 4;
-        if (tvalid && !(p.debug & 1)) *reinterpret_cast<uint4*>(y2row + start) = out;
+        if (tvalid && !(p.debug & TTV_DBG_NO_STORES)) *reinterpret_cast<uint4*>(y2row + start) = out;
       }
     }
   }
@@ -1688,7 +1688,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_rowtile_norm(GemmDev p) {
       const uint2 p0 = pack_bf16x4(acc[i0][j]), p1 = pack_bf16x4(acc[i1][j]);
       const uint4 out = xchg16_pair(p0, p1);     // v_permlane16_swap: even kq (own p0, partner's p0), odd kq (partner's p1, own p1)
       const int start = odd ? f1 - 4 : f0;
-      if (t < p.M && !(p.debug & 1)) *reinterpret_cast<uint4*>((bf16_t*)p.y + (size_t)t * p.ldy + start) = out;
+      if (t < p.M && !(p.debug & TTV_DBG_NO_STORES)) *reinterpret_cast<uint4*>((bf16_t*)p.y + (size_t)t * p.ldy + start) = out;
     }
   }
   if (p.y2) {                           // the NEXT pre-norm of the rows just written: a second exchange of the four waves' partial sums
@@ -1714,7 +1714,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_rowtile_norm(GemmDev p) {
         const uint2 p0 = pack_bf16x4(y0), p1 = pack_bf16x4(y1);
         const uint4 out = xchg16_pair(p0, p1);     // v_permlane16_swap: even kq (own p0, partner's p0), odd kq (partner's p1, own p1)
         const int start = odd ? f1 - 4 : f0;
-        if (t < p.M && !(p.debug & 1)) *reinterpret_cast<uint4*>((bf16_t*)p.y2 + (size_t)t * p.ldy2 + start) = out;
+        if (t < p.M && !(p.debug & TTV_DBG_NO_STORES)) *reinterpret_cast<uint4*>((bf16_t*)p.y2 + (size_t)t * p.ldy2 + start) = out;
       }
     }
   }
@@ -2055,10 +2055,20 @@ __global__ __launch_bounds__(256, 2) void k_gemm_split_dma(GemmDev p, int n_ftil
   }
 }
 
+// Token-tile height of the general-K kernels (bf16, fp32 / split-bf16, fp8, patch gather): rounds of 512 resident blocks x tile height,
+// so the 160-token tile when it saves a (mostly empty) round, else 128.  nf = feature tiles per token tile; `debug` carries the
+// TTV_DBG_GEMM_TILE160 / TTV_DBG_GEMM_TILE128 force bits (diagnostics / tests; TILE160 wins when both are set).
+static int gemm_token_tile(int M, int nf, int debug) {
+  if (debug & TTV_DBG_GEMM_TILE160) return 160;
+  if (debug & TTV_DBG_GEMM_TILE128) return 128;
+  const long cost128 = (long)ttv_cdiv(nf * ttv_cdiv(M, 128), 512) * 128, cost160 = (long)ttv_cdiv(nf * ttv_cdiv(M, 160), 512) * 160;
+  return cost160 < cost128 ? 160 : 128;
+}
+
 template <int EPI>
 static int launch(const GemmDev& d, int dtype, bool prenorm, hipStream_t s) {
   // debug bit 16384 (diagnostics): send a K = 256 GEMM through the general-K kernels instead (no folded pre-norm, no patch scatter there)
-  if (dtype == TTV_BF16 && d.K == 256 && d.N % 8 == 0 && !((d.debug & 16384) && !prenorm && EPI != EPI_STORE_PATCH)) {
+  if (dtype == TTV_BF16 && d.K == 256 && d.N % 8 == 0 && !((d.debug & TTV_DBG_K256_GENERAL) && !prenorm && EPI != EPI_STORE_PATCH)) {
     const int fo = (EPI == EPI_GEGLU) ? 32 : 64;
     const int n_panels = ttv_cdiv(d.N, fo), n_tiles = ttv_cdiv(d.M, K256_TT);
     const int total = n_panels * n_tiles;
@@ -2069,7 +2079,7 @@ static int launch(const GemmDev& d, int dtype, bool prenorm, hipStream_t s) {
     // 34.6 us; 432 blocks x 8 items - one in three - 33.6 us (576 x 6, aligned but more than 512 slots: 35.2; 384 x 9: 37.4).
     // So: the largest grid in [416, 512] that divides the item count, else 512 (a grid much below the slot count loses more
     // than it gains: GEGLU, 6336 items, 396 x 16: 46 us against 41).  TTV_K256_GRID overrides (A/B).
-    static const int grid_env = getenv("TTV_K256_GRID") ? atoi(getenv("TTV_K256_GRID")) : 0;
+    static const int grid_env = ttv_env_int("TTV_K256_GRID", 0);
     int grid = total < 512 ? total : 512;
     if (grid_env > 0) grid = total < grid_env ? total : grid_env;
     else if (total > 512)
@@ -2079,12 +2089,12 @@ static int launch(const GemmDev& d, int dtype, bool prenorm, hipStream_t s) {
     // has (30.3 us against k_gemm_k256's 31.2 inside the benchmark forward, profiles/r04_qkv256_inpipe.txt).  TTV_QKV256=0 / ttv_debug_set
     // bit 15 (32768): k_gemm_k256's QKV instantiation; TTV_QKV256=2 / bit 17 (131072): the weight-stationary kernel k_qkv256ws
     // (ttv_qkv256ws.inc; 34.2 us: measured, kept for A/B) - all three give the same bits without the folded pre-norm
-    static const int qkv256_env = getenv("TTV_QKV256") ? atoi(getenv("TTV_QKV256")) : 1;
+    static const int qkv256_env = ttv_env_int("TTV_QKV256", 1);
     if constexpr (EPI == EPI_QKV_ROPE) {
       const int n_groups = (n_panels + 3) / 4;
-      if (qkv256_env && !(d.debug & 32768) && d.N % 64 == 0 && d.rope_q_end % 64 == 0 && d.rope_k_begin % 64 == 0 && d.rope_k_end % 64 == 0 &&
+      if (qkv256_env && !(d.debug & TTV_DBG_QKV256_OFF) && d.N % 64 == 0 && d.rope_q_end % 64 == 0 && d.rope_k_begin % 64 == 0 && d.rope_k_end % 64 == 0 &&
           !d.row_scale && !d.bias && !d.add_scalar && (uint64_t)d.w_rows * (uint64_t)d.ldw * 2u < (1ull << 32)) {
-        if ((qkv256_env >= 2 || (d.debug & 131072)) && n_groups <= 32) {
+        if ((qkv256_env >= 2 || (d.debug & TTV_DBG_QKV256_WS)) && n_groups <= 32) {
           // one block per CU: blocks b, b + 8, .. (one XCD under round-robin dispatch) share an eighth of the 32-token groups, split between
           // the panel groups; no more blocks than there are units for
           const int tgs = ttv_cdiv(d.M, 32), per_xcd = ttv_cdiv(tgs, 8);
@@ -2113,31 +2123,29 @@ static int launch(const GemmDev& d, int dtype, bool prenorm, hipStream_t s) {
   if (dtype == TTV_BF16) {
     const int ft = (EPI == EPI_GEGLU) ? 64 : TF;
     const int nf = ttv_cdiv(d.N, ft), nt = ttv_cdiv(d.M, TT), nt160 = ttv_cdiv(d.M, 160);
-    // rounds of 512 resident blocks x tile height: the 160-token tile when it saves a (mostly empty) round
-    const int force_tt = (d.debug & 128) ? 160 : (d.debug & 256) ? 128 : 0;   // diagnostics / tests (ttv_debug_set)
-    const long cost128 = (long)ttv_cdiv(nf * nt, 512) * 128, cost160 = (long)ttv_cdiv(nf * nt160, 512) * 160;
+    const bool t160 = gemm_token_tile(d.M, nf, d.debug) == 160;
     // both tiles by LDS-DMA when the k range is whole 64-element tiles and a lane's byte offset fits 32 bits (TTV_GEMM_DMA=0: A/B)
-    static const bool use_dma = !(getenv("TTV_GEMM_DMA") && getenv("TTV_GEMM_DMA")[0] == '0');
+    static const bool use_dma = ttv_env_flag("TTV_GEMM_DMA", true);
     const bool dma_ok = use_dma && d.K % BK == 0 && (uint64_t)d.M * (uint64_t)d.ldx * 2u < (1ull << 32) && (uint64_t)d.w_rows * (uint64_t)d.ldw * 2u < (1ull << 32);
     // large GEMMs of the wide towers: 256 x 256 tiles (k_gemm_bf16_t256) when the grid gives every CU at least one tile.  Measured at
     // the base tower's shapes (36 864 rows, tools/gemm_t256_bench.py): w12 + GEGLU 294 -> 239 us, w3 + residual 154 -> 138, out_proj +
     // residual 76 -> 74, to_qkv + rotary 190 -> 187, plain store 121 -> 121; bench.py --config base 97.6 -> 102.6 clips/s.  With the
     // epilogue's stores knocked out both kernels run their k loops at 0.42-0.50 of the bf16 peak: what separates the cases is the
     // epilogue (fp32 residual sums and rotary factors cost 35-80 us per launch).  TTV_GEMM_T256=0|1 forces (A/B)
-    static const int t256_env = getenv("TTV_GEMM_T256") ? atoi(getenv("TTV_GEMM_T256")) : -1;
+    static const int t256_env = ttv_env_int("TTV_GEMM_T256", -1);
     if constexpr (EPI == EPI_STORE || EPI == EPI_QKV_ROPE || EPI == EPI_GEGLU || EPI == EPI_RESID_T || EPI == EPI_RESID_F32) {
       const int fo = (EPI == EPI_GEGLU) ? 128 : T256_F;
       const long tiles256 = (long)ttv_cdiv(d.N, fo) * ttv_cdiv(d.M, T256_T);
       // ttv_debug_set bit 512 forces the 256 x 256 kernel wherever it is applicable (tests, A/B), bit 1024 forbids it
-      const bool forced = (d.debug & 512) || t256_env == 1;
-      const bool ok256 = dma_ok && d.N % fo == 0 && d.K >= 2 * BK && !(d.debug & 1024) && (forced || tiles256 >= 256);
+      const bool forced = (d.debug & TTV_DBG_GEMM_T256) || t256_env == 1;
+      const bool ok256 = dma_ok && d.N % fo == 0 && d.K >= 2 * BK && !(d.debug & TTV_DBG_GEMM_NO_T256) && (forced || tiles256 >= 256);
       if (ok256 && (forced || (t256_env < 0 && T256_DEFAULT))) {
         hipLaunchKernelGGL((k_gemm_bf16_t256<EPI>), dim3((unsigned)tiles256), dim3(512), 0, s, d, ttv_cdiv(d.N, fo));
         TTV_CHECK_LAUNCH("gemm_t256");
         return TTV_OK;
       }
     }
-    if ((cost160 < cost128 && force_tt != 128) || force_tt == 160) {
+    if (t160) {
       if (dma_ok) hipLaunchKernelGGL((k_gemm_bf16_dma<EPI, 5>), dim3(nf * nt160), dim3(256), 0, s, d, nf);
       else hipLaunchKernelGGL((k_gemm_bf16<EPI, false, 5>), dim3(nf * nt160), dim3(256), 0, s, d, nf);
     } else {
@@ -2145,19 +2153,18 @@ static int launch(const GemmDev& d, int dtype, bool prenorm, hipStream_t s) {
       else hipLaunchKernelGGL((k_gemm_bf16<EPI>), dim3(nf * nt), dim3(256), 0, s, d, nf);
     }
   } else {
-    // 128- or 160-token tiles by the same rounds-of-512-resident-blocks rule as the bf16 kernel: N = 256 at the benchmark batch is 576
-    // tiles of 128 tokens - two rounds, the second an eighth full - and 462 tiles of 160 in one
+    // 128- or 160-token tiles by the same rule as the bf16 kernel (gemm_token_tile): N = 256 at the benchmark batch is 576 tiles of 128
+    // tokens - two rounds, the second an eighth full - and 462 tiles of 160 in one
     if ((uint64_t)d.M * (uint64_t)d.ldx >= (1ull << 31) || (uint64_t)d.w_rows * (uint64_t)d.ldw >= (1ull << 31)) {
       ttv_set_error("gemm (fp32): operand too large for 32-bit element offsets");
       return TTV_ERR_UNSUPPORTED;
     }
     const int nf = ttv_cdiv(d.N, (EPI == EPI_GEGLU) ? 64 : F_TF), nt = ttv_cdiv(d.M, F_TT), nt160 = ttv_cdiv(d.M, 160);
-    const long c128 = (long)ttv_cdiv(nf * nt, 512) * 128, c160 = (long)ttv_cdiv(nf * nt160, 512) * 160;
-    const bool t160 = ((c160 < c128) && !(d.debug & 256)) || (d.debug & 128);
+    const bool t160 = gemm_token_tile(d.M, nf, d.debug) == 160;
     // split image on both sides and whole 32-wide k-tiles: both operands by LDS-DMA (TTV_SPLIT3_DMA=0 / ttv_debug_set bit 13: the
     // register-staged kernel, A/B and tests); byte offsets must fit 32 bits
-    static const bool s3dma_env = !(getenv("TTV_SPLIT3_DMA") && getenv("TTV_SPLIT3_DMA")[0] == '0');
-    const bool s3dma = d.split3 && d.x_image && s3dma_env && !(d.debug & 8192) && d.K % 32 == 0 && d.ldx % 4 == 0 && d.ldw % 4 == 0 &&
+    static const bool s3dma_env = ttv_env_flag("TTV_SPLIT3_DMA", true);
+    const bool s3dma = d.split3 && d.x_image && s3dma_env && !(d.debug & TTV_DBG_SPLIT3_NO_DMA) && d.K % 32 == 0 && d.ldx % 4 == 0 && d.ldw % 4 == 0 &&
                        (uint64_t)d.M * (uint64_t)d.ldx * 4u < (1ull << 32) && (uint64_t)d.w_rows * (uint64_t)d.ldw * 4u < (1ull << 32);
     if (s3dma) {
       if (t160) hipLaunchKernelGGL((k_gemm_split_dma<EPI, 5>), dim3(nf * nt160), dim3(256), 0, s, d, nf);
@@ -2165,7 +2172,7 @@ static int launch(const GemmDev& d, int dtype, bool prenorm, hipStream_t s) {
     } else if (d.split3) {
       if (t160) hipLaunchKernelGGL((k_gemm_f32<EPI, true, 5>), dim3(nf * nt160), dim3(256), 0, s, d, nf);
       else hipLaunchKernelGGL((k_gemm_f32<EPI, true, 4>), dim3(nf * nt), dim3(256), 0, s, d, nf);
-    } else if (s3dma_env && !(d.debug & 8192) && d.K % 32 == 0 && d.ldx % 4 == 0 && d.ldw % 4 == 0 &&
+    } else if (s3dma_env && !(d.debug & TTV_DBG_SPLIT3_NO_DMA) && d.K % 32 == 0 && d.ldx % 4 == 0 && d.ldw % 4 == 0 &&
                (uint64_t)d.M * (uint64_t)d.ldx * 4u < (1ull << 32) && (uint64_t)d.w_rows * (uint64_t)d.ldw * 4u < (1ull << 32)) {
       // exact fp32 with both operands by LDS-DMA: the same products in the same order as the register-staged kernel (bit-identical)
       if (t160) hipLaunchKernelGGL((k_gemm_split_dma<EPI, 5, false>), dim3(nf * nt160), dim3(256), 0, s, d, nf);
@@ -2207,8 +2214,7 @@ int ttvk_gemm_fp8(GemmEpilogue epi, const GemmArgs& a, const float* x_scale, con
   if (epi == EPI_QKV_ROPE) TTV_CHECK_ARG(a.rope_cs && a.rope_q_end % 128 == 0 && a.rope_k_begin % 128 == 0 && a.rope_k_end % 128 == 0, "gemm_fp8: rotary ranges must be multiples of 128 columns");
   const int ft = (epi == EPI_GEGLU) ? 64 : TF;
   const int nf = ttv_cdiv(d.N, ft), nt = ttv_cdiv(d.M, TT), nt160 = ttv_cdiv(d.M, 160);
-  const long cost128 = (long)ttv_cdiv(nf * nt, 512) * 128, cost160 = (long)ttv_cdiv(nf * nt160, 512) * 160;
-  const bool t160 = cost160 < cost128;
+  const bool t160 = gemm_token_tile(d.M, nf, 0) == 160;      // the fp8 kernels never honoured the force bits
   const int kc = epi == EPI_STORE ? TTV_KC_GEMM_STORE : epi == EPI_QKV_ROPE ? TTV_KC_GEMM_QKV : epi == EPI_GEGLU ? TTV_KC_GEMM_GEGLU : TTV_KC_GEMM_RESID;
   TtvProfScope prof(kc, s);
 #define F8_LAUNCH(E_, MX_)                                                                                         \
@@ -2279,9 +2285,7 @@ int ttvk_gemm(GemmEpilogue epi, const GemmArgs& a, hipStream_t s) {
     case EPI_STORE:
       if (a.gather) {
         const int nf = ttv_cdiv(d.N, TF), nt = ttv_cdiv(d.M, TT), nt160 = ttv_cdiv(d.M, 160);
-        const int force_tt = (d.debug & 128) ? 160 : (d.debug & 256) ? 128 : 0;
-        const long cost128 = (long)ttv_cdiv(nf * nt, 512) * 128, cost160 = (long)ttv_cdiv(nf * nt160, 512) * 160;
-        if ((cost160 < cost128 && force_tt != 128) || force_tt == 160)
+        if (gemm_token_tile(d.M, nf, d.debug) == 160)
           hipLaunchKernelGGL((k_gemm_bf16<EPI_STORE, true, 5>), dim3(nf * nt160), dim3(256), 0, s, d, nf);
         else
           hipLaunchKernelGGL((k_gemm_bf16<EPI_STORE, true>), dim3(nf * nt), dim3(256), 0, s, d, nf);

@@ -329,8 +329,8 @@ __device__ __forceinline__ void mlp_wave(const MlpDev& p, uint4* l12, uint4* l3,
   MLP_STAMP();
 
   for (int it = 0; it <= np; ++it) {
-    if (it + 1 < np && !(p.debug & 2)) GLDS_W12(it + 1, (it + 1) & 1);
-    if (it < np && (!(p.debug & 2) || it == 0)) GLDS_W3(it, it & 1);
+    if (it + 1 < np && !(p.debug & TTV_DBG_MLP_NO_WEIGHT_DMA)) GLDS_W12(it + 1, (it + 1) & 1);
+    if (it < np && (!(p.debug & TTV_DBG_MLP_NO_WEIGHT_DMA) || it == 0)) GLDS_W3(it, it & 1);
 
     f32x4 acc1[4][T1A];   // [x 0..15, x 16..31, gate 0..15, gate 16..31][P1 token tile]
     if (T1 > 0 && it < np) {
@@ -359,7 +359,7 @@ __device__ __forceinline__ void mlp_wave(const MlpDev& p, uint4* l12, uint4* l3,
     // GELU_FIRST swaps the order of the two remaining parts (measured: both waves P2-before-GEGLU is the faster setting -
     // the P2 MFMAs cover the latency of the P1 results the GEGLU reads)
     if (!GELU_FIRST) {
-      if (T2 > 0 && it >= 1 && !(p.debug & 16)) {
+      if (T2 > 0 && it >= 1 && !(p.debug & TTV_DBG_MLP_NO_P2)) {
         // ---- P2 MFMAs of panel it-1: y^T += W3slice h^T ----
         const int pn = it - 1;
         const uint4* w3l = l3 + (pn & 1) * MLP_W3_CHUNKS + kq * 256 + l15;
@@ -394,7 +394,7 @@ __device__ __forceinline__ void mlp_wave(const MlpDev& p, uint4* l12, uint4* l3,
             gg[4 * i + e] = acc1[2 + i][j][e] * rstd[j];
             xx[4 * i + e] = acc1[i][j][e] * rstd[j];
           }
-        if (p.debug & 4) {      // diagnostic (tools/mlp_ablate.py): no GEGLU arithmetic, garbage results
+        if (p.debug & TTV_DBG_MLP_NO_GEGLU) {      // diagnostic (tools/mlp_ablate.py): no GEGLU arithmetic, garbage results
 #pragma unroll
           for (int k = 0; k < 8; ++k) hh[k] = gg[k] + xx[k];
         } else {
@@ -411,7 +411,7 @@ __device__ __forceinline__ void mlp_wave(const MlpDev& p, uint4* l12, uint4* l3,
       }
     }
     if (GELU_FIRST) {
-      if (T2 > 0 && it >= 1 && !(p.debug & 16)) {
+      if (T2 > 0 && it >= 1 && !(p.debug & TTV_DBG_MLP_NO_P2)) {
         // ---- P2 MFMAs of panel it-1: y^T += W3slice h^T ----
         const int pn = it - 1;
         const uint4* w3l = l3 + (pn & 1) * MLP_W3_CHUNKS + kq * 256 + l15;
@@ -514,7 +514,7 @@ __device__ __forceinline__ void mlp_wave(const MlpDev& p, uint4* l12, uint4* l3,
         }
       }
       const uint4 ov = xchg16_pair(p0, p1);     // even kq: (own p0, partner's p0), odd kq: (partner's p1, own p1) - one VALU op per dword
-      if (tv && !(p.debug & 1)) *(__attribute__((address_space(1))) u32x4_t*)(gy + yoff + ip * 64) = (u32x4_t){ov.x, ov.y, ov.z, ov.w};
+      if (tv && !(p.debug & TTV_DBG_NO_STORES)) *(__attribute__((address_space(1))) u32x4_t*)(gy + yoff + ip * 64) = (u32x4_t){ov.x, ov.y, ov.z, ov.w};
     }
     if (BACK) {
       ssq = quad16_sum(ssq);
@@ -708,13 +708,13 @@ int ttvk_mlp_fused(const void* ao, int ldao, const float* front_gain, float fron
     const long cost = (long)ttv_cdiv(ttv_cdiv(M, 64 * c), cus) * (16 + 19 * c);
     if (best < 0 || cost < best) { best = cost; tiles = 4 * c; }
   }
-  if (!nq && !(g_ttv_debug & 32)) {      // debug bit5: pair layouts only (A/B)
+  if (!nq && !(g_ttv_debug & TTV_DBG_MLP_PAIRS_ONLY)) {      // debug bit5: pair layouts only (A/B)
     const long cost9 = (long)ttv_cdiv(ttv_cdiv(M, 144), cus) * (16 + 14 * 3);
     if (cost9 < best) { best = cost9; tiles = 9; }
   }
-  if ((g_ttv_debug & 512) && !nq) tiles = 9;   // debug bit9 forces the 9-tile deal (tests)
-  if (g_ttv_debug & 8) tiles = 8;      // debug bit3 forces the 2-tile pair variant
-  if (g_ttv_debug & 64) tiles = 4;     // debug bit6 forces the 1-tile pair variant
+  if ((g_ttv_debug & TTV_DBG_MLP_TILES9) && !nq) tiles = 9;   // debug bit9 forces the 9-tile deal (tests)
+  if (g_ttv_debug & TTV_DBG_MLP_TILES8) tiles = 8;      // debug bit3 forces the 2-tile pair variant
+  if (g_ttv_debug & TTV_DBG_MLP_TILES4) tiles = 4;     // debug bit6 forces the 1-tile pair variant
   d.n_tiles = ttv_cdiv(M, 16 * tiles);
   const int grid = d.n_tiles;
   const size_t smem = (size_t)(2 * MLP_W12_CHUNKS + 2 * MLP_W3_CHUNKS + 2 * tiles * 64) * sizeof(uint4) + 2048;   // 96 KiB + 2 KiB per token tile + gains

@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256, 2) void k_qkv256(GemmDev p, int n_panels, int 
   // chunk c = 2t + gp of the item on panel panel_: features 32t + 16gp + 8h .. + 7
 #define QK_STORE_CHUNK(c_, panel_)                                                                           \
   do {                                                                                                       \
-    if (tok_ok && !(p.debug & 1)) *reinterpret_cast<qk_u32x4*>(ytok + (size_t)(panel_) * 128 + (c_) * 32) = out_; \
+    if (tok_ok && !(p.debug & TTV_DBG_NO_STORES)) *reinterpret_cast<qk_u32x4*>(ytok + (size_t)(panel_) * 128 + (c_) * 32) = out_; \
   } while (0)
   // the whole epilogue of an item at once (pipeline drain: token tile change, last item)
 #define QK_EPILOGUE(acc_, ROT_, panel_)                                                                      \
@@ -284,11 +284,11 @@ __global__ __launch_bounds__(256, 2) void k_qkv256(GemmDev p, int n_panels, int 
     bool counted__ = false;                                                                                  \
     if (pend == 2) {                                                                                         \
       if (buf__) QK_BODY(cur_, prev_, 1, 2); else QK_BODY(cur_, prev_, 0, 2);                                \
-      counted__ = wave_full && !(p.debug & 1);                                                               \
+      counted__ = wave_full && !(p.debug & TTV_DBG_NO_STORES);                                                               \
       QK_STAMP(2);                                                                                           \
     } else if (pend == 1) {                                                                                  \
       if (buf__) QK_BODY(cur_, prev_, 1, 1); else QK_BODY(cur_, prev_, 0, 1);                                \
-      counted__ = wave_full && !(p.debug & 1);                                                               \
+      counted__ = wave_full && !(p.debug & TTV_DBG_NO_STORES);                                                               \
       QK_STAMP(2);                                                                                           \
     } else {                                                                                                 \
       if (buf__) QK_BODY(cur_, prev_, 1, 0); else QK_BODY(cur_, prev_, 0, 0);                                \

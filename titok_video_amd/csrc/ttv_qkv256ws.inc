@@ -124,9 +124,9 @@ __global__ __launch_bounds__(512, 1) void k_qkv256ws(GemmDev p, int n_panels, in
 #define QW_STORE_CHUNK(c_, panel_)                                                                           \
   do {                                                                                                       \
     if (QW_KO_ROWS) {                                                                                        \
-      if (tok_ok && !(p.debug & 1)) *reinterpret_cast<qk_u32x4*>(yrow__ + (size_t)(c_) * 8 * p.ldy * 2 + (size_t)(panel_) * 128) = out_; \
+      if (tok_ok && !(p.debug & TTV_DBG_NO_STORES)) *reinterpret_cast<qk_u32x4*>(yrow__ + (size_t)(c_) * 8 * p.ldy * 2 + (size_t)(panel_) * 128) = out_; \
     } else                                                                                                   \
-    if (tok_ok && !(p.debug & 1)) *reinterpret_cast<qk_u32x4*>(ytok + (size_t)(panel_) * 128 + (c_) * 32) = out_; \
+    if (tok_ok && !(p.debug & TTV_DBG_NO_STORES)) *reinterpret_cast<qk_u32x4*>(ytok + (size_t)(panel_) * 128 + (c_) * 32) = out_; \
   } while (0)
 #define QW_EPILOGUE(acc_, ROT_, panel_)                                                                      \
   do {                                                                                                       \

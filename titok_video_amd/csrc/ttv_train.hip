@@ -33,11 +33,11 @@ struct Tape {
 // half the bytes on the GEMM that writes them, the norm that reads them and the backward chain (round 5; fp32 before).  The opt-in
 // fused-norm tape forward (TTV_TRAIN_FUSED_NORMS=1) writes fp32 sums from its GEMM kernel and keeps fp32.
 static bool tape_fuse_norms() {
-  static const bool v = getenv("TTV_TRAIN_FUSED_NORMS") && getenv("TTV_TRAIN_FUSED_NORMS")[0] == '1';
+  static const bool v = ttv_env_flag("TTV_TRAIN_FUSED_NORMS", false);
   return v;
 }
 static int tape_y_dtype(int dt) {
-  static const bool f32 = getenv("TTV_TAPE_Y_F32") && getenv("TTV_TAPE_Y_F32")[0] == '1';      // A/B: fp32 sums as before round 5
+  static const bool f32 = ttv_env_flag("TTV_TAPE_Y_F32", false);      // A/B: fp32 sums as before round 5
   return (dt == TTV_F32 || tape_fuse_norms() || f32) ? TTV_F32 : TTV_BF16;
 }
 static Tape carve_tape(const ttv_tower_dims* d, const ttv_batch* b, char* base) {
@@ -125,8 +125,8 @@ static int check(const ttv_tower_dims* d, const ttv_batch* b) {
 // of the loss with respect to the last layer's patch-row outputs is zero, so nothing is lost; attention (forward and backward) still runs
 // on every row - a query row with dO = 0 contributes nothing.  TTV_ENC_LATENT_LAST=0 / ttv_debug_set bit 19: every row (A/B, tests).
 static bool latent_tail(const ttv_tower_dims* d, const ttv_batch* b, int layer) {
-  static const bool env = !(getenv("TTV_ENC_LATENT_LAST") && getenv("TTV_ENC_LATENT_LAST")[0] == '0');
-  return env && !(g_ttv_debug & 524288) && d->kind == TTV_ENCODER && layer == d->layers - 1 && b->latent_rows && b->sum_tokens > 0 &&
+  static const bool env = ttv_sw_enc_latent_last();
+  return env && !(g_ttv_debug & TTV_DBG_ENC_ALL_ROWS) && d->kind == TTV_ENCODER && layer == d->layers - 1 && b->latent_rows && b->sum_tokens > 0 &&
          b->sum_tokens < b->total_rows && d->inner >= d->width;
 }
 
@@ -251,7 +251,7 @@ static WgradSide* wgrad_side(bool dp) {
   // 1 (default): on, also with the DP path's per-layer events attached; 0: never; 3: single-process steps only.  (For a while the DP
   // path kept the one-stream backward after a red run of the two-rank test; that run turned out to be the test's own tolerance - an
   // AdamW update of a near-zero gradient element is rounding noise - and showed up again with this stream off: DESIGN 5b.)
-  static const int mode = getenv("TTV_WGRAD_SIDE") ? atoi(getenv("TTV_WGRAD_SIDE")) : 1;
+  static const int mode = ttv_env_int("TTV_WGRAD_SIDE", 1);
   if (mode <= 0 || (dp && mode == 3)) return nullptr;
   static thread_local WgradSide tab[16];
   int dev = 0;

@@ -10,13 +10,12 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from typing import List, Optional, Sequence
 
 import torch
 import torch.nn as nn
 
-from ... import _lib
+from ... import _lib, switches
 from ...plan import BatchPlan, get_plan, host_ints
 from .utils import LinearWeight, RMSNormWeight, geglu_inner_dim, get_model_dims
 
@@ -61,7 +60,7 @@ def _versions(params) -> tuple:
     return tuple((p.data_ptr(), p._version, p.dtype) for p in params)
 
 
-_PACK_CHECK = os.environ.get("TTV_PACK_CHECK", "0") == "1"
+_PACK_CHECK = switches.flag("TTV_PACK_CHECK", False)
 
 
 class _Tower(nn.Module):
@@ -336,11 +335,11 @@ class _WeightPack:
         fold = dtype == torch.bfloat16 and tower.width == 256
         # other widths: the pre-norm gains are folded into to_qkv / w12 as well; the generic GEMM then scales its output rows by the
         # row statistic the producing kernel wrote (ttv_layer_weights.to_qkv_pn / w12_pn; TTV_FOLD_NORMS=0 keeps the stand-alone norms)
-        fold_gen = dtype == torch.bfloat16 and tower.width != 256 and os.environ.get("TTV_FOLD_NORMS", "1") != "0"
+        fold_gen = dtype == torch.bfloat16 and tower.width != 256 and switches.flag("TTV_FOLD_NORMS", True)
 
         # q rows of the folded QKV weight carry head_dim^-0.5 * log2(e): the projection then emits the softmax exponent and the
         # attention kernel saves a multiply-add per score (TTV_ATTN_QSCALED).  Applied in fp32 before the one rounding to bf16.
-        use_qs = dtype == torch.bfloat16 and os.environ.get("TTV_ATTN_QSCALE", "1") != "0"
+        use_qs = dtype == torch.bfloat16 and switches.flag("TTV_ATTN_QSCALE", True)
         q_scale = 0.125 * 1.4426950408889634 if use_qs else None
         self.q_prescaled = 1 if ((fold or fold_gen) and use_qs) else 0
 
@@ -407,7 +406,7 @@ class _WeightPack:
             # split-bf16 towers, opt-in (TTV_SPLIT3_FOLD=1): the folded matrix as a split image, the GEMM scales its rows by the pre-norm's
             # rstd - 8 launches less per tiny encoder (+3 % throughput), but the measured max |pre-rounding FSQ value error| on the
             # benchmark fixture goes from 5.4e-4 to 7.3e-4 of the 1e-3 the index guarantee rests on, so the default keeps the norms apart
-            if self.f32_split3 and os.environ.get("TTV_SPLIT3_FOLD", "0") == "1":
+            if self.f32_split3 and switches.flag("TTV_SPLIT3_FOLD", False):
                 t = (w.detach().to(device=device, dtype=torch.float32) * g.detach().to(device=device, dtype=torch.float32)[None, :]).contiguous()
                 img = torch.empty_like(t)
                 _lib.check(_lib.lib().ttv_split3_pack(t.data_ptr(), t.shape[1], img.data_ptr(), t.shape[1], t.shape[0], t.shape[1], _lib.stream_ptr(device)),

@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ... import _lib
+from ... import _lib, switches
 from ..base.blocks import TiTokEncoder
 from ..base.utils import init_weights
 from ..metrics.lpips_gram import LPIPS
@@ -30,8 +30,8 @@ from ...train import l1_reconstruction_loss
 
 import os
 
-_F32_HEAD = os.environ.get("TTV_DISC_F32_HEAD", "0") == "1"
-_TWO_CALLS = os.environ.get("TTV_DISC_TWO_CALLS", "0") == "1"
+_F32_HEAD = switches.flag("TTV_DISC_F32_HEAD", False)
+_TWO_CALLS = switches.flag("TTV_DISC_TWO_CALLS", False)
 
 
 def _resized_hw(H: int, W: int, size: int):
@@ -43,7 +43,7 @@ def _resized_hw(H: int, W: int, size: int):
 
 def _fused_crops() -> bool:
     """TTV_LPIPS_CROPS=0 selects the eager crop path of `perceptual_preprocess` on GPU tensors too (A/B and tests)."""
-    return os.environ.get("TTV_LPIPS_CROPS", "1") != "0"
+    return switches.flag("TTV_LPIPS_CROPS", True)
 
 
 def perceptual_crop_plan(frame_shapes, size: int, samples: int, resize_prob: float = 0.25):

@@ -24,10 +24,11 @@ its references as soon as `submit` returns.  `drain()` is still the way to make 
 """
 from __future__ import annotations
 
-import os
 from typing import Any, Callable, List, Optional, Sequence, Tuple
 
 import torch
+
+from . import switches
 
 
 def _tensors(obj):
@@ -53,7 +54,7 @@ class ForwardPipeline:
             raise RuntimeError("ForwardPipeline needs a GPU model (there is no CPU path)")
         # TTV_PIPE_PRIO=1 (A/B): the streams get different queue priorities (the first one high), so that one chain is served first and
         # the other fills what it leaves idle, instead of two equal queues splitting every CU
-        prio = os.environ.get("TTV_PIPE_PRIO", "0") == "1"
+        prio = switches.flag("TTV_PIPE_PRIO", False)
         self.streams = [torch.cuda.Stream(device=self.device, priority=(-1 if (prio and i == 0) else 0)) for i in range(depth)]
         self._n = 0
 

@@ -13,13 +13,12 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import math
-import os
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, switches
 
 QBLOCK = 128  # query rows per attention workgroup (csrc/ttv_attn.hip QB)
 ATTN_SLOTS = 1024  # table size below which the last third of every sequence's blocks become half items (set when the kernel held 4 blocks per CU; it holds 3 = 768 since round 2 - the rule was re-measured, not re-derived: see attention_table)
@@ -135,7 +134,7 @@ def _xcd_interleave(units) -> np.ndarray:
     4 MB L2 saw every sequence, and the launch fetched 674 MB from HBM / MALL for ~100 MB of operands at the benchmark batch
     (profiles/r04_train_pmc.txt).  Sequences go to 8 lists (greedy by block count), entry i of the table comes from list i % 8; when the
     short lists run out the rest follows in list order (no padding entries: the kernels take the table as it is)."""
-    if os.environ.get("TTV_BWD_XCD", "1") == "0":       # A/B: sequence-major order
+    if not switches.flag("TTV_BWD_XCD", True):       # A/B: sequence-major order
         return np.asarray([e for u in units for e in u], dtype=np.int32).reshape(-1, 2)
     order = sorted(range(len(units)), key=lambda i: len(units[i]), reverse=True)
     lists, weight = [[] for _ in range(8)], [0] * 8
@@ -239,7 +238,7 @@ class BatchPlan:
             blocks64=base + 4 * offs[4], row_seq=base + 4 * offs[5], n_blocks64=self.n_blocks64)
         # rotary factors by position id (ttv_batch.rope_ids / rope_base): the width-256 to_qkv kernel reads 8 bytes per row and gathers
         # from the cached base table instead of streaming the 256-byte fp32 row of rope_cs (TTV_ROPE_IDS=0: the table path, A/B)
-        if self.device.type == "cuda" and len(self.patch) == 3 and os.environ.get("TTV_ROPE_IDS", "1") != "0":
+        if self.device.type == "cuda" and len(self.patch) == 3 and switches.flag("TTV_ROPE_IDS", True):
             self._rope_base_cs = _rope_base_interleaved(head_dim, len(self.patch), n_ids, str(self.device))
             self._base_fields.update(rope_ids=base + 4 * offs[6], rope_base=self._rope_base_cs.data_ptr())
         self._offs = offs
@@ -287,8 +286,8 @@ class BatchPlan:
         the 128 items beyond 1024 slots at the benchmark batch, +1.5 % one batch at a time, -1 % with two in flight).  Within either regime the choice depends only on the sequence's own length, so a clip's bf16
         result does not depend on what it is packed with (the fp32 kernel computes the same way in both modes).
         `split`: None = that rule, False = never, True = every item (tests)."""
-        if split is None and os.environ.get("TTV_ATTN_SPLIT") in ("0", "1"):      # diagnostics: A/B timing of the table kinds
-            split = os.environ["TTV_ATTN_SPLIT"] == "1"
+        if split is None and switches.text("TTV_ATTN_SPLIT") in ("0", "1"):      # diagnostics: A/B timing of the table kinds
+            split = switches.text("TTV_ATTN_SPLIT") == "1"
         key = (int(q_heads), int(kv_heads), split)
         t = self._attn.get(key)
         if t is None:
@@ -299,7 +298,7 @@ class BatchPlan:
             for b in range(len(self.grids)):
                 s = self.cu_seqlens[b + 1] - self.cu_seqlens[b]
                 nq = -(-s // QBLOCK)
-                tail_div = 3 if small_grid else int(os.environ.get("TTV_ATTN_TAIL_DIV", "0"))
+                tail_div = 3 if small_grid else switches.integer("TTV_ATTN_TAIL_DIV", 0)
                 first_half = 0 if split else (nq if (split is False or tail_div <= 0) else nq - nq // tail_div)
                 for kvh in range(kv_heads):
                     heads = [kvh * rep + r for r in range(rep)]
@@ -437,7 +436,7 @@ class BatchPlan:
     def batch_for(self, q_heads: int, kv_heads: int) -> "_lib.Batch":
         """ttv_batch struct whose attention work table matches the tower's head counts (built once per head counts: every tower call of a
         step asks for it, and a ctypes struct of ~30 fields is 40 us of host time in a step that is launch-bound at small batches)."""
-        skey = (int(q_heads), int(kv_heads)) + tuple(os.environ.get(k) for k in ("TTV_ATTN_SPLIT", "TTV_ATTN_PAIRED", "TTV_ATTN64", "TTV_ATTN_TAIL_DIV"))
+        skey = (int(q_heads), int(kv_heads)) + tuple(switches.text(k) for k in ("TTV_ATTN_SPLIT", "TTV_ATTN_PAIRED", "TTV_ATTN64", "TTV_ATTN_TAIL_DIV"))
         cached = self._batch_structs.get(skey)       # (the diagnostic switches that pick the tables are part of the key)
         if cached is not None:
             return cached
@@ -446,14 +445,14 @@ class BatchPlan:
         # with an even rep, entries 2j and 2j+1 of an XCD list are two q-heads of one kv-head on the same query rows
         # (opt-in, TTV_ATTN_PAIRED=1: the 8-wave blocks halve the K/V tile traffic - +1.5 % with two batches in flight - but make
         # the grid coarser: the launch alone is 10 % slower)
-        paired = 1 if (q_heads // kv_heads) % 2 == 0 and os.environ.get("TTV_ATTN_PAIRED", "0") == "1" else 0
+        paired = 1 if (q_heads // kv_heads) % 2 == 0 and switches.flag("TTV_ATTN_PAIRED", False) else 0
         all_full = 1 if self._attn_all_full.get(t.data_ptr()) else 0
         # the 64-rows-per-wave kernel (ttv_attention64) for inference towers with pre-scaled q: OPT-IN (TTV_ATTN64=1).  Measured in
         # round 3 (profiles/r03_attn64_stamps.txt): per SIMD its key loop needs ~1 060 cycles per 32-query x
         # 64-key unit at two waves per SIMD against ~885 for the 32-rows-per-wave kernel at three, a block's prologue + epilogue
         # are 18 % of its life and 576 workgroups on 512 resident slots leave a tail: 77-80 us against 60-62 us at the benchmark
         # batch; at S = 9216 both kernels reach the same 0.37 of the MFMA peak (1 119 vs 1 120 us).
-        t64 = self.attention_table64(q_heads, kv_heads) if (q_heads <= 255 and os.environ.get("TTV_ATTN64", "0") == "1") else None
+        t64 = self.attention_table64(q_heads, kv_heads) if (q_heads <= 255 and switches.flag("TTV_ATTN64", False)) else None
         # the encoder's last layer on its latent rows only (ttv_batch.qblocks_latent; TTV_ENC_LATENT_LAST=0 in the library: A/B)
         tl = self.attention_table_latent(q_heads, kv_heads) if sum(int(k) for k in self.token_counts) > 0 else None
         # the decoder's last layer without the query blocks that hold latent rows only (ttv_batch.qblocks_patch; TTV_DEC_PATCH_LAST=0: A/B)

@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence
 
 import torch
 
-from . import dp
+from . import dp, switches
 from .optim import HipAdamW, use_hip_adamw
 
 
@@ -105,7 +105,7 @@ def make_optimizer(model: torch.nn.Module, lr: float = 1e-4, beta1: float = 0.5,
     params = [p for p in model.parameters() if p.requires_grad]
     # parameters on the GPU: clip + AdamW as two HIP launches (optim.HipAdamW; TTV_HIP_ADAMW=0 keeps torch's multi-tensor kernels, and
     # so does capturable=True - the HIP step takes its step count from the host)
-    if use_hip_adamw(params) and not capturable and os.environ.get("TTV_HIP_ADAMW", "1") != "0":
+    if use_hip_adamw(params) and not capturable and switches.flag("TTV_HIP_ADAMW", True):
         return HipAdamW(params, lr=lr, betas=(beta1, beta2), weight_decay=weight_decay)
     fused = bool(params) and all(p.is_cuda for p in params)      # one multi-tensor kernel instead of a launch per parameter
     return torch.optim.AdamW(params, lr=lr, betas=(beta1, beta2), weight_decay=weight_decay, fused=fused, capturable=capturable and fused)
@@ -251,7 +251,7 @@ def make_discriminator_optimizer(loss_module: torch.nn.Module, lr: float = 1e-4,
                                  beta2: float = 0.96, weight_decay: float = 1e-4):
     """AdamW over `loss_module.disc_model` at lr * disc_lr_ratio (reference train.py:195-201, configs/tiny.yaml:46)."""
     params = list(loss_module.disc_model.parameters())
-    if use_hip_adamw(params) and os.environ.get("TTV_HIP_ADAMW", "1") != "0":           # as make_optimizer
+    if use_hip_adamw(params) and switches.flag("TTV_HIP_ADAMW", True):           # as make_optimizer
         return HipAdamW(params, lr=lr * disc_lr_ratio, betas=(beta1, beta2), weight_decay=weight_decay)
     fused = bool(params) and all(p.is_cuda for p in params)
     return torch.optim.AdamW(params, lr=lr * disc_lr_ratio, betas=(beta1, beta2), weight_decay=weight_decay, fused=fused)

@@ -11,7 +11,7 @@ from titok_video_amd.model.titok import TiTok
 from titok_video_amd.synthetic import seeded_titok_state, synthetic_clips
 from titok_video_amd.train import freeze_python_gc, limit_host_threads, make_optimizer, training_step
 B = int(os.environ.get("B", "32"))
-if os.environ.get("TTV_DEBUG"):   # diagnostics bits of ttv_debug_set (A/B runs on one box)
+if os.environ.get("TTV_DEBUG"):   # an OR of ttv_debug_set bits by value (the _lib.DBG_* table in tools/README.md; A/B runs on one box)
     from titok_video_amd import _lib
     _lib.lib().ttv_debug_set(int(os.environ["TTV_DEBUG"]))
 cfg = SimpleNamespace(tokenizer=SimpleNamespace(model=SimpleNamespace(patch_size=[4, 8, 8], fsq_levels=[7, 5, 5, 5, 5], encoder_size="tiny", decoder_size="tiny")))

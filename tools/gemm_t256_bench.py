@@ -41,8 +41,8 @@ cases = {
 print(f"{M} rows (batch {B} x 9216)")
 for name, (flops, call) in cases.items():
     row = []
-    nostore = 1 if os.environ.get("NOSTORE") == "1" else 0      # ttv_debug_set bit 0: the epilogue keeps its values alive and stores nothing
-    for bit, tag in ((1024, "128x128"), (512, "256x256")):
+    nostore = _lib.DBG_NO_STORES if os.environ.get("NOSTORE") == "1" else 0      # ttv_debug_set bit 0: the epilogue keeps its values alive and stores nothing
+    for bit, tag in ((_lib.DBG_GEMM_NO_T256, "128x128"), (_lib.DBG_GEMM_T256, "256x256")):
         lib.ttv_debug_set(bit | nostore)
         for _ in range(3):
             _lib.check(call(), name)
@@ -67,9 +67,9 @@ if os.environ.get("CHECK", "1") == "1":
         w = rnd(N, K, scale=K ** -0.5)
         y0 = torch.empty(M, N, dtype=bf, device=DEV)
         y1 = torch.empty(M, N, dtype=bf, device=DEV)
-        lib.ttv_debug_set(1024)
+        lib.ttv_debug_set(_lib.DBG_GEMM_NO_T256)
         _lib.check(lib.ttv_linear(x.data_ptr(), K, w.data_ptr(), K, None, None, y0.data_ptr(), N, M, N, K, code, ST), "linear")
-        lib.ttv_debug_set(512)
+        lib.ttv_debug_set(_lib.DBG_GEMM_T256)
         bad = 0
         for it in range(200):
             y1.fill_(float("nan"))

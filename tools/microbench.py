@@ -60,7 +60,7 @@ ao = torch.empty(L, d, dtype=bf, device=DEV)
 qkv_in = rnd(L, 2 * d + 2 * g)
 
 QUICK = os.environ.get("QUICK")
-for dbg in ([0, 1] if len(sys.argv) < 2 else [int(a) for a in sys.argv[1:]]):
+for dbg in ([0, _lib.DBG_NO_STORES] if len(sys.argv) < 2 else [int(a) for a in sys.argv[1:]]):
     lib.ttv_debug_set(dbg)
     print(f"---- debug flags = {dbg} ----")
     timeit("linear K256 N768 (k256, store)", lambda: lib.ttv_linear(x.data_ptr(), d, wqkv.data_ptr(), d, None, None, qkv.data_ptr(), 768, L, 768, d, 0, S),

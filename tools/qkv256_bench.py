@@ -16,7 +16,7 @@ from titok_video_amd.plan import BatchPlan  # noqa: E402
 DEV = torch.device("cuda:0")
 lib = _lib.lib()
 S = _lib.stream_ptr(DEV)
-OLD, STREAM, WS = 32768, 0, 131072
+OLD, STREAM, WS = _lib.DBG_QKV256_OFF, 0, _lib.DBG_QKV256_WS
 
 
 def t(fn, it=50):

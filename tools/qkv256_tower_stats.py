@@ -9,7 +9,7 @@ model = build(torch.bfloat16)
 shapes = [(8, 32, 48), (4, 16, 16), (16, 64, 32), (16, 128, 128)]; counts = [5, 1, 17, 128]
 clips = synthetic_clips(shapes, seed=29, dtype=torch.bfloat16, device=DEV)
 lib = _lib.lib(); outs = []
-for bits in (0, 1 << 15, 1 << 17):
+for bits in (0, _lib.DBG_QKV256_OFF, _lib.DBG_QKV256_WS):
     lib.ttv_debug_set(bits)
     with torch.no_grad():
         model.encode(clips, counts, want_bounded=True)

@@ -25,7 +25,7 @@ def call():
     _lib.check(lib.ttv_linear_qkv_rope(x.data_ptr(), d, w.data_ptr(), d, qkv.data_ptr(), 2 * d + 2 * g, L, d, g, plan.rope_cs.data_ptr(), 0, S), "qkv")
 
 
-for dbg in (0, 1):
+for dbg in (0, _lib.DBG_NO_STORES):
     lib.ttv_debug_set(dbg)
     for _ in range(200):       # the clock settles over many back-to-back launches
         call()

@@ -40,7 +40,8 @@ def call():
     _lib.check(lib.ttv_linear_qkv_rope(x.data_ptr(), d, w.data_ptr(), d, qkv.data_ptr(), 2 * d + 2 * g, L, d, g, plan.rope_cs.data_ptr(), 0, S), "qkv")
 
 
-for dbg in (0, 1, 2, 4, 8, 1 | 8, 2 | 4, 1 | 2 | 4, 1 | 2 | 4 | 8, 0):
+ST, DMA, RELOAD, MATH = _lib.DBG_NO_STORES, _lib.DBG_K256_NO_PANEL_DMA, _lib.DBG_K256_NO_TILE_RELOAD, _lib.DBG_K256_NO_EPILOGUE_MATH
+for dbg in (0, ST, DMA, RELOAD, MATH, ST | MATH, DMA | RELOAD, ST | DMA | RELOAD, ST | DMA | RELOAD | MATH, 0):
     lib.ttv_debug_set(dbg)
     print(f"debug {dbg:3d}: {t(call):7.1f} us", flush=True)
 lib.ttv_debug_set(0)

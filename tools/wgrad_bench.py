@@ -37,7 +37,7 @@ for name, N, K in (("dX qkv", 256, 768), ("dX w12", 256, 1408), ("fwd w3", 256, 
     x = torch.randn(L, K, device=DEV).bfloat16()
     w = (torch.randn(N, K, device=DEV) * K ** -0.5).bfloat16()
     y = torch.empty(L, N, device=DEV, dtype=torch.bfloat16)
-    for flag, tag in ((256, "tile 128"), (128, "tile 160"), (0, "auto")):
+    for flag, tag in ((_lib.DBG_GEMM_TILE128, "tile 128"), (_lib.DBG_GEMM_TILE160, "tile 160"), (0, "auto")):
         lib.ttv_debug_set(flag)
         fn = lambda: _lib.check(lib.ttv_linear(x.data_ptr(), K, w.data_ptr(), K, None, None, y.data_ptr(), N, L, N, K, _lib.dtype_code(torch.bfloat16), S), "linear")
         for _ in range(3):
