@@ -603,6 +603,41 @@ int ttv_lpips_crops_forward(void* const* recon_clips, void* const* target_clips,
 int ttv_lpips_crops_backward(void* const* recon_clips, void* const* grad_clips, const int32_t* clip_dims, int n_clips, const int32_t* crops,
                              int n_crops, int size, const void* g, int dtype, void* stream);
 
+/* ---- discriminator step: R1 / R2 noise and logit head (model/losses/loss_module.py:165-213) ------------- */
+/* out_real = real + s and out_fake = fake + s for every element of every clip, the SAME s for both (:189-191), in one launch.
+ * table  : DEVICE array of n_clips entries {const void* real; const void* fake; void* out_real; void* out_fake; const void* noise;
+ *          int64 numel; int64 element_offset} (56 bytes each; tensors contiguous, in `dtype` = TTV_BF16 or TTV_F32; numel < 2^31);
+ * chunks : DEVICE int32 [n_chunks][2] = (entry index, first element), first element a multiple of 8192: a chunk is up to 8192 elements.
+ * Accesses are 16 bytes wide where the entry's pointers are 16-byte aligned, element by element otherwise and for the last
+ * numel % (16 / element size) elements of a clip.
+ * generate == 0: s = noise[i] (already scaled; `noise` must be given); out = one rounding of the exact sum, what torch's add gives.
+ * generate != 0: `noise` is ignored and s is drawn, never stored.  Element i of an entry belongs to block (element_offset + i) / 4
+ *   and is lane (element_offset + i) % 4 of it; element_offset must be a multiple of 4 (lay the clips end to end and round each
+ *   clip's offset up).  The block's four words are Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9,
+ *   0xBB67AE85) of counter (block low, block high, draw low, draw high) under key (seed low, seed high).  A word x gives
+ *   u = ((x >> 9) + 0.5) * 2^-23, exact in fp32 and strictly inside (0, 1).  Words (0, 1) and (2, 3) are one Box-Muller pair each:
+ *   r = sqrt(-2 ln u_a), lanes (r cos 2 pi u_b, r sin 2 pi u_b), in fp32 (logf, sqrtf, sincospif).  A normal n is rounded to `dtype`
+ *   (randn_like), s = n * gp_noise is rounded to `dtype`, and the sum is rounded to `dtype`.
+ * Work is enqueued on `stream` only; no synchronisation, no library state. */
+int ttv_gp_noise_add(const void* table, int n_clips, const int32_t* chunks, int n_chunks, int generate, uint64_t seed, uint64_t draw,
+                     float gp_noise, int dtype, void* stream);
+
+/* The logit head of either step and its gradient, one launch of one block.  per_token: the tower's per-token outputs [groups][n_clips]
+ * [tokens_per_clip] in `dtype` (TTV_BF16 or TTV_F32), groups in the order real, fake (, real + noise, fake + noise); per_token_b, when
+ * not NULL, holds the second half of the groups and per_token_a the first.  A clip's logit is the fp32 mean of its tokens rounded once
+ * to `dtype`; everything after is fp32.  softplus is torch's (x above 20, else log1p(exp(x)); derivative 1 above 20, else z / (z + 1),
+ * z = exp(x)).  With m = real - fake per clip:
+ *   TTV_DISC_HEAD_GENERATOR (groups 2):          g_loss = softplus(m);  total = mean g_loss
+ *   TTV_DISC_HEAD_DISCRIMINATOR (groups 2 or 4): d_loss = softplus(-m), logits_relative = m, with 4 groups r1 = (real - noisy real)^2
+ *     and r2 = (fake - noisy fake)^2, with centering_weight > 0 centering = 0.5 (real + fake)^2;
+ *     total = mean d_loss + gp_scale (mean r1 + mean r2) + centering_weight mean centering   (gp_scale = gp_weight / gp_noise^2)
+ * terms fp32 [8]: total, d_loss | g_loss, logits_relative, r1, r2, centering (means over clips; zero where a term is off), 0, 0.
+ * grad fp32 [groups n_clips tokens_per_clip]: d total / d per_token.  Any n_clips >= 1; sums in a fixed order, no atomics. */
+#define TTV_DISC_HEAD_GENERATOR 0
+#define TTV_DISC_HEAD_DISCRIMINATOR 1
+int ttv_disc_head(const void* per_token_a, const void* per_token_b, int mode, int groups, int n_clips, int tokens_per_clip, int dtype,
+                  float gp_scale, float centering_weight, float* terms, float* grad, void* stream);
+
 /* Single operations (tests).  ttv_lpips_conv3x3: x [N][H][W][Cin] -> y [N][H][W][Cout], 3x3, stride 1, zero pad 1 per image, with
  * the weight image the dtype / shape rule above selects.  mode 0: y = relu(conv + bias); 1: y = conv * (h > 0), h [N][H][W][Cout];
  * 2: y = conv.  Workspace: ttv_lpips_conv_workspace_bytes (split-K partials; 0 when none).  ttv_lpips_maxpool: 2x2 / 2 max-pool of

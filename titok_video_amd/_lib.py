@@ -18,6 +18,7 @@ TTV_ENCODER, TTV_DECODER = 0, 1
 TTV_MAX_FSQ = 8
 TTV_MAX_TOKEN = 64
 TTV_MAX_CLIPS_PER_LAUNCH = 64
+TTV_DISC_HEAD_GENERATOR, TTV_DISC_HEAD_DISCRIMINATOR = 0, 1
 
 # ttv_debug_set bits: the TTV_DBG_* enum of include/titok_hip.h under the same names (tests/test_cabi_cpu.py holds the two equal).
 # A value with two names is read by two kernels with two meanings; tools/README.md says what each bit forces.
@@ -229,6 +230,8 @@ SYMBOLS = {
     "ttv_lpips_maxpool_backward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "ttv_lpips_crops_forward": (C.c_int, [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
     "ttv_lpips_crops_backward": (C.c_int, [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp]),
+    "ttv_gp_noise_add": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint64, f32, C.c_int, vp]),
+    "ttv_disc_head": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, f32, vp, vp, vp]),
     "ttv_i3d_workspace_bytes": (C.c_int64, [C.c_int]),
     "ttv_fvd_preprocess": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "ttv_i3d_features": (C.c_int, [C.POINTER(I3dWeights), vp, C.c_int, vp, vp, C.c_int64, vp]),

@@ -1,1 +1,1 @@
-from .loss_module import PerceptualCrops, ReconstructionLoss, perceptual_crop_plan  # noqa: F401
+from .loss_module import DiscHead, PerceptualCrops, ReconstructionLoss, perceptual_crop_plan  # noqa: F401

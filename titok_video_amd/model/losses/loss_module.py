@@ -25,6 +25,7 @@ from ... import _lib, switches
 from ..base.blocks import TiTokEncoder
 from ..base.utils import init_weights
 from ..metrics.lpips_gram import LPIPS
+from ...optim import _Tables
 from ...train import l1_reconstruction_loss
 
 
@@ -44,6 +45,72 @@ def _resized_hw(H: int, W: int, size: int):
 def _fused_crops() -> bool:
     """TTV_LPIPS_CROPS=0 selects the eager crop path of `perceptual_preprocess` on GPU tensors too (A/B and tests)."""
     return switches.flag("TTV_LPIPS_CROPS", True)
+
+
+def _fused_disc() -> bool:
+    """TTV_DISC_FUSED=0 selects the eager noise and logit head of the discriminator step (and the eager g_loss of the generator
+    step) on GPU tensors too (A/B and tests)."""
+    return switches.flag("TTV_DISC_FUSED", True)
+
+
+_GP_CHUNK = 8192       # GP_CHUNK of csrc/ttv_disc.hip
+_HIP_DTYPES = (torch.bfloat16, torch.float32)
+
+
+def gp_noise_layout(numels):
+    """Where `ttv_gp_noise_add` puts the clips of a batch: (counter offsets, output offsets, padded output length, chunk words).
+    A clip's counter offset is its element offset with the clips laid end to end, rounded up to a multiple of 4 (no Philox block
+    straddles two clips); its output offset is rounded up to 8 elements, so that every per-clip view of the flat output is 16-byte
+    aligned in both dtypes; a chunk word is (clip | first element << 32)."""
+    ctr, out, chunks, c_at, o_at = [], [], [], 0, 0
+    for i, n in enumerate(numels):
+        if not 0 < n < 2 ** 31:
+            raise ValueError(f"gp_noise_add: a clip of {n} elements (1 .. 2^31 - 1)")
+        c_at = (c_at + 3) // 4 * 4
+        o_at = (o_at + 7) // 8 * 8
+        ctr.append(c_at)
+        out.append(o_at)
+        chunks += [i | (first << 32) for first in range(0, n, _GP_CHUNK)]
+        c_at += n
+        o_at += n
+    return ctr, out, (o_at + 7) // 8 * 8, chunks
+
+
+class DiscHead(torch.autograd.Function):
+    """Per-token discriminator outputs -> loss terms and their gradient in one HIP launch (csrc/ttv_disc.hip, `ttv_disc_head`).
+    `a` holds the groups (real, fake[, real + noise, fake + noise]) x n clips x R tokens, or their first half with `b` the second.
+    Returns (total, terms): `terms` is the fp32 buffer [total, d_loss | g_loss, logits_relative, r1, r2, centering, 0, 0] of means
+    over clips and is not differentiable; `total` is its element 0 and carries the gradient."""
+
+    @staticmethod
+    def forward(ctx, mode, n, R, gp_scale, centering_weight, a, b):
+        parts = [a] if b is None else [a, b]
+        for t in parts:
+            _lib.require_gpu(t, "DiscHead")
+            if t.dtype != a.dtype or not t.is_contiguous():
+                raise ValueError("DiscHead: per-token outputs must be contiguous and of one dtype")
+        count = sum(t.numel() for t in parts)
+        G = count // (n * R)
+        if G * n * R != count or (b is not None and a.numel() != b.numel()):
+            raise ValueError(f"DiscHead: {count} per-token outputs are not groups x {n} clips x {R} tokens in two equal halves")
+        terms = torch.empty(8, dtype=torch.float32, device=a.device)
+        grad = torch.empty(count, dtype=torch.float32, device=a.device)
+        _lib.check(_lib.lib().ttv_disc_head(a.data_ptr(), _lib.ptr(b), mode, G, n, R, _lib.dtype_code(a.dtype), gp_scale, centering_weight,
+                                            terms.data_ptr(), grad.data_ptr(), _lib.stream_ptr(a.device)), "ttv_disc_head")
+        ctx.save_for_backward(grad)
+        ctx.parts = [(t.numel(), t.shape, t.dtype) for t in parts]
+        ctx.mark_non_differentiable(terms)
+        return terms[0], terms
+
+    @staticmethod
+    def backward(ctx, g, _g_terms):
+        (grad,) = ctx.saved_tensors
+        full = grad * g
+        out, at = [], 0
+        for k, (numel, shape, dtype) in enumerate(ctx.parts):
+            out.append(full[at:at + numel].view(shape).to(dtype) if ctx.needs_input_grad[5 + k] else None)
+            at += numel
+        return (None,) * 5 + tuple(out) + (None,) * (2 - len(out))
 
 
 def perceptual_crop_plan(frame_shapes, size: int, samples: int, resize_prob: float = 0.25):
@@ -192,6 +259,62 @@ class ReconstructionLoss(nn.Module):
             per_token = self.disc_model(list(x), [self.disc_tokens] * n)          # [4 n, 1]
         return per_token.view(n, -1).mean(dim=-1)
 
+    def _disc_per_token(self, x: Sequence[torch.Tensor]) -> torch.Tensor:
+        """The tower's output for the 4 register tokens of every clip, [4 n, 1]: what `disc_wrapper` averages."""
+        n = len(x)
+        if _F32_HEAD:
+            return self.disc_model.forward_z(list(x), [self.disc_tokens] * n)
+        return self.disc_model(list(x), [self.disc_tokens] * n)
+
+    def gp_noise_add(self, real, fake, noise=None):
+        """real + s and fake + s per clip with the same s in one HIP launch (`ttv_gp_noise_add`): s = noise[i] when `noise` is given,
+        otherwise gp_noise times a standard normal drawn in the kernel from (torch.initial_seed(), this module's draw counter, the
+        element's position in the batch) and never stored - tests/gp_noise_ref.py restates it.  The outputs are views of one flat
+        allocation.  Clips: contiguous GPU tensors of one dtype, bf16 or fp32; `fake` and `noise` shaped like `real`."""
+        n = len(real)
+        dev, dtype = real[0].device, real[0].dtype
+        for group in (real, fake) + (() if noise is None else (noise,)):
+            if len(group) != n:
+                raise ValueError("gp_noise_add: lists of different lengths")
+            for t, r in zip(group, real):
+                _lib.require_gpu(t, "gp_noise_add")
+                if t.dtype != dtype or t.shape != r.shape or not t.is_contiguous() or t.device != dev:
+                    raise ValueError("gp_noise_add: clips must be contiguous, of one dtype and device, and shaped alike across the lists")
+        key = (tuple(t.numel() for t in real), dtype)
+        st = self.__dict__.get("_gp_layout")
+        if st is None or st["key"] != key:
+            ctr, out, padded, chunks = gp_noise_layout(key[0])
+            words = torch.zeros(7 * n + len(chunks), dtype=torch.int64)
+            words[:7 * n].view(n, 7)[:, 5] = torch.tensor(key[0], dtype=torch.int64)
+            words[:7 * n].view(n, 7)[:, 6] = torch.tensor(ctr, dtype=torch.int64)
+            words[7 * n:] = torch.tensor(chunks, dtype=torch.int64)
+            st = self.__dict__["_gp_layout"] = {"key": key, "out": out, "padded": padded, "words": words, "n_chunks": len(chunks)}
+        tables = self.__dict__.get("_gp_tables")
+        if tables is None or tables.device != dev:
+            tables = self.__dict__["_gp_tables"] = _Tables(dev)
+        flat = torch.empty(2 * st["padded"], dtype=dtype, device=dev)
+        out_real = [flat[o:o + t.numel()].view_as(t) for o, t in zip(st["out"], real)]
+        out_fake = [flat[st["padded"] + o:st["padded"] + o + t.numel()].view_as(t) for o, t in zip(st["out"], real)]
+        words, n_chunks = st["words"], st["n_chunks"]
+        ptrs = [[r.data_ptr(), f.data_ptr(), a.data_ptr(), b.data_ptr(), 0 if noise is None else noise[i].data_ptr()]
+                for i, (r, f, a, b) in enumerate(zip(real, fake, out_real, out_fake))]
+        words[:7 * n].view(n, 7)[:, :5] = torch.tensor(ptrs, dtype=torch.int64)
+        slot = tables.take(n, n_chunks, entry_words=7)
+        total = words.numel()
+        slot["host"][:total].copy_(words)
+        slot["dev"][:total].copy_(slot["host"][:total], non_blocking=True)
+        base = slot["dev"].data_ptr()
+        generate = noise is None
+        draw = self.__dict__.get("_gp_draw", 0)
+        _lib.check(_lib.lib().ttv_gp_noise_add(base, n, base + 56 * n, n_chunks, int(generate), torch.initial_seed() & (2 ** 64 - 1), draw,
+                                               self.gp_noise, _lib.dtype_code(dtype), _lib.stream_ptr(dev)), "ttv_gp_noise_add")
+        if generate:
+            self.__dict__["_gp_draw"] = draw + 1       # once per generated draw: two steps never share counters
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        slot["event"] = ev
+        return out_real, out_fake
+
     def _set_disc_trainable(self, flag: bool) -> None:
         params = self.__dict__.get("_disc_param_list")          # cached: parameters() walks the module tree, twice per step here
         if params is None:
@@ -238,6 +361,15 @@ class ReconstructionLoss(nn.Module):
                 total = total + self.gram_weight * terms["gram_loss"]
         if self.disc_weight > 0.0:
             self._set_disc_trainable(False)                                   # the generator sees a frozen critic (:144-146)
+            if _fused_disc() and all(c.is_cuda and c.dtype in _HIP_DTYPES for c in real + fake):
+                per_real = self._disc_per_token([t.detach() for t in real])   # no gradient path: runs the fused inference towers
+                per_fake = self._disc_per_token(fake)                         # tape + inputs-only backward into the reconstruction
+                g_mean, head = DiscHead.apply(_lib.TTV_DISC_HEAD_GENERATOR, len(real), self.disc_tokens, 0.0, 0.0, per_real, per_fake)
+                total = total + self.disc_weight * g_mean
+                report = self._report("gen", terms)
+                report["gen/g_loss"] = head[1]                                # mean softplus(real - fake), from the head's buffer
+                report.update(self._report("gen", {"total_loss": total}))
+                return total, report
             score_real = self.disc_wrapper([t.detach() for t in real])        # no gradient path: runs the fused inference towers
             score_fake = self.disc_wrapper(fake)                              # tape + inputs-only backward into the reconstruction
             terms["g_loss"] = F.softplus(score_real - score_fake)             # softplus(-(fake - real)), relativistic (:149-151)
@@ -258,6 +390,9 @@ class ReconstructionLoss(nn.Module):
         # attention, per-row norms), so they are issued here as ONE packed call and the logits split afterwards: same values,
         # one tape / one backward / one set of weight-gradient launches instead of four.
         packed = real + fake
+        hip = _fused_disc() and all(c.is_cuda and c.dtype in _HIP_DTYPES for c in packed)
+        if hip:
+            return self._discriminator_step_fused(real, fake, noise)
         if use_penalty:
             if noise is None:
                 # one generator call for the whole batch instead of one per clip (a launch each), split into per-clip views
@@ -289,3 +424,36 @@ class ReconstructionLoss(nn.Module):
         total = total.mean()
         terms["total_loss"] = total
         return total, self._report("disc", terms)
+
+    def _discriminator_step_fused(self, real, fake, noise):
+        """The same step with the noise and both additions in one launch (`gp_noise_add`) and everything after the towers in one
+        more (`DiscHead`): the reported scalars are views of the head's buffer."""
+        n, packed = len(real), real + fake
+        use_penalty = self.gp_weight > 0.0
+        noisy = []
+        if use_penalty:
+            same = len({t.dtype for t in packed}) == 1 and all(r.shape == f.shape for r, f in zip(real, fake))
+            if noise is not None:
+                noise = [z.contiguous() for z in noise]
+                same = same and len(noise) == n and all(z.is_cuda and z.dtype == r.dtype and z.shape == r.shape for z, r in zip(noise, real))
+            if same:
+                noisy_real, noisy_fake = self.gp_noise_add(real, fake, noise)
+                noisy = noisy_real + noisy_fake
+            elif noise is not None:            # mixed dtypes or shapes that broadcast: torch's promotion rules, as the eager route
+                noisy = list(torch._foreach_add(real, list(noise))) + list(torch._foreach_add(fake, list(noise)))
+            else:
+                raise ValueError("the discriminator step draws its R1 / R2 noise for clips of one dtype, real and fake shaped alike")
+        if use_penalty and _TWO_CALLS:
+            a, b = self._disc_per_token(packed), self._disc_per_token(noisy)
+        else:
+            a, b = self._disc_per_token(packed + noisy), None
+        gp_scale = self.gp_weight / self.gp_noise ** 2 if use_penalty else 0.0
+        total, head = DiscHead.apply(_lib.TTV_DISC_HEAD_DISCRIMINATOR, n, self.disc_tokens, gp_scale, max(self.centering_weight, 0.0),
+                                     a.contiguous(), None if b is None else b.contiguous())
+        report = {"disc/d_loss": head[1], "disc/logits_relative": head[2]}
+        if use_penalty:
+            report["disc/r1_penalty"], report["disc/r2_penalty"] = head[3], head[4]
+        if self.centering_weight > 0.0:
+            report["disc/centering_loss"] = head[5]
+        report["disc/total_loss"] = head[0]
+        return total, report

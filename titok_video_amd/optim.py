@@ -24,12 +24,12 @@ class _Tables:
         self.slots = []
         self.next = 0
 
-    def take(self, n_entries: int, n_chunks: int):
+    def take(self, n_entries: int, n_chunks: int, entry_words: int = 5):
         if len(self.slots) < _SLOTS:
             self.slots.append(None)
         i = self.next
         self.next = (self.next + 1) % _SLOTS
-        need = n_entries * 5 + n_chunks           # int64 words: 5 per entry, one per chunk (two int32)
+        need = n_entries * entry_words + n_chunks           # int64 words: 5 per optimizer entry, one per chunk (two int32)
         s = self.slots[i]
         if s is None or s["host"].numel() < need:
             cap = max(need, 4096)
