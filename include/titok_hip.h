@@ -452,6 +452,16 @@ int ttv_opt_adamw_step(const void* table, const int32_t* chunks, int n_chunks, i
                        float beta1, float beta2, float eps, float weight_decay, float bias_correction1, float bias_correction2_sqrt,
                        float max_norm, float* out_norm, void* stream);
 
+/* Per-parameter gradient norms of one tensor list (the log of reference train.py:78-79, :102-103: lightning.pytorch.utilities.grad_norm
+ * with norm_type 2) from the partials ttv_opt_grad_sumsq has written for the same table, in one launch.  `chunks` (device, n_chunks x
+ * (entry, first element)) lists every entry's chunks together and the entries in ascending order, as ttv_opt_grad_sumsq's caller builds
+ * it; partials[c] belongs to chunks[c].  norms[e] = sqrtf(sum of the partials of entry e, added in ascending chunk order, fp32), 0 for an
+ * entry without chunks; norms[n_entries] = sqrtf(sum of partials[0 .. n_chunks), added in ascending order, fp32).  A fixed order and
+ * no atomics: identical calls give identical bits.  `table` is the entry table of the other two calls (not read: the chunk table
+ * names the entries).  Reads nothing but chunks and partials, writes nothing but norms[0 .. n_entries]. */
+int ttv_opt_param_norms(const void* table, const int32_t* chunks, int n_chunks, int n_entries, const float* partials, float* norms,
+                        void* stream);
+
 /* Single backward ops, exported for parity tests. */
 /* dW[N,K] (fp32, accumulated) += dY[L,N]^T X[L,K]  (weight gradient of y = x w^T; what autograd computes for the
  * nn.Linear weights of base/blocks.py:70-84,147-148).  The token range is split over blocks; with a workspace of
@@ -514,6 +524,22 @@ int ttv_clip_from_u8(const void* frames_thwc, int T, int H, int W, void* clip_ct
  * uses fixed-point weights; this is the float path.)  A scale above 8 on an axis, a window outside the resized frame, a
  * misaligned destination, more clips than the limit or a bad dtype return TTV_ERR_INVALID and launch nothing. */
 int ttv_clip_resample_u8(void* const* frames_thwc, void* const* clips_cthw, const int32_t* geom, int n_clips, int dtype, void* stream);
+
+/* The logged side-by-side videos of the validation step (reference train.py:141-142:
+ * torch.cat((y, x.clamp(-1, 1)), dim=-1).permute(1, 0, 2, 3).cpu().float().numpy(), then ((v + 1) / 2 * 255).astype(np.uint8)), for any
+ * number of clips (host arrays of device pointers; launches of up to TTV_MAX_CLIPS_PER_LAUNCH clips inside).  target[i] (y) and recon[i]
+ * (x): contiguous [3][T][H][W] in `dtype` (TTV_BF16 or TTV_F32), dims = n_clips x (T, H, W) (host); panels[i]: uint8 [T][3][H][2W],
+ * columns 0 .. W-1 from the target, columns W .. 2W-1 from the reconstruction clamped to [-1, 1] (a NaN stays a NaN).
+ * Value of a byte, from its element v widened exactly to fp32: t = v + 1.0f; t = t / 2.0f; t = t * 255.0f, each step rounded to fp32 on
+ * its own (no fused multiply-add, no folding into * 127.5f), then truncated toward zero: numpy's fp32 arithmetic, so every byte is
+ * defined bit for bit.  Where numpy leaves the conversion to the platform this defines it: t < 0 gives 0, t >= 255 gives 255 (a
+ * target outside [-1, 1] saturates) and NaN gives 0.
+ * Any T, H, W >= 1 with a panel below 2^31 bytes, any alignment of the panels; clips with W % 8 == 0, 16-byte aligned sources and an
+ * 8-byte aligned panel move 16 bytes per load and 8 per store, the others 4 bytes per store.  Every input element is read once and
+ * every output byte written once; nothing outside the panels is written.  TTV_ERR_INVALID with nothing launched: a bad dtype or
+ * shape, a null pointer, a source not aligned to its element size.  Work is enqueued on `stream` only. */
+int ttv_recon_panels_u8(void* const* target, void* const* recon, const int32_t* dims, int n_clips, int dtype, void* const* panels,
+                        void* stream);
 
 /* PSNR statistic of the evaluation loop (model/metrics/eval_metrics.py:19,32-36: x.clamp(-1, 1), torchmetrics
  * PeakSignalNoiseRatio(data_range=2) = running sum of squared errors + element count): acc[0] += sum (clamp(recon) - target)^2,

@@ -206,6 +206,7 @@ SYMBOLS = {
                                               C.c_int, C.c_int, C.c_float, C.c_int, vp]),
     "ttv_opt_grad_sumsq": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
     "ttv_opt_adamw_step": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int] + [C.c_float] * 8 + [vp, vp]),
+    "ttv_opt_param_norms": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp]),
     "ttv_linear_wgrad_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "ttv_linear_wgrad": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp]),
     "ttv_rmsnorm_backward": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, f32, C.c_int, vp]),
@@ -217,6 +218,7 @@ SYMBOLS = {
     "ttv_l1_loss": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp]),
     "ttv_clip_from_u8": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "ttv_clip_resample_u8": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
+    "ttv_recon_panels_u8": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp]),
     "ttv_sq_err_accumulate": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "ttv_ssim_workspace_bytes": (C.c_int64, [vp, C.c_int]),
     "ttv_ssim_accumulate": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int64, vp]),

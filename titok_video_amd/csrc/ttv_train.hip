@@ -473,6 +473,45 @@ __global__ __launch_bounds__(256) void k_opt_gradsq(const OptEntry* __restrict__
   const float t = opt_block_sum(acc, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
+// Per-parameter gradient norms (the log of reference train.py:78-79, :102-103: Lightning's grad_norm(module, 2)) from the partials
+// k_opt_gradsq has just written: the segmented sum of numbers the step already has, in one launch.  The chunk table lists every
+// entry's chunks together, entries ascending (optim.py builds it so): a thread finds its entry's first chunk by bisection and adds the
+// entry's partials in ascending chunk order - a fixed order, no atomics, identical calls give identical bits.  The last block sums
+// ALL partials of the table in ascending order for slot n_entries: the waves stage 2 048 of them at a time in LDS and one lane adds
+// (a few hundred terms for the tiny tokenizer; the per-entry sums are a handful each, 44 for its largest matrix).
+// Both sums are one lane's dependent chain, as long as the chunk list: the price of the ascending order include/titok_hip.h
+// promises.  Tiny tokenizer (under 900 chunks): lost in the 0.1 ms the log adds to a step.  At the size of the base configs' towers
+// (20 480 chunks = 168 M elements, the largest entry 2 048 chunks; tools/val_bench.py builds that table) the launch takes 0.30 ms,
+// once per logged step, beside a training step of tens of milliseconds: not worth a tree, which would change the stated order.
+#define OPT_NORM_TILE 2048
+__global__ __launch_bounds__(256) void k_opt_param_norms(const int2* __restrict__ chunks, int n_chunks, int n_entries,
+                                                         const float* __restrict__ partial, float* __restrict__ norms) {
+  __shared__ float tile[OPT_NORM_TILE];
+  if (blockIdx.x == gridDim.x - 1) {
+    float acc = 0.f;
+    for (int c0 = 0; c0 < n_chunks; c0 += OPT_NORM_TILE) {
+      const int n = n_chunks - c0 < OPT_NORM_TILE ? n_chunks - c0 : OPT_NORM_TILE;
+      __syncthreads();
+      for (int i = threadIdx.x; i < n; i += 256) tile[i] = partial[c0 + i];
+      __syncthreads();
+      if (threadIdx.x == 0)
+        for (int i = 0; i < n; ++i) acc += tile[i];
+    }
+    if (threadIdx.x == 0) norms[n_entries] = sqrtf(acc);
+    return;
+  }
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= n_entries) return;
+  int lo = 0, hi = n_chunks;             // the first chunk whose entry is >= e
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (chunks[mid].x < e) lo = mid + 1;
+    else hi = mid;
+  }
+  float acc = 0.f;                       // an entry without elements has no chunk: norm 0
+  for (int c = lo; c < n_chunks && chunks[c].x == e; ++c) acc += partial[c];
+  norms[e] = sqrtf(acc);
+}
 struct OptHyper { float lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, max_norm; };
 __device__ __forceinline__ void opt_update(float& p, float g, float& m, float& v, const OptHyper& h, float step_size) {
   p -= h.lr * h.wd * p;
@@ -723,6 +762,16 @@ int ttv_opt_grad_sumsq(const void* table, const int32_t* chunks, int n_chunks, i
   if (dtype == TTV_BF16) hipLaunchKernelGGL((k_opt_gradsq<bf16_t>), dim3(n_chunks), dim3(256), 0, s, (const OptEntry*)table, (const int2*)chunks, partials);
   else hipLaunchKernelGGL((k_opt_gradsq<float>), dim3(n_chunks), dim3(256), 0, s, (const OptEntry*)table, (const int2*)chunks, partials);
   TTV_CHECK_LAUNCH("opt_grad_sumsq");
+  return TTV_OK;
+}
+
+int ttv_opt_param_norms(const void* table, const int32_t* chunks, int n_chunks, int n_entries, const float* partials, float* norms,
+                        void* stream) {
+  TTV_CHECK_ARG(n_chunks >= 0 && n_entries >= 0 && norms, "opt_param_norms: %d chunks, %d entries, or no destination", n_chunks, n_entries);
+  TTV_CHECK_ARG(n_chunks == 0 || (table && chunks && partials), "opt_param_norms: null buffer");
+  hipLaunchKernelGGL(k_opt_param_norms, dim3((unsigned)((n_entries + 255) / 256 + 1)), dim3(256), 0, (hipStream_t)stream, (const int2*)chunks,
+                     n_chunks, n_entries, partials, norms);
+  TTV_CHECK_LAUNCH("opt_param_norms");
   return TTV_OK;
 }
 

@@ -54,6 +54,7 @@ class HipAdamW(torch.optim.Optimizer):
         self._partials = None
         self._norm = None
         self._static = {}
+        self._param_norms = None          # (parameters, device norms) of the last norms launch
 
     # -- state ----------------------------------------------------------------------------------------------------------------------
     def _state_for(self, p):
@@ -80,10 +81,38 @@ class HipAdamW(torch.optim.Optimizer):
         return loss
 
     @torch.no_grad()
-    def clip_and_step(self, max_norm: float) -> torch.Tensor:
-        return self._run(float(max_norm))
+    def clip_and_step(self, max_norm: float, want_param_norms: bool = False) -> torch.Tensor:
+        """want_param_norms=True: one more launch per (group, dtype) bucket (`ttv_opt_param_norms`) turns the per-chunk sums of squares
+        the clip has just computed into one 2-norm per parameter, read with `last_param_norms()`.  The step itself - launches,
+        arithmetic, return value - is the same with and without."""
+        return self._run(float(max_norm), want_norms=want_param_norms)
 
-    def _run(self, max_norm: Optional[float]):
+    @torch.no_grad()
+    def param_grad_norms(self):
+        """`last_param_norms()` of the gradients as they stand, without stepping: `ttv_opt_grad_sumsq` + `ttv_opt_param_norms` per
+        bucket.  For loops that do not clip (max_grad_norm falsy) and for modules that are not being stepped; creates no
+        optimizer state."""
+        self._run(None, want_norms=True, update=False)
+        return self.last_param_norms()
+
+    def last_param_norms(self):
+        """(params, norms) of the last `clip_and_step(.., want_param_norms=True)` or `param_grad_norms()`: `params` the parameters
+        that had a gradient, in parameter order (group by group, as `param_groups` lists them); `norms` a float32 device tensor of
+        len(params) + B entries - the 2-norm of each parameter's gradient, then the 2-norm over each of the B (group, dtype)
+        buckets (B = 1 for one group of one dtype).  No synchronisation, and no check that the gradients are still the ones the norms
+        were taken from: that is the caller's knowledge.  The norm over ALL parameters is taken from the bucket
+        norms in float64 on the host at read time: `HipAdamW.total_norm(norms.cpu()[len(params):])`.
+        The gradients are the unclipped ones (`clip_and_step` scales in registers and leaves `p.grad` alone)."""
+        if self._param_norms is None:
+            raise RuntimeError("HipAdamW.last_param_norms: no norms yet - clip_and_step(max_norm, want_param_norms=True) or param_grad_norms()")
+        return self._param_norms
+
+    @staticmethod
+    def total_norm(bucket_norms) -> float:
+        """2-norm over all buckets from the bucket norms (host values), in float64."""
+        return math.sqrt(sum(float(v) ** 2 for v in bucket_norms))
+
+    def _run(self, max_norm: Optional[float], want_norms: bool = False, update: bool = True):
         # buckets: (group, dtype) -> parameters with a gradient
         buckets = []
         for g in self.param_groups:
@@ -100,6 +129,8 @@ class HipAdamW(torch.optim.Optimizer):
                 buckets.append((g, dt, ps))
         clip = max_norm is not None
         if not buckets:
+            if want_norms:
+                self._param_norms = ([], torch.zeros(0, dtype=torch.float32, device="cuda"))
             return torch.zeros((), device="cuda") if clip else None
         dev = buckets[0][2][0].device
         if any(p.device != dev for _, _, ps in buckets for p in ps):
@@ -111,9 +142,10 @@ class HipAdamW(torch.optim.Optimizer):
             self._norm = torch.zeros(1, dtype=torch.float32, device=dev)
             self._static = {}
         # Host tables.  Element counts, chunk lists and offsets of a parameter list are built once; the pointers every step.
-        for _, _, ps in buckets:
-            for p in ps:
-                self._state_for(p)
+        if update:
+            for _, _, ps in buckets:
+                for p in ps:
+                    self._state_for(p)
         key = tuple((id(g), dt, tuple((id(p), p.numel()) for p in ps)) for g, dt, ps in buckets)
         st = self._static.get(key)
         if st is None:
@@ -128,13 +160,24 @@ class HipAdamW(torch.optim.Optimizer):
                         c_off += 1
                 layout.append((e_off, len(ps), c0, c_off - c0))
                 e_off += len(ps)
-            st = {"words": torch.tensor(words + chunk_words, dtype=torch.int64), "n_words": len(words), "layout": layout, "n_chunks": c_off}
+            # parameter order -> slot of the norms buffer (bucket b writes its entries and then its own total: e_off + b onwards)
+            slot_of = {}
+            for b, ((g, dt, ps), (eo, ne, _, _)) in enumerate(zip(buckets, layout)):
+                for i, p in enumerate(ps):
+                    slot_of[id(p)] = eo + b + i
+            ordered = [p for g in self.param_groups for p in g["params"] if id(p) in slot_of]
+            order = [slot_of[id(p)] for p in ordered] + [eo + b + ne for b, (eo, ne, _, _) in enumerate(layout)]
+            st = {"words": torch.tensor(words + chunk_words, dtype=torch.int64), "n_words": len(words), "layout": layout, "n_chunks": c_off,
+                  "ordered": ordered, "order": order, "order_dev": None}
             self._static = {key: st}          # one live parameter list at a time
         tmpl, n_words, layout, n_chunks = st["words"], st["n_words"], st["layout"], st["n_chunks"]
         # the four pointer columns are read afresh (a load_state_dict() or a .data assignment may have replaced a tensor)
         flat = [p for _, _, ps in buckets for p in ps]
         ptrs = []
         for p in flat:
+            if not update:                # norms only: the kernels read the gradient column alone
+                ptrs += [p.data_ptr(), p.grad.data_ptr(), 0, 0]
+                continue
             sp = self.state[p]
             if sp["exp_avg"].dtype != p.dtype or sp["exp_avg"].device != p.device:          # a loaded state_dict: bring it to the parameter
                 sp["exp_avg"] = sp["exp_avg"].to(device=p.device, dtype=p.dtype)
@@ -150,11 +193,22 @@ class HipAdamW(torch.optim.Optimizer):
         chunks_base = base + 8 * n_words
         if self._partials is None or self._partials.numel() < max(n_chunks, 1) or self._partials.device != dev:
             self._partials = torch.empty(max(n_chunks, 1024), dtype=torch.float32, device=dev)
-        if clip:
+        if clip or want_norms:
             for (g, dt, ps), (eo, ne, co, nc) in zip(buckets, layout):
                 _lib.check(lib.ttv_opt_grad_sumsq(base + 40 * eo, chunks_base + 8 * co, nc, _lib.dtype_code(dt),
                                                   self._partials.data_ptr() + 4 * co, stream), "opt_grad_sumsq")
-        for (g, dt, ps), (eo, ne, co, nc) in zip(buckets, layout):
+        if want_norms:
+            # a fresh buffer per call: the tensor handed out by last_param_norms() is never rewritten
+            raw = torch.empty(n_words // 5 + len(layout), dtype=torch.float32, device=dev)
+            for b, (eo, ne, co, nc) in enumerate(layout):
+                _lib.check(lib.ttv_opt_param_norms(base + 40 * eo, chunks_base + 8 * co, nc, ne, self._partials.data_ptr() + 4 * co,
+                                                   raw.data_ptr() + 4 * (eo + b), stream), "opt_param_norms")
+            if st["order"] != list(range(raw.numel())):          # several buckets: parameter order, then the bucket norms
+                if st["order_dev"] is None or st["order_dev"].device != dev:
+                    st["order_dev"] = torch.tensor(st["order"], dtype=torch.int64, device=dev)
+                raw = raw.index_select(0, st["order_dev"])
+            self._param_norms = (st["ordered"], raw)
+        for (g, dt, ps), (eo, ne, co, nc) in zip(buckets, layout) if update else ():
             # torch keeps a step count per parameter; they differ only when parameters join a group late, which this path does not support
             steps = {self._step_value(self.state[p]) for p in ps}
             if len(steps) != 1:

@@ -6,12 +6,18 @@ model/losses/loss_module.py:118: L1 between target and reconstruction, mean over
 
 `gan_training_step` adds the reference's discriminator step (train.py:86-107) on top of `model/losses/loss_module.py`'s
 mirror; LPIPS is outside this path's scope (network-fetched weights).
+
+Logging and validation (reference train.py:78-79, :102-103, :118-160): `grad_norm_dict` is the gradient-norm log from the sums the
+optimizer's clip already takes, `recon_panels` the logged side-by-side videos as uint8 from one HIP launch and one device-to-host
+copy, `ValidationLoop` the three validation hooks without a logger.
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import dp, switches
@@ -311,3 +317,137 @@ def gan_training_step(model, loss_module, clips: List[torch.Tensor], token_count
             dp.allreduce_mean_by_count([p.grad for p in d_params], len(clips), group=group)
         clip_and_step(opt_d, d_params, max_grad_norm)
     return loss_dict, out["indices"]
+
+
+# ---- logging and validation (reference train.py:78-79, :102-103, :118-160) ------------------------------------------------------------
+def grad_norm_dict(module: torch.nn.Module, optimizer: HipAdamW, norm_type=2, reuse: bool = False) -> dict:
+    """What `lightning.pytorch.utilities.grad_norm(module, norm_type=2)` returns (reference train.py:78-79, :102-103), from
+    `optimizer`'s kernels and ONE device-to-host copy.  Lightning 2.x defines it as
+        norms = {f"grad_{float(norm_type)}_norm/{name}": p.grad.data.norm(norm_type)
+                 for name, p in module.named_parameters() if p.grad is not None}
+        if norms: norms[f"grad_{float(norm_type)}_norm_total"] = torch.tensor(list(norms.values())).norm(norm_type)
+    so the keys are `grad_2.0_norm/<name>` in `named_parameters()` order plus `grad_2.0_norm_total`, the 2-norm of the listed norms;
+    an empty dict when no parameter has a gradient.  Lightning is not installed where this package is built and tested: the
+    definition above is restated from its source, not pinned by a fixture.  Values are Python floats; the total is taken in float64
+    from the listed fp32 norms (Lightning takes it in fp32).
+    The norms are taken here, by `optimizer.param_grad_norms()` (two launches per bucket, no step), unless the caller says
+    `reuse=True`: then the norms of the optimizer's last `clip_and_step(max_norm, want_param_norms=True)` are read and nothing is
+    launched - for the caller who has just made that step on these very gradients; nothing checks it.  They are norms of
+    `p.grad` as stored: HipAdamW clips in registers, so after a clip the reference's log shows these values times
+    min(1, max_norm / (total + 1e-6)).  Every parameter of `module` that has a gradient must belong to `optimizer`."""
+    if float(norm_type) != 2.0:
+        raise ValueError(f"grad_norm_dict: norm_type {norm_type!r}; the optimizer's kernels take 2-norms only")
+    if not isinstance(optimizer, HipAdamW):
+        raise TypeError("grad_norm_dict: the norms come from optim.HipAdamW's kernels; got " + type(optimizer).__name__)
+    named = [(name, p) for name, p in module.named_parameters() if p.grad is not None]
+    if not named:
+        return {}
+    params, norms = optimizer.last_param_norms() if reuse else optimizer.param_grad_norms()
+    host = norms.cpu().tolist()          # the one copy (synchronises the stream)
+    at = {id(p): i for i, p in enumerate(params)}
+    out = {}
+    for name, p in named:
+        if id(p) not in at:
+            raise RuntimeError(f"grad_norm_dict: parameter '{name}' has a gradient but does not belong to the optimizer")
+        out[f"grad_2.0_norm/{name}"] = host[at[id(p)]]
+    out["grad_2.0_norm_total"] = math.sqrt(sum(v * v for v in out.values()))
+    return out
+
+
+def recon_panels(target: Sequence[torch.Tensor], recon: Sequence[torch.Tensor]) -> List[np.ndarray]:
+    """The logged videos of reference train.py:141-142, one per clip pair ([3,T,H,W] each, any shapes):
+        torch.cat((y, x.clamp(-1, 1)), dim=-1).permute(1, 0, 2, 3).cpu().float().numpy();  ((v + 1) / 2 * 255).astype(np.uint8)
+    as uint8 arrays [T,3,H,2W] - the target on the left, the clamped reconstruction on the right, bit for bit what the expression
+    gives (include/titok_hip.h, ttv_recon_panels_u8; a target outside [-1, 1] saturates, NaN gives 0).  One HIP launch per 64 clips
+    into one device buffer, one device-to-host copy of it into pinned memory (a quarter of the reference's fp32 bytes); the arrays
+    are views of that host buffer.  bf16 or fp32 clips; a bf16 / fp32 pair is widened to fp32 as torch.cat would.  GPU only."""
+    import ctypes as C
+    from . import _lib
+    if len(target) != len(recon):
+        raise ValueError(f"recon_panels: {len(target)} targets, {len(recon)} reconstructions")
+    if not len(recon):
+        return []
+    for y, x in zip(target, recon):
+        _lib.require_gpu(x, "recon_panels")
+        _lib.require_gpu(y, "recon_panels")
+        if x.dim() != 4 or x.shape[0] != 3 or x.shape != y.shape:
+            raise ValueError(f"recon_panels: clips must be [3,T,H,W] pairs of one shape, got {tuple(y.shape)} and {tuple(x.shape)}")
+    dev = recon[0].device
+    dt = recon[0].dtype if all(t.dtype == recon[0].dtype for t in list(recon) + list(target)) else torch.float32
+    ys = [t.detach().to(dt).contiguous() for t in target]
+    xs = [t.detach().to(dt).contiguous() for t in recon]
+    sizes = [int(x.numel()) * 2 for x in xs]                     # bytes of a panel: T * 3 * H * 2W
+    offsets, total = [], 0
+    for n in sizes:
+        offsets.append(total)
+        total += (n + 15) // 16 * 16                              # every panel 16-byte aligned
+    buf = torch.empty(total, dtype=torch.uint8, device=dev)
+    dims = (C.c_int32 * (3 * len(xs)))(*[int(d) for x in xs for d in x.shape[1:]])
+    outs = (C.c_void_p * len(xs))(*[buf.data_ptr() + o for o in offsets])
+    _lib.check(_lib.lib().ttv_recon_panels_u8(_lib.ptr_array(ys), _lib.ptr_array(xs), dims, len(xs), _lib.dtype_code(dt), outs,
+                                              _lib.stream_ptr(dev)), "ttv_recon_panels_u8")
+    host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+    host.copy_(buf, non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()
+    flat = host.numpy()
+    return [flat[o:o + n].reshape(x.shape[1], 3, x.shape[2], 2 * x.shape[3]) for o, n, x in zip(offsets, sizes, xs)]
+
+
+class ValidationLoop:
+    """The validation hooks of the reference's TitokTrainer (train.py:118-160) without Lightning and without a logger:
+
+        loop = ValidationLoop(model, eval_metrics, log_recon_num, eval_samples, random_recon, codebook_logger)
+        loop.start()                                   # on_validation_epoch_start
+        for batch in eval_loader:                      # {'video': clips, 'fps': .., 'token_counts': ..}
+            for v in loop.step(batch):                 # validation_step
+                logger.log_video(key=v["key"], videos=[v["video"]], fps=[v["fps"]], caption=[v["caption"]], format=["mp4"])
+        logger.log_metrics(loop.end())                 # on_validation_epoch_end
+
+    `start()` draws the logged clips: `torch.randperm(eval_samples)[:log_recon_num]` when `random_recon`, else the first
+    `log_recon_num`; `seen_eval` and `seen_recon` go to zero.  `step()` runs the model and `eval_metrics.update(recon, orig)` under
+    no_grad, then builds the panels of the selected clips of the batch with one `recon_panels` call; `seen_eval` counts every clip,
+    selected or not, `seen_recon` numbers the logged ones from 1.  `end()` returns `eval_metrics.compute()` (then `reset()`),
+    merged with the codebook scores when a logger is given and ready."""
+
+    def __init__(self, model, eval_metrics, log_recon_num: int, eval_samples: int, random_recon: bool, codebook_logger=None):
+        self.model, self.eval_metrics, self.codebook_logger = model, eval_metrics, codebook_logger
+        self.log_recon_num, self.eval_samples, self.random_recon = int(log_recon_num), int(eval_samples), bool(random_recon)
+        self.recon_indexes: List[int] = []
+        self.seen_eval = 0
+        self.seen_recon = 0
+
+    def start(self) -> None:
+        if self.random_recon:
+            self.recon_indexes = torch.randperm(self.eval_samples)[:self.log_recon_num].tolist()
+        else:
+            self.recon_indexes = list(range(self.log_recon_num))
+        self.seen_eval = 0
+        self.seen_recon = 0
+
+    def step(self, batch) -> List[dict]:
+        orig, fps, token_counts = batch["video"], batch["fps"], batch["token_counts"]
+        with torch.no_grad():
+            recon, _ = self.model(orig, token_counts)
+            self.eval_metrics.update(recon, orig)
+        picked = []
+        for i in range(len(recon)):
+            if self.seen_eval in self.recon_indexes:
+                picked.append(i)
+            self.seen_eval += 1
+        if not picked:
+            return []
+        panels = recon_panels([orig[i] for i in picked], [recon[i] for i in picked])
+        logged = []
+        for i, video in zip(picked, panels):
+            self.seen_recon += 1
+            f, t = fps[i], token_counts[i]
+            logged.append({"key": f"Video recon {self.seen_recon}", "video": video, "fps": f.item() if torch.is_tensor(f) else f,
+                           "caption": f"{int(t)} tokens"})
+        return logged
+
+    def end(self) -> dict:
+        metrics = dict(self.eval_metrics.compute())
+        self.eval_metrics.reset()
+        if self.codebook_logger is not None and self.codebook_logger.is_score_ready():
+            metrics.update(self.codebook_logger.get_scores() or {})
+        return metrics
