@@ -446,11 +446,12 @@ int ttv_fsq_backward(const ttv_fsq_params* p, const float* z, const void* dcodes
  * (all chunks of ALL tensor lists of the step: the global gradient norm, written to out_norm when not NULL), scales the gradients by
  * min(1, max_norm / (norm + 1e-6)) in registers (NaN when the norm is NaN, as torch's clamp: every updated element becomes NaN;
  * max_norm <= 0 or n_partials == 0: no clipping; p.grad is NOT rewritten) and applies
- * AdamW with the given bias corrections 1 - beta1^t and sqrt(1 - beta2^t). */
+ * AdamW with the given complements 1 - beta1, 1 - beta2 and bias corrections 1 - beta1^t, sqrt(1 - beta2^t): all four are formed in
+ * double by the caller and rounded to float once (1.0f - (float)beta2 would be 1.3e-5 off at beta2 = 0.999). */
 int ttv_opt_grad_sumsq(const void* table, const int32_t* chunks, int n_chunks, int dtype, float* partials, void* stream);
 int ttv_opt_adamw_step(const void* table, const int32_t* chunks, int n_chunks, int dtype, const float* partials, int n_partials, float lr,
-                       float beta1, float beta2, float eps, float weight_decay, float bias_correction1, float bias_correction2_sqrt,
-                       float max_norm, float* out_norm, void* stream);
+                       float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay,
+                       float bias_correction1, float bias_correction2_sqrt, float max_norm, float* out_norm, void* stream);
 
 /* Per-parameter gradient norms of one tensor list (the log of reference train.py:78-79, :102-103: lightning.pytorch.utilities.grad_norm
  * with norm_type 2) from the partials ttv_opt_grad_sumsq has written for the same table, in one launch.  `chunks` (device, n_chunks x

@@ -21,13 +21,11 @@ def _grads(dtype, seed, scale):
     return [(torch.randn(s, generator=g) * scale).to(DEV, dtype) for s in SHAPES]
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("max_norm", [None, 1.0, 1e6])
-def test_matches_torch_adamw_over_several_steps(dtype, max_norm):
+def _several_steps_against_torch(dtype, max_norm, hyper):
     from titok_video_amd.optim import HipAdamW
     ours, ref = _params(dtype, 0), _params(dtype, 0)
-    opt = HipAdamW(ours, **HYPER)
-    opt_ref = torch.optim.AdamW(ref, foreach=False, fused=False, **HYPER)
+    opt = HipAdamW(ours, **hyper)
+    opt_ref = torch.optim.AdamW(ref, foreach=False, fused=False, **hyper)
     for step in range(5):
         gs = _grads(dtype, step, 0.02 * (step + 1))          # total norm ~ 2 .. 12: max_norm = 1 clips, 1e6 does not
         for p, r, g in zip(ours, ref, gs):
@@ -52,6 +50,22 @@ def test_matches_torch_adamw_over_several_steps(dtype, max_norm):
         assert float(so["step"]) == float(sr["step"]) == 5.0
         scale = sr["exp_avg"].float().abs().max().item()
         assert (so["exp_avg"].float() - sr["exp_avg"].float()).abs().max().item() <= (1e-6 if dtype == torch.float32 else 2e-2) * max(scale, 1e-12)
+        scale = sr["exp_avg_sq"].float().abs().max().item()
+        assert (so["exp_avg_sq"].float() - sr["exp_avg_sq"].float()).abs().max().item() <= (1e-6 if dtype == torch.float32 else 2e-2) * max(scale, 1e-12)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("max_norm", [None, 1.0, 1e6])
+def test_matches_torch_adamw_over_several_steps(dtype, max_norm):
+    _several_steps_against_torch(dtype, max_norm, HYPER)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("max_norm", [None, 1.0, 1e6])
+def test_matches_torch_adamw_at_torchs_default_betas(dtype, max_norm):
+    """betas = (0.9, 0.999): the `m + w (g - m)` branch of the lerp, and the beta2 at which a complement taken from the float32 beta
+    would leave exp_avg_sq 1.3e-5 low.  The float64 replay of tests/test_hip_adamw_f64.py is the tight check."""
+    _several_steps_against_torch(dtype, max_norm, dict(HYPER, betas=(0.9, 0.999)))
 
 
 def test_state_dict_round_trip_with_torch_adamw():

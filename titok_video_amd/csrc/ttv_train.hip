@@ -512,12 +512,14 @@ __global__ __launch_bounds__(256) void k_opt_param_norms(const int2* __restrict_
   for (int c = lo; c < n_chunks && chunks[c].x == e; ++c) acc += partial[c];
   norms[e] = sqrtf(acc);
 }
-struct OptHyper { float lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, max_norm; };
+// om_beta1 / om_beta2 are 1 - beta formed in double by the caller and rounded once, as bc1 and bc2_sqrt are (1.0f - (float)0.999 is
+// 1.3e-5 below 0.001: a constant bias of that size on exp_avg_sq); the lerp's 1 - w for beta1 <= 0.5 is then beta1 itself.
+struct OptHyper { float lr, beta1, beta2, om_beta1, om_beta2, eps, wd, bc1, bc2_sqrt, max_norm; };
 __device__ __forceinline__ void opt_update(float& p, float g, float& m, float& v, const OptHyper& h, float step_size) {
   p -= h.lr * h.wd * p;
-  const float w = 1.0f - h.beta1;
-  m = w < 0.5f ? m + w * (g - m) : g - (g - m) * (1.0f - w);        // at::native::lerp
-  v = h.beta2 * v + (1.0f - h.beta2) * g * g;
+  const float w = h.om_beta1;
+  m = w < 0.5f ? m + w * (g - m) : g - (g - m) * h.beta1;        // at::native::lerp
+  v = h.beta2 * v + h.om_beta2 * g * g;
   const float denom = sqrtf(v) / h.bc2_sqrt + h.eps;
   p -= step_size * m / denom;
 }
@@ -776,15 +778,15 @@ int ttv_opt_param_norms(const void* table, const int32_t* chunks, int n_chunks, 
 }
 
 int ttv_opt_adamw_step(const void* table, const int32_t* chunks, int n_chunks, int dtype, const float* partials, int n_partials, float lr,
-                       float beta1, float beta2, float eps, float weight_decay, float bias_correction1, float bias_correction2_sqrt,
-                       float max_norm, float* out_norm, void* stream) {
+                       float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay,
+                       float bias_correction1, float bias_correction2_sqrt, float max_norm, float* out_norm, void* stream) {
   if (n_chunks == 0) return TTV_OK;
   TTV_CHECK_ARG(n_chunks > 0 && table && chunks, "opt_adamw_step: null buffer");
   TTV_CHECK_ARG(n_partials == 0 || partials, "opt_adamw_step: partials missing");
   TTV_CHECK_ARG(dtype == TTV_BF16 || dtype == TTV_F32, "opt_adamw_step: dtype");
   TTV_CHECK_ARG(bias_correction1 > 0.f && bias_correction2_sqrt > 0.f, "opt_adamw_step: bias corrections must be positive");
   hipStream_t s = (hipStream_t)stream;
-  const OptHyper h = {lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2_sqrt, max_norm};
+  const OptHyper h = {lr, beta1, beta2, one_minus_beta1, one_minus_beta2, eps, weight_decay, bias_correction1, bias_correction2_sqrt, max_norm};
   if (dtype == TTV_BF16) hipLaunchKernelGGL((k_opt_adamw<bf16_t>), dim3(n_chunks), dim3(256), 0, s, (const OptEntry*)table, (const int2*)chunks, partials, n_partials, h, out_norm);
   else hipLaunchKernelGGL((k_opt_adamw<float>), dim3(n_chunks), dim3(256), 0, s, (const OptEntry*)table, (const int2*)chunks, partials, n_partials, h, out_norm);
   TTV_CHECK_LAUNCH("opt_adamw_step");

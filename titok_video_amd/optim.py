@@ -216,8 +216,8 @@ class HipAdamW(torch.optim.Optimizer):
             t = steps.pop() + 1.0
             b1, b2 = g["betas"]
             _lib.check(lib.ttv_opt_adamw_step(base + 40 * eo, chunks_base + 8 * co, nc, _lib.dtype_code(dt), self._partials.data_ptr(),
-                                              n_chunks if clip else 0, float(g["lr"]), float(b1), float(b2), float(g["eps"]),
-                                              float(g["weight_decay"]), 1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t),
+                                              n_chunks if clip else 0, float(g["lr"]), float(b1), float(b2), 1.0 - b1, 1.0 - b2,
+                                              float(g["eps"]), float(g["weight_decay"]), 1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t),
                                               float(max_norm) if clip else 0.0, self._norm.data_ptr() if clip else None, stream),
                        "opt_adamw_step")
             for p in ps:          # one tensor PER parameter, as torch keeps them (its single-tensor step increments each in place)
