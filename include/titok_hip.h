@@ -82,6 +82,43 @@ int ttv_vq_lookup(const void* codebook, int dtype, int ldc, const int32_t* indic
  * reference's instance of the same estimator). */
 int ttv_vq_lookup_backward(const void* dcodes, int dtype, int ld, const int32_t* indices, int rows, int C, float* dcodebook, int ldc, void* stream);
 
+/* ---- training the L2 quantiser: commitment term, EMA codebook, restart of dead entries (ttv_vq_train.hip) ----------------------------
+ * Not reference components (the reference trains FSQ, which has no codebook).  Every sum below has a fixed order and no float atomic:
+ * two calls on the same inputs give the same bits, whatever the grid.  z [rows, C] in `dtype` (TTV_BF16 or TTV_F32), 1 <= rows < 2^24,
+ * C <= 64; z, codebook and workspace 16-byte aligned (rows need no alignment of their own).  All work is enqueued on `stream`.
+ * workspace: ttv_vq_train_workspace_bytes(rows, N) bytes, shared by the four calls of one step. */
+int64_t ttv_vq_train_workspace_bytes(int rows, int N);
+/* loss[0] = mean over rows and C of (z - e)^2 in fp32, e = codebook[indices[r]] read from the compute-dtype codebook the argmin read.
+ * Order: a block of 256 threads owns 64 consecutive rows; thread t folds elements t, t + 256, .. of that stretch (row-major) with
+ * acc = fmaf(d, d, acc); the 256 values meet by halves (t += t + 128, then 64, .., 1).  One block then folds the per-block sums the same
+ * way (thread t takes partials t, t + 256, ..) and multiplies by (float)(1 / (rows C)). */
+int ttv_vq_commit_forward(const void* z, int dtype, int ldz, const void* codebook, int ldc, const int32_t* indices, int rows, int N, int C,
+                          float* loss, void* workspace, int64_t workspace_bytes, void* stream);
+/* dz = grad + scale (z - e) per element, all four [rows, C] in `dtype`; e = the rows the lookup returned.  Formed in fp64 and rounded
+ * once to fp32 (bf16: once more, to bf16).  scale = commitment_weight 2 / (rows C) for the mean above. */
+int ttv_vq_commit_backward(const void* grad, int ldg, const void* z, int ldz, const void* e, int lde, int dtype, int rows, int C, double scale,
+                           void* dz, int ldd, void* stream);
+/* stats: fp32 [N (2 C + 1)] = count [N] | sum [N, C] | cand [N, C], every element written.  count[n] = rows with indices[r] == n (an
+ * index outside [0, N) is counted nowhere); sum[n, :] = those rows of z as fp32, added one after the other in ascending row order
+ * starting from 0 (float32 np.add.at).  cand is zero unless cluster_size is given and cluster_size[n] < dead_threshold: then Philox4x32-10
+ * (the generator of ttv_gp_noise_add) of counter (n, 0, step low, step high), step = ema_step[0] read on the device, under key (seed low,
+ * seed high) gives words w; if w[0] % world_size == rank, cand[n, :] = z[w[1] % rows, :] as fp32. */
+int ttv_vq_ema_stats(const void* z, int dtype, int ldz, const int32_t* indices, int rows, int N, int C, const float* cluster_size,
+                     float dead_threshold, uint64_t seed, const int64_t* ema_step, int rank, int world_size, float* stats, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+/* The update, in place, from `stats` (summed over ranks by the caller).  With d = decay, m = one_minus_decay (1 - d formed by the caller
+ * in double), t = dead_threshold and dead[n] = cluster_size[n] < t before the call, in fp32:
+ *   cluster_size[n] = dead ? t : fmaf(d, cluster_size[n], m count[n]);   total = their sum (thread u of 1024 folds n = u, u + 1024, ..,
+ *   then by halves 512, 256, .., 1);   live: embed_avg = fmaf(d, embed_avg, m sum), smoothed = (cluster_size + eps) / fmaf(N, eps, total) total,
+ *   codebook = embed_avg / smoothed (IEEE divisions);   dead: embed_avg = t cand, codebook = cand;   ema_step[0] += 1.
+ * codebook is the fp32 master [N, C]; codebook_copy the compute-dtype copy the next argmin reads (TTV_BF16: written too, rounded once;
+ * TTV_F32: must be `codebook` itself); cnorm [N] = ||copy_n||^2 with the fmaf chain of ttv_vq_codebook_norms - the same bits.
+ * eps > 0 (with eps = 0 an entry whose cluster size is 0 would divide by smoothed = 0).
+ * workspace: (N + 1) floats at least; ttv_vq_train_workspace_bytes covers it. */
+int ttv_vq_ema_update(const float* stats, float* cluster_size, float* embed_avg, float* codebook, void* codebook_copy, int copy_dtype,
+                      float* cnorm, int64_t* ema_step, int N, int C, float decay, float one_minus_decay, float eps, float dead_threshold,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- mixed bf16 / fp8 linears (BASELINE config #5; not a reference feature: the reference runs bf16 autocast) -------------
  * Row-wise OCP e4m3 quantisation: y = gain ? RMSNorm(x) * gain (eps) : x;  scales[r] = max|y_r| / 448;  out[r] = e4m3(y_r / scales[r]).
  * in [rows, width] (dtype, leading dim ld_in), out uint8 [rows, ld_out], width % 4 == 0, width <= 1024. */

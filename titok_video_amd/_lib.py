@@ -156,6 +156,11 @@ SYMBOLS = {
     "ttv_vq_l2_argmin": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int64, vp]),
     "ttv_vq_lookup": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp]),
     "ttv_vq_lookup_backward": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp]),
+    "ttv_vq_train_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "ttv_vq_commit_forward": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int64, vp]),
+    "ttv_vq_commit_backward": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, C.c_int, vp]),
+    "ttv_vq_ema_stats": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, f32, C.c_uint64, vp, C.c_int, C.c_int, vp, vp, C.c_int64, vp]),
+    "ttv_vq_ema_update": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, f32, f32, f32, f32, vp, C.c_int64, vp]),
     "ttv_quant_rows_fp8": (C.c_int, [vp, C.c_int, C.c_int, vp, f32, vp, C.c_int, vp, C.c_int, C.c_int, vp]),
     "ttv_linear_fp8": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]),
     "ttv_split3_pack": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),

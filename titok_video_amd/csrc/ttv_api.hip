@@ -421,6 +421,39 @@ int ttv_vq_lookup_backward(const void* dcodes, int dtype, int ld, const int32_t*
   return ttvk_vq_lookup_bwd(dcodes, dtype, ld, indices, rows, C, dcodebook, ldc, (hipStream_t)stream);
 }
 
+int64_t ttv_vq_train_workspace_bytes(int rows, int N) {
+  if (rows < 1 || N < 1) { ttv_set_error("vq_train_workspace_bytes: %d rows, %d entries", rows, N); return -1; }
+  return ttvk_vq_train_workspace_bytes(rows, N);
+}
+
+int ttv_vq_commit_forward(const void* z, int dtype, int ldz, const void* codebook, int ldc, const int32_t* indices, int rows, int N, int C,
+                          float* loss, void* workspace, int64_t workspace_bytes, void* stream) {
+  TTV_CHECK_ARG(z && codebook && indices && loss && workspace, "vq_commit_forward: null buffer");
+  return ttvk_vq_commit_forward(z, dtype, ldz, codebook, ldc, indices, rows, N, C, loss, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ttv_vq_commit_backward(const void* grad, int ldg, const void* z, int ldz, const void* e, int lde, int dtype, int rows, int C, double scale,
+                           void* dz, int ldd, void* stream) {
+  TTV_CHECK_ARG(grad && z && e && dz, "vq_commit_backward: null buffer");
+  return ttvk_vq_commit_backward(grad, ldg, z, ldz, e, lde, dtype, rows, C, scale, dz, ldd, (hipStream_t)stream);
+}
+
+int ttv_vq_ema_stats(const void* z, int dtype, int ldz, const int32_t* indices, int rows, int N, int C, const float* cluster_size,
+                     float dead_threshold, uint64_t seed, const int64_t* ema_step, int rank, int world_size, float* stats, void* workspace,
+                     int64_t workspace_bytes, void* stream) {
+  TTV_CHECK_ARG(z && indices && stats && workspace, "vq_ema_stats: null buffer");
+  return ttvk_vq_ema_stats(z, dtype, ldz, indices, rows, N, C, cluster_size, dead_threshold, seed, ema_step, rank, world_size, stats, workspace,
+                           workspace_bytes, (hipStream_t)stream);
+}
+
+int ttv_vq_ema_update(const float* stats, float* cluster_size, float* embed_avg, float* codebook, void* codebook_copy, int copy_dtype,
+                      float* cnorm, int64_t* ema_step, int N, int C, float decay, float one_minus_decay, float eps, float dead_threshold,
+                      void* workspace, int64_t workspace_bytes, void* stream) {
+  TTV_CHECK_ARG(stats && cluster_size && embed_avg && codebook && codebook_copy && cnorm && ema_step && workspace, "vq_ema_update: null buffer");
+  return ttvk_vq_ema_update(stats, cluster_size, embed_avg, codebook, codebook_copy, copy_dtype, cnorm, ema_step, N, C, decay, one_minus_decay, eps,
+                            dead_threshold, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int ttv_quant_rows_fp8(const void* in, int dtype, int ld_in, const float* gain, float eps, void* out, int ld_out, float* scales, int rows,
                        int width, void* stream) {
   TTV_CHECK_ARG(rows == 0 || (in && out && scales), "quant_rows_fp8: null buffer");

@@ -169,6 +169,19 @@ __device__ __forceinline__ uint4 xchg16_pair(uint2 p0, uint2 p1) {
   return make_uint4(x0, y0, x1, y1);
 }
 
+// ---- Philox4x32-10 (Salmon et al., SC'11): ten rounds, the key bumped between rounds (ttv_disc.hip's noise, ttv_vq_train.hip's restart draw) ----
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
+    const uint32_t lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
+    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+    c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+
 // ---- optional HIP-event bracketing of one kernel class (ttv_prof_begin / ttv_prof_end) ----------------
 extern int g_ttv_prof_class;
 extern thread_local int g_ttv_debug;

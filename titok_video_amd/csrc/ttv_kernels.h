@@ -131,6 +131,19 @@ int ttvk_vq_l2_argmin(const void* z, int dtype, int ldz, const void* cb, int ldc
 int ttvk_vq_lookup(const void* cb, int dtype, int ldc, const int* indices, int rows, int C, void* codes, int ldo, hipStream_t s);
 int ttvk_vq_lookup_bwd(const void* dcodes, int dtype, int ld, const int* indices, int rows, int C, float* dcb, int ldc, hipStream_t s);
 
+// ---- ttv_vq_train.hip (commitment term, EMA codebook update, dead-entry restart) ----
+int64_t ttvk_vq_train_workspace_bytes(int rows, int N);
+int ttvk_vq_commit_forward(const void* z, int dtype, int ldz, const void* cb, int ldc, const int* idx, int rows, int N, int C, float* loss,
+                           void* workspace, int64_t workspace_bytes, hipStream_t s);
+int ttvk_vq_commit_backward(const void* g, int ldg, const void* z, int ldz, const void* e, int lde, int dtype, int rows, int C, double scale,
+                            void* dz, int ldd, hipStream_t s);
+int ttvk_vq_ema_stats(const void* z, int dtype, int ldz, const int* idx, int rows, int N, int C, const float* cluster_size, float dead_threshold,
+                      uint64_t seed, const int64_t* ema_step, int rank, int world_size, float* stats, void* workspace, int64_t workspace_bytes,
+                      hipStream_t s);
+int ttvk_vq_ema_update(const float* stats, float* cluster_size, float* embed_avg, float* codebook, void* copy, int copy_dtype, float* cnorm,
+                       int64_t* ema_step, int N, int C, float decay, float one_minus_decay, float eps, float dead_threshold, void* workspace,
+                       int64_t workspace_bytes, hipStream_t s);
+
 // ---- ttv_mlp.hip ----
 bool ttvk_mlp_fused_supported(int dtype, int width, int inner);
 struct MlpNextQkv {     // optional fused back of the layer-tail kernel: the next layer's qkv projection + rotary

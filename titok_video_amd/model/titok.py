@@ -41,7 +41,13 @@ class TiTok(nn.Module):
         elif self.quantizer_kind == "l2":
             n_code, n_entries = int(m.token_size), int(m.codebook_size)
             g = torch.Generator().manual_seed(int(getattr(m, "codebook_seed", 0)))
-            quantize = L2Quantizer(torch.randn(n_entries, n_code, generator=g))     # synthetic start; `quantize.codebook` is a Parameter
+            # synthetic start; `quantize.codebook` is a Parameter.  The optional keys switch on the commitment term and the EMA codebook
+            # with its data-dependent restart (vq_l2.py); absent, the quantiser is the plain straight-through lookup.
+            quantize = L2Quantizer(torch.randn(n_entries, n_code, generator=g),
+                                   commitment_weight=float(getattr(m, "commitment_weight", 0.0)),
+                                   codebook_update=str(getattr(m, "codebook_update", "grad")).lower(),
+                                   decay=float(getattr(m, "codebook_decay", 0.99)), eps=float(getattr(m, "codebook_eps", 1e-5)),
+                                   dead_code_threshold=float(getattr(m, "dead_code_threshold", 0.0)), seed=int(getattr(m, "codebook_seed", 0)))
         else:
             raise ValueError(f"tokenizer.model.quantizer must be 'fsq' or 'l2', got {self.quantizer_kind!r}")
         towers = dict(encoder=TiTokEncoder(model_size=m.encoder_size, patch_size=patch, in_channels=3, out_channels=n_code),
