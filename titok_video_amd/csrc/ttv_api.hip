@@ -21,6 +21,10 @@ void ttv_set_error(const char* fmt, ...) {
 int g_ttv_prof_class = 0;
 // The switches that more than one site reads (declared in ttv_common.h): name and default live here, the sites cache the value.
 bool ttv_sw_enc_latent_last() { static const bool v = ttv_env_flag("TTV_ENC_LATENT_LAST", true); return v; }
+bool ttv_enc_latent_rows_only(const ttv_tower_dims* d, const ttv_batch* b) {
+  return ttv_sw_enc_latent_last() && !(g_ttv_debug & TTV_DBG_ENC_ALL_ROWS) && d->kind == TTV_ENCODER && b->latent_rows && b->sum_tokens > 0 &&
+         b->sum_tokens < b->total_rows;
+}
 bool ttv_sw_keel_f32sum() { static const bool v = ttv_env_flag("TTV_KEEL_F32SUM", false); return v; }
 bool ttv_sw_fused_patch() { static const bool v = ttv_env_flag("TTV_FUSED_PATCH", true); return v; }
 bool ttv_sw_attn_pipe() { static const bool v = ttv_env_flag("TTV_ATTN_PIPE", false); return v; }
@@ -41,15 +45,6 @@ TtvProfScope::~TtvProfScope() {
   if (slot >= 0) (void)hipEventRecord(g_prof_stop[slot], s);
 }
 
-#define TTV_TRY(expr)            \
-  do {                           \
-    int rc__ = (expr);           \
-    if (rc__ != TTV_OK) return rc__; \
-  } while (0)
-
-static inline int esize(int dtype) { return dtype == TTV_BF16 ? 2 : 4; }
-static inline int64_t align_up(int64_t v) { return (v + 255) & ~(int64_t)255; }
-
 struct TowerWs {
   char *x, *xn, *qkv, *ao, *h, *pa, *pb;
   char *xl, *aol;    // [sum_tokens, width]: the latent rows of x and of the attention output, compact (encoder, last layer)
@@ -60,13 +55,13 @@ struct TowerWs {
 };
 
 static TowerWs carve(const ttv_tower_dims* d, const ttv_batch* b, char* base) {
-  const int64_t e = esize(d->dtype);
+  const int64_t e = dtype_bytes(d->dtype);
   const int64_t L = b->total_rows, P = b->sum_patches;
   const int64_t g = (int64_t)d->kv_heads * d->head_dim;
-  const int64_t pd = (int64_t)d->pix_channels * d->patch_t * d->patch_h * d->patch_w;
+  const int64_t pd = patch_dim(d);
   int64_t off = 0;
   TowerWs w;
-  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes); return p; };
+  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
   w.x = take(L * d->width * e);
   w.xn = take(L * d->width * e);
   w.qkv = take(L * (2 * d->width + 2 * g) * e);
@@ -100,12 +95,34 @@ static int check_dims(const ttv_tower_dims* d, const ttv_batch* b) {
   return TTV_OK;
 }
 
+// What run_layers decides once per call and the helpers below read.
+struct LayerCtx {
+  const ttv_tower_dims* d; const ttv_batch* b; const TowerWs& ws; hipStream_t s;
+  int split3, s3img;   // fp32 tower on the three-pass bf16 kernels / its activations travel as split images
+  bool gen_ok;         // a folded pre-norm may take its row statistic as the GEMM's row scale (wide bf16 towers, split-bf16 towers)
+  int pair, all_full, pipe;   // TTV_ATTN_PAIRED / _ALLFULL / _PIPE where the batch's own table (pair, all_full) or the switch (pipe) says so, else 0
+};
+
+// The towers' attention: ws.qkv -> ws.ao over one work table.  The gate, the q pre-scale and the split-bf16 formats are the same at
+// every site; `site` holds the TTV_ATTN_PAIRED / _ALLFULL / _PIPE bits that this table and this site may take (see the callers).
+static int tower_attention(const LayerCtx& c, bool q_scaled, const int32_t* table, int n_table, int site) {
+  const ttv_tower_dims* d = c.d;
+  const int flags = TTV_ATTN_GATE | (q_scaled ? TTV_ATTN_QSCALED : 0) | (c.split3 ? TTV_ATTN_SPLIT3 : 0) |
+                    (c.s3img ? (TTV_ATTN_SPLIT_OUT | TTV_ATTN_SPLIT_IN) : 0) | site;
+  return ttvk_attention(c.ws.qkv, 2 * d->width + 2 * d->kv_heads * d->head_dim, c.ws.ao, d->width, c.b->cu_seqlens, table, n_table, d->q_heads,
+                        d->kv_heads, d->head_dim, flags, d->dtype, c.s);
+}
+
 // One layer with all four linears on the block-scaled fp8 MFMA (BASELINE config #5; ttv_layer_weights.to_qkv_mx ...): every linear's
 // input is quantised by k_quant_mx_fp8, the pre-norm gains live in the weight images and the rstd of the pre-norm is the activation's
 // per-row factor in the GEMM epilogue; attention, the KEEL sums and norms stay bf16 / fp32 as in the bf16 tower.
-static int run_layer_mx(const ttv_tower_dims* d, const ttv_layer_weights& lw, const ttv_batch* b, const TowerWs& ws, int i, bool& rstd_valid,
-                        bool& xq_valid, bool attn_pipe, hipStream_t s) {
+static int run_layer_mx(const LayerCtx& c, const ttv_layer_weights& lw, int i, bool& rstd_valid, bool& xq_valid) {
+  const ttv_tower_dims* d = c.d;
+  const ttv_batch* b = c.b;
+  const TowerWs& ws = c.ws;
+  hipStream_t s = c.s;
   const int L = b->total_rows, dm = d->width, g = d->kv_heads * d->head_dim, dt = d->dtype, nq = 2 * dm + 2 * g, I = d->inner;
+  const float alpha = keel_alpha(d, i);
   // Quantisation is fused into the producers where the producer owns whole 32-element blocks (TTV_MX_FUSED_QUANT=0: every operand by a
   // pass of its own, A/B): the KEEL post-norm kernel writes x also as its block-scaled image (ws.f8 / ws.f8mx), the w12 GEMM's GEGLU
   // epilogue writes h only as its image (into the bf16 h buffer and the xn buffer, both unused in this mode).  Left as passes: the
@@ -115,26 +132,20 @@ static int run_layer_mx(const ttv_tower_dims* d, const ttv_layer_weights& lw, co
   if (!rstd_valid) TTV_TRY(ttvk_row_rstd(ws.x, dt, dm, ws.rstd, L, dm, d->eps, s));
   if (!xq_valid) TTV_TRY(ttvk_quant_mx_fp8(ws.x, dt, dm, ws.f8, dm, ws.f8mx, nullptr, L, dm, s));
   xq_valid = false;
-  GemmArgs a = {};
-  a.dtype = dt; a.x = ws.f8; a.ldx = dm; a.w = lw.to_qkv_f8; a.ldw = dm; a.M = L; a.N = nq; a.K = dm; a.y = ws.qkv; a.ldy = nq;
-  a.rope_cs = b->rope_cs; a.rope_q_end = dm; a.rope_k_begin = 2 * dm; a.rope_k_end = 2 * dm + g;
+  const GemmArgs a = gemm_rope_qk(gemm_args(dt, ws.f8, dm, lw.to_qkv_f8, dm, L, nq, dm, ws.qkv, nq), b->rope_cs, dm, g);
   TTV_TRY(ttvk_gemm_fp8(EPI_QKV_ROPE, a, ws.rstd, lw.to_qkv_f8_scale, s, ws.f8mx, lw.to_qkv_mx));
   const bool q_scaled = lw.qkv_q_prescaled != 0;
-  if (fused_q && q_scaled && !b->qblocks_paired && !attn_pipe && d->head_dim == 64) {
+  if (fused_q && q_scaled && !c.pair && !c.pipe && d->head_dim == 64) {
     // the attention epilogue writes out_proj's operand itself (no bf16 output, no pass over it); ws.f8 is free: the qkv GEMM has read it
     TTV_TRY(ttvk_attention_mxout(ws.qkv, nq, ws.f8, ws.f8mx, (int)ttvk_mx_scale_ld(dm), b->cu_seqlens, b->qblocks, b->n_qblocks, d->q_heads,
                                  d->kv_heads, s));
   } else {
     // (no TTV_ATTN_ALLFULL unless the pipelined kernel is asked for: this is the A/B twin of the attention kernel with the fused MX
     // epilogue above, which is k_attn_bf16 - the two must produce the same bits, tested)
-    TTV_TRY(ttvk_attention(ws.qkv, nq, ws.ao, dm, b->cu_seqlens, b->qblocks, b->n_qblocks, d->q_heads, d->kv_heads, d->head_dim,
-                           TTV_ATTN_GATE | (b->qblocks_paired ? TTV_ATTN_PAIRED : 0) | (q_scaled ? TTV_ATTN_QSCALED : 0) |
-                               ((b->qblocks_all_full && attn_pipe) ? TTV_ATTN_ALLFULL : 0) | (attn_pipe ? TTV_ATTN_PIPE : 0), dt, s));
+    TTV_TRY(tower_attention(c, q_scaled, b->qblocks, b->n_qblocks, c.pair | (c.pipe ? c.all_full | c.pipe : 0)));
     TTV_TRY(ttvk_quant_mx_fp8(ws.ao, dt, dm, ws.f8, dm, ws.f8mx, nullptr, L, dm, s));
   }
-  GemmArgs o = {};
-  o.dtype = dt; o.x = ws.f8; o.ldx = dm; o.w = lw.out_proj_f8; o.ldw = dm; o.M = L; o.N = dm; o.K = dm; o.resid = ws.x; o.ldr = dm;
-  o.alpha = i == 0 ? 1.f : d->alpha; o.y = ws.x; o.ldy = dm;
+  const GemmArgs o = gemm_resid(gemm_args(dt, ws.f8, dm, lw.out_proj_f8, dm, L, dm, dm, ws.x, dm), ws.x, dm, alpha);
   TTV_TRY(ttvk_gemm_fp8(EPI_RESID_T, o, nullptr, lw.out_proj_f8_scale, s, ws.f8mx, lw.out_proj_mx));
   if (i > 0) {
     TTV_TRY(ttvk_rmsnorm(ws.x, dt, dm, nullptr, ws.x, dt, dm, nullptr, lw.attn_post_ln, L, dm, d->eps, s, ws.rstd, fused_q ? ws.f8 : nullptr,
@@ -144,22 +155,14 @@ static int run_layer_mx(const ttv_tower_dims* d, const ttv_layer_weights& lw, co
     TTV_TRY(ttvk_row_rstd(ws.x, dt, dm, ws.rstd, L, dm, d->eps, s));
     TTV_TRY(ttvk_quant_mx_fp8(ws.x, dt, dm, ws.f8, dm, ws.f8mx, nullptr, L, dm, s));
   }
-  GemmArgs f = {};
-  f.dtype = dt; f.x = ws.f8; f.ldx = dm; f.w = lw.w12_f8; f.ldw = dm; f.M = L; f.N = I; f.K = dm; f.y = ws.h; f.ldy = I;
+  GemmArgs f = gemm_args(dt, ws.f8, dm, lw.w12_f8, dm, L, I, dm, ws.h, I);
   char* const hq = ws.h;          // fp8 image of h [L, I] in the bf16 h buffer; its scales in the xn buffer (L * dm * 2 bytes >= L * 4 * nkp(I))
   char* const hq_mx = ws.xn;
   const bool h_fused = fused_q && (int64_t)ttvk_mx_scale_ld(I) <= (int64_t)dm * 2;
   if (h_fused) { f.yq = hq; f.yq_mx = hq_mx; }
   TTV_TRY(ttvk_gemm_fp8(EPI_GEGLU, f, ws.rstd, lw.w12_f8_scale, s, ws.f8mx, lw.w12_mx));
-  GemmArgs f3 = {};
-  if (h_fused) {
-    f3.x = hq;
-  } else {
-    TTV_TRY(ttvk_quant_mx_fp8(ws.h, dt, I, ws.f8, I, ws.f8mx, nullptr, L, I, s));
-    f3.x = ws.f8;
-  }
-  f3.dtype = dt; f3.ldx = I; f3.w = lw.w3_f8; f3.ldw = I; f3.M = L; f3.N = dm; f3.K = I; f3.resid = ws.x; f3.ldr = dm;
-  f3.alpha = i == 0 ? 1.f : d->alpha; f3.y = ws.x; f3.ldy = dm;
+  if (!h_fused) TTV_TRY(ttvk_quant_mx_fp8(ws.h, dt, I, ws.f8, I, ws.f8mx, nullptr, L, I, s));
+  const GemmArgs f3 = gemm_resid(gemm_args(dt, h_fused ? hq : ws.f8, I, lw.w3_f8, I, L, dm, I, ws.x, dm), ws.x, dm, alpha);
   TTV_TRY(ttvk_gemm_fp8(EPI_RESID_T, f3, nullptr, lw.w3_f8_scale, s, h_fused ? hq_mx : ws.f8mx, lw.w3_mx));
   rstd_valid = false;
   if (i > 0) {
@@ -179,13 +182,6 @@ static bool rows_f8(int dt, int dm, const void* img, const void* row_scale, cons
   return dt == TTV_BF16 && img && row_scale && !mx && dm % 128 == 0 && !(dm == 256 && folded);
 }
 
-// What run_layers decides once per call and its two helpers below read.
-struct LayerCtx {
-  const ttv_tower_dims* d; const ttv_batch* b; const TowerWs& ws; hipStream_t s;
-  int split3, s3img;   // fp32 tower on the three-pass bf16 kernels / its activations travel as split images
-  bool gen_ok;         // a folded pre-norm may take its row statistic as the GEMM's row scale (wide bf16 towers, split-bf16 towers)
-};
-
 // A pre-normed projection's weight in every form a tower may carry: plain, with the pre-norm gain folded in (NULL: not packed),
 // and the row-scaled e4m3 image (f8: use it, see rows_f8).
 struct PreNormW { const float* gain; const void *w, *w_pn, *w_f8; const float* w_f8_scale; bool f8; };
@@ -202,13 +198,10 @@ static int prenorm_proj(const LayerCtx& c, GemmEpilogue epi, const char* x, int 
   const ttv_tower_dims* d = c.d;
   const TowerWs& ws = c.ws;
   const int dm = d->width, dt = d->dtype;
-  GemmArgs a = {};
-  a.dtype = dt; a.ldx = dm; a.ldw = dm; a.M = rows; a.N = N; a.K = dm; a.y = y; a.ldy = N;
-  if (epi == EPI_QKV_ROPE) {
-    a.rope_cs = c.b->rope_cs; a.rope_q_end = dm; a.rope_k_begin = 2 * dm; a.rope_k_end = 2 * dm + d->kv_heads * d->head_dim;
-  }
+  GemmArgs a = gemm_args(dt, nullptr, dm, nullptr, dm, rows, N, dm, y, N);       // operand and weight: by route
+  if (epi == EPI_QKV_ROPE) a = gemm_rope_qk(a, c.b->rope_cs, dm, d->kv_heads * d->head_dim);
   if (p.f8) {
-    float* const f8_scales = reinterpret_cast<float*>(ws.xn + (((size_t)c.b->total_rows * dm + 255) & ~(size_t)255));
+    float* const f8_scales = reinterpret_cast<float*>(ws.xn + align256((int64_t)c.b->total_rows * dm));
     TTV_TRY(ttvk_quant_rows_fp8(x, dt, dm, p.gain, d->eps, ws.xn, dm, f8_scales, rows, dm, c.s));
     a.x = ws.xn; a.w = p.w_f8;
     return ttvk_gemm_fp8(epi, a, f8_scales, p.w_f8_scale, c.s);
@@ -226,26 +219,27 @@ static int prenorm_proj(const LayerCtx& c, GemmEpilogue epi, const char* x, int 
   return ttvk_gemm(epi, a, c.s);
 }
 
-// The tail of a KEEL sub-layer (out_proj and w3): x <- RMSNorm(alpha * x + in @ W^T) * gain, in place on the rows of cx; layer 0 has
-// no norm and alpha = 1.  `o` arrives with operand, weight, shapes and the residual set.  Width 256 does it in one kernel
-// (EPI_RESID_NORM; in place is safe: a token row is read as residual and written by the same wave only).  Wide towers: the sum leaves
-// the GEMM through HBM and a row kernel normalises it.  bf16 towers store it in the compute dtype, in place on x (a token row element
+// The tail of a KEEL sub-layer (out_proj and w3): x <- RMSNorm(alpha * x + in @ W^T) * gain, in place on the rows of cx = o.y; layer 0
+// has no norm and alpha = 1.  `o` arrives with operand, weight, shapes and the output cx; the residual (cx again) and alpha are set
+// here.  Width 256 does it in one kernel (EPI_RESID_NORM; in place is safe: a token row is read as residual and written by the same
+// wave only).  Wide towers: the sum leaves the GEMM through HBM and a row kernel normalises it.  bf16 towers store it in the compute dtype, in place on x (a token row element
 // is read as residual and written by the same lane) - the reference's autocast rounds that sum to bf16 as well (transformer.py:141:
 // bf16 * alpha + bf16) -: half the bytes of the fp32 buffer on both kernels.  fp32 towers, and TTV_KEEL_F32SUM=1 (A/B), keep the fp32
 // buffer.  want_rstd: the row kernel also leaves the statistic of the row it wrote in ws.rstd, for a folded pre-norm behind it;
 // rstd_valid is set to it on that route and left alone on the others.
-static int keel_tail(const LayerCtx& c, GemmArgs o, int layer, const float* post_gain, char* cx, bool want_rstd, bool& rstd_valid) {
+static int keel_tail(const LayerCtx& c, GemmArgs o, int layer, const float* post_gain, bool want_rstd, bool& rstd_valid) {
   const ttv_tower_dims* d = c.d;
   const int dm = d->width, dt = d->dtype;
-  static const bool keel_f32sum = ttv_sw_keel_f32sum();
-  o.alpha = layer == 0 ? 1.f : d->alpha; o.y = cx; o.ldy = dm;
+  char* const cx = (char*)o.y;
+  o = gemm_resid(o, cx, dm, keel_alpha(d, layer));
+  o.split3 = c.split3; o.x_image = c.s3img;
   if (layer == 0) return ttvk_gemm(EPI_RESID_T, o, c.s);
   if (ttvk_gemm_supports_resid_norm(dt, dm, o.K)) {
     o.norm_gain = post_gain; o.eps = d->eps;
     return ttvk_gemm(EPI_RESID_NORM, o, c.s);
   }
   float* const next_rstd = want_rstd ? c.ws.rstd : nullptr;
-  if (dt == TTV_BF16 && !keel_f32sum) {
+  if (dt == TTV_BF16 && !ttv_sw_keel_f32sum()) {
     TTV_TRY(ttvk_gemm(EPI_RESID_T, o, c.s));
     TTV_TRY(ttvk_rmsnorm(cx, dt, dm, nullptr, cx, dt, dm, nullptr, post_gain, o.M, dm, d->eps, c.s, next_rstd));
   } else {
@@ -267,17 +261,15 @@ static int run_layers(const ttv_tower_dims* d, const ttv_tower_weights* w, const
   static const bool s3img_env = ttv_env_flag("TTV_SPLIT3_IMAGES", true);
   const int s3img = (split3 && s3img_env && !(g_ttv_debug & TTV_DBG_SPLIT3_NO_IMAGES)) ? 1 : 0;     // ttv_debug_set bit 12: fp32 activations, split inside the GEMMs (tests)
   const int nq = 2 * dm + 2 * g;
+  const int64_t row_bytes = (int64_t)dm * dtype_bytes(dt);       // a split image (hi0..3 | lo0..3 per 16 bytes) has the bytes of the fp32 row
   bool qkv_ready = false;   // the previous layer's tail kernel already produced this layer's rotated qkv
   bool rstd_valid = false;  // ws.rstd holds rsqrt(mean(x^2) + eps) of the current ws.x (written by the kernel that produced x)
   bool xq_valid = false;    // ws.f8 / ws.f8mx hold the block-scaled e4m3 image of the current ws.x (run_layer_mx)
-  static const bool attn_pipe = ttv_sw_attn_pipe();   // opt-in pipelined attention kernel
   // The encoder's output is its latent rows (blocks.py:101-103): with the batch's latent-query table the LAST layer runs its attention for
   // those query rows only and everything behind the attention on the sum K_b latent rows, gathered into compact buffers (ws.xl, ws.aol) and
   // scattered back into ws.x at the end.  Row-wise kernels on other rows: the values of the rows that are read are the same bits.
   // TTV_ENC_LATENT_LAST=0: every row, as the reference computes it (A/B, tests).  Not for the block-scaled fp8 layers (run_layer_mx).
-  static const bool lat_env = ttv_sw_enc_latent_last();
-  const bool lat_last = lat_env && !(g_ttv_debug & TTV_DBG_ENC_ALL_ROWS) && d->kind == TTV_ENCODER && b->qblocks_latent && b->n_qblocks_latent > 0 &&
-                        b->latent_rows && b->sum_tokens > 0 && b->sum_tokens < L;
+  const bool lat_last = ttv_enc_latent_rows_only(d, b) && b->qblocks_latent && b->n_qblocks_latent > 0;
   // The decoder's output is its patch rows (blocks.py:171): with the batch's patch-query table the LAST layer's attention skips the query
   // blocks that hold latent rows only.  Their rows of ws.ao keep the previous layer's values (finite), everything behind the attention
   // is row-wise, the tail gathers patch rows: no patch row changes a bit.  TTV_DEC_PATCH_LAST=0 / debug bit 21: every block (A/B, tests).
@@ -285,14 +277,15 @@ static int run_layers(const ttv_tower_dims* d, const ttv_tower_weights* w, const
   const bool pat_last = pat_env && !(g_ttv_debug & TTV_DBG_DEC_ALL_BLOCKS) && d->kind == TTV_DECODER && d->layers >= 2 && b->qblocks_patch &&
                         b->n_qblocks_patch > 0 && !split3 && !b->qblocks_paired;
   bool compacted = false;
-  const LayerCtx ctx = {d, b, ws, s, split3, s3img, gen_ok};
+  const LayerCtx ctx = {d, b, ws, s, split3, s3img, gen_ok, b->qblocks_paired ? TTV_ATTN_PAIRED : 0, b->qblocks_all_full ? TTV_ATTN_ALLFULL : 0,
+                        ttv_sw_attn_pipe() ? TTV_ATTN_PIPE : 0};       // (pipe: the opt-in pipelined attention kernel)
   for (int i = 0; i < d->layers; ++i) {
     const ttv_layer_weights& lw = w->layers[i];
-    static const bool keel_f32 = ttv_sw_keel_f32sum();
-    if (dt == TTV_BF16 && dm != 256 && dm % 128 == 0 && d->inner % 128 == 0 && !keel_f32 && lw.to_qkv_f8 && lw.to_qkv_mx && lw.w12_f8 && lw.w12_mx &&
-        lw.out_proj_f8 && lw.out_proj_mx && lw.w3_f8 && lw.w3_mx &&
-        !(lat_last && i == d->layers - 1)) {    // the encoder's last layer: its latent rows on the bf16 kernels instead (a ninth of the rows)
-      TTV_TRY(run_layer_mx(d, lw, b, ws, i, rstd_valid, xq_valid, attn_pipe, s));
+    const bool last = i == d->layers - 1;
+    if (dt == TTV_BF16 && dm != 256 && dm % 128 == 0 && d->inner % 128 == 0 && !ttv_sw_keel_f32sum() && lw.to_qkv_f8 && lw.to_qkv_mx && lw.w12_f8 &&
+        lw.w12_mx && lw.out_proj_f8 && lw.out_proj_mx && lw.w3_f8 && lw.w3_mx &&
+        !(lat_last && last)) {    // the encoder's last layer: its latent rows on the bf16 kernels instead (a ninth of the rows)
+      TTV_TRY(run_layer_mx(ctx, lw, i, rstd_valid, xq_valid));
       qkv_ready = false;
       continue;
     }
@@ -313,32 +306,26 @@ static int run_layers(const ttv_tower_dims* d, const ttv_tower_weights* w, const
     const bool q_scaled = dt == TTV_BF16 && (lw.to_qkv_pn ? lw.qkv_q_prescaled != 0 : lw.to_qkv_qs != nullptr);
     rstd_valid = false;
     qkv_ready = false;
-    const bool lat_now = lat_last && i == d->layers - 1;
+    const bool lat_now = lat_last && last;
     if (lat_now)
-      // (the latent table holds full items only; it is declared so only when the batch's own table is too: ttvk_attention picks its
-      // kernel by that flag, and the latent-rows forward must run the kernel the all-rows forward runs - same bits, tested)
-      TTV_TRY(ttvk_attention(ws.qkv, nq, ws.ao, dm, b->cu_seqlens, b->qblocks_latent, b->n_qblocks_latent, d->q_heads, d->kv_heads, d->head_dim,
-                             TTV_ATTN_GATE | (b->qblocks_all_full ? TTV_ATTN_ALLFULL : 0) | (q_scaled ? TTV_ATTN_QSCALED : 0) | (split3 ? TTV_ATTN_SPLIT3 : 0) |
-                                 (s3img ? (TTV_ATTN_SPLIT_OUT | TTV_ATTN_SPLIT_IN) : 0), dt, s));
-    else if (pat_last && i == d->layers - 1 && dt == TTV_BF16 && !attn_pipe)
-      TTV_TRY(ttvk_attention(ws.qkv, nq, ws.ao, dm, b->cu_seqlens, b->qblocks_patch, b->n_qblocks_patch, d->q_heads, d->kv_heads, d->head_dim,
-                             TTV_ATTN_GATE | (b->qblocks_all_full ? TTV_ATTN_ALLFULL : 0) | (q_scaled ? TTV_ATTN_QSCALED : 0), dt, s));
+      // never paired, never pipelined.  The latent table holds full items only; it is declared so only when the batch's own table is too:
+      // ttvk_attention picks its kernel by that flag, and the latent-rows forward must run the kernel the all-rows forward runs - same
+      // bits, tested
+      TTV_TRY(tower_attention(ctx, q_scaled, b->qblocks_latent, b->n_qblocks_latent, ctx.all_full));
+    else if (pat_last && last && dt == TTV_BF16 && !ctx.pipe)     // (pat_last: the batch's table is unpaired)
+      TTV_TRY(tower_attention(ctx, q_scaled, b->qblocks_patch, b->n_qblocks_patch, ctx.all_full));
     else if (q_scaled && b->items64 && b->n_items64 > 0 && d->head_dim == 64)
       TTV_TRY(ttvk_attention64(ws.qkv, nq, ws.ao, dm, b->cu_seqlens, b->items64, b->n_items64, d->q_heads, d->kv_heads,
                                TTV_ATTN_GATE | TTV_ATTN_QSCALED, s));
     else
-    TTV_TRY(ttvk_attention(ws.qkv, nq, ws.ao, dm, b->cu_seqlens, b->qblocks, b->n_qblocks, d->q_heads, d->kv_heads, d->head_dim,
-                           TTV_ATTN_GATE | (b->qblocks_paired ? TTV_ATTN_PAIRED : 0) | (q_scaled ? TTV_ATTN_QSCALED : 0) |
-                               (b->qblocks_all_full ? TTV_ATTN_ALLFULL : 0) | (attn_pipe ? TTV_ATTN_PIPE : 0) | (split3 ? TTV_ATTN_SPLIT3 : 0) |
-                               (s3img ? (TTV_ATTN_SPLIT_OUT | TTV_ATTN_SPLIT_IN) : 0), dt, s));
+      TTV_TRY(tower_attention(ctx, q_scaled, b->qblocks, b->n_qblocks, ctx.pair | ctx.all_full | ctx.pipe));
     // from here on the layer works on (cx, cao, Lc): the whole packed batch, or - last encoder layer - its latent rows, compact
     char* cx = ws.x;
     char* cao = ws.ao;
     int Lc = L;
     if (lat_now) {
-      const int64_t rb = (int64_t)dm * esize(dt);       // a split image (hi0..3 | lo0..3 per 16 bytes) has the bytes of the fp32 row
-      TTV_TRY(ttvk_copy_rows(ws.x, (int64_t)dm * esize(dt), b->latent_rows, ws.xl, (int64_t)dm * esize(dt), nullptr, b->sum_tokens, dm * (int)esize(dt), s));
-      TTV_TRY(ttvk_copy_rows(ws.ao, rb, b->latent_rows, ws.aol, rb, nullptr, b->sum_tokens, (int)rb, s));
+      TTV_TRY(gather_rows(ws.x, ws.xl, b->latent_rows, b->sum_tokens, row_bytes, s));
+      TTV_TRY(gather_rows(ws.ao, ws.aol, b->latent_rows, b->sum_tokens, row_bytes, s));
       cx = ws.xl; cao = ws.aol; Lc = b->sum_tokens;
       compacted = true;
     }
@@ -348,36 +335,40 @@ static int run_layers(const ttv_tower_dims* d, const ttv_tower_weights* w, const
     // of the tail kernel: 31 us against 35 us stand-alone in isolation, worse in the pipeline), so it is opt-in.
     static const bool use_fused_mlp = ttv_env_flag("TTV_FUSED_MLP", true);
     static const bool use_fused_qkv = ttv_env_flag("TTV_FUSED_QKV", false);
+    const float alpha = keel_alpha(d, i);
     if (use_fused_mlp && ttvk_mlp_fused_supported(dt, dm, d->inner) && lw.mlp_pack) {
       // one kernel for the rest of the layer: out_proj + residual/KEEL norm, then pre-norm + w12 + GEGLU + w3 +
       // residual/KEEL norm, in place on x, and (when the pack carries it) the NEXT layer's pre_ln + to_qkv + rotary
       MlpNextQkv nx = {};
-      const bool back = use_fused_qkv && i + 1 < d->layers && lw.mlp_pack_qkv_rows == nq && nq % 64 == 0 && dm % 64 == 0 && g % 64 == 0;
+      const bool back = use_fused_qkv && !last && lw.mlp_pack_qkv_rows == nq && nq % 64 == 0 && dm % 64 == 0 && g % 64 == 0;
       if (back) { nx.qkv = ws.qkv; nx.ld = nq; nx.rope_cs = b->rope_cs; nx.rows = nq; nx.rope_q_end = dm; nx.rope_k_begin = 2 * dm; nx.rope_k_end = 2 * dm + g; }
-      TTV_TRY(ttvk_mlp_fused(cao, dm, i == 0 ? nullptr : lw.attn_post_ln, i == 0 ? 1.f : d->alpha, cx, dm, lw.mlp_pack, d->inner,
-                             cx, dm, i == 0 ? nullptr : lw.ffd_post_ln, i == 0 ? 1.f : d->alpha, d->eps, Lc, back ? &nx : nullptr, s));
+      TTV_TRY(ttvk_mlp_fused(cao, dm, i == 0 ? nullptr : lw.attn_post_ln, alpha, cx, dm, lw.mlp_pack, d->inner, cx, dm, i == 0 ? nullptr : lw.ffd_post_ln,
+                             alpha, d->eps, Lc, back ? &nx : nullptr, s));
       qkv_ready = back;
       continue;
     }
-    GemmArgs o = {};
-    o.dtype = dt; o.split3 = split3; o.x_image = s3img;
-    o.x = cao; o.ldx = dm; o.w = lw.out_proj; o.ldw = dm; o.M = Lc; o.N = dm; o.K = dm; o.resid = cx; o.ldr = dm;
-    TTV_TRY(keel_tail(ctx, o, i, lw.attn_post_ln, cx, gen_ok && lw.w12_pn && !f8_w12, rstd_valid));
+    TTV_TRY(keel_tail(ctx, gemm_args(dt, cao, dm, lw.out_proj, dm, Lc, dm, dm, cx, dm), i, lw.attn_post_ln, gen_ok && lw.w12_pn && !f8_w12, rstd_valid));
     // ---- GEGLU sub-layer (transformer.py:47-56) ----
     const PreNormW fw = {lw.ffd_norm, lw.w12, lw.w12_pn, lw.w12_f8, lw.w12_f8_scale, f8_w12};
     TTV_TRY(prenorm_proj(ctx, EPI_GEGLU, cx, Lc, fw, d->inner, ws.h, s3img, rstd_valid));
     rstd_valid = false;
-    GemmArgs f3 = {};
-    f3.dtype = dt; f3.split3 = split3; f3.x_image = s3img;
-    f3.x = ws.h; f3.ldx = d->inner; f3.w = lw.w3; f3.ldw = d->inner; f3.M = Lc; f3.N = dm; f3.K = d->inner; f3.resid = cx; f3.ldr = dm;
     // the next layer's to_qkv takes the row statistic when it runs with the folded weight on the bf16 kernels
-    const bool next_rstd = gen_ok && i + 1 < d->layers && w->layers[i + 1].to_qkv_pn &&
-                           !rows_f8(dt, dm, w->layers[i + 1].to_qkv_f8, w->layers[i + 1].to_qkv_f8_scale, w->layers[i + 1].to_qkv_mx, w->layers[i + 1].to_qkv_pn);
-    TTV_TRY(keel_tail(ctx, f3, i, lw.ffd_post_ln, cx, next_rstd, rstd_valid));
+    const ttv_layer_weights* nl = last ? nullptr : &w->layers[i + 1];
+    const bool next_rstd = gen_ok && nl && nl->to_qkv_pn && !rows_f8(dt, dm, nl->to_qkv_f8, nl->to_qkv_f8_scale, nl->to_qkv_mx, nl->to_qkv_pn);
+    TTV_TRY(keel_tail(ctx, gemm_args(dt, ws.h, d->inner, lw.w3, d->inner, Lc, dm, d->inner, cx, dm), i, lw.ffd_post_ln, next_rstd, rstd_valid));
   }
   if (compacted)     // the latent rows back where the encoder's tail (and anybody else) reads them
-    TTV_TRY(ttvk_copy_rows(ws.xl, (int64_t)dm * esize(dt), nullptr, ws.x, (int64_t)dm * esize(dt), b->latent_rows, b->sum_tokens, dm * (int)esize(dt), s));
+    TTV_TRY(scatter_rows(ws.xl, ws.x, b->latent_rows, b->sum_tokens, row_bytes, s));
   return TTV_OK;
+}
+
+// What the encoder's gathering proj_in and the decoder's scattering proj_out (GemmArgs.gather / EPI_STORE_PATCH) both need: bf16, a patch
+// whose pixel rows are 16 bytes and whose other extents are powers of two, one launch's worth of clips, the row -> sequence map.
+// TTV_FUSED_PATCH=0: the copy kernels (A/B).  Each caller adds its own width condition.
+static bool fused_patch_ok(const ttv_tower_dims* d, const ttv_batch* b, int dt) {
+  auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
+  return ttv_sw_fused_patch() && dt == TTV_BF16 && d->patch_w == 8 && pow2(d->patch_t) && pow2(d->patch_h) &&
+         b->n_clips <= TTV_MAX_CLIPS_PER_LAUNCH && b->row_seq && patch_dim(d) % 64 == 0;
 }
 
 extern "C" {
@@ -467,8 +458,8 @@ int ttv_split3_pack(const float* w, int ldw, void* out, int ldo, int rows, int K
 
 int ttv_linear_split3(const float* x, int ldx, const void* w_image, int ldw, const float* bias, float* y, int ldy, int M, int N, int K, void* stream) {
   TTV_CHECK_ARG(M == 0 || (x && w_image && y), "linear_split3: null buffer");
-  GemmArgs a = {};
-  a.dtype = TTV_F32; a.split3 = 1; a.x = x; a.ldx = ldx; a.w = w_image; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.y = y; a.ldy = ldy; a.bias = bias;
+  GemmArgs a = gemm_args(TTV_F32, x, ldx, w_image, ldw, M, N, K, y, ldy);
+  a.split3 = 1; a.bias = bias;
   return ttvk_gemm(EPI_STORE, a, (hipStream_t)stream);
 }
 
@@ -485,13 +476,12 @@ int ttv_linear_fp8_mx(const void* xq, int ldx, const void* x_mx, const float* x_
                       int gqa_dim, const void* resid, int ldr, float alpha, void* stream) {
   TTV_CHECK_ARG(M == 0 || (xq && wq && y && x_mx && w_mx), "linear_fp8_mx: null buffer");
   TTV_CHECK_ARG(epilogue >= 0 && epilogue <= 3, "linear_fp8_mx: epilogue 0 (store), 1 (qkv + rotary), 2 (GEGLU) or 3 (alpha * resid + acc)");
-  GemmArgs a = {};
-  a.dtype = TTV_BF16; a.x = xq; a.ldx = ldx; a.w = wq; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.y = y; a.ldy = ldy;
+  GemmArgs a = gemm_args(TTV_BF16, xq, ldx, wq, ldw, M, N, K, y, ldy);
   if (epilogue == 1) {
     TTV_CHECK_ARG(rope_cs && N == 2 * d_model + 2 * gqa_dim, "linear_fp8_mx: qkv epilogue needs rope_cs and N = 2 d_model + 2 gqa_dim");
-    a.rope_cs = rope_cs; a.rope_q_end = d_model; a.rope_k_begin = 2 * d_model; a.rope_k_end = 2 * d_model + gqa_dim;
+    a = gemm_rope_qk(a, rope_cs, d_model, gqa_dim);
   }
-  if (epilogue == 3) { a.resid = resid; a.ldr = ldr; a.alpha = alpha; }
+  if (epilogue == 3) a = gemm_resid(a, resid, ldr, alpha);
   return ttvk_gemm_fp8(epilogue == 0 ? EPI_STORE : epilogue == 1 ? EPI_QKV_ROPE : epilogue == 2 ? EPI_GEGLU : EPI_RESID_T, a, x_row_scale,
                        w_row_scale, (hipStream_t)stream, x_mx, w_mx);
 }
@@ -500,11 +490,10 @@ int ttv_linear_fp8(const void* xq, int ldx, const float* x_scale, const void* wq
                    int K, int epilogue, const float* rope_cs, int d_model, int gqa_dim, void* stream) {
   TTV_CHECK_ARG(M == 0 || (xq && wq && y), "linear_fp8: null buffer");
   TTV_CHECK_ARG(epilogue >= 0 && epilogue <= 2, "linear_fp8: epilogue 0 (store), 1 (qkv + rotary) or 2 (GEGLU)");
-  GemmArgs a = {};
-  a.dtype = TTV_BF16; a.x = xq; a.ldx = ldx; a.w = wq; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.y = y; a.ldy = ldy;
+  GemmArgs a = gemm_args(TTV_BF16, xq, ldx, wq, ldw, M, N, K, y, ldy);
   if (epilogue == 1) {
     TTV_CHECK_ARG(rope_cs && N == 2 * d_model + 2 * gqa_dim, "linear_fp8: qkv epilogue needs rope_cs and N = 2 d_model + 2 gqa_dim");
-    a.rope_cs = rope_cs; a.rope_q_end = d_model; a.rope_k_begin = 2 * d_model; a.rope_k_end = 2 * d_model + gqa_dim;
+    a = gemm_rope_qk(a, rope_cs, d_model, gqa_dim);
   }
   return ttvk_gemm_fp8(epilogue == 0 ? EPI_STORE : epilogue == 1 ? EPI_QKV_ROPE : EPI_GEGLU, a, x_scale, w_scale, (hipStream_t)stream);
 }
@@ -524,8 +513,7 @@ int ttv_rope_apply(void* x, int dtype, int ld, int rows, int heads, const float*
 int ttv_linear(const void* x, int ldx, const void* w, int ldw, const void* bias, const float* add_scalar, void* y, int ldy, int M,
                int N, int K, int dtype, void* stream) {
   TTV_CHECK_ARG(M == 0 || (x && w && y), "linear: null buffer");
-  GemmArgs a = {};
-  a.dtype = dtype; a.x = x; a.ldx = ldx; a.w = w; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.y = y; a.ldy = ldy;
+  GemmArgs a = gemm_args(dtype, x, ldx, w, ldw, M, N, K, y, ldy);
   a.bias = bias; a.add_scalar = add_scalar;
   return ttvk_gemm(EPI_STORE, a, (hipStream_t)stream);
 }
@@ -533,34 +521,27 @@ int ttv_linear(const void* x, int ldx, const void* w, int ldw, const void* bias,
 int ttv_linear_qkv_rope(const void* x, int ldx, const void* w, int ldw, void* y, int ldy, int M, int d_model, int gqa_dim,
                         const float* rope_cs, int dtype, void* stream) {
   TTV_CHECK_ARG(M == 0 || (x && w && y && rope_cs), "linear_qkv_rope: null buffer");
-  GemmArgs a = {};
-  a.dtype = dtype; a.x = x; a.ldx = ldx; a.w = w; a.ldw = ldw; a.M = M; a.N = 2 * d_model + 2 * gqa_dim; a.K = d_model;
-  a.y = y; a.ldy = ldy; a.rope_cs = rope_cs; a.rope_q_end = d_model; a.rope_k_begin = 2 * d_model; a.rope_k_end = 2 * d_model + gqa_dim;
-  return ttvk_gemm(EPI_QKV_ROPE, a, (hipStream_t)stream);
+  const GemmArgs a = gemm_args(dtype, x, ldx, w, ldw, M, 2 * d_model + 2 * gqa_dim, d_model, y, ldy);
+  return ttvk_gemm(EPI_QKV_ROPE, gemm_rope_qk(a, rope_cs, d_model, gqa_dim), (hipStream_t)stream);
 }
 
 int ttv_linear_geglu(const void* x, int ldx, const void* w, int ldw, void* y, int ldy, int M, int I, int K, int dtype, void* stream) {
   TTV_CHECK_ARG(M == 0 || (x && w && y), "linear_geglu: null buffer");
-  GemmArgs a = {};
-  a.dtype = dtype; a.x = x; a.ldx = ldx; a.w = w; a.ldw = ldw; a.M = M; a.N = I; a.K = K; a.y = y; a.ldy = ldy;
-  return ttvk_gemm(EPI_GEGLU, a, (hipStream_t)stream);
+  return ttvk_gemm(EPI_GEGLU, gemm_args(dtype, x, ldx, w, ldw, M, I, K, y, ldy), (hipStream_t)stream);
 }
 
 int ttv_linear_residual(const void* x, int ldx, const void* w, int ldw, const void* resid, int ldr, float alpha, void* y, int ldy,
                         int y_f32, int M, int N, int K, int dtype, void* stream) {
   TTV_CHECK_ARG(M == 0 || (x && w && y && resid), "linear_residual: null buffer");
-  GemmArgs a = {};
-  a.dtype = dtype; a.x = x; a.ldx = ldx; a.w = w; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.y = y; a.ldy = ldy;
-  a.resid = resid; a.ldr = ldr; a.alpha = alpha;
+  const GemmArgs a = gemm_resid(gemm_args(dtype, x, ldx, w, ldw, M, N, K, y, ldy), resid, ldr, alpha);
   return ttvk_gemm(y_f32 ? EPI_RESID_F32 : EPI_RESID_T, a, (hipStream_t)stream);
 }
 
 int ttv_linear_residual_norm(const void* x, int ldx, const void* w, int ldw, const void* resid, int ldr, float alpha,
                              const float* gain, float eps, void* y, int ldy, int M, int N, int K, int dtype, void* stream) {
   TTV_CHECK_ARG(M == 0 || (x && w && y && resid && gain), "linear_residual_norm: null buffer");
-  GemmArgs a = {};
-  a.dtype = dtype; a.x = x; a.ldx = ldx; a.w = w; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.y = y; a.ldy = ldy;
-  a.resid = resid; a.ldr = ldr; a.alpha = alpha; a.norm_gain = gain; a.eps = eps;
+  GemmArgs a = gemm_resid(gemm_args(dtype, x, ldx, w, ldw, M, N, K, y, ldy), resid, ldr, alpha);
+  a.norm_gain = gain; a.eps = eps;
   if (!ttvk_gemm_supports_resid_norm(dtype, N, K)) {
     ttv_set_error("linear_residual_norm: only bf16 with N == 256 has a fused kernel");
     return TTV_ERR_UNSUPPORTED;
@@ -654,23 +635,13 @@ int ttv_encoder_forward(const ttv_tower_dims* d, const ttv_tower_weights* w, con
   hipStream_t s = (hipStream_t)stream;
   TowerWs ws = carve(d, b, (char*)workspace);
   TTV_CHECK_ARG(ws.total <= workspace_bytes, "encoder_forward: workspace too small (%lld < %lld)", (long long)workspace_bytes, (long long)ws.total);
-  const int dm = d->width, dt = d->dtype, P = b->sum_patches;
-  const int pd = d->pix_channels * d->patch_t * d->patch_h * d->patch_w;
+  const int dm = d->width, dt = d->dtype, P = b->sum_patches, pd = patch_dim(d);
 
   // patchify (utils.py:26-34) + proj_in (blocks.py:91-93); when the shapes allow it the GEMM reads its K = (c, pt, ph, pw)
   // operand straight from the clips (16-byte pixel-row segments) instead of from a gathered [P, pd] copy
-  static const bool use_fused_patch = ttv_sw_fused_patch();
-  auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
-  const bool gather = use_fused_patch && dt == TTV_BF16 && d->patch_w == 8 && pow2(d->patch_t) && pow2(d->patch_h) &&
-                      b->n_clips <= TTV_MAX_CLIPS_PER_LAUNCH && b->row_seq && pd % 64 == 0 && pd != 256;
-  if (!gather) {
-    for (int c0 = 0; c0 < b->n_clips; c0 += TTV_MAX_CLIPS_PER_LAUNCH) {
-      const int n = b->n_clips - c0 < TTV_MAX_CLIPS_PER_LAUNCH ? b->n_clips - c0 : TTV_MAX_CLIPS_PER_LAUNCH;
-      TTV_TRY(ttvk_patch_copy(false, (void* const*)(clips + c0), b->clip_desc, c0, n, d->patch_t, d->patch_h, d->patch_w, d->pix_channels, ws.pa, pd, dt, b->max_patches_per_clip, s));
-    }
-  }
-  GemmArgs a = {};
-  a.dtype = dt; a.x = ws.pa; a.ldx = pd; a.w = w->proj_in_w; a.ldw = pd; a.M = P; a.N = dm; a.K = pd; a.y = ws.pb; a.ldy = dm;
+  const bool gather = fused_patch_ok(d, b, dt) && pd != 256;
+  if (!gather) TTV_TRY(patch_copy_all(false, (void* const*)clips, d, b, ws.pa, dt, s));
+  GemmArgs a = gemm_args(dt, ws.pa, pd, w->proj_in_w, pd, P, dm, pd, ws.pb, dm);
   a.bias = w->proj_in_b; a.add_scalar = w->mask_token;
   a.split3 = (dt == TTV_F32 && w->f32_split3) ? 1 : 0;
   if (gather) {
@@ -697,8 +668,7 @@ int ttv_decoder_forward(const ttv_tower_dims* d, const ttv_tower_weights* w, con
   hipStream_t s = (hipStream_t)stream;
   TowerWs ws = carve(d, b, (char*)workspace);
   TTV_CHECK_ARG(ws.total <= workspace_bytes, "decoder_forward: workspace too small (%lld < %lld)", (long long)workspace_bytes, (long long)ws.total);
-  const int dm = d->width, dt = d->dtype, P = b->sum_patches;
-  const int pd = d->pix_channels * d->patch_t * d->patch_h * d->patch_w;
+  const int dm = d->width, dt = d->dtype, P = b->sum_patches, pd = patch_dim(d);
 
   // x[latent rows] = ln_pre_t(proj_in(codes) + mask_token); x[patch rows] = ln_pre_p(mask_token * 1) (blocks.py:165-167)
   TTV_TRY(ttvk_dec_embed(codes, d->token_size, w->proj_in_w, w->proj_in_b, w->mask_token, w->ln_pre_t, ws.x, dt, dm, b->latent_rows, b->sum_tokens, dm, d->eps, s));
@@ -707,8 +677,7 @@ int ttv_decoder_forward(const ttv_tower_dims* d, const ttv_tower_weights* w, con
   TTV_TRY(run_layers(d, w, b, ws, s));
 
   // patches = proj_out(ln_post(x[patch rows])) -> unpatchify (blocks.py:171-176)
-  GemmArgs a = {};
-  a.dtype = dt; a.w = w->proj_out_w; a.ldw = dm; a.M = P; a.N = pd; a.K = dm; a.y = ws.pa; a.ldy = pd; a.ldx = dm;
+  GemmArgs a = gemm_args(dt, nullptr, dm, w->proj_out_w, dm, P, pd, dm, ws.pa, pd);      // operand: ws.x in place or its normed patch rows, below
   a.split3 = (dt == TTV_F32 && w->f32_split3) ? 1 : 0;
   a.bias = w->proj_out_b;
   if (dt == TTV_BF16 && dm == 256 && w->proj_out_pn && pd % 8 == 0) {
@@ -720,20 +689,13 @@ int ttv_decoder_forward(const ttv_tower_dims* d, const ttv_tower_weights* w, con
   }
   // unpatchify inside the GEMM epilogue (8 consecutive output features = one 16-byte pixel row segment of a patch) when the
   // shapes allow it: saves the [P, pd] round trip and the copy kernel.  TTV_FUSED_PATCH=0 keeps the two-kernel sequence.
-  static const bool use_fused_patch = ttv_sw_fused_patch();
-  auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
-  if (use_fused_patch && dt == TTV_BF16 && dm == 256 && d->patch_w == 8 && pow2(d->patch_t) && pow2(d->patch_h) &&
-      b->n_clips <= TTV_MAX_CLIPS_PER_LAUNCH && b->row_seq && pd % 64 == 0) {
+  if (fused_patch_ok(d, b, dt) && dm == 256) {
     a.clips = clips_out; a.n_clips = b->n_clips; a.clip_desc = b->clip_desc; a.patch_rows = b->patch_rows; a.row_seq = b->row_seq;
     a.patch_t = d->patch_t; a.patch_h = d->patch_h; a.patch_w = d->patch_w;
     return ttvk_gemm(EPI_STORE_PATCH, a, s);
   }
   TTV_TRY(ttvk_gemm(EPI_STORE, a, s));
-  for (int c0 = 0; c0 < b->n_clips; c0 += TTV_MAX_CLIPS_PER_LAUNCH) {
-    const int n = b->n_clips - c0 < TTV_MAX_CLIPS_PER_LAUNCH ? b->n_clips - c0 : TTV_MAX_CLIPS_PER_LAUNCH;
-    TTV_TRY(ttvk_patch_copy(true, clips_out + c0, b->clip_desc, c0, n, d->patch_t, d->patch_h, d->patch_w, d->pix_channels, ws.pa, pd, dt, b->max_patches_per_clip, s));
-  }
-  return TTV_OK;
+  return patch_copy_all(true, clips_out, d, b, ws.pa, dt, s);
 }
 
 int ttv_rope_table_build(const float* base_cos, const float* base_sin, int n_ids, int n_freqs, const int32_t* clip_desc, const int32_t* cu_seqlens,
@@ -746,11 +708,9 @@ int ttv_rope_table_build(const float* base_cos, const float* base_sin, int n_ids
 int ttv_l1_loss(void* const* recon, void* const* target, void* const* grad, const int32_t* sizes, int n_clips, int dtype, float* loss,
                 void* stream) {
   // loss must be zeroed by the caller; clips are processed in groups of TTV_MAX_CLIPS_PER_LAUNCH
-  for (int c0 = 0; c0 < n_clips; c0 += TTV_MAX_CLIPS_PER_LAUNCH) {
-    const int n = n_clips - c0 < TTV_MAX_CLIPS_PER_LAUNCH ? n_clips - c0 : TTV_MAX_CLIPS_PER_LAUNCH;
-    TTV_TRY(ttvk_l1_loss(recon + c0, target + c0, grad ? grad + c0 : nullptr, sizes + c0, n, n_clips, dtype, loss, (hipStream_t)stream));
-  }
-  return TTV_OK;
+  return for_clip_groups(n_clips, [&](int c0, int n) {
+    return ttvk_l1_loss(recon + c0, target + c0, grad ? grad + c0 : nullptr, sizes + c0, n, n_clips, dtype, loss, (hipStream_t)stream);
+  });
 }
 
 int ttv_clip_from_u8(const void* frames_thwc, int T, int H, int W, void* clip_cthw, int dtype, void* stream) {
@@ -764,11 +724,7 @@ int ttv_clip_resample_u8(void* const* frames_thwc, void* const* clips_cthw, cons
 
 int ttv_sq_err_accumulate(void* const* recon, void* const* target, const int32_t* sizes, int n_clips, int dtype, int clamp, double* acc,
                           void* stream) {
-  for (int c0 = 0; c0 < n_clips; c0 += TTV_MAX_CLIPS_PER_LAUNCH) {
-    const int n = n_clips - c0 < TTV_MAX_CLIPS_PER_LAUNCH ? n_clips - c0 : TTV_MAX_CLIPS_PER_LAUNCH;
-    TTV_TRY(ttvk_sq_err(recon + c0, target + c0, sizes + c0, n, dtype, clamp, acc, (hipStream_t)stream));
-  }
-  return TTV_OK;
+  return for_clip_groups(n_clips, [&](int c0, int n) { return ttvk_sq_err(recon + c0, target + c0, sizes + c0, n, dtype, clamp, acc, (hipStream_t)stream); });
 }
 
 int64_t ttv_ssim_workspace_bytes(const int32_t* dims, int n_clips) { return ttvk_ssim_workspace_bytes(dims, n_clips); }

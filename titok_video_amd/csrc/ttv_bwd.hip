@@ -18,11 +18,6 @@
 #include "ttv_kernels.h"
 
 #define BW_MAX_ITERS 4
-#define BW_TRY(expr)                 \
-  do {                               \
-    const int rc__ = (expr);         \
-    if (rc__ != TTV_OK) return rc__; \
-  } while (0)
 
 // ------------------------------------------------------------------------------------------------ rmsnorm backward
 template <typename TX, typename TG, typename TO>
@@ -1177,7 +1172,7 @@ int ttvk_wgrad(const void* dy, int lddy, const void* x, int ldx, float* dw, int 
                int64_t part_bytes, hipStream_t s, WgradBatch* batch) {
   if (L == 0 || N == 0 || K == 0 || !dw) return TTV_OK;   // dw == NULL: frozen weight
   static const bool batch_env = ttv_env_flag("TTV_WGRAD_BATCHED", true);   // A/B
-  if (!batch_env && batch) { BW_TRY(ttvk_wgrad_flush(batch, s)); batch = nullptr; }
+  if (!batch_env && batch) { TTV_TRY(ttvk_wgrad_flush(batch, s)); batch = nullptr; }
   if (dt == TTV_BF16 && N % 8 == 0 && K % 8 == 0 && lddy % 8 == 0 && ldx % 8 == 0) {
     // TTV_WGRAD_TILE64 is on when merely present, whatever its value: only a set variable reads the same under two defaults
     static const int wg_tile64 = ttv_env_int("TTV_WGRAD_TILE64", 0) == ttv_env_int("TTV_WGRAD_TILE64", 1) ? 1 : 0;
@@ -1202,7 +1197,7 @@ int ttvk_wgrad(const void* dy, int lddy, const void* x, int ldx, float* dw, int 
       dim3 grid(tn * tk * (splits >= 8 ? 8 * ttv_cdiv(splits, 8) : splits));
       const int64_t need = (int64_t)tn * tk * splits * 65536;
       if (batch && part && ((uintptr_t)part % 16 == 0) && (batch->n == TTV_WGRAD_BATCH || batch->used_bytes + need > part_bytes))
-        BW_TRY(ttvk_wgrad_flush(batch, s));        // does not fit behind what is pending: sum that first, start over at the scratch's base
+        TTV_TRY(ttvk_wgrad_flush(batch, s));        // does not fit behind what is pending: sum that first, start over at the scratch's base
       if (batch && part && ((uintptr_t)part % 16 == 0) && batch->used_bytes + need <= part_bytes) {
         float* mine = reinterpret_cast<float*>(reinterpret_cast<char*>(part) + batch->used_bytes);
         hipLaunchKernelGGL(k_wgrad128_bf16<true>, grid, dim3(256 + 64 * WG_NL), WG_RING * WG_STAGE_BYTES, s, (const bf16_t*)dy, lddy, (const bf16_t*)x, ldx, dw, lddw, L, N, K,
@@ -1211,7 +1206,7 @@ int ttvk_wgrad(const void* dy, int lddy, const void* x, int ldx, float* dw, int 
         en.part = mine; en.dw = dw; en.splits = splits; en.lddw = lddw; en.N = N; en.K = K; en.tiles_n = tn; en.tiles = tn * tk;
         batch->used_bytes += need;
       } else if (part && part_bytes >= need && ((uintptr_t)part % 16 == 0)) {
-        if (batch) BW_TRY(ttvk_wgrad_flush(batch, s));
+        if (batch) TTV_TRY(ttvk_wgrad_flush(batch, s));
         hipLaunchKernelGGL(k_wgrad128_bf16<true>, grid, dim3(256 + 64 * WG_NL), WG_RING * WG_STAGE_BYTES, s, (const bf16_t*)dy, lddy, (const bf16_t*)x, ldx, dw, lddw, L, N, K,
                            tpb, part, tn, tk, splits);
         hipLaunchKernelGGL(k_wgrad_reduce, dim3(tn * tk * 64), dim3(256), 0, s, part, splits, dw, lddw, N, K, tn);

@@ -211,7 +211,11 @@ static inline float ttv_env_float(const char* name, float dflt) {
   return v ? (float)atof(v) : dflt;
 }
 // Switches that more than one site reads: one accessor each (ttv_api.hip), so that the name and the default are written once.
-bool ttv_sw_enc_latent_last();       // TTV_ENC_LATENT_LAST (default on): run_layers, the training forward
+bool ttv_sw_enc_latent_last();       // TTV_ENC_LATENT_LAST (default on): the precondition below
+// The encoder's last layer may work on its latent rows only: the switch, not ttv_debug_set's TTV_DBG_ENC_ALL_ROWS, an encoder, and a batch
+// whose latent rows are a proper, non-empty subset of its rows.  run_layers adds the latent work table; the training forward and
+// backward add what their compact tape needs (ttv_train.hip: latent_tail, latent_attn).
+bool ttv_enc_latent_rows_only(const ttv_tower_dims* d, const ttv_batch* b);
 bool ttv_sw_keel_f32sum();           // TTV_KEEL_F32SUM (default off): run_layers' path choice and its KEEL tails
 bool ttv_sw_fused_patch();           // TTV_FUSED_PATCH (default on): the encoder's and the decoder's patch kernels
 bool ttv_sw_attn_pipe();             // TTV_ATTN_PIPE (default off): the opt-in pipelined attention kernel

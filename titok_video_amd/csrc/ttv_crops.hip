@@ -326,7 +326,7 @@ int ttvk_lpips_crops_forward(void* const* recon, void* const* target, const int3
   TTV_CHECK_ARG(recon && target && recon_crops && target_crops, "lpips_crops_forward: null argument");
   for (int i = 0; i < n_clips; ++i) TTV_CHECK_ARG(recon[i] && target[i], "lpips_crops_forward: null pointer in clip %d", i);
   TTV_CHECK_ARG((uintptr_t)recon_crops % 16 == 0 && (uintptr_t)target_crops % 16 == 0, "lpips_crops_forward: a destination is not 16-byte aligned");
-  const size_t esz = dtype == TTV_BF16 ? 2 : 4;
+  const size_t esz = dtype_bytes(dtype);
   const int V = 16 / (int)esz;
   const unsigned tiles = (unsigned)ttv_cdiv(3 * size * (size / V), 256);
   for (int c0 = 0; c0 < n_crops; c0 += CR_FWD_CROPS) {

@@ -2237,7 +2237,7 @@ bool ttvk_gemm_supports_resid_norm(int dtype, int N, int K) { return dtype == TT
 
 int ttvk_gemm(GemmEpilogue epi, const GemmArgs& a, hipStream_t s) {
   if (a.M == 0 || a.N == 0) return TTV_OK;
-  const int esz = a.dtype == TTV_BF16 ? 2 : 4;
+  const int esz = dtype_bytes(a.dtype);
   const int vec = 16 / esz;
   TTV_CHECK_ARG(a.dtype == TTV_BF16 || a.dtype == TTV_F32, "gemm: bad dtype %d", a.dtype);
   TTV_CHECK_ARG(a.K > 0 && a.K % vec == 0, "gemm: K=%d must be a multiple of %d", a.K, vec);

@@ -23,12 +23,6 @@
 #include "ttv_common.h"
 #include "ttv_kernels.h"
 
-#define TTV_TRY(expr)            \
-  do {                           \
-    const int rc__ = (expr);     \
-    if (rc__ != TTV_OK) return rc__; \
-  } while (0)
-
 namespace {
 
 constexpr int PREP_T = 3, PREP_FRAMES = 10, PREP_S = 224;
@@ -295,7 +289,6 @@ constexpr int INC[9][6] = {{64, 96, 128, 16, 32, 32},     {128, 128, 192, 32, 96
 
 // per-clip float counts of the workspace buffers (P, Q: the ping-pong activations; T1, T2, T3: Inception temporaries)
 constexpr int64_t WS_PQ = (int64_t)5 * 112 * 112 * 64, WS_T = (int64_t)5 * 28 * 28 * 256;
-inline int64_t al256(int64_t b) { return (b + 255) & ~(int64_t)255; }
 
 int conv_launch(const float* x, int N, int Ti, int Hi, int Wi, int Cin, int k, int s, const float* w, const float* scale,
                 const float* shift, int Cout, int relu, float* y, int ldc, int c_off, hipStream_t st) {
@@ -346,7 +339,7 @@ int64_t ttvk_i3d_workspace_bytes(int n) {
     ttv_set_error("i3d: n = %d clips, 1 .. %d allowed", n, TTV_MAX_CLIPS_PER_LAUNCH);
     return -1;
   }
-  return 2 * al256(WS_PQ * 4 * n) + 3 * al256(WS_T * 4 * n);
+  return 2 * align256(WS_PQ * 4 * n) + 3 * align256(WS_T * 4 * n);
 }
 
 int ttvk_fvd_preprocess(void* const* clips, const int32_t* dims, int n_clips, int dtype, int clamp, float* out, hipStream_t st) {
@@ -404,10 +397,10 @@ int ttvk_i3d_features(const ttv_i3d_weights* wt, const float* x, int n, float* f
   TTV_CHECK_ARG((((uintptr_t)x | (uintptr_t)ws) & 255) == 0, "i3d features: x and workspace must be 256-byte aligned");
   char* wp = reinterpret_cast<char*>(ws);
   float* P = reinterpret_cast<float*>(wp);
-  float* Q = reinterpret_cast<float*>(wp + al256(WS_PQ * 4 * n));
-  float* T1 = reinterpret_cast<float*>(wp + 2 * al256(WS_PQ * 4 * n));
-  float* T2 = reinterpret_cast<float*>(wp + 2 * al256(WS_PQ * 4 * n) + al256(WS_T * 4 * n));
-  float* T3 = reinterpret_cast<float*>(wp + 2 * al256(WS_PQ * 4 * n) + 2 * al256(WS_T * 4 * n));
+  float* Q = reinterpret_cast<float*>(wp + align256(WS_PQ * 4 * n));
+  float* T1 = reinterpret_cast<float*>(wp + 2 * align256(WS_PQ * 4 * n));
+  float* T2 = reinterpret_cast<float*>(wp + 2 * align256(WS_PQ * 4 * n) + align256(WS_T * 4 * n));
+  float* T3 = reinterpret_cast<float*>(wp + 2 * align256(WS_PQ * 4 * n) + 2 * align256(WS_T * 4 * n));
   auto conv = [&](int i, const float* in, int t, int h, int w, int cin, int k, int s, int cout, float* out, int ldc, int off) {
     return conv_launch(in, n, t, h, w, cin, k, s, wt->w[i], wt->scale[i], wt->shift[i], cout, 1, out, ldc, off, st);
   };

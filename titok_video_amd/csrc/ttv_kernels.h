@@ -256,3 +256,56 @@ int ttvk_vjepa_layernorm(const float* x, int ldx, int rows, int width, const flo
 int ttvk_vjepa_linear(const void* x, int ldx, const void* w, int ldw, const void* bias, int M, int N, int K, int epilogue,
                       const float* resid, int ldr, int resid_rows, void* y, int ldy, hipStream_t s);
 int ttvk_vjepa_pool_attention(const void* q, const void* kv, int n, int rows, void* out, hipStream_t s);
+
+// ---- host helpers of the launch sequences (ttv_api.hip, ttv_train.hip, the feature extractors) ----
+#define TTV_TRY(expr)                \
+  do {                               \
+    const int rc__ = (expr);         \
+    if (rc__ != TTV_OK) return rc__; \
+  } while (0)
+
+static inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+static inline int dtype_bytes(int dt) { return dt == TTV_BF16 ? 2 : 4; }
+static inline int patch_dim(const ttv_tower_dims* d) { return d->pix_channels * d->patch_t * d->patch_h * d->patch_w; }   // pixels of a patch = K of proj_in
+static inline float keel_alpha(const ttv_tower_dims* d, int layer) { return layer == 0 ? 1.f : d->alpha; }             // layer 0: plain residual, no post-norm
+
+// y[M, N] (ldy) = x[M, K] (ldx) @ w[N, K]^T (ldw); every other field zero
+static inline GemmArgs gemm_args(int dtype, const void* x, int ldx, const void* w, int ldw, int M, int N, int K, void* y, int ldy) {
+  GemmArgs a = {};
+  a.dtype = dtype; a.x = x; a.ldx = ldx; a.w = w; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.y = y; a.ldy = ldy;
+  return a;
+}
+// EPI_QKV_ROPE: rotary on the q columns [0, d_model) and the k columns [2 d_model, 2 d_model + gqa_dim) of (q | gate | k | v)
+static inline GemmArgs gemm_rope_qk(GemmArgs a, const float* rope_cs, int d_model, int gqa_dim) {
+  a.rope_cs = rope_cs; a.rope_q_end = d_model; a.rope_k_begin = 2 * d_model; a.rope_k_end = 2 * d_model + gqa_dim;
+  return a;
+}
+// EPI_RESID_*: alpha * resid + acc
+static inline GemmArgs gemm_resid(GemmArgs a, const void* resid, int ldr, float alpha) {
+  a.resid = resid; a.ldr = ldr; a.alpha = alpha;
+  return a;
+}
+
+// compact rows: dst[r] = src[index[r]] / dst[index[r]] = src[r], r < n_rows, both sides row_bytes apart
+static inline int gather_rows(const void* src, void* dst, const int* index, int n_rows, int64_t row_bytes, hipStream_t s) {
+  return ttvk_copy_rows(src, row_bytes, index, dst, row_bytes, nullptr, n_rows, (int)row_bytes, s);
+}
+static inline int scatter_rows(const void* src, void* dst, const int* index, int n_rows, int64_t row_bytes, hipStream_t s) {
+  return ttvk_copy_rows(src, row_bytes, nullptr, dst, row_bytes, index, n_rows, (int)row_bytes, s);
+}
+
+// f(first clip, count) for every group of at most TTV_MAX_CLIPS_PER_LAUNCH clips
+template <typename F> static inline int for_clip_groups(int n_clips, F f) {
+  for (int c0 = 0; c0 < n_clips; c0 += TTV_MAX_CLIPS_PER_LAUNCH) {
+    const int n = n_clips - c0 < TTV_MAX_CLIPS_PER_LAUNCH ? n_clips - c0 : TTV_MAX_CLIPS_PER_LAUNCH;
+    TTV_TRY(f(c0, n));
+  }
+  return TTV_OK;
+}
+// patchify (scatter = false: clips -> buf [sum_patches, patch_dim]) / unpatchify (true: buf -> clips) of a tower's whole batch
+static inline int patch_copy_all(bool scatter, void* const* clips, const ttv_tower_dims* d, const ttv_batch* b, void* buf, int dtype, hipStream_t s) {
+  return for_clip_groups(b->n_clips, [&](int c0, int n) {
+    return ttvk_patch_copy(scatter, clips + c0, b->clip_desc, c0, n, d->patch_t, d->patch_h, d->patch_w, d->pix_channels, buf, patch_dim(d), dtype,
+                           b->max_patches_per_clip, s);
+  });
+}

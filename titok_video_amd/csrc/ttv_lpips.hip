@@ -40,12 +40,6 @@
 #include <algorithm>
 #include <utility>
 
-#define TTV_TRY(expr)            \
-  do {                           \
-    const int rc__ = (expr);     \
-    if (rc__ != TTV_OK) return rc__; \
-  } while (0)
-
 namespace {
 
 constexpr int LP_LAYERS = 13;
@@ -526,8 +520,6 @@ int64_t conv_ws_bytes(int dtype, int N, int H, int W, int Cin, int Cout) {
   return S > 1 ? (int64_t)S * N * H * W * Cout * 4 : 0;
 }
 
-size_t esize(int dtype) { return dtype == TTV_BF16 ? 2 : 4; }
-
 int conv_launch(int dtype, const void* x, int N, int H, int W, int Cin, int Cout, const void* w, const float* bias, int mode, const void* h,
                 void* y, void* ws, hipStream_t st) {
   if (use_mfma(dtype, Cin, Cout)) {
@@ -585,20 +577,18 @@ struct Layout {
   size_t part, gpart, hg[5], D[5], bufa, bufb, bufp, split, ws;
 };
 
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 Layout layout(int n, int H, int W, int dtype) {
   Layout L{};
-  const size_t es = esize(dtype);
+  const size_t es = dtype_bytes(dtype);
   size_t o = 0;
   int pi = 0;
   for (int l = 0; l < LP_LAYERS; ++l) {
     const int s = LP_STAGE[l];
     L.act[l] = o;
-    o = al256(o + (size_t)2 * n * (H >> s) * (W >> s) * LP_COUT[l] * es);
+    o = align256(o + (size_t)2 * n * (H >> s) * (W >> s) * LP_COUT[l] * es);
     if (l == 1 || l == 3 || l == 6 || l == 9) {
       L.pool[pi++] = o;
-      o = al256(o + (size_t)2 * n * (H >> (s + 1)) * (W >> (s + 1)) * LP_COUT[l] * es);
+      o = align256(o + (size_t)2 * n * (H >> (s + 1)) * (W >> (s + 1)) * LP_COUT[l] * es);
     }
   }
   L.tape = o;
@@ -610,24 +600,24 @@ Layout layout(int n, int H, int W, int dtype) {
     ng += (size_t)n * LP_TAP_C[k] * LP_TAP_C[k] / 256;
   }
   L.part = o;
-  o = al256(o + np * 8);
+  o = align256(o + np * 8);
   L.gpart = o;
-  o = al256(o + ng * 8);
+  o = align256(o + ng * 8);
   for (int k = 0; k < 5; ++k) {
     L.hg[k] = o;
-    o = al256(o + (size_t)n * (H >> k) * (W >> k) * LP_TAP_C[k] * 4);
+    o = align256(o + (size_t)n * (H >> k) * (W >> k) * LP_TAP_C[k] * 4);
   }
   for (int k = 0; k < 5; ++k) {
     L.D[k] = o;
-    o = al256(o + (size_t)n * LP_TAP_C[k] * LP_TAP_C[k] * 4);
+    o = align256(o + (size_t)n * LP_TAP_C[k] * LP_TAP_C[k] * 4);
   }
   const size_t big = (size_t)n * H * W * 64 * es;
   L.bufa = o;
-  o = al256(o + big);
+  o = align256(o + big);
   L.bufb = o;
-  o = al256(o + big);
+  o = align256(o + big);
   L.bufp = o;
-  o = al256(o + big / 4);
+  o = align256(o + big / 4);
   int64_t sp = 0;
   for (int l = 1; l < LP_LAYERS; ++l) {
     const int s = LP_STAGE[l];
@@ -635,7 +625,7 @@ Layout layout(int n, int H, int W, int dtype) {
     sp = std::max(sp, conv_ws_bytes(dtype, n, H >> s, W >> s, LP_COUT[l], LP_CIN[l]));
   }
   L.split = o;
-  o = al256(o + (size_t)sp);
+  o = align256(o + (size_t)sp);
   L.ws = o;
   return L;
 }

@@ -125,7 +125,7 @@ int ttv_recon_panels_u8(void* const* target, void* const* recon, const int32_t* 
   if (n_clips == 0) return TTV_OK;
   TTV_CHECK_ARG(dtype == TTV_BF16 || dtype == TTV_F32, "recon_panels_u8: dtype %d is neither TTV_BF16 nor TTV_F32", dtype);
   TTV_CHECK_ARG(n_clips > 0 && target && recon && dims && panels, "recon_panels_u8: %d clips, or a null table", n_clips);
-  const size_t esz = dtype == TTV_BF16 ? 2 : 4;
+  const size_t esz = dtype_bytes(dtype);
   for (int i = 0; i < n_clips; ++i) {
     const int T = dims[3 * i], H = dims[3 * i + 1], W = dims[3 * i + 2];
     TTV_CHECK_ARG(T >= 1 && H >= 1 && W >= 1 && T <= 65536 && H <= 65536 && W <= 65536 && (int64_t)3 * T * H * 2 * W < ((int64_t)1 << 31),

@@ -9,15 +9,6 @@
 #include "ttv_common.h"
 #include "ttv_kernels.h"
 
-#define TTV_TRY(expr)                \
-  do {                               \
-    int rc__ = (expr);               \
-    if (rc__ != TTV_OK) return rc__; \
-  } while (0)
-
-static inline int64_t al(int64_t v) { return (v + 255) & ~(int64_t)255; }
-static inline int esz(int dt) { return dt == TTV_BF16 ? 2 : 4; }
-
 struct Tape {
   char* base;
   int64_t total;
@@ -42,12 +33,12 @@ static int tape_y_dtype(int dt) {
 }
 static Tape carve_tape(const ttv_tower_dims* d, const ttv_batch* b, char* base) {
   Tape t;
-  const int64_t ye = esz(tape_y_dtype(d->dtype));
-  const int64_t e = esz(d->dtype), L = b->total_rows, P = b->sum_patches, K = b->sum_tokens, dm = d->width;
+  const int64_t ye = dtype_bytes(tape_y_dtype(d->dtype));
+  const int64_t e = dtype_bytes(d->dtype), L = b->total_rows, P = b->sum_patches, K = b->sum_tokens, dm = d->width;
   const int64_t g = (int64_t)d->kv_heads * d->head_dim, nq = 2 * dm + 2 * g;
-  const int64_t pd = (int64_t)d->pix_channels * d->patch_t * d->patch_h * d->patch_w;
+  const int64_t pd = patch_dim(d);
   int64_t off = 0;
-  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += al(bytes); return p; };
+  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
   t.base = base;
   t.patches = t.pe = t.hpre = t.pn = nullptr;
   t.agc = t.xc = nullptr;
@@ -76,11 +67,11 @@ struct BwdWs {
 };
 static BwdWs carve_bwd(const ttv_tower_dims* d, const ttv_batch* b, char* base) {
   BwdWs w;
-  const int64_t e = esz(d->dtype), L = b->total_rows, P = b->sum_patches, dm = d->width;
+  const int64_t e = dtype_bytes(d->dtype), L = b->total_rows, P = b->sum_patches, dm = d->width;
   const int64_t g = (int64_t)d->kv_heads * d->head_dim, nq = 2 * dm + 2 * g;
-  const int64_t pd = (int64_t)d->pix_channels * d->patch_t * d->patch_h * d->patch_w;
+  const int64_t pd = patch_dim(d);
   int64_t off = 0;
-  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += al(bytes); return p; };
+  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
   w.dxa = (float*)take(L * dm * 4); w.dxb = (float*)take(L * dm * 4);
   w.delta = (float*)take(L * d->q_heads * 4);
   w.dkv = (float*)take(d->dtype == TTV_F32 ? L * 2 * g * 4 : 0);
@@ -125,9 +116,7 @@ static int check(const ttv_tower_dims* d, const ttv_batch* b) {
 // of the loss with respect to the last layer's patch-row outputs is zero, so nothing is lost; attention (forward and backward) still runs
 // on every row - a query row with dO = 0 contributes nothing.  TTV_ENC_LATENT_LAST=0 / ttv_debug_set bit 19: every row (A/B, tests).
 static bool latent_tail(const ttv_tower_dims* d, const ttv_batch* b, int layer) {
-  static const bool env = ttv_sw_enc_latent_last();
-  return env && !(g_ttv_debug & TTV_DBG_ENC_ALL_ROWS) && d->kind == TTV_ENCODER && layer == d->layers - 1 && b->latent_rows && b->sum_tokens > 0 &&
-         b->sum_tokens < b->total_rows && d->inner >= d->width;
+  return ttv_enc_latent_rows_only(d, b) && layer == d->layers - 1 && d->inner >= d->width;
 }
 
 // ... and the attention itself for the latent QUERY rows only (keys / values: every row), forward and backward, when the batch carries the
@@ -146,15 +135,15 @@ static int layers_forward_train(const ttv_tower_dims* d, const ttv_tower_weights
   // launch-bound - so the proven sequence stays the default.
   const bool fuse_norms = tape_fuse_norms();
   const int ydt = tape_y_dtype(dt);
+  const int64_t row_bytes = (int64_t)dm * dtype_bytes(dt);
   bool xn1_ready = false;          // this layer's xn1 was written by the layer below
   for (int i = 0; i < d->layers; ++i) {
     const ttv_layer_weights& lw = w->layers[i];
     Tape::L& l = t.l[i];
+    const float alpha = keel_alpha(d, i);
     if (!xn1_ready) TTV_TRY(ttvk_rmsnorm(t.X[i], dt, dm, nullptr, l.xn1, dt, dm, nullptr, lw.pre_ln, L, dm, d->eps, s));
     xn1_ready = false;
-    GemmArgs a = {};
-    a.dtype = dt; a.x = l.xn1; a.ldx = dm; a.w = lw.to_qkv; a.ldw = dm; a.M = L; a.N = nq; a.K = dm; a.y = l.qkvg; a.ldy = nq;
-    a.rope_cs = b->rope_cs; a.rope_q_end = dm; a.rope_k_begin = 2 * dm; a.rope_k_end = 2 * dm + g;
+    GemmArgs a = gemm_rope_qk(gemm_args(dt, l.xn1, dm, lw.to_qkv, dm, L, nq, dm, l.qkvg, nq), b->rope_cs, dm, g);
     a.rope_ids = b->rope_ids; a.rope_base = b->rope_ids ? b->rope_base : nullptr;
     TTV_TRY(ttvk_gemm(EPI_QKV_ROPE, a, s));
     // encoder, last layer: attention outputs are needed for the latent query rows only (latent_attn); the raw output of the other rows is
@@ -163,13 +152,13 @@ static int layers_forward_train(const ttv_tower_dims* d, const ttv_tower_weights
     const int32_t* qb = lat_q ? b->qblocks_latent : b->qblocks;
     const int nqb = lat_q ? b->n_qblocks_latent : b->n_qblocks;
     const int pair = (!lat_q && b->qblocks_paired) ? TTV_ATTN_PAIRED : 0;
-    if (lat_q) (void)hipMemsetAsync(l.a, 0, (size_t)L * dm * esz(dt), s);
+    if (lat_q) (void)hipMemsetAsync(l.a, 0, (size_t)L * dm * dtype_bytes(dt), s);
     if (dt == TTV_BF16) {
       // one launch writes the raw output a (tape) and the gated one ag = a * sigmoid(gate) (gate applied to the stored, rounded a)
       TTV_TRY(ttvk_attention(l.qkvg, nq, l.ag, dm, b->cu_seqlens, qb, nqb, d->q_heads, d->kv_heads, d->head_dim, TTV_ATTN_GATE | pair, dt, s, l.lse, l.a));
     } else {
       TTV_TRY(ttvk_attention(l.qkvg, nq, l.a, dm, b->cu_seqlens, qb, nqb, d->q_heads, d->kv_heads, d->head_dim, pair, dt, s, l.lse));
-      TTV_TRY(ttvk_gate_fwd(l.a, dm, (const char*)l.qkvg + (size_t)dm * esz(dt), nq, l.ag, dm, L, dm, dt, s));
+      TTV_TRY(ttvk_gate_fwd(l.a, dm, (const char*)l.qkvg + (size_t)dm * dtype_bytes(dt), nq, l.ag, dm, L, dm, dt, s));
     }
     // the rest of the layer on (Lc rows: ag_in, x_in): every row, or - encoder, last layer - the latent rows, compact
     const bool lat = latent_tail(d, b, i);
@@ -178,44 +167,41 @@ static int layers_forward_train(const ttv_tower_dims* d, const ttv_tower_weights
     char* x_in = t.X[i];
     char* x_out = t.X[i + 1];
     if (lat) {
-      TTV_TRY(ttvk_copy_rows(l.ag, (int64_t)dm * esz(dt), b->latent_rows, t.agc, (int64_t)dm * esz(dt), nullptr, Lc, dm * esz(dt), s));
-      TTV_TRY(ttvk_copy_rows(t.X[i], (int64_t)dm * esz(dt), b->latent_rows, t.xc, (int64_t)dm * esz(dt), nullptr, Lc, dm * esz(dt), s));
+      TTV_TRY(gather_rows(l.ag, t.agc, b->latent_rows, Lc, row_bytes, s));
+      TTV_TRY(gather_rows(t.X[i], t.xc, b->latent_rows, Lc, row_bytes, s));
       ag_in = t.agc; x_in = t.xc; x_out = t.xc;          // the layer's output: compact in place of its input rows, scattered below
     }
-    GemmArgs o = {};
-    o.dtype = dt; o.x = ag_in; o.ldx = dm; o.w = lw.out_proj; o.ldw = dm; o.M = Lc; o.N = dm; o.K = dm; o.resid = x_in; o.ldr = dm;
+    // out_proj + residual: the sum into x1 (layer 0, and the fused route which norms it in the kernel) or into the tape's y1
+    const bool o_fused = i > 0 && fuse_norms && ttvk_gemm_supports_resid_norm(dt, dm, dm);
+    GemmArgs o = gemm_resid(gemm_args(dt, ag_in, dm, lw.out_proj, dm, Lc, dm, dm, (i == 0 || o_fused) ? l.x1 : l.y1, dm), x_in, dm, alpha);
     if (i == 0) {
-      o.alpha = 1.f; o.y = l.x1; o.ldy = dm;
       TTV_TRY(ttvk_gemm(EPI_RESID_T, o, s));
-    } else if (fuse_norms && ttvk_gemm_supports_resid_norm(dt, dm, dm)) {
-      o.alpha = d->alpha; o.y = l.x1; o.ldy = dm; o.norm_gain = lw.attn_post_ln; o.eps = d->eps;
+    } else if (o_fused) {
+      o.norm_gain = lw.attn_post_ln; o.eps = d->eps;
       o.sum_f32 = (float*)l.y1; o.ld_sum = dm; o.y2 = l.xn2; o.ldy2 = dm; o.norm_gain2 = lw.ffd_norm;
       TTV_TRY(ttvk_gemm(EPI_RESID_NORM, o, s));
     } else {
-      o.alpha = d->alpha; o.y = l.y1; o.ldy = dm;
       TTV_TRY(ttvk_gemm(ydt == TTV_F32 ? EPI_RESID_F32 : EPI_RESID_T, o, s));
       TTV_TRY(ttvk_rmsnorm(l.y1, ydt, dm, nullptr, l.x1, dt, dm, nullptr, lw.attn_post_ln, Lc, dm, d->eps, s));
     }
-    if (!(i > 0 && fuse_norms && ttvk_gemm_supports_resid_norm(dt, dm, dm)))
+    if (!o_fused)
       TTV_TRY(ttvk_rmsnorm(l.x1, dt, dm, nullptr, l.xn2, dt, dm, nullptr, lw.ffd_norm, Lc, dm, d->eps, s));
-    GemmArgs f = {};
     if (dt == TTV_BF16) {
-      // one launch: u = xn2 W12^T kept for the backward (through `resid`) and h = gelu(gate) * x from the stored values
-      f.dtype = dt; f.x = l.xn2; f.ldx = dm; f.w = lw.w12; f.ldw = dm; f.M = Lc; f.N = I; f.K = dm; f.y = l.h; f.ldy = I;
+      // one launch: u = xn2 W12^T kept for the backward (through `resid`, no alpha) and h = gelu(gate) * x from the stored values
+      GemmArgs f = gemm_args(dt, l.xn2, dm, lw.w12, dm, Lc, I, dm, l.h, I);
       f.resid = l.u; f.ldr = 2 * I;
       TTV_TRY(ttvk_gemm(EPI_GEGLU, f, s));
     } else {
-      f.dtype = dt; f.x = l.xn2; f.ldx = dm; f.w = lw.w12; f.ldw = dm; f.M = Lc; f.N = 2 * I; f.K = dm; f.y = l.u; f.ldy = 2 * I;
-      TTV_TRY(ttvk_gemm(EPI_STORE, f, s));
+      TTV_TRY(ttvk_gemm(EPI_STORE, gemm_args(dt, l.xn2, dm, lw.w12, dm, Lc, 2 * I, dm, l.u, 2 * I), s));
       TTV_TRY(ttvk_geglu_fwd(l.u, 2 * I, l.h, I, Lc, I, dt, s));
     }
-    GemmArgs f3 = {};
-    f3.dtype = dt; f3.x = l.h; f3.ldx = I; f3.w = lw.w3; f3.ldw = I; f3.M = Lc; f3.N = dm; f3.K = I; f3.resid = l.x1; f3.ldr = dm;
+    // w3 + residual: as out_proj above, into the layer's output rows or the tape's y2
+    const bool f3_fused = i > 0 && fuse_norms && ttvk_gemm_supports_resid_norm(dt, dm, I);
+    GemmArgs f3 = gemm_resid(gemm_args(dt, l.h, I, lw.w3, I, Lc, dm, I, (i == 0 || f3_fused) ? x_out : l.y2, dm), l.x1, dm, alpha);
     if (i == 0) {
-      f3.alpha = 1.f; f3.y = x_out; f3.ldy = dm;
       TTV_TRY(ttvk_gemm(EPI_RESID_T, f3, s));
-    } else if (fuse_norms && ttvk_gemm_supports_resid_norm(dt, dm, I)) {
-      f3.alpha = d->alpha; f3.y = x_out; f3.ldy = dm; f3.norm_gain = lw.ffd_post_ln; f3.eps = d->eps;
+    } else if (f3_fused) {
+      f3.norm_gain = lw.ffd_post_ln; f3.eps = d->eps;
       f3.sum_f32 = (float*)l.y2; f3.ld_sum = dm;
       if (i + 1 < d->layers) {          // the next layer's pre-norm rides along
         f3.y2 = t.l[i + 1].xn1; f3.ldy2 = dm; f3.norm_gain2 = w->layers[i + 1].pre_ln;
@@ -223,12 +209,11 @@ static int layers_forward_train(const ttv_tower_dims* d, const ttv_tower_weights
       }
       TTV_TRY(ttvk_gemm(EPI_RESID_NORM, f3, s));
     } else {
-      f3.alpha = d->alpha; f3.y = l.y2; f3.ldy = dm;
       TTV_TRY(ttvk_gemm(ydt == TTV_F32 ? EPI_RESID_F32 : EPI_RESID_T, f3, s));
       TTV_TRY(ttvk_rmsnorm(l.y2, ydt, dm, nullptr, x_out, dt, dm, nullptr, lw.ffd_post_ln, Lc, dm, d->eps, s));
     }
     if (lat)     // the latent rows of the tower's output where the tail (and the backward) read them; its patch rows are never read
-      TTV_TRY(ttvk_copy_rows(t.xc, (int64_t)dm * esz(dt), nullptr, t.X[i + 1], (int64_t)dm * esz(dt), b->latent_rows, Lc, dm * esz(dt), s));
+      TTV_TRY(scatter_rows(t.xc, t.X[i + 1], b->latent_rows, Lc, row_bytes, s));
   }
   return TTV_OK;
 }
@@ -316,7 +301,7 @@ static int layers_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, 
     const long nLc = (long)Lc * dm;
     float* const dxf = dx;                 // the full-size gradient buffer
     if (lat) {
-      TTV_TRY(ttvk_copy_rows(dxf, (int64_t)dm * 4, b->latent_rows, ws.dxc, (int64_t)dm * 4, nullptr, Lc, dm * 4, s));
+      TTV_TRY(gather_rows(dxf, ws.dxc, b->latent_rows, Lc, (int64_t)dm * 4, s));
       dx = ws.dxc;
     }
     float* dx1;
@@ -331,17 +316,13 @@ static int layers_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, 
     }
     dx1 = dx;
     // dh = df W3 ; dW3 += df^T h
-    GemmArgs a = {};
-    a.dtype = dt; a.x = df; a.ldx = dm; a.w = lt.w3_t; a.ldw = dm; a.M = Lc; a.N = I; a.K = dm; a.y = ws.g_i; a.ldy = I;
     TTV_TRY(side_fork(sd, 0, s));          // df is complete
-    TTV_TRY(ttvk_gemm(EPI_STORE, a, s));
+    TTV_TRY(ttvk_gemm(EPI_STORE, gemm_args(dt, df, dm, lt.w3_t, dm, Lc, I, dm, ws.g_i, I), s));
     TTV_TRY(ttvk_wgrad(df, dm, l.h, I, lg.w3, I, Lc, dm, I, dt, ws.wg_part, ws.wg_part_bytes, sw, &wgb));
     TTV_TRY(ttvk_geglu_bwd(l.u, 2 * I, ws.g_i, I, ws.g_2i, 2 * I, Lc, I, dt, s));
     TTV_TRY(side_fork(sd, 1, s));          // du is complete
     // dxn2 = du W12 ; dW12 += du^T xn2
-    GemmArgs c = {};
-    c.dtype = dt; c.x = ws.g_2i; c.ldx = 2 * I; c.w = lt.w12_t; c.ldw = 2 * I; c.M = Lc; c.N = dm; c.K = 2 * I; c.y = ws.g_d2; c.ldy = dm;
-    TTV_TRY(ttvk_gemm(EPI_STORE, c, s));
+    TTV_TRY(ttvk_gemm(EPI_STORE, gemm_args(dt, ws.g_2i, 2 * I, lt.w12_t, 2 * I, Lc, dm, 2 * I, ws.g_d2, dm), s));
     TTV_TRY(ttvk_wgrad(ws.g_2i, 2 * I, l.xn2, dm, lg.w12, dm, Lc, 2 * I, dm, dt, ws.wg_part, ws.wg_part_bytes, sw, &wgb));
     // dx1 += rmsnorm_bwd(x1, ffd_norm, dxn2), then straight through the attention sub-layer's post-norm:
     // ---------------- attention sub-layer: x1 = post_ln(alpha*x + out_proj ag) ----------------
@@ -351,34 +332,29 @@ static int layers_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, 
                                    dm, d->eps, dt, s));
     TTV_TRY(side_fork(sd, 2, s));          // do is complete
     // dag = do Wo ; dWo += do^T ag
-    GemmArgs e = {};
-    e.dtype = dt; e.x = ws.g_do; e.ldx = dm; e.w = lt.out_proj_t; e.ldw = dm; e.M = Lc; e.N = dm; e.K = dm; e.y = ws.g_d2; e.ldy = dm;
-    TTV_TRY(ttvk_gemm(EPI_STORE, e, s));
+    TTV_TRY(ttvk_gemm(EPI_STORE, gemm_args(dt, ws.g_do, dm, lt.out_proj_t, dm, Lc, dm, dm, ws.g_d2, dm), s));
     TTV_TRY(ttvk_wgrad(ws.g_do, dm, lat ? t.agc : l.ag, dm, lg.out_proj, dm, Lc, dm, dm, dt, ws.wg_part, ws.wg_part_bytes, sw, &wgb));
     // back to every row: the gradient of the attention output and of the residual stream are zero outside the latent rows
     char* dag = ws.g_d2;
+    const size_t es = dtype_bytes(dt);
     if (lat) {
-      const size_t es_ = esz(dt);
-      (void)hipMemsetAsync(ws.g_i, 0, (size_t)L * dm * es_, s);
-      TTV_TRY(ttvk_copy_rows(ws.g_d2, (int64_t)dm * es_, nullptr, ws.g_i, (int64_t)dm * es_, b->latent_rows, Lc, dm * (int)es_, s));
+      (void)hipMemsetAsync(ws.g_i, 0, (size_t)L * dm * es, s);
+      TTV_TRY(scatter_rows(ws.g_d2, ws.g_i, b->latent_rows, Lc, (int64_t)dm * es, s));
       dag = ws.g_i;
       (void)hipMemsetAsync(dxf, 0, (size_t)L * dm * sizeof(float), s);
-      TTV_TRY(ttvk_copy_rows(ws.dxc, (int64_t)dm * 4, nullptr, dxf, (int64_t)dm * 4, b->latent_rows, Lc, dm * 4, s));
+      TTV_TRY(scatter_rows(ws.dxc, dxf, b->latent_rows, Lc, (int64_t)dm * 4, s));
       dx = dxf;
     }
     // da = dag*sigmoid(gate) (into the df buffer this layer does not use) ; dgate -> dqkvg[:, d:2d]
     char* dqkvg = ws.g_nq;
-    const size_t es = esz(dt);
     TTV_TRY(ttvk_gate_bwd(dag, dm, l.a, dm, (const char*)l.qkvg + (size_t)dm * es, nq, da, dm, dqkvg + (size_t)dm * es, nq, L, dm, dt,
                           ws.delta, s));   // also fills delta = sum_d da * a per (row, head) for the attention backward
     // attention backward -> dq, dk, dv columns of dqkvg
     TTV_TRY(ttvk_attention_bwd(l.qkvg, nq, l.a, dm, da, dm, l.lse, ws.delta, b->cu_seqlens, b->blocks64, b->n_blocks64, b->row_seq, dqkvg, nq,
                                ws.dkv, L, d->q_heads, d->kv_heads, dt, b->rope_cs, s, 1, latent_attn(d, b, i) ? b->clip_desc : nullptr));   // dq, dk come back un-rotated; delta from the gate backward
     // dxn1 = dqkvg Wqkv ; dWqkv += dqkvg^T xn1
-    GemmArgs q = {};
-    q.dtype = dt; q.x = dqkvg; q.ldx = nq; q.w = lt.to_qkv_t; q.ldw = nq; q.M = L; q.N = dm; q.K = nq; q.y = ws.g_d2; q.ldy = dm;
     TTV_TRY(side_fork(sd, 3, s));          // dqkvg is complete
-    TTV_TRY(ttvk_gemm(EPI_STORE, q, s));
+    TTV_TRY(ttvk_gemm(EPI_STORE, gemm_args(dt, dqkvg, nq, lt.to_qkv_t, nq, L, dm, nq, ws.g_d2, dm), s));
     TTV_TRY(ttvk_wgrad(dqkvg, nq, l.xn1, dm, lg.to_qkv, dm, L, nq, dm, dt, ws.wg_part, ws.wg_part_bytes, sw, &wgb));
     TTV_TRY(ttvk_wgrad_flush(&wgb, sw));     // the layer's four weight gradients: one summing launch
     // dx += rmsnorm_bwd(X[i], pre_ln, dxn1) = dL/dX[i]; chained with the head of the layer below: through its feed-forward
@@ -591,14 +567,9 @@ int ttv_encoder_forward_train(const ttv_tower_dims* d, const ttv_tower_weights* 
   hipStream_t s = (hipStream_t)stream;
   Tape t = carve_tape(d, b, (char*)tape);
   TTV_CHECK_ARG(t.total <= tape_bytes, "encoder_forward_train: tape too small");
-  const int dm = d->width, dt = d->dtype, P = b->sum_patches;
-  const int pd = d->pix_channels * d->patch_t * d->patch_h * d->patch_w;
-  for (int c0 = 0; c0 < b->n_clips; c0 += TTV_MAX_CLIPS_PER_LAUNCH) {
-    const int n = b->n_clips - c0 < TTV_MAX_CLIPS_PER_LAUNCH ? b->n_clips - c0 : TTV_MAX_CLIPS_PER_LAUNCH;
-    TTV_TRY(ttvk_patch_copy(false, (void* const*)(clips + c0), b->clip_desc, c0, n, d->patch_t, d->patch_h, d->patch_w, d->pix_channels, t.patches, pd, dt, b->max_patches_per_clip, s));
-  }
-  GemmArgs a = {};
-  a.dtype = dt; a.x = t.patches; a.ldx = pd; a.w = w->proj_in_w; a.ldw = pd; a.M = P; a.N = dm; a.K = pd; a.y = t.pe; a.ldy = dm;
+  const int dm = d->width, dt = d->dtype, P = b->sum_patches, pd = patch_dim(d);
+  TTV_TRY(patch_copy_all(false, (void* const*)clips, d, b, t.patches, dt, s));
+  GemmArgs a = gemm_args(dt, t.patches, pd, w->proj_in_w, pd, P, dm, pd, t.pe, dm);
   a.bias = w->proj_in_b; a.add_scalar = w->mask_token;
   TTV_TRY(ttvk_gemm(EPI_STORE, a, s));
   TTV_TRY(ttvk_rmsnorm(t.pe, dt, dm, nullptr, t.X[0], dt, dm, b->patch_rows, w->ln_pre_p, P, dm, d->eps, s));
@@ -624,8 +595,7 @@ int ttv_encoder_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, co
   Tape t = carve_tape(d, b, (char*)tape);
   BwdWs ws = carve_bwd(d, b, (char*)workspace);
   TTV_CHECK_ARG(ws.total <= workspace_bytes, "encoder_backward: workspace too small");
-  const int L = b->total_rows, dm = d->width, dt = d->dtype, P = b->sum_patches, K = b->sum_tokens, C = d->token_size;
-  const int pd = d->pix_channels * d->patch_t * d->patch_h * d->patch_w;
+  const int L = b->total_rows, dm = d->width, dt = d->dtype, P = b->sum_patches, K = b->sum_tokens, C = d->token_size, pd = patch_dim(d);
   // ---- tail: z = proj_out(n) + b, n = ln_post(X_last[latent rows]) ----
   TTV_TRY(ttvk_rmsnorm(t.X[d->layers], dt, dm, b->latent_rows, ws.g_d, dt, dm, nullptr, w->ln_post, K, dm, d->eps, s));   // n
   TTV_TRY(ttvk_outer_small(dz, TTV_F32, C, C, ws.g_d, dt, dm, nullptr, gr->proj_out_w, dm, 0, K, dm, s));
@@ -645,13 +615,8 @@ int ttv_encoder_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, co
   TTV_TRY(ttvk_colsum(ws.g_d, dt, dm, nullptr, P, dm, gr->proj_in_b, s));
   TTV_TRY(ttvk_wgrad(ws.g_d, dm, t.patches, pd, gr->proj_in_w, pd, P, dm, pd, dt, ws.wg_part, ws.wg_part_bytes, s));
   if (dclips) {
-    GemmArgs a = {};
-    a.dtype = dt; a.x = ws.g_d; a.ldx = dm; a.w = wt->proj_in_t; a.ldw = dm; a.M = P; a.N = pd; a.K = dm; a.y = ws.g_pd; a.ldy = pd;
-    TTV_TRY(ttvk_gemm(EPI_STORE, a, s));
-    for (int c0 = 0; c0 < b->n_clips; c0 += TTV_MAX_CLIPS_PER_LAUNCH) {
-      const int n = b->n_clips - c0 < TTV_MAX_CLIPS_PER_LAUNCH ? b->n_clips - c0 : TTV_MAX_CLIPS_PER_LAUNCH;
-      TTV_TRY(ttvk_patch_copy(true, dclips + c0, b->clip_desc, c0, n, d->patch_t, d->patch_h, d->patch_w, d->pix_channels, ws.g_pd, pd, dt, b->max_patches_per_clip, s));
-    }
+    TTV_TRY(ttvk_gemm(EPI_STORE, gemm_args(dt, ws.g_d, dm, wt->proj_in_t, dm, P, pd, dm, ws.g_pd, pd), s));
+    TTV_TRY(patch_copy_all(true, dclips, d, b, ws.g_pd, dt, s));
   }
   return TTV_OK;
 }
@@ -663,22 +628,16 @@ int ttv_decoder_forward_train(const ttv_tower_dims* d, const ttv_tower_weights* 
   hipStream_t s = (hipStream_t)stream;
   Tape t = carve_tape(d, b, (char*)tape);
   TTV_CHECK_ARG(t.total <= tape_bytes, "decoder_forward_train: tape too small");
-  const int dm = d->width, dt = d->dtype, P = b->sum_patches;
-  const int pd = d->pix_channels * d->patch_t * d->patch_h * d->patch_w;
-  TTV_CHECK_ARG((int64_t)P * pd * esz(dt) <= workspace_bytes, "decoder_forward_train: workspace too small");
+  const int dm = d->width, dt = d->dtype, P = b->sum_patches, pd = patch_dim(d);
+  TTV_CHECK_ARG((int64_t)P * pd * dtype_bytes(dt) <= workspace_bytes, "decoder_forward_train: workspace too small");
   TTV_TRY(ttvk_dec_embed_ex(codes, d->token_size, w->proj_in_w, w->proj_in_b, w->mask_token, w->ln_pre_t, t.X[0], dt, dm, b->latent_rows, b->sum_tokens, dm, d->eps, t.hpre, s));
   TTV_TRY(ttvk_fill_const_rows(t.X[0], dt, dm, b->patch_rows, P, dm, w->mask_token, w->ln_pre_p, d->eps, s));
   TTV_TRY(layers_forward_train(d, w, b, t, s));
   TTV_TRY(ttvk_rmsnorm(t.X[d->layers], dt, dm, b->patch_rows, t.pn, dt, dm, nullptr, w->ln_post, P, dm, d->eps, s));
-  GemmArgs a = {};
-  a.dtype = dt; a.x = t.pn; a.ldx = dm; a.w = w->proj_out_w; a.ldw = dm; a.M = P; a.N = pd; a.K = dm; a.y = workspace; a.ldy = pd;
+  GemmArgs a = gemm_args(dt, t.pn, dm, w->proj_out_w, dm, P, pd, dm, workspace, pd);
   a.bias = w->proj_out_b;
   TTV_TRY(ttvk_gemm(EPI_STORE, a, s));
-  for (int c0 = 0; c0 < b->n_clips; c0 += TTV_MAX_CLIPS_PER_LAUNCH) {
-    const int n = b->n_clips - c0 < TTV_MAX_CLIPS_PER_LAUNCH ? b->n_clips - c0 : TTV_MAX_CLIPS_PER_LAUNCH;
-    TTV_TRY(ttvk_patch_copy(true, clips_out + c0, b->clip_desc, c0, n, d->patch_t, d->patch_h, d->patch_w, d->pix_channels, workspace, pd, dt, b->max_patches_per_clip, s));
-  }
-  return TTV_OK;
+  return patch_copy_all(true, clips_out, d, b, workspace, dt, s);
 }
 
 int ttv_decoder_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_tower_weights_t* wt, const ttv_batch* b, const void* codes,
@@ -690,18 +649,12 @@ int ttv_decoder_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, co
   Tape t = carve_tape(d, b, (char*)tape);
   BwdWs ws = carve_bwd(d, b, (char*)workspace);
   TTV_CHECK_ARG(ws.total <= workspace_bytes, "decoder_backward: workspace too small");
-  const int L = b->total_rows, dm = d->width, dt = d->dtype, P = b->sum_patches, K = b->sum_tokens, C = d->token_size;
-  const int pd = d->pix_channels * d->patch_t * d->patch_h * d->patch_w;
+  const int L = b->total_rows, dm = d->width, dt = d->dtype, P = b->sum_patches, K = b->sum_tokens, C = d->token_size, pd = patch_dim(d);
   // ---- tail: clips = unpatch(proj_out(pn) + bias), pn = ln_post(X_last[patch rows]) ----
-  for (int c0 = 0; c0 < b->n_clips; c0 += TTV_MAX_CLIPS_PER_LAUNCH) {
-    const int n = b->n_clips - c0 < TTV_MAX_CLIPS_PER_LAUNCH ? b->n_clips - c0 : TTV_MAX_CLIPS_PER_LAUNCH;
-    TTV_TRY(ttvk_patch_copy(false, (void* const*)(dclips_out + c0), b->clip_desc, c0, n, d->patch_t, d->patch_h, d->patch_w, d->pix_channels, ws.g_pd, pd, dt, b->max_patches_per_clip, s));
-  }
+  TTV_TRY(patch_copy_all(false, (void* const*)dclips_out, d, b, ws.g_pd, dt, s));
   TTV_TRY(ttvk_colsum(ws.g_pd, dt, pd, nullptr, P, pd, gr->proj_out_b, s));
   TTV_TRY(ttvk_wgrad(ws.g_pd, pd, t.pn, dm, gr->proj_out_w, dm, P, pd, dm, dt, ws.wg_part, ws.wg_part_bytes, s));
-  GemmArgs a = {};
-  a.dtype = dt; a.x = ws.g_pd; a.ldx = pd; a.w = wt->proj_out_t; a.ldw = pd; a.M = P; a.N = dm; a.K = pd; a.y = ws.g_d2; a.ldy = dm;   // dpn
-  TTV_TRY(ttvk_gemm(EPI_STORE, a, s));
+  TTV_TRY(ttvk_gemm(EPI_STORE, gemm_args(dt, ws.g_pd, pd, wt->proj_out_t, pd, P, dm, pd, ws.g_d2, dm), s));   // dpn
   (void)hipMemsetAsync(ws.dxa, 0, (size_t)L * dm * sizeof(float), s);
   TTV_TRY(ttvk_rmsnorm_bwd(t.X[d->layers], dt, dm, b->patch_rows, ws.g_d2, dt, dm, nullptr, w->ln_post, ws.dxa, TTV_F32, dm, b->patch_rows, 0, gr->ln_post, P, dm, d->eps, s));
   TTV_TRY(layers_backward(d, w, wt, b, t, gr, ws, s));

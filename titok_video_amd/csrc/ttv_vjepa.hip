@@ -23,12 +23,6 @@
 #include "ttv_common.h"
 #include "ttv_kernels.h"
 
-#define TTV_TRY(expr)                \
-  do {                               \
-    const int rc__ = (expr);         \
-    if (rc__ != TTV_OK) return rc__; \
-  } while (0)
-
 namespace {
 
 constexpr int VJ_S = 224, VJ_P = 16, VJ_G = VJ_S / VJ_P, VJ_FRAMES = 16, VJ_TOK = (VJ_FRAMES / 2) * VJ_G * VJ_G;   // 1568 tokens
@@ -253,7 +247,7 @@ struct Ws {
 Ws carve(char* base, int n) {
   Ws w;
   int64_t off = 0;
-  auto take = [&](int64_t b) { char* p = base ? base + off : nullptr; off += (b + 255) & ~(int64_t)255; return p; };
+  auto take = [&](int64_t b) { char* p = base ? base + off : nullptr; off += align256(b); return p; };
   const int64_t M = (int64_t)n * VJ_TOK;
   w.tab = (int*)take((int64_t)n * VJ_H * VJ_QB * 4 * 4);
   w.cu = (int*)take((int64_t)(n + 1) * 4);

@@ -251,14 +251,13 @@ struct Ws {
   int *seg_row, *seg_key, *order;
   float* cs_new;
 };
-int64_t al256(int64_t v) { return (v + 255) / 256 * 256; }
 Ws carve(void* ws, int rows, int N) {
   char* p = (char*)ws;
   Ws w;
-  w.partial = (float*)p; p += al256((int64_t)ttv_cdiv(rows, VQC_ROWS) * 4);
-  w.seg_row = (int*)p;   p += al256((int64_t)rows * 4);
-  w.seg_key = (int*)p;   p += al256((int64_t)rows * 4);
-  w.order = (int*)p;     p += al256((int64_t)rows * 4);
+  w.partial = (float*)p; p += align256((int64_t)ttv_cdiv(rows, VQC_ROWS) * 4);
+  w.seg_row = (int*)p;   p += align256((int64_t)rows * 4);
+  w.seg_key = (int*)p;   p += align256((int64_t)rows * 4);
+  w.order = (int*)p;     p += align256((int64_t)rows * 4);
   w.cs_new = (float*)p;
   return w;
 }
@@ -266,7 +265,7 @@ Ws carve(void* ws, int rows, int N) {
 }  // namespace
 
 int64_t ttvk_vq_train_workspace_bytes(int rows, int N) {
-  return al256((int64_t)ttv_cdiv(rows, VQC_ROWS) * 4) + 3 * al256((int64_t)rows * 4) + al256(((int64_t)N + 1) * 4);
+  return align256((int64_t)ttv_cdiv(rows, VQC_ROWS) * 4) + 3 * align256((int64_t)rows * 4) + align256(((int64_t)N + 1) * 4);
 }
 
 #define VQT_COMMON(what)                                                                                                      \
