@@ -500,6 +500,21 @@ int ttv_opt_adamw_step(const void* table, const int32_t* chunks, int n_chunks, i
 int ttv_opt_param_norms(const void* table, const int32_t* chunks, int n_chunks, int n_entries, const float* partials, float* norms,
                         void* stream);
 
+/* Exponential moving average of a parameter list in fp32 shadow tensors (titok_video_amd/ema.py; not in the reference, which validates
+ * its raw weights), on the table layout of the optimizer step: entries of 40 bytes, `chunks` = device int32 [n_chunks][2] = (entry index,
+ * first element), one block per chunk of up to 8192 elements.  dtype (TTV_F32 or TTV_BF16) is the PARAMETERS' type; a shadow is float
+ * whatever the dtype.  16-byte accesses when every pointer of an entry that the call touches is 16-byte aligned, element by element
+ * otherwise.  n_chunks == 0: TTV_OK and no launch.
+ * ttv_opt_ema_update  : entries {const void* param; unused (0); float* shadow; unused (0); int64 numel}.  Per element, in fp32 and in
+ *          this order: d = (float)param - shadow ; shadow = shadow + weight * d.  weight = 1 - decay, formed in double by the caller and
+ *          rounded to float once (1.0f - (float)0.9999 is 1.7e-8 off 1e-4: 1.7e-4 of the weight).  weight == 0: no launch, every shadow bit stays.  Reads the
+ *          parameters, writes elements [0, numel) of the shadows and nothing else.
+ * ttv_opt_ema_exchange: entries {void* param; unused (0); const float* shadow; void* backup (the parameter's type and size); int64 numel}.
+ *          mode 0 (apply): backup = param (its bits), then param = shadow cast to dtype (bf16: round to nearest even, NaN stays NaN);
+ *          mode 1 (restore): param = backup (its bits).  The shadows are only read. */
+int ttv_opt_ema_update(const void* table, const int32_t* chunks, int n_chunks, int dtype, float weight, void* stream);
+int ttv_opt_ema_exchange(const void* table, const int32_t* chunks, int n_chunks, int dtype, int mode, void* stream);
+
 /* Single backward ops, exported for parity tests. */
 /* dW[N,K] (fp32, accumulated) += dY[L,N]^T X[L,K]  (weight gradient of y = x w^T; what autograd computes for the
  * nn.Linear weights of base/blocks.py:70-84,147-148).  The token range is split over blocks; with a workspace of

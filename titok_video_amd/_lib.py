@@ -212,6 +212,8 @@ SYMBOLS = {
     "ttv_opt_grad_sumsq": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
     "ttv_opt_adamw_step": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int] + [C.c_float] * 10 + [vp, vp]),
     "ttv_opt_param_norms": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp]),
+    "ttv_opt_ema_update": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_float, vp]),
+    "ttv_opt_ema_exchange": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "ttv_linear_wgrad_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "ttv_linear_wgrad": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp]),
     "ttv_rmsnorm_backward": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, f32, C.c_int, vp]),

@@ -54,14 +54,33 @@ def load_trainer_state_dict(state_dict: Dict[str, torch.Tensor], model: torch.nn
     return res
 
 
-def save_checkpoint(path: str, model: torch.nn.Module, loss_module: Optional[torch.nn.Module] = None, global_step: int = 0) -> None:
-    """Write the subset of a Lightning checkpoint the reference reads back (train.py:265-267: ['state_dict'], 'global_step')."""
+WEIGHT_EMA_KEY = "weight_ema"          # not a reference key: the reference ignores top-level entries it does not read
+
+
+def save_checkpoint(path: str, model: torch.nn.Module, loss_module: Optional[torch.nn.Module] = None, global_step: int = 0,
+                    ema=None) -> None:
+    """Write the subset of a Lightning checkpoint the reference reads back (train.py:265-267: ['state_dict'], 'global_step').
+    `ema` (ema.WeightEMA / ema.ShadowState): its state_dict() goes under the top-level key 'weight_ema' as CPU tensors; 'state_dict'
+    and 'global_step' are what they are without it."""
     sd = OrderedDict((k, v.detach().cpu()) for k, v in trainer_state_dict(model, loss_module).items())
-    torch.save({"state_dict": sd, "global_step": int(global_step)}, path)
+    ck = {"state_dict": sd, "global_step": int(global_step)}
+    if ema is not None:
+        state = dict(ema.state_dict())
+        state["shadow"] = OrderedDict((k, v.detach().cpu()) for k, v in state["shadow"].items())
+        ck[WEIGHT_EMA_KEY] = state
+    torch.save(ck, path)
 
 
-def load_checkpoint(path: str, model: torch.nn.Module, loss_module: Optional[torch.nn.Module] = None, strict: bool = False) -> int:
-    """`init_from_checkpoint` (train.py:265-267; the reference loads with strict=False).  Returns the stored global step."""
+def load_checkpoint(path: str, model: torch.nn.Module, loss_module: Optional[torch.nn.Module] = None, strict: bool = False,
+                    ema=None) -> int:
+    """`init_from_checkpoint` (train.py:265-267; the reference loads with strict=False).  Returns the stored global step.
+    `ema`: loads the file's 'weight_ema' entry (strict on names and shapes); a file without one - the reference's, or one saved without
+    an average - restarts the average from the loaded weights (`ema.reset()`)."""
     ck = torch.load(path, map_location="cpu", weights_only=False)
     load_trainer_state_dict(ck["state_dict"], model, loss_module, strict=strict)
+    if ema is not None:
+        if WEIGHT_EMA_KEY in ck:
+            ema.load_state_dict(ck[WEIGHT_EMA_KEY])
+        else:
+            ema.reset()
     return int(ck.get("global_step", 0))

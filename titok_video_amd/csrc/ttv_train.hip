@@ -544,6 +544,71 @@ __global__ __launch_bounds__(256) void k_opt_adamw(const OptEntry* __restrict__ 
   }
 }
 
+// ------------------------------------------------------------------------------------------------ weight EMA
+// fp32 shadow weights of a parameter list (titok_video_amd/ema.py::WeightEMA; not a reference module: the reference validates its raw
+// weights).  The OptEntry table and chunk list of the optimizer step, one block per chunk, the same vector / element-wise split:
+//   k_opt_ema_update  : p = parameter (T, read only), m = shadow (ALWAYS float, whatever T: a bf16 shadow at decay 0.9999 never moves,
+//                       the increment is below half an ulp), g and v unused.  d = (float)p - s ; s = s + weight d, in that order in fp32
+//                       (the compiler may contract the last two roundings into one fma).  12 bytes per element for fp32 parameters
+//                       (4 read + 4 read + 4 written), 10 for bf16.
+//   k_opt_ema_exchange: p (written), m = shadow (const float), v = backup (T, the size of p).  mode 0: backup = p ; p = (T)shadow - for
+//                       bf16 the round-to-nearest-even cast of OptVec<bf16_t>::store.  mode 1: p = backup.  The shadow is only read.
+// weight = 1 - decay is formed in double by the caller and rounded once, as om_beta1 / om_beta2 below are.
+template <typename T>
+__global__ __launch_bounds__(256) void k_opt_ema_update(const OptEntry* __restrict__ tab, const int2* __restrict__ chunks, float weight) {
+  const int2 c = chunks[blockIdx.x];
+  const OptEntry e = tab[c.x];
+  const T* p = (const T*)e.p; float* s = (float*)e.m;
+  const long long end = e.n < (long long)c.y + OPT_CHUNK ? e.n : (long long)c.y + OPT_CHUNK;
+  if ((((uintptr_t)p | (uintptr_t)s) & 15) == 0) {
+    long long i = (long long)c.y + threadIdx.x * 8;
+    for (; i + 8 <= end; i += 256 * 8) {
+      float pv[8], sv[8];
+      OptVec<T>::load(p + i, pv); OptVec<float>::load(s + i, sv);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) { const float d = pv[k] - sv[k]; sv[k] = sv[k] + weight * d; }
+      OptVec<float>::store(s + i, sv);
+    }
+    if (i < end)
+      for (long long j = i; j < end; ++j) { const float sv = s[j], d = (float)p[j] - sv; s[j] = sv + weight * d; }
+  } else {
+    for (long long j = (long long)c.y + threadIdx.x; j < end; j += 256) { const float sv = s[j], d = (float)p[j] - sv; s[j] = sv + weight * d; }
+  }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_opt_ema_exchange(const OptEntry* __restrict__ tab, const int2* __restrict__ chunks, int mode) {
+  const int2 c = chunks[blockIdx.x];
+  const OptEntry e = tab[c.x];
+  T* p = (T*)e.p; const float* s = (const float*)e.m; T* b = (T*)e.v;
+  const long long end = e.n < (long long)c.y + OPT_CHUNK ? e.n : (long long)c.y + OPT_CHUNK;
+  if ((((uintptr_t)p | (uintptr_t)s | (uintptr_t)b) & 15) == 0) {
+    long long i = (long long)c.y + threadIdx.x * 8;
+    for (; i + 8 <= end; i += 256 * 8) {
+      if (mode == 0) {
+        // the parameter's bits go to the backup as they are (OptVec<bf16_t> would widen and round: a signalling NaN would come back quiet)
+        *reinterpret_cast<uint4*>(b + i) = *reinterpret_cast<const uint4*>(p + i);
+        if (sizeof(T) == 4) *reinterpret_cast<uint4*>(b + i + 4) = *reinterpret_cast<const uint4*>(p + i + 4);
+        float sv[8];
+        OptVec<float>::load(s + i, sv);
+        OptVec<T>::store(p + i, sv);
+      } else {
+        *reinterpret_cast<uint4*>(p + i) = *reinterpret_cast<const uint4*>(b + i);
+        if (sizeof(T) == 4) *reinterpret_cast<uint4*>(p + i + 4) = *reinterpret_cast<const uint4*>(b + i + 4);
+      }
+    }
+    if (i < end)
+      for (long long j = i; j < end; ++j) {
+        if (mode == 0) { b[j] = p[j]; p[j] = (T)s[j]; }
+        else p[j] = b[j];
+      }
+  } else {
+    for (long long j = (long long)c.y + threadIdx.x; j < end; j += 256) {
+      if (mode == 0) { b[j] = p[j]; p[j] = (T)s[j]; }
+      else p[j] = b[j];
+    }
+  }
+}
+
 extern "C" {
 
 int64_t ttv_tower_tape_bytes(const ttv_tower_dims* dims, const ttv_batch* batch) {
@@ -743,6 +808,31 @@ int ttv_opt_adamw_step(const void* table, const int32_t* chunks, int n_chunks, i
   if (dtype == TTV_BF16) hipLaunchKernelGGL((k_opt_adamw<bf16_t>), dim3(n_chunks), dim3(256), 0, s, (const OptEntry*)table, (const int2*)chunks, partials, n_partials, h, out_norm);
   else hipLaunchKernelGGL((k_opt_adamw<float>), dim3(n_chunks), dim3(256), 0, s, (const OptEntry*)table, (const int2*)chunks, partials, n_partials, h, out_norm);
   TTV_CHECK_LAUNCH("opt_adamw_step");
+  return TTV_OK;
+}
+
+int ttv_opt_ema_update(const void* table, const int32_t* chunks, int n_chunks, int dtype, float weight, void* stream) {
+  TTV_CHECK_ARG(dtype == TTV_BF16 || dtype == TTV_F32, "opt_ema_update: dtype %d is neither TTV_BF16 nor TTV_F32", dtype);
+  if (n_chunks == 0) return TTV_OK;
+  TTV_CHECK_ARG(n_chunks > 0 && table && chunks, "opt_ema_update: null buffer");
+  // s + 0 * d is s only for finite d and s other than -0: weight 0 keeps every shadow bit by not launching
+  if (weight == 0.0f) return TTV_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == TTV_BF16) hipLaunchKernelGGL((k_opt_ema_update<bf16_t>), dim3(n_chunks), dim3(256), 0, s, (const OptEntry*)table, (const int2*)chunks, weight);
+  else hipLaunchKernelGGL((k_opt_ema_update<float>), dim3(n_chunks), dim3(256), 0, s, (const OptEntry*)table, (const int2*)chunks, weight);
+  TTV_CHECK_LAUNCH("opt_ema_update");
+  return TTV_OK;
+}
+
+int ttv_opt_ema_exchange(const void* table, const int32_t* chunks, int n_chunks, int dtype, int mode, void* stream) {
+  TTV_CHECK_ARG(dtype == TTV_BF16 || dtype == TTV_F32, "opt_ema_exchange: dtype %d is neither TTV_BF16 nor TTV_F32", dtype);
+  TTV_CHECK_ARG(mode == 0 || mode == 1, "opt_ema_exchange: mode %d is neither 0 (apply) nor 1 (restore)", mode);
+  if (n_chunks == 0) return TTV_OK;
+  TTV_CHECK_ARG(n_chunks > 0 && table && chunks, "opt_ema_exchange: null buffer");
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == TTV_BF16) hipLaunchKernelGGL((k_opt_ema_exchange<bf16_t>), dim3(n_chunks), dim3(256), 0, s, (const OptEntry*)table, (const int2*)chunks, mode);
+  else hipLaunchKernelGGL((k_opt_ema_exchange<float>), dim3(n_chunks), dim3(256), 0, s, (const OptEntry*)table, (const int2*)chunks, mode);
+  TTV_CHECK_LAUNCH("opt_ema_exchange");
   return TTV_OK;
 }
 

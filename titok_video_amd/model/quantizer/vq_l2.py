@@ -84,6 +84,11 @@ class L2Quantizer(nn.Module):
             self._norms, self._norms_key = (cbd, norms), key
         return self._norms
 
+    def invalidate_lookup_cache(self) -> None:
+        """Forget the compute-dtype copy of the codebook and its norms.  The key sees what bumps the codebook's version counter and this
+        module's own EMA updates; code that writes the codebook any other way (a kernel, `.data`) calls this afterwards."""
+        self._norms, self._norms_key = None, None
+
     @torch.no_grad()
     def indices(self, z: torch.Tensor, want_distance: bool = False):
         _lib.require_gpu(z, "L2Quantizer")

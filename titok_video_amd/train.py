@@ -9,7 +9,8 @@ mirror; LPIPS is outside this path's scope (network-fetched weights, SURVEY.md s
 
 Logging and validation (reference train.py:78-79, :102-103, :118-160): `grad_norm_dict` is the gradient-norm log from the sums the
 optimizer's clip already takes, `recon_panels` the logged side-by-side videos as uint8 from one HIP launch and one device-to-host
-copy, `ValidationLoop` the three validation hooks without a logger.
+copy, `ValidationLoop` the three validation hooks without a logger.  `make_weight_ema` builds the optional fp32 average of the generator's
+weights (ema.py) that `ValidationLoop(..., ema=)` validates on.
 """
 from __future__ import annotations
 
@@ -115,6 +116,24 @@ def make_optimizer(model: torch.nn.Module, lr: float = 1e-4, beta1: float = 0.5,
         return HipAdamW(params, lr=lr, betas=(beta1, beta2), weight_decay=weight_decay)
     fused = bool(params) and all(p.is_cuda for p in params)      # one multi-tensor kernel instead of a launch per parameter
     return torch.optim.AdamW(params, lr=lr, betas=(beta1, beta2), weight_decay=weight_decay, fused=fused, capturable=capturable and fused)
+
+
+def make_weight_ema(model: torch.nn.Module, config):
+    """The weight average of `model` that `config.training.main` asks for, or None: `ema_decay` (absent or <= 0: no average) and
+    `ema_warmup` (default True: decay_t = min(ema_decay, (1 + t) / (10 + t))).  Not reference keys: the reference keeps no average.
+    Call `ema.update()` after every optimizer step and hand the instance to `ValidationLoop` and `save_checkpoint`."""
+    from .ema import WeightEMA
+
+    def key(node, name):          # attribute-style (OmegaConf, SimpleNamespace) and mapping-style nodes alike; absent or null -> None
+        if node is None:
+            return None
+        return node.get(name) if isinstance(node, dict) else getattr(node, name, None)
+    main = key(key(config, "training"), "main")
+    decay = key(main, "ema_decay")
+    if decay is None or not float(decay) > 0.0:
+        return None
+    warmup = key(main, "ema_warmup")
+    return WeightEMA(model, decay=float(decay), warmup=True if warmup is None else bool(warmup))
 
 
 def _param_list(module) -> list:
@@ -407,10 +426,14 @@ class ValidationLoop:
     `log_recon_num`; `seen_eval` and `seen_recon` go to zero.  `step()` runs the model and `eval_metrics.update(recon, orig)` under
     no_grad, then builds the panels of the selected clips of the batch with one `recon_panels` call; `seen_eval` counts every clip,
     selected or not, `seen_recon` numbers the logged ones from 1.  `end()` returns `eval_metrics.compute()` (then `reset()`),
-    merged with the codebook scores when a logger is given and ready."""
+    merged with the codebook scores when a logger is given and ready.
 
-    def __init__(self, model, eval_metrics, log_recon_num: int, eval_samples: int, random_recon: bool, codebook_logger=None):
+    `ema` (an `ema.WeightEMA` of `model`, default None): `start()` enters `ema.applied()` and `end()` leaves it, so every `step()` and
+    every metric see the averaged weights and training resumes on the raw ones, bit for bit."""
+
+    def __init__(self, model, eval_metrics, log_recon_num: int, eval_samples: int, random_recon: bool, codebook_logger=None, ema=None):
         self.model, self.eval_metrics, self.codebook_logger = model, eval_metrics, codebook_logger
+        self.ema, self._ema_block = ema, None
         self.log_recon_num, self.eval_samples, self.random_recon = int(log_recon_num), int(eval_samples), bool(random_recon)
         self.recon_indexes: List[int] = []
         self.seen_eval = 0
@@ -423,6 +446,9 @@ class ValidationLoop:
             self.recon_indexes = list(range(self.log_recon_num))
         self.seen_eval = 0
         self.seen_recon = 0
+        if self.ema is not None:
+            self._ema_block = self.ema.applied()
+            self._ema_block.__enter__()
 
     def step(self, batch) -> List[dict]:
         orig, fps, token_counts = batch["video"], batch["fps"], batch["token_counts"]
@@ -446,7 +472,12 @@ class ValidationLoop:
         return logged
 
     def end(self) -> dict:
-        metrics = dict(self.eval_metrics.compute())
+        try:
+            metrics = dict(self.eval_metrics.compute())
+        finally:
+            if self._ema_block is not None:
+                block, self._ema_block = self._ema_block, None
+                block.__exit__(None, None, None)
         self.eval_metrics.reset()
         if self.codebook_logger is not None and self.codebook_logger.is_score_ready():
             metrics.update(self.codebook_logger.get_scores() or {})

@@ -2,7 +2,8 @@
 """Training-step timing at the benchmark shape (32 x 16x128x128 clips, K=128, bf16): forward (tape) + L1 + backward + AdamW.
 B= batch (5 = the reference's 6144-token budget), GRAPH=1: the whole step captured once in a HIP graph (torch.cuda.CUDAGraph) and
 replayed - the step is a fixed launch sequence for a fixed batch shape, and at small batches the host cannot issue ~280 launches
-as fast as the GPU runs them."""
+as fast as the GPU runs them.  EMA=1: an ema.WeightEMA of the model (decay 0.9999) updated after every step (not with GRAPH=1: the update
+takes its weight from the host)."""
 import json, os, sys, time
 from types import SimpleNamespace
 import torch
@@ -24,6 +25,10 @@ if os.environ.get("GC_FREEZE", "1") == "1":
     freeze_python_gc()
     limit_host_threads()
 n = int(os.environ.get("STEPS", "10"))
+EMA = os.environ.get("EMA", "0") == "1" and not GRAPH
+if EMA:
+    from titok_video_amd.ema import WeightEMA
+    ema = WeightEMA(m, decay=0.9999)
 if GRAPH:
     from titok_video_amd.train import GraphedTrainingStep
     step = GraphedTrainingStep(m, opt, clips, counts)
@@ -37,10 +42,14 @@ if GRAPH:
 else:
     for _ in range(3):
         training_step(m, clips, counts, opt)
+        if EMA:
+            ema.update()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(n):
         loss, gn, _ = training_step(m, clips, counts, opt)
+        if EMA:
+            ema.update()
     torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / n
-print(json.dumps({"train_ms_per_step": 1e3 * dt, "clips_per_s": B / dt, "batch": B, "loss": float(loss), "graph": GRAPH}))
+print(json.dumps({"train_ms_per_step": 1e3 * dt, "clips_per_s": B / dt, "batch": B, "loss": float(loss), "graph": GRAPH, "ema": EMA}))

@@ -10,6 +10,13 @@
                     re-read) and from the sums of a clip_and_step(want_param_norms=True) that has just run - against a loop of
                     p.grad.norm(2) per parameter with one .cpu() of the stacked norms (Lightning's grad_norm).
   norms launch      ttv_opt_param_norms alone on a chunk table of the base configs' size (20 480 chunks).
+  ema update        ttv_opt_ema_update (ema.WeightEMA.update: fp32 shadows += w (parameter - shadow), one launch) alone, by HIP events, on
+                    the tiny tokenizer's parameter list (rotating over working sets larger than the Infinity Cache, as a training step
+                    between two updates leaves it) and on the base-size table, fp32 and bf16 parameters: us and the GB/s they imply
+                    at 12 / 10 bytes per element - against the eager form on fp32 tensors in the same run,
+                    torch._foreach_mul_(shadows, decay) + torch._foreach_add_(shadows, params, alpha=1 - decay).
+  ema exchange      ttv_opt_ema_exchange on the same tables: apply (backup = p, p = cast shadow: 16 / 10 bytes per element) and
+                    restore (p = backup: 8 / 4 bytes per element).
 
 Reported, not gated.  GPU box only; writes what it prints to the file given as the first argument, if any."""
 import ctypes as C
@@ -52,17 +59,17 @@ def wall(fn):
     return (time.perf_counter() - t0) * 1e6 / ITERS
 
 
-def events(fn):
+def events(fn, iters=ITERS):
     for _ in range(WARMUP):
         fn()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    for _ in range(ITERS):
+    for _ in range(iters):
         fn()
     e1.record()
     torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / ITERS
+    return e0.elapsed_time(e1) * 1e3 / iters
 
 
 def eager_panels(target, recon):
@@ -162,11 +169,84 @@ def bench_norms_launch_at_base_size():
         f"{us:7.1f} us per launch (bucket norm {float(norms[-1]):.6g}, float64 {want:.6g})")
 
 
+def ema_tables(sizes, dtype, sets):
+    """`sets` independent working sets over tensors of `sizes` elements: parameters of `dtype`, fp32 shadows, backups of `dtype`, each
+    family carved from one flat buffer (every tensor starts on a 16-byte boundary), with the device entry table and chunk list."""
+    offs, total = [], 0
+    for n in sizes:
+        offs.append(total)
+        total += (n + 7) // 8 * 8
+    chunk_words = [i | (first << 32) for i, n in enumerate(sizes) for first in range(0, n, 8192)]
+    chunks = torch.tensor(chunk_words, dtype=torch.int64).to(DEV)
+    out = []
+    for _ in range(sets):
+        p = (torch.randn(total, device=DEV) * 0.5).to(dtype)
+        sh = p.float() + 0.01
+        bk = torch.empty_like(p)
+        words = []
+        for n, o in zip(sizes, offs):
+            words += [p.data_ptr() + o * p.element_size(), 0, sh.data_ptr() + 4 * o, bk.data_ptr() + o * p.element_size(), n]
+        out.append({"p": p, "shadow": sh, "backup": bk, "table": torch.tensor(words, dtype=torch.int64).to(DEV),
+                    "views": [(p[o:o + n], sh[o:o + n]) for n, o in zip(sizes, offs)]})
+    return out, chunks, len(chunk_words)
+
+
+def bench_ema():
+    """ttv_opt_ema_update / ttv_opt_ema_exchange alone and the eager foreach form, at the tiny tokenizer's table and at base size."""
+    cfg = SimpleNamespace(tokenizer=SimpleNamespace(model=SimpleNamespace(patch_size=[4, 8, 8], fsq_levels=[7, 5, 5, 5, 5], encoder_size="tiny",
+                                                                          decoder_size="tiny")))
+    tiny = [p.numel() for p in TiTok(cfg).parameters()]
+    n_entries, big = 300, BIG_CHUNKS // 10
+    per = (BIG_CHUNKS - big) // (n_entries - 1)
+    base = [big * 8192] + [per * 8192] * (n_entries - 2) + [(BIG_CHUNKS - big - per * (n_entries - 2)) * 8192]
+    lib, stream, decay = _lib.lib(), _lib.stream_ptr(torch.device(DEV)), 0.9999
+    for name, sizes in (("tiny tokenizer", tiny), ("base size", base)):
+        elements = sum(sizes)
+        for dtype in (torch.float32, torch.bfloat16):
+            item = 4 if dtype == torch.float32 else 2
+            # the working sets together exceed twice the 256 MiB Infinity Cache: every launch reads and writes HBM
+            sets = max(1, -(-(2 * 256 * 2 ** 20) // (elements * (8 + item))))
+            tabs, chunks, n_chunks = ema_tables(sizes, dtype, sets)
+            code, turn = _lib.dtype_code(dtype), [0]
+            iters = 10 * ITERS if sets > 1 else ITERS          # launches of tens of microseconds: a longer window
+
+            def pick():
+                turn[0] += 1
+                return tabs[turn[0] % sets]
+
+            def update():
+                t = pick()
+                _lib.check(lib.ttv_opt_ema_update(t["table"].data_ptr(), chunks.data_ptr(), n_chunks, code, 1.0 - decay, stream), "ttv_opt_ema_update")
+
+            def exchange(mode):
+                t = pick()
+                _lib.check(lib.ttv_opt_ema_exchange(t["table"].data_ptr(), chunks.data_ptr(), n_chunks, code, mode, stream), "ttv_opt_ema_exchange")
+            tag = f"{name}, {'fp32' if item == 4 else 'bf16'} parameters: {len(sizes)} tensors, {elements / 1e6:.2f} M elements, {n_chunks} chunks, {sets} working set(s), {iters} launches timed"
+            us = events(update, iters)
+            say(f"ema update    {tag}: {us:8.1f} us per launch = {elements * (8 + item) / us / 1e3:7.1f} GB/s at {8 + item} bytes per element")
+            us0 = events(lambda: exchange(0), iters)
+            us1 = events(lambda: exchange(1), iters)
+            say(f"ema exchange  {tag}: apply {us0:8.1f} us = {elements * (4 + 3 * item) / us0 / 1e3:7.1f} GB/s at {4 + 3 * item} bytes per element; "
+                f"restore {us1:8.1f} us = {elements * 2 * item / us1 / 1e3:7.1f} GB/s at {2 * item}")
+            if dtype == torch.float32:
+                def eager():
+                    t = pick()
+                    shadows, params = [v[1] for v in t["views"]], [v[0] for v in t["views"]]
+                    torch._foreach_mul_(shadows, decay)
+                    torch._foreach_add_(shadows, params, alpha=1.0 - decay)
+                us_e = events(eager, iters)
+                say(f"ema eager     {tag}: _foreach_mul_ + _foreach_add_ {us_e:8.1f} us per update ({us_e / us:.2f}x the launch; it moves "
+                    f"{elements * 20 / 1e6:.0f} MB: {elements * 20 / us_e / 1e3:7.1f} GB/s at 20 bytes per element)")
+            del tabs
+            torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
     say(f"device: {torch.cuda.get_device_name(0)}; wall times over {ITERS} calls after {WARMUP}")
     bench_panels()
     bench_norms()
     bench_norms_launch_at_base_size()
+    bench_ema()
     if len(sys.argv) > 1:
         os.makedirs(os.path.dirname(os.path.abspath(sys.argv[1])), exist_ok=True)
         with open(sys.argv[1], "w") as f:
