@@ -651,6 +651,28 @@ int ttv_lpips_forward(const ttv_lpips_weights* w, const void* recon, const void*
 int ttv_lpips_backward(const ttv_lpips_weights* w, const void* tape, int n, int H, int W, int dtype, const float* glpips,
                        const float* ggram, void* drecon, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Per-frame LPIPS of whole frames for evaluation (EvalMetrics 'lpips'): no tape, no backward, any frame size.
+ * Host arrays: recon_clips[i], target_clips[i] = contiguous clips [3][frames[i]][H][W] in `dtype` (device), all n_clips of ONE frame
+ * size H x W, each in 16 .. 2048 and not necessarily a multiple of anything.  Frame t of a clip is read in place (channel stride
+ * frames[i] * H * W); with clamp_recon != 0 the reconstruction is clamped to [-1, 1] in `dtype` before the scaling layer, the target
+ * never.  Every frame pair is a batch entry of its own of the network above; the max-pools floor (torch MaxPool2d(2, 2): an odd stage
+ * loses its last row or column), so stage s is (H >> s) x (W >> s) and tap k is averaged over its true (H >> k) * (W >> k) pixels.
+ * TTV_F32 runs the exact-fp32 kernels, TTV_BF16 the MFMA path with the first convolution's scaled input rounded to bf16, as
+ * ttv_lpips_forward does; for H and W multiples of 16 a call whose frames fit one pass gives ttv_lpips_forward's bits.
+ * Outputs, either may be NULL but not both: per_frame (fp32, device) = one value per frame in clip then frame order
+ * (sum of frames[] values); acc (double[2], device): acc[0] += every value, added one by one in that order by one thread,
+ * acc[1] += the frame count.  No atomics: identical calls give identical bits.
+ * The workspace (caller-owned, 256-byte aligned) holds two activation buffers for the largest stage, the head partials and the
+ * split-K partials of one pass; the frames are worked through in passes of the largest size that workspace_bytes holds (at most
+ * 2048 frames).  ttv_lpips_eval_workspace_bytes gives the size for passes of `frames` frames (1 .. 2048), -1 on a bad argument; less
+ * than its value for one frame is TTV_ERR_INVALID.  Values of a frame may differ in the last bits between pass sizes in bf16 (the
+ * split-K factor of a layer follows the stack's size).  Errors in the arguments return before any launch.
+ * Work is enqueued on `stream` only; no synchronisation, no library state. */
+int64_t ttv_lpips_eval_workspace_bytes(int frames, int H, int W, int dtype);
+int ttv_lpips_eval_accumulate(const ttv_lpips_weights* w, void* const* recon_clips, void* const* target_clips, const int32_t* frames,
+                              int n_clips, int H, int W, int dtype, int clamp_recon, float* per_frame, double* acc, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+
 /* The perceptual crops of the generator step (model/losses/loss_module.py:59-93) and their backward: what lies between the towers
  * and ttv_lpips_forward / ttv_lpips_backward.  Host arrays: recon_clips[i], target_clips[i] = contiguous clips [3][T][H][W] in `dtype`
  * (device), clip_dims = n_clips x (T, H, W), crops = n_crops x (clip, frame, H, W, Hr, Wr, oy, ox): the crop is cut from that frame

@@ -233,6 +233,9 @@ SYMBOLS = {
     "ttv_lpips_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ttv_lpips_forward": (C.c_int, [C.POINTER(LpipsWeights), vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int64, vp]),
     "ttv_lpips_backward": (C.c_int, [C.POINTER(LpipsWeights), vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int64, vp]),
+    "ttv_lpips_eval_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ttv_lpips_eval_accumulate": (C.c_int, [C.POINTER(LpipsWeights), vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp,
+                                            C.c_int64, vp]),
     "ttv_lpips_conv_workspace_bytes": (C.c_int64, [C.c_int] * 6),
     "ttv_lpips_conv3x3": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int64, vp]),
     "ttv_lpips_maxpool": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),

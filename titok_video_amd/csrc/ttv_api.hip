@@ -748,6 +748,15 @@ int ttv_lpips_backward(const ttv_lpips_weights* w, const void* tape, int n, int 
   return ttvk_lpips_backward(w, tape, n, H, W, dtype, glpips, ggram, drecon, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+int64_t ttv_lpips_eval_workspace_bytes(int frames, int H, int W, int dtype) { return ttvk_lpips_eval_workspace_bytes(frames, H, W, dtype); }
+
+int ttv_lpips_eval_accumulate(const ttv_lpips_weights* w, void* const* recon_clips, void* const* target_clips, const int32_t* frames,
+                              int n_clips, int H, int W, int dtype, int clamp_recon, float* per_frame, double* acc, void* workspace,
+                              int64_t workspace_bytes, void* stream) {
+  return ttvk_lpips_eval_accumulate(w, recon_clips, target_clips, frames, n_clips, H, W, dtype, clamp_recon, per_frame, acc, workspace,
+                                    workspace_bytes, (hipStream_t)stream);
+}
+
 int ttv_lpips_crops_forward(void* const* recon_clips, void* const* target_clips, const int32_t* clip_dims, int n_clips, const int32_t* crops,
                             int n_crops, int size, void* recon_crops, void* target_crops, int dtype, void* stream) {
   return ttvk_lpips_crops_forward(recon_clips, target_clips, clip_dims, n_clips, crops, n_crops, size, recon_crops, target_crops, dtype,

@@ -231,6 +231,9 @@ int ttvk_lpips_forward(const ttv_lpips_weights* w, const void* recon, const void
                        float* gram, void* tape, void* ws, int64_t ws_bytes, hipStream_t s);
 int ttvk_lpips_backward(const ttv_lpips_weights* w, const void* tape, int n, int H, int W, int dtype, const float* glpips, const float* ggram,
                         void* drecon, void* ws, int64_t ws_bytes, hipStream_t s);
+int64_t ttvk_lpips_eval_workspace_bytes(int frames, int H, int W, int dtype);
+int ttvk_lpips_eval_accumulate(const ttv_lpips_weights* w, void* const* recon, void* const* target, const int32_t* frames, int n_clips, int H,
+                               int W, int dtype, int clamp_recon, float* per_frame, double* acc, void* ws, int64_t ws_bytes, hipStream_t s);
 int64_t ttvk_lpips_conv_workspace_bytes(int N, int H, int W, int Cin, int Cout, int dtype);
 int ttvk_lpips_conv3x3(const void* x, int N, int H, int W, int Cin, int Cout, const void* w, const float* bias, int mode, const void* h,
                        void* y, int dtype, void* ws, int64_t ws_bytes, hipStream_t s);

@@ -33,6 +33,13 @@
 //                  D = (F0^T F0 - F1^T F1) / hw per image and tap, sum D^2 per block -> partials; backward
 //                  dF0 += g * 4 / (5 C^2 hw) * F0 D.  One launch per tap.
 //
+//   k_conv_first_clip / k_eval_finish : the evaluation path (per-frame LPIPS of whole frames of any size 16 .. 2048, no tape): conv1_1
+//                  read in place from frame t of a [3][T][H][W] clip with the reconstruction's clamp fused, and the finish step that
+//                  is given each tap's true pixel count (H >> k)(W >> k) and adds the per-frame values to a double [sum, count] pair
+//                  in frame order.  Everything between is the kernels above: k_conv_mfma tiles partial columns and odd per-image
+//                  heights as it is (columns >= W and rows >= R load zero and are not stored; the image row is (tall row) % H),
+//                  k_pool floors with the input's own pitch, k_head_fwd takes any hw.
+//
 // The lin layers are applied with eval semantics (no dropout), the way the reference builds the module (.eval()).
 #include "ttv_common.h"
 #include "ttv_kernels.h"
@@ -498,6 +505,84 @@ __global__ void k_head_finish(const double* __restrict__ part, const double* __r
   if (gram) gram[img] = (float)(gr / 5.0);
 }
 
+// ---- evaluation: per-frame LPIPS of whole frames (EvalMetrics 'lpips') ----------------------------------------------------------
+// conv1_1 forward read in place from a clip pair [3][T][H][W] (channel stride T*H*W): frames t0 .. t0 + cnt - 1 of the reconstruction
+// go to images img0 .. of the stack y, the same frames of the target to images F + img0 ..  (F = frames of the pass).  The
+// reconstruction is clamped to [-1, 1] in T before the scaling when `clamp` (a NaN stays a NaN, as torch.clamp).  Per pixel the same
+// arithmetic in the same order as k_conv_first.
+template <typename T>
+__global__ __launch_bounds__(256) void k_conv_first_clip(const T* __restrict__ rc, const T* __restrict__ tg, int Tn, int t0, int cnt, int img0,
+                                                         int F, int H, int W, int clamp, const T* __restrict__ wg,
+                                                         const float* __restrict__ bias, T* __restrict__ y) {
+  const size_t hw = (size_t)H * W, pix = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (pix >= 2 * (size_t)cnt * hw) return;
+  const int xx = (int)(pix % W), yy = (int)((pix / W) % H), fi = (int)(pix / hw) % cnt, side = (int)(pix / (hw * cnt));
+  const T* src = (side ? tg : rc) + (size_t)(t0 + fi) * hw;
+  const size_t cs = (size_t)Tn * hw;
+  const bool cl = clamp && side == 0;
+  float v[27];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    const int sy = yy + t / 3 - 1, sx = xx + t % 3 - 1;
+    const bool in = sy >= 0 && sy < H && sx >= 0 && sx < W;
+#pragma unroll
+    for (int ci = 0; ci < 3; ++ci) {
+      float p = in ? Cvt<T>::to_f(src[ci * cs + (size_t)sy * W + sx]) : 0.f;
+      if (cl) p = p < -1.f ? -1.f : (p > 1.f ? 1.f : p);
+      v[t * 3 + ci] = in ? round_to<T>((p - c_shift[ci]) / c_scale[ci]) : 0.f;
+    }
+  }
+  T* out = y + (((size_t)side * F + img0 + fi) * hw + (size_t)yy * W + xx) * 64;
+  for (int c0 = 0; c0 < 64; c0 += 8) {
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 27; ++k)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] = fmaf(v[k], Cvt<T>::to_f(wg[k * 64 + c0 + j]), acc[j]);
+#pragma unroll
+    for (int j = 0; j < 8; j += 4) {
+      f32x4 o = {fmaxf(acc[j] + bias[c0 + j], 0.f), fmaxf(acc[j + 1] + bias[c0 + j + 1], 0.f), fmaxf(acc[j + 2] + bias[c0 + j + 2], 0.f),
+                 fmaxf(acc[j + 3] + bias[c0 + j + 3], 0.f)};
+      Vec4<T>::store(out + c0 + j, o);
+    }
+  }
+}
+
+constexpr int EV_MAX_FRAMES = 2048;   // frames of one pass (a stack of 4096 images, what check_shape allows the loss path)
+
+// Each tap's true pixel count (H >> k) * (W >> k): hw0 >> 2k is wrong once a stage is odd (24 x 40: tap 4 has 1 x 2 = 2 pixels,
+// 960 >> 8 = 3).
+struct EvalTaps {
+  int hw[5];
+};
+
+// value[f] = sum over taps of (sum of the tap's partials, block order) / hw_k for the F frames of a pass; one block.  `out`
+// (or NULL) gets the values; `acc` (or NULL) gets acc[0] += value[f] for f = 0 .. F-1 in that order by one thread, acc[1] += F.
+__global__ __launch_bounds__(256) void k_eval_finish(const double* __restrict__ part, EvalTaps tp, int F, float* __restrict__ out,
+                                                     double* __restrict__ acc) {
+  __shared__ float s_v[EV_MAX_FRAMES];
+  for (int f = threadIdx.x; f < F; f += 256) {
+    double lp = 0.0;
+    size_t off = 0;
+    for (int k = 0; k < 5; ++k) {
+      const int blocks = (tp.hw[k] + HD_PIX - 1) / HD_PIX;
+      double s = 0.0;
+      for (int b = 0; b < blocks; ++b) s += part[off + (size_t)f * blocks + b];
+      lp += s / tp.hw[k];
+      off += (size_t)F * blocks;
+    }
+    s_v[f] = (float)lp;
+    if (out) out[f] = (float)lp;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && acc) {
+    double s = acc[0];
+    for (int f = 0; f < F; ++f) s += (double)s_v[f];
+    acc[0] = s;
+    acc[1] += (double)F;
+  }
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 unsigned grid_for(size_t total) {
   const size_t b = (total + 255) / 256;
@@ -645,6 +730,76 @@ int check_weights(const ttv_lpips_weights* w) {
   return TTV_OK;
 }
 
+// One evaluation pass of F frame pairs: two ping-pong activation buffers sized for the largest stage (2F images x H x W x 64), the
+// head partials of the five taps, the largest split-K partial buffer.  No tape.
+struct EvalLayout {
+  size_t bufa, bufb, part, split, ws;
+};
+
+EvalLayout eval_layout(int F, int H, int W, int dtype) {
+  EvalLayout L{};
+  const size_t big = (size_t)2 * F * H * W * 64 * dtype_bytes(dtype);
+  size_t o = 0, np = 0;
+  L.bufa = o;
+  o = align256(o + big);
+  L.bufb = o;
+  o = align256(o + big);
+  for (int k = 0; k < 5; ++k) np += (size_t)F * (((size_t)(H >> k) * (W >> k) + HD_PIX - 1) / HD_PIX);
+  L.part = o;
+  o = align256(o + np * 8);
+  int64_t sp = 0;
+  for (int l = 1; l < LP_LAYERS; ++l) sp = std::max(sp, conv_ws_bytes(dtype, 2 * F, H >> LP_STAGE[l], W >> LP_STAGE[l], LP_CIN[l], LP_COUT[l]));
+  L.split = o;
+  o = align256(o + (size_t)sp);
+  L.ws = o;
+  return L;
+}
+
+int check_eval_shape(int H, int W, int dtype) {
+  TTV_CHECK_ARG(dtype == TTV_BF16 || dtype == TTV_F32, "lpips eval: dtype %d is neither TTV_BF16 nor TTV_F32", dtype);
+  TTV_CHECK_ARG(H >= 16 && W >= 16 && H <= 2048 && W <= 2048, "lpips eval: %d x %d frames; H and W must lie in 16 .. 2048", H, W);
+  return TTV_OK;
+}
+
+template <typename T>
+int eval_pass(const ttv_lpips_weights* wt, void* const* recon, void* const* target, const int32_t* frames, int clip, int t, int F, int H,
+              int W, int dtype, int clamp, float* out, double* acc, char* wp, const EvalLayout& L, hipStream_t st) {
+  T* cur = reinterpret_cast<T*>(wp + L.bufa);
+  T* other = reinterpret_cast<T*>(wp + L.bufb);
+  for (int done = 0; done < F;) {   // conv1_1 from the clips: one launch per clip that has frames in this pass
+    const int cnt = std::min(F - done, frames[clip] - t);
+    const unsigned blocks = (unsigned)(((size_t)2 * cnt * H * W + 255) / 256);
+    hipLaunchKernelGGL(k_conv_first_clip<T>, dim3(blocks), dim3(256), 0, st, (const T*)recon[clip], (const T*)target[clip], frames[clip], t,
+                       cnt, done, F, H, W, clamp, (const T*)wt->w[0], wt->b[0], cur);
+    TTV_CHECK_LAUNCH("lpips eval conv1_1");
+    done += cnt;
+    t += cnt;
+    if (t == frames[clip]) ++clip, t = 0;
+  }
+  EvalTaps tp;
+  size_t off = 0;
+  int tap = 0;
+  for (int l = 1; l < LP_LAYERS; ++l) {
+    const int s = LP_STAGE[l], Hs = H >> s, Ws = W >> s, C = LP_COUT[l];
+    TTV_TRY(conv_launch(dtype, cur, 2 * F, Hs, Ws, LP_CIN[l], C, wt->w[l], wt->b[l], MODE_FWD, nullptr, other, wp + L.split, st));
+    std::swap(cur, other);
+    if (l != LP_TAP_LAYER[tap]) continue;
+    const int hw = Hs * Ws, blocks = ttv_cdiv(hw, HD_PIX);   // the tap's head, before its buffer is reused
+    hipLaunchKernelGGL(k_head_fwd<T>, dim3(blocks, F), dim3(256), 0, st, (const T*)cur, F, hw, C, wt->lin[tap],
+                       reinterpret_cast<double*>(wp + L.part) + off);
+    TTV_CHECK_LAUNCH("lpips eval head");
+    off += (size_t)F * blocks;
+    tp.hw[tap++] = hw;
+    if (tap < 5) {   // floor pool: (Hs >> 1) x (Ws >> 1), an odd stage loses its last row or column
+      TTV_TRY(pool_launch(dtype, cur, 2 * F, Hs, Ws, C, other, st));
+      std::swap(cur, other);
+    }
+  }
+  hipLaunchKernelGGL(k_eval_finish, dim3(1), dim3(256), 0, st, (const double*)(wp + L.part), tp, F, out, acc);
+  TTV_CHECK_LAUNCH("lpips eval finish");
+  return TTV_OK;
+}
+
 }  // namespace
 
 int64_t ttvk_lpips_tape_bytes(int n, int H, int W, int dtype) {
@@ -774,6 +929,56 @@ int ttvk_lpips_backward(const ttv_lpips_weights* wt, const void* tape, int n, in
     else
       hipLaunchKernelGGL(k_conv_last<float>, dim3(blocks), dim3(256), 0, st, (const float*)cur, n, H, W, (const float*)wt->wd[0], (float*)drecon);
     TTV_CHECK_LAUNCH("lpips conv1_1 dgrad");
+  }
+  return TTV_OK;
+}
+
+// ---- evaluation -------------------------------------------------------------------------------------------------------------------
+int64_t ttvk_lpips_eval_workspace_bytes(int frames, int H, int W, int dtype) {
+  if (check_eval_shape(H, W, dtype) != TTV_OK) return -1;
+  if (frames < 1 || frames > EV_MAX_FRAMES) {
+    ttv_set_error("lpips eval: %d frames in a pass (1 .. %d)", frames, EV_MAX_FRAMES);
+    return -1;
+  }
+  return (int64_t)eval_layout(frames, H, W, dtype).ws;
+}
+
+int ttvk_lpips_eval_accumulate(const ttv_lpips_weights* wt, void* const* recon, void* const* target, const int32_t* frames, int n_clips, int H,
+                               int W, int dtype, int clamp_recon, float* per_frame, double* acc, void* ws, int64_t ws_bytes, hipStream_t st) {
+  TTV_TRY(check_eval_shape(H, W, dtype));
+  TTV_TRY(check_weights(wt));
+  TTV_CHECK_ARG(recon && target && frames && ws && (per_frame || acc), "lpips eval: null argument");
+  TTV_CHECK_ARG(n_clips >= 1 && n_clips <= (1 << 20), "lpips eval: %d clips", n_clips);
+  int64_t total = 0;
+  for (int i = 0; i < n_clips; ++i) {
+    TTV_CHECK_ARG(recon[i] && target[i], "lpips eval: null pointer in clip %d", i);
+    TTV_CHECK_ARG(frames[i] >= 1 && frames[i] <= (1 << 20), "lpips eval: clip %d has %d frames", i, frames[i]);
+    total += frames[i];
+  }
+  TTV_CHECK_ARG(total <= (1 << 24), "lpips eval: %lld frames in one call", (long long)total);
+  TTV_CHECK_ARG(((uintptr_t)ws & 255) == 0, "lpips eval: the workspace must be 256-byte aligned");
+  // the largest pass the workspace holds (split-K partials make the size not quite monotone in F: walk down)
+  const int64_t per_frame_bytes = (int64_t)eval_layout(1, H, W, dtype).bufb * 2;
+  int F = (int)std::min<int64_t>(std::min<int64_t>(total, EV_MAX_FRAMES), std::max<int64_t>(ws_bytes / per_frame_bytes, 1));
+  const auto fits = [&](int64_t n) { return n == 0 || (int64_t)eval_layout((int)n, H, W, dtype).ws <= ws_bytes; };
+  while (F > 1 && !(fits(F) && fits(total % F))) --F;   // the last, shorter pass must fit too
+  TTV_CHECK_ARG(fits(F), "lpips eval: workspace of %lld bytes, one %d x %d frame needs %lld",
+                (long long)ws_bytes, H, W, (long long)eval_layout(1, H, W, dtype).ws);
+  char* wp = reinterpret_cast<char*>(ws);
+  int clip = 0, t = 0;
+  for (int64_t f0 = 0; f0 < total;) {
+    const int n = (int)std::min<int64_t>(F, total - f0);
+    const EvalLayout L = eval_layout(n, H, W, dtype);
+    float* out = per_frame ? per_frame + f0 : nullptr;
+    if (dtype == TTV_BF16) TTV_TRY(eval_pass<bf16_t>(wt, recon, target, frames, clip, t, n, H, W, dtype, clamp_recon, out, acc, wp, L, st));
+    else TTV_TRY(eval_pass<float>(wt, recon, target, frames, clip, t, n, H, W, dtype, clamp_recon, out, acc, wp, L, st));
+    f0 += n;
+    for (int left = n; left > 0;) {   // advance (clip, t) by n frames
+      const int cnt = std::min(left, frames[clip] - t);
+      left -= cnt;
+      t += cnt;
+      if (t == frames[clip]) ++clip, t = 0;
+    }
   }
   return TTV_OK;
 }

@@ -20,6 +20,14 @@ them `x.clamp(-1, 1)` per clip, CTHW -> TCHW (eval_metrics.py:19-21, 32-37).
   `training.eval.jedi_probe`; without them 'jedi' raises as before.  `training.eval.jedi_jepa_model` is honoured (vit_large only).
   Both clips are clamped (get_feats clamps again), each goes in as a batch of one; see jedi.py.  The weights are not part of
   state_dict().
+- LPIPS (the 'lpips' entry): per-frame LPIPS of whole frames, `LPIPS.frame_distances` (lpips_gram.py; csrc/ttv_lpips.hip, the
+  evaluation path: any frame size in 16 .. 2048 with floor max-pools, no tape).  Needs the VGG16 + LPIPS weights from a local file or
+  state dict with the reference LPIPS keys, given as `EvalMetrics(config, lpips_weights=path_or_state_dict)` or the optional config key
+  `training.eval.lpips_weights`, or an `LPIPS` module as `lpips_model=` (the loss module's `perceptual_model`, so the weights are
+  loaded and packed once); without any of them 'lpips' raises as before.  The reconstruction is clamped, the target is not
+  (eval_metrics.py:33-37), each frame pair is a batch entry of its own.  State: a running sum of per-frame values and a frame
+  count (double, on the device), so compute() is a mean of per-frame values like SSIM; no cross-rank sum in compute(), as for PSNR
+  and SSIM.  The weights are not part of state_dict().
 No host sync until compute().
 """
 from __future__ import annotations
@@ -37,12 +45,14 @@ AVAILABLE = ("psnr", "ssim")
 
 
 class EvalMetrics(nn.Module):
-    def __init__(self, config=None, eval_prefix: str = "eval", fvd_detector=None, jedi_weights=None, jedi_probe=None):
+    def __init__(self, config=None, eval_prefix: str = "eval", fvd_detector=None, jedi_weights=None, jedi_probe=None,
+                 lpips_weights=None, lpips_model=None):
         super().__init__()
         self.eval_prefix = eval_prefix
         names = ["psnr"]
         self._fvd = None
         self._jedi = None
+        self._lpips = None
         if config is not None:
             names = [m for m in config.training.eval.log_metrics]
             if fvd_detector is None:
@@ -51,8 +61,20 @@ class EvalMetrics(nn.Module):
                 jedi_weights = getattr(config.training.eval, "jedi_weights", None)
             if jedi_probe is None:
                 jedi_probe = getattr(config.training.eval, "jedi_probe", None)
+            if lpips_weights is None and lpips_model is None:
+                lpips_weights = getattr(config.training.eval, "lpips_weights", None)
             for m in names:
-                if m == "fvd" and fvd_detector is not None:
+                if m == "lpips" and (lpips_model is not None or lpips_weights is not None):
+                    from .lpips_gram import LPIPS
+                    if lpips_model is None:
+                        if isinstance(lpips_weights, (str, bytes)) or hasattr(lpips_weights, "__fspath__"):
+                            lpips_model = LPIPS.from_file(lpips_weights)
+                        else:
+                            lpips_model = LPIPS()
+                            lpips_model.load_state_dict(lpips_weights, strict=True)
+                            lpips_model.eval()
+                    self.__dict__["_lpips"] = lpips_model      # not a submodule: the weights stay out of state_dict(), like _fvd
+                elif m == "fvd" and fvd_detector is not None:
                     from .fvd import FVDCalculator
                     self.__dict__["_fvd"] = FVDCalculator(detector=fvd_detector)
                 elif m == "jedi" and jedi_weights is not None:
@@ -66,6 +88,7 @@ class EvalMetrics(nn.Module):
         self._acc = None         # psnr: (sum of squared errors, element count), double
         self._ssim_acc = None    # ssim: (sum of per-frame SSIM, frame count), double
         self._ssim_ws = None     # ssim: per-tile partial sums, grown as needed
+        self._lpips_acc = None   # lpips: (sum of per-frame LPIPS, frame count), double
 
     def _ssim_groups(self, rs, ts):
         """Host-side shapes and workspace sizes of every call of up to TTV_MAX_CLIPS_PER_LAUNCH clips (raises before any launch)."""
@@ -91,6 +114,8 @@ class EvalMetrics(nn.Module):
         ts = [t.to(r0.dtype).contiguous() for t in target]
         dt, stream = _lib.dtype_code(r0.dtype), _lib.stream_ptr(r0.device)
         groups = self._ssim_groups(rs, ts) if "ssim" in self.names else []
+        if self._lpips is not None:
+            self._lpips._check_clips(rs, ts)      # raises before any launch
         if "psnr" in self.names:
             if self._acc is None or self._acc.device != r0.device:
                 self._acc = torch.zeros(2, dtype=torch.float64, device=r0.device)
@@ -107,6 +132,10 @@ class EvalMetrics(nn.Module):
                 rc = _lib.lib().ttv_ssim_accumulate(_lib.ptr_array(r), _lib.ptr_array(t), dims, len(r), dt, 1, self._ssim_acc.data_ptr(),
                                                     self._ssim_ws.data_ptr(), self._ssim_ws.numel(), stream)
                 _lib.check(rc, "ttv_ssim_accumulate")
+        if self._lpips is not None:
+            if self._lpips_acc is None or self._lpips_acc.device != r0.device:
+                self._lpips_acc = torch.zeros(2, dtype=torch.float64, device=r0.device)
+            self._lpips.frame_distances(rs, ts, clamp_recon=True, acc=self._lpips_acc)
         if self._fvd is not None:
             self._fvd.update_clips(recon, target, clamp_recon=True)
         if self._jedi is not None:
@@ -121,6 +150,9 @@ class EvalMetrics(nn.Module):
             elif name == "ssim" and self._ssim_acc is not None:
                 s, n = (float(v) for v in self._ssim_acc.cpu())
                 out[f"{self.eval_prefix}/ssim"] = s / n if n > 0 else float("nan")
+            elif name == "lpips" and self._lpips_acc is not None:
+                s, n = (float(v) for v in self._lpips_acc.cpu())
+                out[f"{self.eval_prefix}/lpips"] = s / n if n > 0 else float("nan")
             elif name == "fvd" and self._fvd is not None:
                 out[f"{self.eval_prefix}/fvd"] = self._fvd.compute()
             elif name == "jedi" and self._jedi is not None:
@@ -128,7 +160,7 @@ class EvalMetrics(nn.Module):
         return out
 
     def reset(self) -> None:
-        for acc in (self._acc, self._ssim_acc):
+        for acc in (self._acc, self._ssim_acc, self._lpips_acc):
             if acc is not None:
                 acc.zero_()
         if self._fvd is not None:

@@ -11,11 +11,14 @@ Differences from the reference, all deliberate:
   * the lin layers always use eval semantics (no dropout).  The reference builds the module with `.eval()`; whether a trainer's
     `train()` later switches its dropouts back on depends on the Lightning version.  Here `train()` changes nothing.
   * inputs must be bf16 or fp32 CUDA tensors [B, 3, H, W] with H and W multiples of 16; anything else raises.
+
+`LPIPS.frame_distances(recon_clips, target_clips)` is the evaluation path (EvalMetrics 'lpips'): per-frame values of whole frames
+of CTHW clips, any H and W in 16 .. 2048 (the max-pools floor, as torch's), no tape, no autograd node.
 """
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import Dict
+from typing import Dict, Sequence
 
 import torch
 import torch.nn as nn
@@ -33,6 +36,8 @@ VGG_FEATURES = [(0, "conv", 3, 64), (1, "relu"), (2, "conv", 64, 64), (3, "relu"
                 (24, "conv", 512, 512), (25, "relu"), (26, "conv", 512, 512), (27, "relu"), (28, "conv", 512, 512), (29, "relu")]
 SLICES = [(0, 4), (4, 9), (9, 16), (16, 23), (23, 30)]
 CONV_INDICES = [f[0] for f in VGG_FEATURES if f[1] == "conv"]
+EVAL_WORKSPACE_BYTES = 1 << 30      # default budget of frame_distances: 127 bf16 frame pairs of 128 x 128 in one pass
+EVAL_MAX_FRAMES = 2048              # frames of one pass at most (ttv_lpips_eval_workspace_bytes)
 
 
 def _slice_of(index: int) -> int:
@@ -199,6 +204,7 @@ class LPIPS(nn.Module):
             p.requires_grad = False
         self.compute_gram = True
         self._pack_cache = None
+        self._eval_ws = None       # frame_distances: the workspace, kept between calls and grown as needed
 
     @classmethod
     def from_file(cls, path: str) -> "LPIPS":
@@ -226,3 +232,77 @@ class LPIPS(nn.Module):
         want_gram = self.compute_gram if compute_gram is None else bool(compute_gram)
         pack = self._pack(input.dtype, input.device)
         return _LpipsFunction.apply(input, target.detach(), pack, want_gram)
+
+    @staticmethod
+    def _check_clips(recon_clips, target_clips):
+        """Shape rules first (ValueError), then device and dtype (TypeError); nothing is launched before all clips pass."""
+        if len(recon_clips) == 0 or len(recon_clips) != len(target_clips):
+            raise ValueError(f"LPIPS.frame_distances: {len(recon_clips)} reconstruction and {len(target_clips)} target clips")
+        for i, (r, t) in enumerate(zip(recon_clips, target_clips)):
+            if r.dim() != 4 or r.shape[0] != 3 or r.shape[1] < 1 or r.shape != t.shape:
+                raise ValueError(f"LPIPS.frame_distances: clip {i}: expected a [3, T, H, W] pair of one shape, got {tuple(r.shape)} "
+                                 f"and {tuple(t.shape)}")
+            H, W = r.shape[2], r.shape[3]
+            if H < 16 or W < 16 or H > 2048 or W > 2048:
+                raise ValueError(f"LPIPS.frame_distances: clip {i}: {H} x {W} frames; H and W must lie in 16 .. 2048")
+        r0 = recon_clips[0]
+        for i, (r, t) in enumerate(zip(recon_clips, target_clips)):
+            if not (r.is_cuda and t.is_cuda) or r.device != r0.device or t.device != r0.device:
+                raise TypeError(f"LPIPS.frame_distances: clip {i} is on {r.device} / {t.device}; the clips of a call must be on one GPU "
+                                f"(there is no CPU path)")
+            if r.dtype != r0.dtype or r.dtype not in (torch.bfloat16, torch.float32):
+                raise TypeError(f"LPIPS.frame_distances: clip {i} is {r.dtype}; reconstructions must all be bf16 or all fp32")
+
+    @torch.no_grad()
+    def frame_distances(self, recon_clips: Sequence[torch.Tensor], target_clips: Sequence[torch.Tensor], clamp_recon: bool = True,
+                        workspace_bytes: int = EVAL_WORKSPACE_BYTES, acc: torch.Tensor = None) -> torch.Tensor:
+        """Per-frame LPIPS of whole frames: fp32 [sum of T], in clip then frame order.  Clips are [3, T, H, W] pairs, bf16 or fp32,
+        H and W anything in 16 .. 2048; a target is cast to its reconstruction's dtype.  With `clamp_recon` the reconstruction is
+        clamped to [-1, 1] (in the kernel that reads it), the target never.  Each frame pair is a batch entry of its own of
+        `forward`'s network with floor max-pools; no tape, no autograd node, no host sync.
+        Clips are grouped by (H, W), one call of ttv_lpips_eval_accumulate per group, and a group is worked through in passes of as
+        many frames as `workspace_bytes` holds (at least one frame, whatever the budget).  The workspace is kept on the module.
+        `acc` (double [2] on the device, optional) gets += (sum of the values, frame count); within a group the values are added
+        in frame order by one thread, the groups in the order their first clips appear."""
+        self._check_clips(recon_clips, target_clips)
+        dev, dtype = recon_clips[0].device, recon_clips[0].dtype
+        dt, L = _lib.dtype_code(dtype), _lib.lib()
+        rs = [r.detach().contiguous() for r in recon_clips]
+        ts = [t.detach().to(dtype).contiguous() for t in target_clips]
+        groups: Dict[tuple, list] = OrderedDict()
+        for i, r in enumerate(rs):
+            groups.setdefault((r.shape[2], r.shape[3]), []).append(i)
+        if acc is not None and not (acc.is_cuda and acc.device == dev and acc.dtype == torch.float64 and acc.numel() == 2
+                                    and acc.is_contiguous()):
+            raise TypeError("LPIPS.frame_distances: acc must be a contiguous float64 [2] on the clips' device")
+        nbytes = {}
+        for (H, W), idx in groups.items():
+            frames = min(sum(rs[i].shape[1] for i in idx), EVAL_MAX_FRAMES)
+            whole, one = L.ttv_lpips_eval_workspace_bytes(frames, H, W, dt), L.ttv_lpips_eval_workspace_bytes(1, H, W, dt)
+            if whole < 0 or one < 0:
+                _lib.check(1, "ttv_lpips_eval_workspace_bytes")
+            nbytes[(H, W)] = whole if whole <= workspace_bytes else max(int(workspace_bytes), one)
+        need = max(nbytes.values())
+        if self._eval_ws is None or self._eval_ws.device != dev or self._eval_ws.numel() < need:
+            self._eval_ws = _alloc_bytes(need, dev)
+        pack = self._pack(dtype, dev)
+        starts, total = [], 0
+        for r in rs:
+            starts.append(total)
+            total += r.shape[1]
+        out = torch.empty(total, dtype=torch.float32, device=dev)
+        single = len(groups) == 1
+        for (H, W), idx in groups.items():
+            r, t = [rs[i] for i in idx], [ts[i] for i in idx]
+            frames = (_lib.C.c_int32 * len(idx))(*[int(c.shape[1]) for c in r])
+            vals = out if single else torch.empty(sum(frames), dtype=torch.float32, device=dev)
+            _lib.check(L.ttv_lpips_eval_accumulate(_lib.C.byref(pack.w), _lib.ptr_array(r), _lib.ptr_array(t), frames, len(idx), H, W, dt,
+                                                   int(bool(clamp_recon)), vals.data_ptr(), _lib.ptr(acc), self._eval_ws.data_ptr(),
+                                                   nbytes[(H, W)], _lib.stream_ptr(dev)),
+                       "ttv_lpips_eval_accumulate")
+            if not single:
+                o = 0
+                for i, n in zip(idx, frames):
+                    out[starts[i]:starts[i] + n] = vals[o:o + n]
+                    o += n
+        return out
