@@ -421,6 +421,42 @@ int ttv_encoder_forward(const ttv_tower_dims* dims, const ttv_tower_weights* w, 
 int ttv_decoder_forward(const ttv_tower_dims* dims, const ttv_tower_weights* w, const ttv_batch* batch, const void* codes,
                         void* const* clips_out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The decoder's patch rows enter layer 0 as one constant vector, ln_pre_p(mask_token) (blocks.py:165-167): their q | gate | k | v in
+ * layer 0 depend on the weights and on the rows' rotary positions only, so they are the same for every clip of one geometry (pixel grid
+ * and latent count) on every call.  A CONSTANT BLOCK holds them once per (weights, geometry): `rows` bf16 [patch_rows, 2d+2g], written by
+ * the kernels the forward itself runs (ttv_fill_const_rows, then layer 0's to_qkv with the folded pre-norm, the q pre-scale and the
+ * rotary factors of one clip's patch rows), hence the bits the forward would write into its own workspace.  With it layer 0's to_qkv
+ * computes only the 128-row token tiles that hold latent rows, and its attention reads the patch rows' q, gate, k and v from the block.
+ * `state`: for every (128-row patch query block, q-head) the raw fp32 accumulators and row sums of the attention kernel (k_attn_swp keeps
+ * no softmax reference: O and l are plain sums of 2^score terms) over the PATCH keys, in the kernel's register layout.  With it a patch
+ * query block loops over the latent keys only and adds the state once: one fp32 addition per accumulator in another place of the sum.
+ * The builder's flag word (int32 at flag_offset, device) is nonzero when one of those row sums left the kernel's 2^-60 .. 2^60 window:
+ * pass state = NULL then (the attention then still reads the rows, over every key).
+ * bf16 decoders of width 256, head_dim 64, with ttv_layer_weights.to_qkv_pn and qkv_q_prescaled on layer 0.
+ * ttv_dec_l0_const_bytes: bytes of the block (the rows first, then the builder's scratch); -1 when the tower is not of that kind.
+ * ttv_dec_l0_const_build: iota = device int32 [patch_rows] 0, 1, ..; rope_cs [patch_rows, 64] / rope_ids [patch_rows, 2] (optional, with
+ * rope_base) = the rows of ttv_batch.rope_cs / rope_ids that belong to the patch rows of ONE clip of the geometry; block 256-byte aligned.
+ * Rebuild after any change of the weights. */
+typedef struct ttv_dec_l0_const {
+  const void* rows;       /* the block (its first patch_rows * (2d+2g) bf16 are the rows) */
+  int32_t latent_rows;    /* K: latent rows of every clip of the batch (they come first in a sequence) */
+  int32_t patch_rows;     /* P: patch rows of every clip of the batch */
+  const float* state;     /* block + state_offset, or NULL (flag set, or A/B) */
+  const int32_t* qblocks; /* optional attention work table for layer 0 (format of ttv_batch.qblocks, full items): the batch's items with */
+  int32_t n_qblocks;      /* the latent query blocks - the long ones - first; NULL / 0: ttv_batch.qblocks */
+} ttv_dec_l0_const;
+int64_t ttv_dec_l0_const_bytes(const ttv_tower_dims* dims, int patch_rows);
+int ttv_dec_l0_const_build(const ttv_tower_dims* dims, const ttv_tower_weights* w, const int32_t* iota, const float* rope_cs,
+                           const int32_t* rope_ids, const float* rope_base, int patch_rows, void* block, int64_t block_bytes,
+                           int64_t* state_offset, int64_t* flag_offset, void* stream);
+/* ttv_decoder_forward with the constant block of this batch's geometry (NULL: ttv_decoder_forward).  The caller promises that EVERY clip
+ * of the batch has the geometry the block was built for and that the block belongs to `w`.  The block is used when K and P are multiples
+ * of 128, the batch's table holds full unpaired items and layer 0 runs the width-256 bf16 kernels; otherwise, and with TTV_DEC_L0_CONST=0,
+ * the call is ttv_decoder_forward.  Without `state` the output is the same bits; with it the patch query rows of layer 0's attention
+ * differ by the re-association of one fp32 sum. */
+int ttv_decoder_forward_const(const ttv_tower_dims* dims, const ttv_tower_weights* w, const ttv_batch* batch, const void* codes,
+                              void* const* clips_out, void* workspace, int64_t workspace_bytes, const ttv_dec_l0_const* l0, void* stream);
+
 /* ---- training step: tape-recording forward + backward (reference train.py:65-83 = autograd through the towers) ------- */
 /* Transposed linear weights for the data-gradient GEMMs (dX = dY W is run as dY (W^T)^T), compute dtype. */
 typedef struct ttv_layer_weights_t {
@@ -892,7 +928,8 @@ enum {
   TTV_DBG_QKV256_WS = 131072,          /* to_qkv at K = 256: the weight-stationary k_qkv256ws, as TTV_QKV256=2 (ttv_gemm.hip) */
   TTV_DBG_ENC_ALL_ROWS = 524288,       /* encoder's last layer on every row, as TTV_ENC_LATENT_LAST=0 (ttv_api.hip, ttv_train.hip) */
   TTV_DBG_ATTN_NO_SWP = 1048576,       /* ttvk_attention keeps k_attn_bf16 where it would take k_attn_swp, as TTV_ATTN_SWP=0 (ttv_attn.hip) */
-  TTV_DBG_DEC_ALL_BLOCKS = 2097152     /* decoder's last attention on every query block, as TTV_DEC_PATCH_LAST=0 (ttv_api.hip) */
+  TTV_DBG_DEC_ALL_BLOCKS = 2097152,    /* decoder's last attention on every query block, as TTV_DEC_PATCH_LAST=0 (ttv_api.hip) */
+  TTV_DBG_DEC_L0_NO_CONST = 4194304    /* decoder's layer 0 ignores the constant block, as TTV_DEC_L0_CONST=0 (ttv_api.hip) */
 };
 int ttv_debug_set(int flags);
 /* Diagnostics: device buffer (>= 256 int64) that instrumented kernels fill with s_memtime stamps of block 0; NULL = off. */

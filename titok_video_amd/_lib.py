@@ -46,6 +46,7 @@ DBG_QKV256_WS = 131072
 DBG_ENC_ALL_ROWS = 524288
 DBG_ATTN_NO_SWP = 1048576
 DBG_DEC_ALL_BLOCKS = 2097152
+DBG_DEC_L0_NO_CONST = 4194304
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # TTV_LIB_PATH: diagnostics only (an instrumented build of the same sources, tools/attn_stamps.py)
@@ -91,6 +92,10 @@ class Batch(C.Structure):
                 ("n_blocks64", i32), ("qblocks_paired", i32), ("qblocks_all_full", i32), ("items64", vp), ("n_items64", i32),
                 ("rope_ids", vp), ("rope_base", vp), ("qblocks_latent", vp), ("n_qblocks_latent", i32), ("qblocks_patch", vp),
                 ("n_qblocks_patch", i32)]
+
+
+class DecL0Const(C.Structure):
+    _fields_ = [("rows", vp), ("latent_rows", i32), ("patch_rows", i32), ("state", vp), ("qblocks", vp), ("n_qblocks", i32)]
 
 
 class LayerWeightsT(C.Structure):
@@ -196,6 +201,10 @@ SYMBOLS = {
                                       C.POINTER(FsqParams), vp, vp, vp, vp, vp, i64, vp]),
     "ttv_decoder_forward": (C.c_int, [C.POINTER(TowerDims), C.POINTER(TowerWeights), C.POINTER(Batch), vp, C.POINTER(vp),
                                       vp, i64, vp]),
+    "ttv_dec_l0_const_bytes": (i64, [C.POINTER(TowerDims), C.c_int]),
+    "ttv_dec_l0_const_build": (C.c_int, [C.POINTER(TowerDims), C.POINTER(TowerWeights), vp, vp, vp, vp, C.c_int, vp, i64, C.POINTER(i64), C.POINTER(i64), vp]),
+    "ttv_decoder_forward_const": (C.c_int, [C.POINTER(TowerDims), C.POINTER(TowerWeights), C.POINTER(Batch), vp, C.POINTER(vp),
+                                            vp, i64, C.POINTER(DecL0Const), vp]),
     "ttv_tower_tape_bytes": (i64, [C.POINTER(TowerDims), C.POINTER(Batch)]),
     "ttv_tower_bwd_workspace_bytes": (i64, [C.POINTER(TowerDims), C.POINTER(Batch)]),
     "ttv_encoder_forward_train": (C.c_int, [C.POINTER(TowerDims), C.POINTER(TowerWeights), C.POINTER(Batch), C.POINTER(vp), vp, vp,

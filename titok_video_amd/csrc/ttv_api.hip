@@ -28,6 +28,7 @@ bool ttv_enc_latent_rows_only(const ttv_tower_dims* d, const ttv_batch* b) {
 bool ttv_sw_keel_f32sum() { static const bool v = ttv_env_flag("TTV_KEEL_F32SUM", false); return v; }
 bool ttv_sw_fused_patch() { static const bool v = ttv_env_flag("TTV_FUSED_PATCH", true); return v; }
 bool ttv_sw_attn_pipe() { static const bool v = ttv_env_flag("TTV_ATTN_PIPE", false); return v; }
+static bool sw_dec_l0_const() { static const bool v = ttv_env_flag("TTV_DEC_L0_CONST", true); return v; }
 float ttv_sw_attn_thr() { static const float v = ttv_env_float("TTV_ATTN_THR", 8.0f); return v; }   // log2 units; 0 = exact running maximum
 thread_local int g_ttv_debug = 0;     // per host thread: a thread that forces a kernel variant (tests, A/B tools) does not change what another thread launches
 long long* g_ttv_stamps = nullptr;   // diagnostics: device buffer for in-kernel clock stamps (ttv_debug_stamps)
@@ -194,7 +195,7 @@ struct PreNormW { const float* gain; const void *w, *w_pn, *w_f8; const float* w
 // Split-bf16 towers: the normalised row is written as the projection's split image (its producer splits it once, the GEMM's staging
 // threads copy bytes); TTV_SPLIT3_IMAGES=0 keeps fp32 activations and the split in the GEMM (A/B).
 static int prenorm_proj(const LayerCtx& c, GemmEpilogue epi, const char* x, int rows, const PreNormW& p, int N, char* y, int y_image,
-                        bool rstd_valid) {
+                        bool rstd_valid, int tile_run = 0, int tile_period = 0) {
   const ttv_tower_dims* d = c.d;
   const TowerWs& ws = c.ws;
   const int dm = d->width, dt = d->dtype;
@@ -216,6 +217,7 @@ static int prenorm_proj(const LayerCtx& c, GemmEpilogue epi, const char* x, int 
   a.row_scale = fold_gen ? ws.rstd : nullptr;
   a.x = fold ? x : ws.xn; a.w = fold ? p.w_pn : p.w;
   if (epi == EPI_QKV_ROPE) { a.rope_ids = c.b->rope_ids; a.rope_base = c.b->rope_ids ? c.b->rope_base : nullptr; }
+  a.tile_run = tile_run; a.tile_period = tile_period;       // (the caller has asked ttvk_gemm_qkv_tiles_supported)
   return ttvk_gemm(epi, a, c.s);
 }
 
@@ -252,7 +254,25 @@ static int keel_tail(const LayerCtx& c, GemmArgs o, int layer, const float* post
 }
 
 // One ResidualAttentionBlock stack (reference transformer.py:126-146) on ws.x in place.
-static int run_layers(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_batch* b, const TowerWs& ws, hipStream_t s) {
+// Can the decoder's layer 0 take its patch rows' q | gate | k | v from the constant block (ttv_dec_l0_const)?  The block's geometry must
+// be every clip's (the caller's promise; the sums are checked), rows and keys split at a multiple of the 128-row tiles of both kernels,
+// and layer 0 must run the two kernels that know about it: k_qkv256 with the folded pre-norm and k_attn_swp over the batch's own table.
+static bool dec_l0_const_ok(const LayerCtx& c, const ttv_tower_weights* w, const ttv_dec_l0_const* l0) {
+  const ttv_tower_dims* d = c.d;
+  const ttv_batch* b = c.b;
+  if (!l0 || !l0->rows || !sw_dec_l0_const() || (g_ttv_debug & TTV_DBG_DEC_L0_NO_CONST)) return false;
+  if (d->kind != TTV_DECODER || d->dtype != TTV_BF16 || d->width != 256 || d->head_dim != 64 || c.split3) return false;
+  const int K = l0->latent_rows, P = l0->patch_rows;
+  if (K <= 0 || P <= 0 || K % 128 || P % 128 || (int64_t)b->n_clips * K != b->sum_tokens || (int64_t)b->n_clips * P != b->sum_patches) return false;
+  const ttv_layer_weights& lw = w->layers[0];
+  if (!lw.to_qkv_pn || !lw.qkv_q_prescaled) return false;
+  if (c.pair || c.pipe || !c.all_full || (b->items64 && b->n_items64 > 0)) return false;
+  return ttvk_gemm_qkv_tiles_supported(d->width, d->kv_heads * d->head_dim, d->width) &&
+         ttvk_attention_takes_swp(TTV_ATTN_GATE | TTV_ATTN_QSCALED | TTV_ATTN_ALLFULL);
+}
+
+static int run_layers(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_batch* b, const TowerWs& ws, hipStream_t s,
+                      const ttv_dec_l0_const* l0 = nullptr) {
   const int L = b->total_rows, dm = d->width, g = d->kv_heads * d->head_dim, dt = d->dtype;
   const int split3 = (dt == TTV_F32 && w->f32_split3) ? 1 : 0;       // fp32 towers on the three-pass bf16 kernels (ttv_tower_weights.f32_split3)
   // pre-norm gains folded into the weight (to_qkv_pn / w12_pn) with the row statistic applied to the GEMM's output rows: the wide bf16
@@ -279,9 +299,17 @@ static int run_layers(const ttv_tower_dims* d, const ttv_tower_weights* w, const
   bool compacted = false;
   const LayerCtx ctx = {d, b, ws, s, split3, s3img, gen_ok, b->qblocks_paired ? TTV_ATTN_PAIRED : 0, b->qblocks_all_full ? TTV_ATTN_ALLFULL : 0,
                         ttv_sw_attn_pipe() ? TTV_ATTN_PIPE : 0};       // (pipe: the opt-in pipelined attention kernel)
+  // The decoder's patch rows enter layer 0 as one constant vector (blocks.py:165-167), so their q | gate | k | v depend on the weights
+  // and the rows' positions only: with the block built for this (weight pack, clip geometry) layer 0's to_qkv computes the token tiles
+  // that hold latent rows and its attention reads the patch rows from the block - one copy for every clip, L2-resident - instead of
+  // from ws.qkv; with the block's state a patch query block loops over the latent keys only and adds the cached sums over the patch keys
+  // (latent query rows keep their bits, patch query rows differ by one fp32 re-association).  TTV_DEC_L0_CONST=0 / debug bit
+  // 22: every row and key recomputed (A/B, tests).
+  const bool l0_const = dec_l0_const_ok(ctx, w, l0);
   for (int i = 0; i < d->layers; ++i) {
     const ttv_layer_weights& lw = w->layers[i];
     const bool last = i == d->layers - 1;
+    const bool l0c = l0_const && i == 0;
     if (dt == TTV_BF16 && dm != 256 && dm % 128 == 0 && d->inner % 128 == 0 && !ttv_sw_keel_f32sum() && lw.to_qkv_f8 && lw.to_qkv_mx && lw.w12_f8 &&
         lw.w12_mx && lw.out_proj_f8 && lw.out_proj_mx && lw.w3_f8 && lw.w3_mx &&
         !(lat_last && last)) {    // the encoder's last layer: its latent rows on the bf16 kernels instead (a ninth of the rows)
@@ -300,7 +328,8 @@ static int run_layers(const ttv_tower_dims* d, const ttv_tower_weights* w, const
     if (!qkv_ready) {
       const void* w_plain = (dt == TTV_BF16 && lw.to_qkv_qs) ? lw.to_qkv_qs : lw.to_qkv;   // inference copy with scaled q rows, if packed
       const PreNormW qw = {lw.pre_ln, w_plain, lw.to_qkv_pn, lw.to_qkv_f8, lw.to_qkv_f8_scale, f8_qkv};
-      TTV_TRY(prenorm_proj(ctx, EPI_QKV_ROPE, ws.x, L, qw, nq, ws.qkv, s3img ? 2 : 0, rstd_valid));
+      if (l0c) TTV_TRY(prenorm_proj(ctx, EPI_QKV_ROPE, ws.x, L, qw, nq, ws.qkv, 0, rstd_valid, l0->latent_rows / 128, (l0->latent_rows + l0->patch_rows) / 128));
+      else TTV_TRY(prenorm_proj(ctx, EPI_QKV_ROPE, ws.x, L, qw, nq, ws.qkv, s3img ? 2 : 0, rstd_valid));
     }
     // q arrives pre-scaled when the projection used the folded weight whose q rows carry scale * log2(e)
     const bool q_scaled = dt == TTV_BF16 && (lw.to_qkv_pn ? lw.qkv_q_prescaled != 0 : lw.to_qkv_qs != nullptr);
@@ -312,7 +341,14 @@ static int run_layers(const ttv_tower_dims* d, const ttv_tower_weights* w, const
       // ttvk_attention picks its kernel by that flag, and the latent-rows forward must run the kernel the all-rows forward runs - same
       // bits, tested
       TTV_TRY(tower_attention(ctx, q_scaled, b->qblocks_latent, b->n_qblocks_latent, ctx.all_full));
-    else if (pat_last && last && dt == TTV_BF16 && !ctx.pipe)     // (pat_last: the batch's table is unpaired)
+    else if (l0c) {
+      TtvProfScope prof(TTV_KC_ATTENTION, s);
+      // (the block's own table, when given: the latent query blocks - every key - in front of the patch blocks, which now loop over the
+      // latent keys only)
+      const bool own = l0->qblocks && l0->n_qblocks > 0;
+      TTV_TRY(ttvk_attention_swp(ws.qkv, nq, ws.ao, dm, b->cu_seqlens, own ? l0->qblocks : b->qblocks, own ? l0->n_qblocks : b->n_qblocks, d->q_heads,
+                                 d->kv_heads, 1, s, l0->rows, l0->latent_rows, l0->state));
+    } else if (pat_last && last && dt == TTV_BF16 && !ctx.pipe)     // (pat_last: the batch's table is unpaired)
       TTV_TRY(tower_attention(ctx, q_scaled, b->qblocks_patch, b->n_qblocks_patch, ctx.all_full));
     else if (q_scaled && b->items64 && b->n_items64 > 0 && d->head_dim == 64)
       TTV_TRY(ttvk_attention64(ws.qkv, nq, ws.ao, dm, b->cu_seqlens, b->items64, b->n_items64, d->q_heads, d->kv_heads,
@@ -660,8 +696,61 @@ int ttv_encoder_forward(const ttv_tower_dims* d, const ttv_tower_weights* w, con
   return TTV_OK;
 }
 
+int64_t ttv_dec_l0_const_bytes(const ttv_tower_dims* d, int patch_rows) {
+  if (!d || patch_rows <= 0 || d->dtype != TTV_BF16 || d->width != 256 || d->head_dim != 64 || d->kv_heads <= 0) {
+    ttv_set_error("dec_l0_const_bytes: bf16 decoders of width 256 and head_dim 64 only");
+    return -1;
+  }
+  if (patch_rows % 128) {
+    ttv_set_error("dec_l0_const_bytes: patch_rows must be a multiple of 128");
+    return -1;
+  }
+  const int64_t nq = 2 * (int64_t)d->width + 2 * (int64_t)d->kv_heads * d->head_dim;
+  // rows | attention state of every (patch query block, q-head) + the flag word | the builder's scratch x
+  return align256(patch_rows * nq * 2) + align256(ttvk_attention_swp_state_floats(patch_rows, d->q_heads) * 4 + 4) + align256((int64_t)patch_rows * d->width * 2);
+}
+
+int ttv_dec_l0_const_build(const ttv_tower_dims* d, const ttv_tower_weights* w, const int32_t* iota, const float* rope_cs, const int32_t* rope_ids,
+                           const float* rope_base, int patch_rows, void* block, int64_t block_bytes, int64_t* state_offset, int64_t* flag_offset,
+                           void* stream) {
+  TTV_CHECK_ARG(d && w && w->layers && iota && rope_cs && block && patch_rows > 0, "dec_l0_const_build: null argument");
+  const int64_t need = ttv_dec_l0_const_bytes(d, patch_rows);
+  if (need < 0) return TTV_ERR_UNSUPPORTED;
+  TTV_CHECK_ARG(d->kind == TTV_DECODER && need <= block_bytes && (uintptr_t)block % 256 == 0, "dec_l0_const_build: not a decoder, or block too small / unaligned");
+  const ttv_layer_weights& lw = w->layers[0];
+  if (!lw.to_qkv_pn || !lw.qkv_q_prescaled) {
+    ttv_set_error("dec_l0_const_build: layer 0 needs the folded, q-pre-scaled to_qkv weight");
+    return TTV_ERR_UNSUPPORTED;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int dm = d->width, g = d->kv_heads * d->head_dim, nq = 2 * dm + 2 * g, dt = d->dtype;
+  char* const rows = (char*)block;
+  const int64_t state_floats = ttvk_attention_swp_state_floats(patch_rows, d->q_heads);
+  float* const state = (float*)(rows + align256((int64_t)patch_rows * nq * 2));
+  char* const x = (char*)state + align256(state_floats * 4 + 4);
+  if (state_offset) *state_offset = (char*)state - rows;
+  if (flag_offset) *flag_offset = (char*)(state + state_floats) - rows;
+  // the forward's own two kernels on patch_rows rows of a scratch x: ln_pre_p(mask_token), then layer 0's to_qkv with the folded pre-norm
+  TTV_TRY(ttvk_fill_const_rows(x, dt, dm, iota, patch_rows, dm, w->mask_token, w->ln_pre_p, d->eps, s));
+  GemmArgs a = gemm_rope_qk(gemm_args(dt, x, dm, lw.to_qkv_pn, dm, patch_rows, nq, dm, rows, nq), rope_cs, dm, g);
+  a.prenorm = 1; a.eps = d->eps;
+  a.rope_ids = rope_ids; a.rope_base = rope_ids ? rope_base : nullptr;
+  TTV_TRY(ttvk_gemm(EPI_QKV_ROPE, a, s));
+  // what k_attn_swp accumulates for every patch query block over the patch keys, raw; the flag says whether a row sum left its window
+  if (hipMemsetAsync(state + state_floats, 0, 4, s) != hipSuccess) {
+    ttv_set_error("dec_l0_const_build: hipMemsetAsync failed");
+    return TTV_ERR_LAUNCH;
+  }
+  return ttvk_attention_swp_dump(rows, nq, patch_rows, d->q_heads, d->kv_heads, state, s);
+}
+
 int ttv_decoder_forward(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_batch* b, const void* codes,
                         void* const* clips_out, void* workspace, int64_t workspace_bytes, void* stream) {
+  return ttv_decoder_forward_const(d, w, b, codes, clips_out, workspace, workspace_bytes, nullptr, stream);
+}
+
+int ttv_decoder_forward_const(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_batch* b, const void* codes,
+                              void* const* clips_out, void* workspace, int64_t workspace_bytes, const ttv_dec_l0_const* l0, void* stream) {
   TTV_TRY(check_dims(d, b));
   TTV_CHECK_ARG(d->kind == TTV_DECODER, "decoder_forward: dims.kind is not TTV_DECODER");
   TTV_CHECK_ARG(w && w->layers && codes && clips_out && workspace, "decoder_forward: null argument");
@@ -672,9 +761,9 @@ int ttv_decoder_forward(const ttv_tower_dims* d, const ttv_tower_weights* w, con
 
   // x[latent rows] = ln_pre_t(proj_in(codes) + mask_token); x[patch rows] = ln_pre_p(mask_token * 1) (blocks.py:165-167)
   TTV_TRY(ttvk_dec_embed(codes, d->token_size, w->proj_in_w, w->proj_in_b, w->mask_token, w->ln_pre_t, ws.x, dt, dm, b->latent_rows, b->sum_tokens, dm, d->eps, s));
-  TTV_TRY(ttvk_fill_const_rows(ws.x, dt, dm, b->patch_rows, P, dm, w->mask_token, w->ln_pre_p, d->eps, s));
+  TTV_TRY(ttvk_fill_const_rows(ws.x, dt, dm, b->patch_rows, P, dm, w->mask_token, w->ln_pre_p, d->eps, s));      // (the residual stream needs them with or without l0)
 
-  TTV_TRY(run_layers(d, w, b, ws, s));
+  TTV_TRY(run_layers(d, w, b, ws, s, l0));
 
   // patches = proj_out(ln_post(x[patch rows])) -> unpatchify (blocks.py:171-176)
   GemmArgs a = gemm_args(dt, nullptr, dm, w->proj_out_w, dm, P, pd, dm, ws.pa, pd);      // operand: ws.x in place or its normed patch rows, below

@@ -1646,6 +1646,14 @@ int ttvk_attention_mxout(const void* qkvg, int ld, void* out_q, void* out_mx, in
   return TTV_OK;
 }
 
+// Does a bf16 launch without tape outputs run k_attn_swp?  (ttvk_attention's own choice; the decoder's layer 0 asks before it hands that
+// kernel a second source.)
+bool ttvk_attention_takes_swp(int flags) {
+  static const bool swp_env = ttv_env_flag("TTV_ATTN_SWP", true);
+  return swp_env && !(flags & TTV_ATTN_PIPE) && (flags & TTV_ATTN_ALLFULL) && (flags & TTV_ATTN_QSCALED) && !(flags & TTV_ATTN_PAIRED) &&
+         !(g_ttv_debug & TTV_DBG_ATTN_NO_SWP);
+}
+
 // flags: bit 0 (TTV_ATTN_GATE) multiply by sigmoid(gate); bit 1 (TTV_ATTN_PAIRED) the table is paired (see k_attn_bf16, NE = 2)
 // out_raw (bf16 only, with TTV_ATTN_GATE; leading dimension ldo): additionally receives the UNGATED attention output
 int ttvk_attention(const void* qkvg, int ld, void* out, int ldo, const int* cu_seqlens, const int* qblocks, int n_qblocks,
@@ -1682,8 +1690,7 @@ int ttvk_attention(const void* qkvg, int ld, void* out, int ldo, const int* cu_s
     // tables of full items only with pre-scaled q, no tape: the software-pipelined kernel on request (flag TTV_ATTN_PIPE; slower
     // than the plain loop, see its header)
     // round 5: the in-wave software pipeline of ttv_attn_swp.hip is the default for such tables (TTV_ATTN_SWP=0: k_attn_bf16, A/B)
-    static const bool swp_env = ttv_env_flag("TTV_ATTN_SWP", true);
-    if (swp_env && !(flags & TTV_ATTN_PIPE) && (flags & TTV_ATTN_ALLFULL) && prescaled && !paired && !tape && !(g_ttv_debug & TTV_DBG_ATTN_NO_SWP)) {
+    if (ttvk_attention_takes_swp(flags) && !tape) {
       return ttvk_attention_swp(qkvg, ld, out, ldo, cu_seqlens, qblocks, n_qblocks, q_heads, kv_heads, gate_mul, s);
     }
     if ((flags & TTV_ATTN_PIPE) && (flags & TTV_ATTN_ALLFULL) && prescaled && !paired && !tape) {

@@ -72,12 +72,27 @@ __device__ __forceinline__ bf16x4 swp_read_tr16(const char* lds_ptr) {
 #define SWP_STAMP(seg_)
 #endif
 
-template <bool GATE>
-__global__ __launch_bounds__(256, SWP_OCC) void k_attn_swp(const bf16_t* __restrict__ qkvg, int ld, bf16_t* __restrict__ out, int ldo,
-                                                     const int* __restrict__ cu, const int* __restrict__ qblocks, int d_model, int gqa,
-                                                     int rep, long long* __restrict__ stamps) {
-  __shared__ __attribute__((aligned(16))) uint4 kl[SWP_NS][SWP_KB * 8];
-  __shared__ __attribute__((aligned(16))) uint4 vl[SWP_NS][SWP_KB * 8];
+// MODE (the decoder's layer 0 with its constant block, ttv_dec_l0_const; 0: none of this):
+//   1  two sources: rows [kwin, S) of EVERY sequence are the same and live once in rows2 [S - kwin, ld] instead of in qkvg - a query
+//      block behind kwin takes q and gate from there, every block the K / V tiles behind kwin.  kwin % 128 == 0 (a query block and a
+//      key tile lie on one side).  Same keys in the same order: the same bits as with the rows in qkvg.
+//   2  the block's builder: qkvg is the block's rows, ONE sequence of kwin rows; item blockIdx.x = (query block, q-head) without a table.
+//      The loop's raw state - the un-normalised fp32 O accumulators and the lane's row-sum chain, in the register layout - is dumped to
+//      state[item] (SWP_STATE floats); nothing is normalised or stored to out.  A row sum outside the window sets the flag behind the
+//      last item: such a block is not used.
+//   3  mode 1, and a query block behind kwin runs its loop over the keys [0, kwin) only and adds state[its block, its head] - what mode
+//      2 summed over the keys [kwin, S), the same for every sequence and every call - before the range check: plain loads, nothing
+//      crosses between blocks at run time.  One fp32 addition per accumulator in another place of the sum; P and its rounding are the
+//      same.  Out of the window (the combined sum): the exact loop over ALL keys of both sources, as in mode 1.
+#define SWP_STATE (33 * 256)      // floats per item: o0, o1 as eight float4 per lane ([j][tid][4]), then l_run [tid]
+// (The kernel's body as a function: mode 3 runs it twice specialised - a block is either a mode-1 block or one whose keys behind kwin are
+// cached - so that neither loop carries the other's scalars; with both in one body the register allocation spilled q fragments in the loop.)
+template <bool GATE, int MODE>
+__device__ __forceinline__ void swp_body(const bf16_t* __restrict__ qkvg, int ld, bf16_t* __restrict__ out, int ldo,
+                                         const int* __restrict__ cu, const int* __restrict__ qblocks, int d_model, int gqa,
+                                         int rep, long long* __restrict__ stamps, const bf16_t* __restrict__ rows2, int kwin,
+                                         float* state, uint4 (*kl)[SWP_KB * 8], uint4 (*vl)[SWP_KB * 8]) {
+  constexpr bool TWO = MODE == 1 || MODE == 3;
 
 #ifdef SWP_STAMPS
   unsigned long long st_entry__;
@@ -87,15 +102,25 @@ __global__ __launch_bounds__(256, SWP_OCC) void k_attn_swp(const bf16_t* __restr
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
   const int tix = blockIdx.x;
-  const int seq = qblocks[4 * tix], q0 = qblocks[4 * tix + 1], head = qblocks[4 * tix + 2];
+  const int seq = MODE == 2 ? 0 : qblocks[4 * tix];
+  const int q0 = MODE == 2 ? (tix / (d_model >> 6)) * 128 : qblocks[4 * tix + 1];
+  const int head = MODE == 2 ? tix % (d_model >> 6) : qblocks[4 * tix + 2];
   if (seq < 0) return;                       // padding entry of the XCD-interleaved order (whole block)
-  const int s0 = cu[seq], S = cu[seq + 1] - s0;
+  const int s0 = MODE == 2 ? 0 : cu[seq], S = MODE == 2 ? kwin : cu[seq + 1] - s0;
+  constexpr bool cached = MODE == 3;                // this block's keys behind kwin come as the cached state (q0 >= kwin: the caller)
+  int Sk = cached ? kwin : S;                       // keys of the loop
   const int kvh = head / rep;
-  const bf16_t* qbase = qkvg + (size_t)s0 * ld + head * 64;
-  const bf16_t* gbase = qkvg + (size_t)s0 * ld + d_model + head * 64;
-  const bf16_t* kbase = qkvg + (size_t)s0 * ld + 2 * d_model + kvh * 64;
+  const bf16_t* const seq1 = qkvg + (size_t)s0 * ld;
+  // the second source, moved back by kwin rows: the sequence's own row numbers index it (only rows >= kwin are ever formed)
+  const bf16_t* const seq2 = TWO ? rows2 - (ptrdiff_t)kwin * ld : seq1;
+  const bf16_t* const qsrc = (TWO && q0 >= kwin) ? seq2 : seq1;
+  const bf16_t* qbase = qsrc + head * 64;
+  const bf16_t* gbase = qsrc + d_model + head * 64;
+  const bf16_t* kbase = seq1 + 2 * d_model + kvh * 64;
   const bf16_t* vbase = kbase + gqa;
-  const int nkt = (S + SWP_KB - 1) / SWP_KB;
+  const bf16_t* kbase2 = seq2 + 2 * d_model + kvh * 64;
+  const bf16_t* vbase2 = kbase2 + gqa;
+  int nkt = (Sk + SWP_KB - 1) / SWP_KB;
 
   // K / V staging by LDS-DMA as in k_attn_bf16: lane >> 3 picks the row of an 8-row piece,
   // lane & 7 the 16-byte LDS chunk; the XOR swizzles are applied on the global side (K chunk c holds global chunk
@@ -119,27 +144,27 @@ __global__ __launch_bounds__(256, SWP_OCC) void k_attn_swp(const bf16_t* __restr
   // One operand tile = two DMA instructions per wave into ring slot slot_; tiles past the sequence's end are not issued (SWP_TOP
   // counts accordingly).  The tile is a SCALAR base, the lane's share of it one constant offset; only a sequence's last, partial
   // tile computes clamped rows on the vector unit.
-#define SWP_DMA_TILE(base_, lds_, kt_, slot_, d_, c_)                                                            \
+#define SWP_DMA_TILE(base_, base2_, lds_, kt_, slot_, d_, c_)                                                    \
   do {                                                                                                           \
     const int key0__ = (kt_) * SWP_KB;                                                                           \
-    if (key0__ >= S) break;                                                                                      \
-    const bf16_t* b__ = (base_) + (size_t)key0__ * ld;                                                           \
+    if (key0__ >= Sk) break;                                                                                     \
+    const bf16_t* b__ = ((TWO && key0__ >= kwin) ? (base2_) : (base_)) + (size_t)key0__ * ld;                    \
     const uint32_t dst__ = (lds_) + (slot_) * (SWP_KB * 128) + wave * 1024;                                      \
-    if (key0__ + SWP_KB <= S) {                                                                                  \
+    if (key0__ + SWP_KB <= Sk) {                                                                                 \
       const bf16_t* b32__ = b__ + (size_t)32 * ld;                                                               \
       unsigned keep__;                                                                                           \
       asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"         \
                    "s_add_u32 m0, %4, 0x1000\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"      \
                    : "=&s"(keep__) : "v"(d_), "s"(b__), "s"(b32__), "s"(dst__) : "memory", "scc");                   \
     } else {                                                                                                     \
-      const int lim__ = S - 1 - key0__;                                                                          \
+      const int lim__ = Sk - 1 - key0__;                                                                         \
       const int g0__ = drow < lim__ ? drow : lim__, g1__ = drow + 32 < lim__ ? drow + 32 : lim__;                \
       SWP_DMA16((uint32_t)(g0__ * ld + (c_)) * 2u, b__, dst__);                                                  \
       SWP_DMA16((uint32_t)(g1__ * ld + (c_)) * 2u, b__, dst__ + 4096);                                           \
     }                                                                                                            \
   } while (0)
-#define SWP_DMA_K(kt_, slot_) SWP_DMA_TILE(kbase, kl_lds, kt_, slot_, dK, kc)
-#define SWP_DMA_V(kt_, slot_) SWP_DMA_TILE(vbase, vl_lds, kt_, slot_, dV, vc)
+#define SWP_DMA_K(kt_, slot_) SWP_DMA_TILE(kbase, kbase2, kl_lds, kt_, slot_, dK, kc)
+#define SWP_DMA_V(kt_, slot_) SWP_DMA_TILE(vbase, vbase2, vl_lds, kt_, slot_, dV, vc)
 
   // ---- prologue, part 1: K(0), V(0), K(1), K(2), V(1) in flight before anything is waited for; then Q ----
   SWP_DMA_K(0, 0);
@@ -226,13 +251,13 @@ __global__ __launch_bounds__(256, SWP_OCC) void k_attn_swp(const bf16_t* __restr
   // keys past the end of the sequence (only in the last tile, only when S is not a multiple of 64)
 #define SWP_MASK(c0_, c1_, kt_)                                                                                  \
   do {                                                                                                           \
-    if ((kt_) == nkt - 1 && nkt * SWP_KB > S) {                                                                  \
+    if ((kt_) == nkt - 1 && nkt * SWP_KB > Sk) {                                                                 \
       int h4__ = 4 * h;                                                                                          \
       asm volatile("" : "+v"(h4__));      /* computed here, once per sequence: not 32 loop-invariant lane masks in SGPRs */ \
       _Pragma("unroll") for (int e__ = 0; e__ < 16; ++e__) {                                                     \
         const int key__ = (kt_) * SWP_KB + (e__ & 3) + 8 * (e__ >> 2) + h4__;                                    \
-        if (key__ >= S) c0_[e__] = -INFINITY;                                                                    \
-        if (key__ + 32 >= S) c1_[e__] = -INFINITY;                                                               \
+        if (key__ >= Sk) c0_[e__] = -INFINITY;                                                                   \
+        if (key__ + 32 >= Sk) c1_[e__] = -INFINITY;                                                              \
       }                                                                                                          \
     }                                                                                                            \
   } while (0)
@@ -297,7 +322,7 @@ __global__ __launch_bounds__(256, SWP_OCC) void k_attn_swp(const bf16_t* __restr
     SWP_GAPS4(2);                                                                                                \
     SWP_STAMP(2);                                                                                                \
     l_run += sum_a + sum_b;                                                                                      \
-    if (tt__ + 1 == nkt - 1 && nkt * SWP_KB > S) {                                                               \
+    if (tt__ + 1 == nkt - 1 && nkt * SWP_KB > Sk) {                                                              \
       asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" ::: "memory");     /* S(t+1)'s last MFMA may still be writing */ \
       SWP_MASK(nxt0_, nxt1_, tt__ + 1);                                                                          \
     }                                                                                                            \
@@ -385,9 +410,36 @@ __global__ __launch_bounds__(256, SWP_OCC) void k_attn_swp(const bf16_t* __restr
 #endif
 
   // ---- the row sums say whether the reference-free exponents were in range; otherwise the whole block again, exactly ----
+  if constexpr (MODE == 2 || MODE == 3) {
+    // the raw state of this (query block behind kwin, q-head): dumped by the builder, added here
+    const int item = (MODE == 2 ? q0 : q0 - kwin) / 128 * (d_model >> 6) + head;
+    float* const st = state + (size_t)item * SWP_STATE;
+    if (MODE == 2) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        *reinterpret_cast<f32x4*>(st + (j * 256 + tid) * 4) = (f32x4){o0[4 * j], o0[4 * j + 1], o0[4 * j + 2], o0[4 * j + 3]};
+        *reinterpret_cast<f32x4*>(st + ((4 + j) * 256 + tid) * 4) = (f32x4){o1[4 * j], o1[4 * j + 1], o1[4 * j + 2], o1[4 * j + 3]};
+      }
+      st[8 * 1024 + tid] = l_run;
+      const float lt = l_run + __shfl_xor(l_run, 32, 64);
+      if (!(lt > 8.6736174e-19f && lt < 1.1529215e18f)) *reinterpret_cast<int*>(state + (size_t)gridDim.x * SWP_STATE) = 1;
+      return;
+    }
+    if (cached) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const f32x4 c0 = *reinterpret_cast<const f32x4*>(st + (j * 256 + tid) * 4);
+        const f32x4 c1 = *reinterpret_cast<const f32x4*>(st + ((4 + j) * 256 + tid) * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { o0[4 * j + e] += c0[e]; o1[4 * j + e] += c1[e]; }
+      }
+      l_run += st[8 * 1024 + tid];
+    }
+  }
   float l_tot = l_run + __shfl_xor(l_run, 32, 64);
   const bool out_of_range = !(l_tot > 8.6736174e-19f && l_tot < 1.1529215e18f);       // [2^-60, 2^60]; NaN fails both
   if (__syncthreads_or(out_of_range)) {
+    if constexpr (MODE == 3) { Sk = S; nkt = (S + SWP_KB - 1) / SWP_KB; }       // a cached block: every key again
     // Exact online softmax (running maximum per tile, rescale on every change), one tile at a time through ring slot 0: any score
     // range the fp32 exponent can express.  Rare by construction (|exponent| beyond ~60 somewhere in the block's rows).
     float m_run = -INFINITY;
@@ -479,17 +531,48 @@ __global__ __launch_bounds__(256, SWP_OCC) void k_attn_swp(const bf16_t* __restr
 #endif
 }
 
+template <bool GATE, int MODE>
+__global__ __launch_bounds__(256, SWP_OCC) void k_attn_swp(const bf16_t* __restrict__ qkvg, int ld, bf16_t* __restrict__ out, int ldo,
+                                                     const int* __restrict__ cu, const int* __restrict__ qblocks, int d_model, int gqa,
+                                                     int rep, long long* __restrict__ stamps, const bf16_t* __restrict__ rows2, int kwin,
+                                                     float* state) {
+  __shared__ __attribute__((aligned(16))) uint4 kl[SWP_NS][SWP_KB * 8];
+  __shared__ __attribute__((aligned(16))) uint4 vl[SWP_NS][SWP_KB * 8];
+  if constexpr (MODE == 3) {
+    if (qblocks[4 * blockIdx.x + 1] >= kwin) swp_body<GATE, 3>(qkvg, ld, out, ldo, cu, qblocks, d_model, gqa, rep, stamps, rows2, kwin, state, kl, vl);
+    else swp_body<GATE, 1>(qkvg, ld, out, ldo, cu, qblocks, d_model, gqa, rep, stamps, rows2, kwin, state, kl, vl);
+  } else {
+    swp_body<GATE, MODE>(qkvg, ld, out, ldo, cu, qblocks, d_model, gqa, rep, stamps, rows2, kwin, state, kl, vl);
+  }
+}
+
 // Launcher: called by ttvk_attention for bf16 tables of full items with pre-scaled q and no tape outputs.
 int ttvk_attention_swp(const void* qkvg, int ld, void* out, int ldo, const int* cu_seqlens, const int* qblocks, int n_qblocks,
-                       int q_heads, int kv_heads, int gate_mul, hipStream_t s) {
+                       int q_heads, int kv_heads, int gate_mul, hipStream_t s, const void* rows2, int kwin, const float* state) {
   const int d_model = q_heads * 64, gqa = kv_heads * 64, rep = q_heads / kv_heads;
   dim3 grid(n_qblocks);
-  if (gate_mul)
-    hipLaunchKernelGGL((k_attn_swp<true>), grid, dim3(256), 0, s, (const bf16_t*)qkvg, ld, (bf16_t*)out, ldo, cu_seqlens, qblocks, d_model,
-                       gqa, rep, g_ttv_stamps);
-  else
-    hipLaunchKernelGGL((k_attn_swp<false>), grid, dim3(256), 0, s, (const bf16_t*)qkvg, ld, (bf16_t*)out, ldo, cu_seqlens, qblocks, d_model,
-                       gqa, rep, g_ttv_stamps);
+  TTV_CHECK_ARG(!rows2 || (kwin > 0 && kwin % 128 == 0 && (uintptr_t)rows2 % 16 == 0), "attention_swp: the second source starts at a multiple of 128 rows");
+  TTV_CHECK_ARG(!state || (rows2 && (uintptr_t)state % 16 == 0), "attention_swp: the cached state comes with the second source");
+#define SWP_LAUNCH(G_, M_)                                                                                                       \
+  hipLaunchKernelGGL((k_attn_swp<G_, M_>), grid, dim3(256), 0, s, (const bf16_t*)qkvg, ld, (bf16_t*)out, ldo, cu_seqlens, qblocks, d_model, \
+                     gqa, rep, g_ttv_stamps, (const bf16_t*)rows2, kwin, const_cast<float*>(state))
+  if (state) { if (gate_mul) SWP_LAUNCH(true, 3); else SWP_LAUNCH(false, 3); }
+  else if (rows2) { if (gate_mul) SWP_LAUNCH(true, 1); else SWP_LAUNCH(false, 1); }
+  else if (gate_mul) SWP_LAUNCH(true, 0);
+  else SWP_LAUNCH(false, 0);
+#undef SWP_LAUNCH
   TTV_CHECK_LAUNCH("attention_swp");
+  return TTV_OK;
+}
+
+// The builder's launch (k_attn_swp MODE 2): rows [n_rows, ld] as one sequence, one block per (128-row query block, q-head); writes
+// ttvk_attention_swp_state_floats(...) floats of state and, behind them, the int32 "a row sum left the window" flag (zero it first).
+int64_t ttvk_attention_swp_state_floats(int n_rows, int q_heads) { return (int64_t)(n_rows / 128) * q_heads * SWP_STATE; }
+int ttvk_attention_swp_dump(const void* rows, int ld, int n_rows, int q_heads, int kv_heads, float* state, hipStream_t s) {
+  TTV_CHECK_ARG(rows && state && n_rows > 0 && n_rows % 128 == 0 && (uintptr_t)state % 16 == 0 && (uintptr_t)rows % 16 == 0, "attention_swp_dump: whole 128-row blocks");
+  const int d_model = q_heads * 64, gqa = kv_heads * 64, rep = q_heads / kv_heads;
+  hipLaunchKernelGGL((k_attn_swp<false, 2>), dim3(n_rows / 128 * q_heads), dim3(256), 0, s, (const bf16_t*)rows, ld, (bf16_t*)nullptr, 0,
+                     (const int*)nullptr, (const int*)nullptr, d_model, gqa, rep, (long long*)nullptr, (const bf16_t*)nullptr, n_rows, state);
+  TTV_CHECK_LAUNCH("attention_swp_dump");
   return TTV_OK;
 }

@@ -54,6 +54,7 @@ struct GemmDev {
   int clip0, pt_shift, ph_shift;   // log2(patch_t), log2(patch_h); patch_w == 8
   long long* stamps;               // diagnostic builds only (-DQKV_STAMPS): g_ttv_stamps
   int resid_rows;                  // EPI_BIAS_RESID_F32R: residual row = token % resid_rows (0: token)
+  int tile_run, tile_period;       // k_qkv256: item tile t is token tile (t / tile_run) * tile_period + t % tile_run (tile_period 0: t)
 };
 
 // per-token part of a patch destination (EPI_STORE_PATCH), computed once per token tile
@@ -2065,12 +2066,23 @@ static int gemm_token_tile(int M, int nf, int debug) {
   return cost160 < cost128 ? 160 : 128;
 }
 
+static int sw_qkv256() { static const int v = ttv_env_int("TTV_QKV256", 1); return v; }
+// Does a bf16 K = 256 to_qkv of N = 2 d_model + 2 gqa_dim outputs run on k_qkv256, the one kernel that takes a tile list?  (launch()'s own
+// conditions; neither bias, scalar nor row scale on that call.)
+bool ttvk_gemm_qkv_tiles_supported(int d_model, int gqa_dim, int ldw) {
+  const int N = 2 * d_model + 2 * gqa_dim;
+  return sw_qkv256() == 1 && !(g_ttv_debug & (TTV_DBG_QKV256_OFF | TTV_DBG_QKV256_WS)) && N % 64 == 0 && d_model % 64 == 0 && gqa_dim % 64 == 0 &&
+         (uint64_t)N * (uint64_t)ldw * 2u < (1ull << 32);
+}
+
 template <int EPI>
 static int launch(const GemmDev& d, int dtype, bool prenorm, hipStream_t s) {
   // debug bit 16384 (diagnostics): send a K = 256 GEMM through the general-K kernels instead (no folded pre-norm, no patch scatter there)
   if (dtype == TTV_BF16 && d.K == 256 && d.N % 8 == 0 && !((d.debug & TTV_DBG_K256_GENERAL) && !prenorm && EPI != EPI_STORE_PATCH)) {
     const int fo = (EPI == EPI_GEGLU) ? 32 : 64;
-    const int n_panels = ttv_cdiv(d.N, fo), n_tiles = ttv_cdiv(d.M, K256_TT);
+    // (a tile list - GemmArgs.tile_run / tile_period - counts the listed tiles only: with one item per block below 512 items, the 32 x 12
+    // items of the decoder's latent tiles at the benchmark batch are 384 co-resident blocks on the 256 CUs)
+    const int n_panels = ttv_cdiv(d.N, fo), n_tiles = d.tile_period ? d.M / K256_TT / d.tile_period * d.tile_run : ttv_cdiv(d.M, K256_TT);
     const int total = n_panels * n_tiles;
     // 2 co-resident blocks per CU = 512 slots.  Blocks take contiguous (tile, panel) item ranges and reload their token rows
     // whenever a range crosses into the next tile (-5 us of 34.6 with that reload knocked out).  With an item count per block that
@@ -2089,12 +2101,12 @@ static int launch(const GemmDev& d, int dtype, bool prenorm, hipStream_t s) {
     // has (30.3 us against k_gemm_k256's 31.2 inside the benchmark forward, profiles/r04_qkv256_inpipe.txt).  TTV_QKV256=0 / ttv_debug_set
     // bit 15 (32768): k_gemm_k256's QKV instantiation; TTV_QKV256=2 / bit 17 (131072): the weight-stationary kernel k_qkv256ws
     // (ttv_qkv256ws.inc; 34.2 us: measured, kept for A/B) - all three give the same bits without the folded pre-norm
-    static const int qkv256_env = ttv_env_int("TTV_QKV256", 1);
+    const int qkv256_env = sw_qkv256();
     if constexpr (EPI == EPI_QKV_ROPE) {
       const int n_groups = (n_panels + 3) / 4;
       if (qkv256_env && !(d.debug & TTV_DBG_QKV256_OFF) && d.N % 64 == 0 && d.rope_q_end % 64 == 0 && d.rope_k_begin % 64 == 0 && d.rope_k_end % 64 == 0 &&
           !d.row_scale && !d.bias && !d.add_scalar && (uint64_t)d.w_rows * (uint64_t)d.ldw * 2u < (1ull << 32)) {
-        if ((qkv256_env >= 2 || (d.debug & TTV_DBG_QKV256_WS)) && n_groups <= 32) {
+        if ((qkv256_env >= 2 || (d.debug & TTV_DBG_QKV256_WS)) && n_groups <= 32 && !d.tile_period) {
           // one block per CU: blocks b, b + 8, .. (one XCD under round-robin dispatch) share an eighth of the 32-token groups, split between
           // the panel groups; no more blocks than there are units for
           const int tgs = ttv_cdiv(d.M, 32), per_xcd = ttv_cdiv(tgs, 8);
@@ -2110,6 +2122,10 @@ static int launch(const GemmDev& d, int dtype, bool prenorm, hipStream_t s) {
         TTV_CHECK_LAUNCH("qkv256");
         return TTV_OK;
       }
+    }
+    if (d.tile_period) {
+      ttv_set_error("gemm: a tile list needs k_qkv256 (ttvk_gemm_qkv_tiles_supported)");
+      return TTV_ERR_UNSUPPORTED;
     }
     if (prenorm) hipLaunchKernelGGL((k_gemm_k256<EPI, true>), dim3(grid), dim3(256), 0, s, d, n_panels, total);
     else hipLaunchKernelGGL((k_gemm_k256<EPI, false>), dim3(grid), dim3(256), 0, s, d, n_panels, total);
@@ -2265,6 +2281,12 @@ int ttvk_gemm(GemmEpilogue epi, const GemmArgs& a, hipStream_t s) {
   d.row_scale = a.row_scale;
   d.stamps = g_ttv_stamps;
   d.resid_rows = a.resid_rows;
+  d.tile_run = d.tile_period = 0;
+  if (a.tile_period) {
+    TTV_CHECK_ARG(epi == EPI_QKV_ROPE && a.dtype == TTV_BF16 && a.K == 256 && a.tile_run > 0 && a.tile_run < a.tile_period &&
+                  a.M % (K256_TT * a.tile_period) == 0, "gemm: a tile list is a to_qkv option of the bf16 K=256 kernel, M a whole number of periods");
+    d.tile_run = a.tile_run; d.tile_period = a.tile_period;
+  }
   TTV_CHECK_ARG(!a.row_scale || ((a.dtype == TTV_BF16 || a.split3) && (epi == EPI_STORE || epi == EPI_QKV_ROPE || epi == EPI_GEGLU)),
                 "gemm: row_scale is a STORE / QKV_ROPE / GEGLU option of the bf16 and the split-bf16 kernels");
   TTV_CHECK_ARG(!a.x_rows || (a.dtype == TTV_BF16 && a.K == 256 && a.N % 8 == 0 && epi != EPI_RESID_NORM), "gemm: x_rows needs the bf16 K=256 kernel");

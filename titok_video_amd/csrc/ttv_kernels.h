@@ -100,6 +100,9 @@ struct GemmArgs {
   const int* row_seq;              // device [L]
   int patch_t, patch_h, patch_w;   // powers of two; patch_w * sizeof(bf16) == 16
   int resid_rows;                  // EPI_BIAS_RESID_F32R: the residual row of GEMM row t is t % resid_rows (0: t)
+  // optional (EPI_QKV_ROPE on k_qkv256 only): of every tile_period consecutive 128-row token tiles only the first tile_run are computed
+  // and stored, rows and outputs in place; the other rows of y are not touched.  0 / 0: every tile.  M % (128 * tile_period) == 0.
+  int tile_run, tile_period;
 };
 struct ClipPtrs { void* p[TTV_MAX_CLIPS_PER_LAUNCH]; };
 int ttvk_gemm(GemmEpilogue epi, const GemmArgs& a, hipStream_t s);
@@ -107,6 +110,7 @@ int ttvk_gemm(GemmEpilogue epi, const GemmArgs& a, hipStream_t s);
 int ttvk_gemm_fp8(GemmEpilogue epi, const GemmArgs& a, const float* x_scale, const float* w_scale, hipStream_t s, const void* x_mx = nullptr,
                   const void* w_mx = nullptr);
 bool ttvk_gemm_supports_resid_norm(int dtype, int N, int K);
+bool ttvk_gemm_qkv_tiles_supported(int d_model, int gqa_dim, int ldw);   // GemmArgs.tile_run / tile_period: will this to_qkv take them?
 
 // ---- ttv_attn.hip ----
 int ttvk_attention(const void* qkvg, int ld, void* out, int ldo, const int* cu_seqlens, const int* qblocks, int n_qblocks,
@@ -114,8 +118,14 @@ int ttvk_attention(const void* qkvg, int ld, void* out, int ldo, const int* cu_s
                    void* out_raw = nullptr);
 
 // bf16 tables of full items, pre-scaled q, no tape outputs: the software-pipelined kernel (ttv_attn_swp.hip); ttvk_attention dispatches
+bool ttvk_attention_takes_swp(int flags);
+// rows2 / kwin (optional): rows [kwin, S) of every sequence are read from rows2 [S - kwin, ld] instead of from qkvg; state (optional, with
+// rows2): what ttvk_attention_swp_dump wrote for rows2 - query blocks behind kwin loop over the keys [0, kwin) and add it (see k_attn_swp)
 int ttvk_attention_swp(const void* qkvg, int ld, void* out, int ldo, const int* cu_seqlens, const int* qblocks, int n_qblocks,
-                       int q_heads, int kv_heads, int gate_mul, hipStream_t s);
+                       int q_heads, int kv_heads, int gate_mul, hipStream_t s, const void* rows2 = nullptr, int kwin = 0,
+                       const float* state = nullptr);
+int64_t ttvk_attention_swp_state_floats(int n_rows, int q_heads);
+int ttvk_attention_swp_dump(const void* rows, int ld, int n_rows, int q_heads, int kv_heads, float* state, hipStream_t s);
 int ttvk_attention_mxout(const void* qkvg, int ld, void* out_q, void* out_mx, int ld_mx, const int* cu_seqlens, const int* qblocks,
                          int n_qblocks, int q_heads, int kv_heads, hipStream_t s);
 

@@ -251,7 +251,9 @@ __global__ __launch_bounds__(256, 2) void k_qkv256(GemmDev p, int n_panels, int 
       cur_tile = tile__;                                                                                     \
       /* the new rows are requested first: the epilogue owed to the previous tile (it needs that tile's factors and addresses) */ \
       /* runs under their latency */                                                                         \
-      const int t0__ = tile__ * K256_TT + wave * 32;                                                         \
+      /* a tile list (GemmDev.tile_run / tile_period): item tile -> token tile, rows and outputs in place */  \
+      const int ttile__ = p.tile_period ? (tile__ / p.tile_run) * p.tile_period + tile__ % p.tile_run : tile__; \
+      const int t0__ = ttile__ * K256_TT + wave * 32;                                                        \
       int ntk__ = t0__ + r;                                                                                  \
       const bool nok__ = ntk__ < p.M;                                                                        \
       ntk__ = nok__ ? ntk__ : p.M - 1;                                                                       \

@@ -483,6 +483,7 @@ class _WeightPack:
         self.keep = keep
         self.kind, self.n_layers = tower.kind, n
         self._t = None
+        self._l0_const = {}                            # clip geometry -> the decoder's constant block (dec_l0_const)
         if self.device.type == "cuda":
             self.build_stream = torch.cuda.current_stream(self.device)
             self.ready = torch.cuda.Event()
@@ -497,6 +498,50 @@ class _WeightPack:
         if cur != self.build_stream and cur.cuda_stream not in self.reader_streams:
             cur.wait_event(self.ready)
         self.reader_streams[cur.cuda_stream] = cur
+
+    def dec_l0_const(self, dims: "_lib.TowerDims", plan: BatchPlan) -> Optional["_lib.DecL0Const"]:
+        """The decoder's constant block for this plan's clip geometry (ttv_dec_l0_const: layer 0's q | gate | k | v of the patch rows,
+        which enter the tower as ln_pre_p(mask_token) whatever the input, and the attention kernel's raw sums over those keys), or
+        None where there is none: clips of several geometries, a latent or patch count that is no multiple of 128, a tower without the
+        width-256 bf16 kernels.  One per geometry, built on first use by the forward's own kernels on the pack's stream (one host sync
+        there, for the builder's range flag) and dropped with the pack, i.e. on any weight-version change."""
+        geo = plan.uniform_geometry()
+        if geo is None or self.kind != _lib.TTV_DECODER or self.device.type != "cuda":
+            return None
+        if geo in self._l0_const:
+            ent = self._l0_const[geo]
+        else:
+            k, p = plan.token_counts[0], plan.grid_sizes[0]
+            need = _lib.lib().ttv_dec_l0_const_bytes(C.byref(dims), p) if (k > 0 and k % 128 == 0 and p % 128 == 0 and self.q_prescaled) else -1
+            ent = None
+            if need > 0:
+                with torch.cuda.stream(self.build_stream):       # behind `ready`: the folded weights are queued on this stream
+                    plan.use_on_current_stream()
+                    block = torch.empty(int(need), dtype=torch.uint8, device=self.device)
+                    iota = torch.arange(p, dtype=torch.int32, device=self.device)
+                    cs, ids, base = plan.clip0_patch_rope()
+                    so, fo = C.c_int64(0), C.c_int64(0)
+                    rc = _lib.lib().ttv_dec_l0_const_build(C.byref(dims), C.byref(self.struct), iota.data_ptr(), cs, ids, base, p,
+                                                           block.data_ptr(), block.numel(), C.byref(so), C.byref(fo), _lib.stream_ptr(self.device))
+                    _lib.check(rc, "ttv_dec_l0_const_build")
+                    out_of_window = int(block[fo.value:fo.value + 4].view(torch.int32).item()) != 0      # (waits for the builder)
+                    done = torch.cuda.Event()
+                    done.record(self.build_stream)
+                state = None if out_of_window else block.data_ptr() + so.value
+                ent = dict(rows=block.data_ptr(), latent_rows=k, patch_rows=p, state=state, keep=(block, iota), done=done, seen=set(), structs={})
+            self._l0_const[geo] = ent
+        if ent is None:
+            return None
+        cur = torch.cuda.current_stream(self.device)
+        if cur != self.build_stream and cur.cuda_stream not in ent["seen"]:
+            cur.wait_event(ent["done"])
+            ent["seen"].add(cur.cuda_stream)
+        hit = ent["structs"].get(id(plan))       # (per plan: the work table's clip count is the plan's; the entry keeps the plan alive)
+        if hit is None:
+            table = plan.attention_table_l0(int(dims.q_heads), int(dims.kv_heads))
+            hit = ent["structs"][id(plan)] = (_lib.DecL0Const(rows=ent["rows"], latent_rows=ent["latent_rows"], patch_rows=ent["patch_rows"],
+                                                              state=ent["state"], qblocks=table.data_ptr(), n_qblocks=int(table.shape[0])), plan)
+        return hit[0]
 
     def transposed(self) -> "_lib.TowerWeightsT":
         """W^T copies for the data-gradient GEMMs of the backward pass (built on first use, per weight version)."""
@@ -623,8 +668,11 @@ class TiTokDecoder(_Tower):
             outs.append(flat[off:off + n].view(self.out_channels, t, h, w))
             off += n
         batch = plan.batch_for(self.heads[0], self.heads[1])
-        rc = _lib.lib().ttv_decoder_forward(C.byref(dims), C.byref(pack.struct), C.byref(batch), tokens.data_ptr(),
-                                            _lib.ptr_array(outs), ws.data_ptr(), ws.numel(), _lib.stream_ptr(device))
+        # (the no-grad entry only: the training forward records every row on its tape)
+        l0 = pack.dec_l0_const(dims, plan)
+        rc = _lib.lib().ttv_decoder_forward_const(C.byref(dims), C.byref(pack.struct), C.byref(batch), tokens.data_ptr(),
+                                                  _lib.ptr_array(outs), ws.data_ptr(), ws.numel(), C.byref(l0) if l0 is not None else None,
+                                                  _lib.stream_ptr(device))
         _lib.check(rc, "ttv_decoder_forward")
         return outs
 

@@ -394,6 +394,40 @@ class BatchPlan:
             self._attn[key] = t
         return self._attn[key]
 
+    def attention_table_l0(self, q_heads: int, kv_heads: int) -> torch.Tensor:
+        """int32 [n,4] attention work table like `attention_table` (full items only) for the decoder's layer 0 with a constant block
+        (`ttv_dec_l0_const.qblocks`): every XCD list holds the LATENT query blocks of its (sequence, kv-head) units first - they loop over
+        every key - and the patch query blocks, which loop over the latent keys only, behind them, so the long items start first."""
+        key = ("l0", int(q_heads), int(kv_heads))
+        t = self._attn.get(key)
+        if t is None:
+            rep = q_heads // kv_heads
+            lat, pat = [], []
+            for b in range(len(self.grids)):
+                s = self.cu_seqlens[b + 1] - self.cu_seqlens[b]
+                nq, first = -(-s // QBLOCK), int(self.token_counts[b]) // QBLOCK
+                for kvh in range(kv_heads):
+                    lat.append([(b, qb * QBLOCK, kvh * rep + r, 0) for qb in range(first) for r in range(rep)])
+                    pat.append([(b, qb * QBLOCK, kvh * rep + r, 0) for qb in range(first, nq) for r in range(rep)])
+            order = sorted(range(len(lat)), key=lambda i: len(lat[i]) + len(pat[i]), reverse=True)
+            first_l, then_l, weight = [[] for _ in range(8)], [[] for _ in range(8)], [0] * 8
+            for i in order:
+                x = min(range(8), key=lambda j: weight[j])
+                first_l[x].extend(lat[i])
+                then_l[x].extend(pat[i])
+                weight[x] += len(lat[i]) + len(pat[i])
+            lists = [a + b for a, b in zip(first_l, then_l)]
+            depth = max(len(l) for l in lists)
+            table = np.full((depth, 8, 4), -1, dtype=np.int32)
+            for x, l in enumerate(lists):
+                if l:
+                    table[: len(l), x, :] = np.asarray(l, dtype=np.int32)
+            flat = table.reshape(-1, 4)
+            last = int(np.max(np.nonzero(flat[:, 0] >= 0)[0])) + 1
+            t = _upload(np.ascontiguousarray(flat[:last]), self.device)
+            self._attn[key] = t
+        return t
+
     def attention_table64(self, q_heads: int, kv_heads: int) -> torch.Tensor:
         """int32 [n,8] work table of ttv_attention64 (the 64-query-rows-per-wave kernel): one entry per workgroup =
         (sequence, kv-head, 4 x wave item, first packed row of the sequence, its length); a wave item is
@@ -464,6 +498,21 @@ class BatchPlan:
                           qblocks_patch=tp.data_ptr() if tp is not None else None, n_qblocks_patch=int(tp.shape[0]) if tp is not None else 0,
                           **self._base_fields)
         return out
+
+    def uniform_geometry(self) -> Optional[tuple]:
+        """(patch grid, latent count, rotary id table size) when every clip of the batch has the same patch grid and latent count, else
+        None: what the rows of a decoder's constant block (ttv_dec_l0_const) depend on besides the weights."""
+        g, k = self.grids[0], self.token_counts[0]
+        if any(gb != g for gb in self.grids) or any(kb != k for kb in self.token_counts):
+            return None
+        return (g, k, self.n_rope_ids)
+
+    def clip0_patch_rope(self) -> Tuple[int, Optional[int], Optional[int]]:
+        """Device pointers to the rotary tables of the FIRST clip's patch rows: (rope_cs rows, rope_ids rows or None, rope_base or None)."""
+        k = self.token_counts[0]
+        ids = self._base_fields.get("rope_ids")
+        return (self.rope_cs.data_ptr() + 4 * self.rope_cs.shape[1] * k, ids + 8 * k if ids else None,
+                self._base_fields.get("rope_base") if ids else None)
 
     # views used by tests that call single ops
     def table(self, i: int, n: int) -> torch.Tensor:
