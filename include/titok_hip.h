@@ -405,6 +405,85 @@ typedef struct ttv_batch {
 int ttv_rope_table_build(const float* base_cos, const float* base_sin, int n_ids, int n_freqs, const int32_t* clip_desc,
                          const int32_t* cu_seqlens, const int32_t* row_seq, float* rope_cs, int total_rows, void* stream);
 
+/* ---- batch plans: a ttv_batch without Python ---------------------------------------------------------------
+ * Everything a ttv_batch points at, from three host arrays: pixel_dims int32 [n_clips,3] = (T, H, W) of every clip, token_counts int32
+ * [n_clips] = K_b, patch int32 [3] = (pt, ph, pw).  The tables are the ones titok_video_amd/plan.py (BatchPlan) builds, element for
+ * element.  A host makes five calls per batch shape (plus one ttv_rope_base_table per table size, once):
+ *
+ *   ttv_plan_rows_sizes  -> ttv_plan_sizes (counts, word offsets)               host only
+ *   ttv_plan_rows_fill   -> the HOST SEGMENT in the caller's pinned buffer      host only
+ *   ttv_plan_rows_build  -> async copy + fill kernel + rope_cs, fills ttv_batch enqueues on `stream`
+ *   ttv_plan_attn_sizes / ttv_plan_attn_fill -> the attention work tables of one (q_heads, kv_heads) in a pinned buffer   host only
+ *   ttv_plan_attn_set    -> async copy, sets the qblocks* fields of the ttv_batch  enqueues on `stream`
+ *
+ * The host-only calls touch no device and read no environment variable: they work where there is no GPU, like
+ * ttv_tower_workspace_bytes.  Invalid input (a null pointer, n_clips < 1, a clip dimension that is not a positive multiple of the patch,
+ * a negative token count, an empty sequence, a position id table that does not fit rope_ids' uint16 slots) returns TTV_ERR_INVALID with
+ * a message in ttv_error_string() and writes nothing.
+ *
+ * Segments are arrays of int32 words; every table in them starts 16-byte aligned (offsets are multiples of 4 words, the words between
+ * a table's end and the next table are zero in the host segment and never written in the device part).
+ *   HOST SEGMENT [host_words]: cu_seqlens [n_clips+1] | clip_desc [n_clips,8] (see ttv_patch_gather) | blocks64 [n_blocks64,2].
+ *     blocks64 = (sequence, first row) of every 64-row block for the attention backward: whole sequences are dealt over 8 lists (longest
+ *     first, stable; each to the first list with the fewest blocks), entry i comes from list i % 8 while every list has one, the rest
+ *     follows list by list (no padding entries).  bwd_xcd = 0 gives the sequence-major order instead.
+ *   DEVICE SEGMENT [dev_words]: the host segment's words at the same offsets, then latent_rows [sum_tokens] | patch_rows [sum_patches]
+ *     | row_seq [total_rows] | rope_ids [total_rows,2], written by the fill kernel from cu_seqlens and clip_desc alone.
+ * n_rope_ids is the smallest power of two that is >= 512 and > max_b(K_b + max(grid_b)). */
+typedef struct ttv_plan_sizes {
+  int32_t n_clips, total_rows, sum_tokens, sum_patches, max_patches_per_clip, max_seqlen, n_rope_ids, n_blocks64;
+  int64_t host_words;                                    /* int32 words of the host segment */
+  int64_t off_cu_seqlens, off_clip_desc, off_blocks64;   /* word offsets, the same in the host and in the device segment */
+  int64_t dev_words;                                     /* int32 words of the device segment (>= host_words) */
+  int64_t off_latent_rows, off_patch_rows, off_row_seq, off_rope_ids;   /* word offsets in the device segment */
+} ttv_plan_sizes;
+
+int ttv_plan_rows_sizes(const int32_t* pixel_dims, const int32_t* token_counts, int n_clips, const int32_t* patch, ttv_plan_sizes* sizes);
+/* host_segment: at least sizes.host_words words (given as host_words).  For ttv_plan_rows_build it must be pinned host memory. */
+int ttv_plan_rows_fill(const int32_t* pixel_dims, const int32_t* token_counts, int n_clips, const int32_t* patch, int bwd_xcd,
+                       int32_t* host_segment, int64_t host_words);
+
+/* Enqueues on `stream`: the copy of host_segment [sizes.host_words] to the head of dev_segment [sizes.dev_words, 16-byte aligned], one
+ * kernel that writes latent_rows, patch_rows, row_seq and rope_ids, and the kernel of ttv_rope_table_build for rope_cs fp32
+ * [total_rows,64] (base_cos / base_sin fp32 [n_rope_ids, n_freqs] on the DEVICE: ttv_rope_base_table's values).  Then fills *batch (a
+ * HOST struct) with the counts and the device pointers; the qblocks* fields and items64 are left NULL / 0 for ttv_plan_attn_set.
+ * rope_base: NULL (the towers read rope_cs), or the DEVICE table fp32 [n_rope_ids+1, n_freqs, 2] = (cos, sin) of ttv_rope_base_table
+ * with row n_rope_ids = (1, 0); then batch.rope_ids / rope_base are set.  No allocation and no synchronisation: the caller promises
+ * that host_segment is pinned and stays unchanged until the stream has passed the copy (an event recorded behind this call). */
+int ttv_plan_rows_build(const ttv_plan_sizes* sizes, const int32_t* host_segment, int32_t* dev_segment, const float* base_cos,
+                        const float* base_sin, int n_freqs, float* rope_cs, const float* rope_base, ttv_batch* batch, void* stream);
+
+/* The attention work tables of one (q_heads, kv_heads) (entry format: ttv_attention), int32 [words] = qblocks [n_qblocks,4] |
+ * qblocks_latent [n_qblocks_latent,4] | qblocks_patch [n_qblocks_patch,4] | the decoder's layer-0 table [n_qblocks_l0,4]
+ * (ttv_dec_l0_const.qblocks: every list holds the latent-only query blocks of its units first, the others behind them).
+ * Every table: the blocks of one (sequence, kv-head) unit share K / V, so units are dealt over 8 lists (heaviest first, stable; weight
+ * 2 * full + half items; each to the first list of least weight), a list holds the full items of its units and behind all of them
+ * their half items, entry i of the table belongs to list i % 8, shorter lists are padded with (-1,-1,-1,-1) and only the padding
+ * entries at the end of the table are dropped.  Half items: split = 1 every item, 0 never, -1 the rule - with fewer than 1024 items
+ * (sum of 128-row blocks * q_heads) the last third of every sequence's blocks, otherwise the last 1 / tail_div of them (tail_div <= 0:
+ * none).  qblocks_latent is absent (0 entries) when sum K_b = 0; qblocks_patch exists only beside a `qblocks` of full items, and only
+ * when at least one latent-only block is dropped and at least one block remains.  cu_seqlens: HOST [n_clips+1]. */
+typedef struct ttv_plan_attn {
+  int32_t n_qblocks, qblocks_all_full, n_qblocks_latent, n_qblocks_patch, n_qblocks_l0, reserved;
+  int64_t words;                                                              /* int32 words of the four tables together */
+  int64_t off_qblocks, off_qblocks_latent, off_qblocks_patch, off_qblocks_l0; /* word offsets (multiples of 4) */
+} ttv_plan_attn;
+
+int ttv_plan_attn_sizes(const int32_t* cu_seqlens, const int32_t* token_counts, int n_clips, int q_heads, int kv_heads, int split,
+                        int tail_div, ttv_plan_attn* sizes);
+int ttv_plan_attn_fill(const int32_t* cu_seqlens, const int32_t* token_counts, int n_clips, int q_heads, int kv_heads, int split,
+                       int tail_div, int32_t* host_tables, int64_t host_words);
+/* Enqueues the copy of host_tables [sizes.words] (pinned, unchanged until the stream has passed it) to dev_tables (16-byte aligned) and
+ * sets batch.qblocks / n_qblocks / qblocks_all_full / qblocks_latent / qblocks_patch and their counts; qblocks_paired = 0, items64 =
+ * NULL.  The layer-0 table is at dev_tables + off_qblocks_l0 for ttv_dec_l0_const.qblocks. */
+int ttv_plan_attn_set(const ttv_plan_attn* sizes, const int32_t* host_tables, int32_t* dev_tables, ttv_batch* batch, void* stream);
+
+/* base_cos / base_sin fp32 [n_ids, F], F = head_dim / (2 * nd): cos / sin of inv_freq[f] * n for every position id n < n_ids, evaluated
+ * as rope.py:40-54 does - float64 theta ** linspace(0, 1, F) * pi / 2 (torch's linspace: step * i below the middle, 1 - step * (F-1-i)
+ * above), float64 product with the id, cast to fp32.  Host only (libm).  ttv_batch.rope_base is these values interleaved,
+ * rope_base[n][f] = (cos[n][f], sin[n][f]), with one more row n_ids = (1, 0). */
+int ttv_rope_base_table(int head_dim, int nd, int n_ids, double theta, float* base_cos, float* base_sin);
+
 /* bytes of scratch a tower forward needs for this batch */
 int64_t ttv_tower_workspace_bytes(const ttv_tower_dims* dims, const ttv_batch* batch);
 

@@ -94,6 +94,19 @@ class Batch(C.Structure):
                 ("n_qblocks_patch", i32)]
 
 
+class PlanSizes(C.Structure):
+    _fields_ = [("n_clips", i32), ("total_rows", i32), ("sum_tokens", i32), ("sum_patches", i32), ("max_patches_per_clip", i32),
+                ("max_seqlen", i32), ("n_rope_ids", i32), ("n_blocks64", i32), ("host_words", i64), ("off_cu_seqlens", i64),
+                ("off_clip_desc", i64), ("off_blocks64", i64), ("dev_words", i64), ("off_latent_rows", i64), ("off_patch_rows", i64),
+                ("off_row_seq", i64), ("off_rope_ids", i64)]
+
+
+class PlanAttn(C.Structure):
+    _fields_ = [("n_qblocks", i32), ("qblocks_all_full", i32), ("n_qblocks_latent", i32), ("n_qblocks_patch", i32), ("n_qblocks_l0", i32),
+                ("reserved", i32), ("words", i64), ("off_qblocks", i64), ("off_qblocks_latent", i64), ("off_qblocks_patch", i64),
+                ("off_qblocks_l0", i64)]
+
+
 class DecL0Const(C.Structure):
     _fields_ = [("rows", vp), ("latent_rows", i32), ("patch_rows", i32), ("state", vp), ("qblocks", vp), ("n_qblocks", i32)]
 
@@ -231,6 +244,13 @@ SYMBOLS = {
     "ttv_attention_lse": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "ttv_codebook_histogram": (C.c_int, [vp, C.c_int, vp, C.c_int, vp]),
     "ttv_rope_table_build": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp]),
+    "ttv_plan_rows_sizes": (C.c_int, [vp, vp, C.c_int, vp, C.POINTER(PlanSizes)]),
+    "ttv_plan_rows_fill": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, i64]),
+    "ttv_plan_rows_build": (C.c_int, [C.POINTER(PlanSizes), vp, vp, vp, vp, C.c_int, vp, vp, C.POINTER(Batch), vp]),
+    "ttv_plan_attn_sizes": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PlanAttn)]),
+    "ttv_plan_attn_fill": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64]),
+    "ttv_plan_attn_set": (C.c_int, [C.POINTER(PlanAttn), vp, vp, C.POINTER(Batch), vp]),
+    "ttv_rope_base_table": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, vp, vp]),
     "ttv_l1_loss": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp]),
     "ttv_clip_from_u8": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "ttv_clip_resample_u8": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),

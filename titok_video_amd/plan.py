@@ -535,19 +535,237 @@ class BatchPlan:
         return self.table(3, 8 * len(self.grids))
 
 
+# ---- the same plan built by the library (ttv_plan_* of include/titok_hip.h): TTV_NATIVE_PLAN=1 -------------------------------------------
+def _i32s(values) -> "C.Array":
+    return (C.c_int32 * len(values))(*values)
+
+
+def _split_code(split: Optional[bool]) -> int:
+    return -1 if split is None else (1 if split else 0)
+
+
+def native_host_tables(pixel_grids, token_counts, patch, q_heads: int, kv_heads: int, split: Optional[bool] = None, tail_div: int = 0,
+                       bwd_xcd: bool = True) -> dict:
+    """The library's host-only plan calls (no device): the sizes, the host segment's tables and the attention work tables of one
+    (q_heads, kv_heads) as numpy arrays.  What a C host computes before it touches the GPU; tests/test_native_plan_cpu.py holds it to
+    BatchPlan, tools/plan_host_time.py times it."""
+    lib = _lib.lib()
+    n = len(pixel_grids)
+    dims, counts, pt = _i32s([int(v) for g in pixel_grids for v in g]), _i32s([int(k) for k in token_counts]), _i32s([int(p) for p in patch])
+    sz = _lib.PlanSizes()
+    _lib.check(lib.ttv_plan_rows_sizes(dims, counts, n, pt, C.byref(sz)), "ttv_plan_rows_sizes")
+    seg = np.empty(int(sz.host_words), dtype=np.int32)
+    _lib.check(lib.ttv_plan_rows_fill(dims, counts, n, pt, 1 if bwd_xcd else 0, seg.ctypes.data, seg.size), "ttv_plan_rows_fill")
+    cu = seg[sz.off_cu_seqlens: sz.off_cu_seqlens + n + 1]
+    az = _lib.PlanAttn()
+    args = (cu.ctypes.data, counts, n, int(q_heads), int(kv_heads), _split_code(split), int(tail_div))
+    _lib.check(lib.ttv_plan_attn_sizes(*args, C.byref(az)), "ttv_plan_attn_sizes")
+    tab = np.empty(int(az.words), dtype=np.int32)
+    _lib.check(lib.ttv_plan_attn_fill(*args, tab.ctypes.data, tab.size), "ttv_plan_attn_fill")
+
+    def part(off, entries):
+        return tab[off: off + 4 * entries].reshape(-1, 4) if entries else None
+    out = {k: int(getattr(sz, k)) for k, _ in _lib.PlanSizes._fields_}
+    out.update(cu_seqlens=cu, clip_desc=seg[sz.off_clip_desc: sz.off_clip_desc + 8 * n].reshape(n, 8),
+               blocks64=seg[sz.off_blocks64: sz.off_blocks64 + 2 * sz.n_blocks64].reshape(-1, 2), host_segment=seg,
+               qblocks=part(az.off_qblocks, az.n_qblocks), qblocks_all_full=int(az.qblocks_all_full),
+               qblocks_latent=part(az.off_qblocks_latent, az.n_qblocks_latent), qblocks_patch=part(az.off_qblocks_patch, az.n_qblocks_patch),
+               qblocks_l0=part(az.off_qblocks_l0, az.n_qblocks_l0))
+    return out
+
+
+_STAGE_MAX_SLOTS = 64       # pinned staging buffers per device (64 KiB each unless a segment is larger): a training step takes ~6, and the host runs several steps ahead of the GPU
+_STAGE_MIN_WORDS = 1 << 14
+
+
+class _StageRing:
+    """Pinned host buffers for the segments the library copies to the device (ttv_plan_rows_build, ttv_plan_attn_set).  The copy is only
+    queued when the call returns, so a slot carries the event recorded behind its copy and is rewritten only once that event has
+    completed (as optim._Tables guards its slots).  A busy oldest slot is not waited for: the ring grows up to _STAGE_MAX_SLOTS, and
+    only a host that is that many segments ahead of the GPU waits - for the oldest copy alone, never for a stream."""
+
+    def __init__(self):
+        self.slots = []
+        self.next = 0
+
+    def take(self, words: int) -> dict:
+        # slots are handed out in ring order and their copies complete in that order (per stream), so only the oldest is looked at
+        n = len(self.slots)
+        slot = self.slots[self.next] if n else None
+        if slot is not None and (slot["event"] is None or slot["event"].query()):
+            self.next = (self.next + 1) % n
+        elif n < _STAGE_MAX_SLOTS:
+            slot = {"host": None, "event": None, "words": 0}
+            self.slots.insert(self.next, slot)      # (in front of the oldest, which stays the next one to be looked at)
+            self.next = (self.next + 1) % (n + 1)
+        else:
+            self.next = (self.next + 1) % n
+            slot["event"].synchronize()
+        slot["event"] = None
+        if slot["words"] < words:       # (the slot's last copy has run: its buffer may go)
+            cap = max(int(words), _STAGE_MIN_WORDS)
+            slot["host"] = torch.empty(cap, dtype=torch.int32).pin_memory()
+            slot["np"], slot["ptr"], slot["words"] = slot["host"].numpy(), slot["host"].data_ptr(), cap
+        return slot
+
+
+_stage_rings = {}
+
+
+def _stage_ring(device) -> _StageRing:
+    ring = _stage_rings.get(str(device))
+    if ring is None:
+        ring = _stage_rings[str(device)] = _StageRing()
+    return ring
+
+
+class NativeBatchPlan:
+    """BatchPlan's device tables and ttv_batch structs, built by the library: the host writes cu_seqlens, the clip descriptors, the
+    backward blocks and the attention work tables in C++ (csrc/ttv_plan_host.cpp) into pinned staging, the copies are queued on the
+    building stream without waiting for them, and the per-row tables (latent_rows, patch_rows, row_seq, rope_ids) are written on the
+    device by one kernel (csrc/ttv_plan.hip).  Same attributes and methods as BatchPlan, the same tables element for element
+    (tests/test_native_plan_cpu.py, tests/test_hip_native_plan.py); GPU only, three patch axes.  items64 and the paired flag (opt-in
+    kernels, TTV_ATTN64 / TTV_ATTN_PAIRED) are not built: the struct leaves them NULL / 0."""
+
+    def __init__(self, pixel_grids: Sequence[Sequence[int]], token_counts: Sequence[int], patch: Sequence[int],
+                 device: torch.device, head_dim: int = 64):
+        if head_dim != 64:
+            raise ValueError("head_dim is fixed at 64 (reference model/base/utils.py:8)")
+        self.device = torch.device(device)
+        self.patch = tuple(int(p) for p in patch)
+        if self.device.type != "cuda" or len(self.patch) != 3:
+            raise ValueError("NativeBatchPlan: GPU plans with three patch axes only (BatchPlan builds the others)")
+        self.pixel_grids = [tuple(int(v) for v in g) for g in pixel_grids]
+        self.token_counts = [int(k) for k in token_counts]
+        if len(self.pixel_grids) != len(self.token_counts) or not self.pixel_grids or any(len(g) != 3 for g in self.pixel_grids):
+            raise ValueError("need one token count per clip, at least one clip, and three dimensions per clip")
+        lib = _lib.lib()
+        B = len(self.pixel_grids)
+        self._counts = _i32s(self.token_counts)
+        dims, pt = _i32s([v for g in self.pixel_grids for v in g]), _i32s(self.patch)
+        sz = self._sizes = _lib.PlanSizes()
+        if lib.ttv_plan_rows_sizes(dims, self._counts, B, pt, C.byref(sz)) != 0:
+            raise ValueError(lib.ttv_error_string().decode("utf-8", "replace"))
+        self.grids = [tuple(v // p for v, p in zip(g, self.patch)) for g in self.pixel_grids]
+        self.grid_sizes = [g[0] * g[1] * g[2] for g in self.grids]
+        self.total_rows, self.sum_tokens, self.sum_patches = int(sz.total_rows), int(sz.sum_tokens), int(sz.sum_patches)
+        self.max_seqlen, self.n_rope_ids, self.n_blocks64 = int(sz.max_seqlen), int(sz.n_rope_ids), int(sz.n_blocks64)
+        self._ring = _stage_ring(self.device)
+        slot = self._ring.take(int(sz.host_words))
+        _lib.check(lib.ttv_plan_rows_fill(dims, self._counts, B, pt, 1 if switches.flag("TTV_BWD_XCD", True) else 0, slot["ptr"], slot["words"]),
+                   "ttv_plan_rows_fill")
+        self.cu_seqlens = slot["np"][sz.off_cu_seqlens: sz.off_cu_seqlens + B + 1].tolist()
+        self._cu = _i32s(self.cu_seqlens)
+        self.int_tables = torch.empty(int(sz.dev_words), dtype=torch.int32, device=self.device)
+        self.rope_cs = torch.empty((self.total_rows, head_dim), dtype=torch.float32, device=self.device)
+        bc, bs = _rope_base_device(head_dim, 3, self.n_rope_ids, str(self.device))
+        # rotary factors by position id beside the table, as in BatchPlan (TTV_ROPE_IDS=0: the table path alone, A/B)
+        self._rope_base_cs = _rope_base_interleaved(head_dim, 3, self.n_rope_ids, str(self.device)) if switches.flag("TTV_ROPE_IDS", True) else None
+        self._base = _lib.Batch()
+        self.build_stream = torch.cuda.current_stream(self.device)
+        rc = lib.ttv_plan_rows_build(C.byref(sz), slot["ptr"], self.int_tables.data_ptr(), bc.data_ptr(), bs.data_ptr(), bc.shape[1],
+                                     self.rope_cs.data_ptr(), _lib.ptr(self._rope_base_cs), C.byref(self._base), self.build_stream.cuda_stream)
+        # the tables are written by a copy and two kernels on the building stream: other streams wait for this event before their
+        # first use, and the staging slot is rewritten only once it has completed
+        self.ready = torch.cuda.Event()
+        self.ready.record(self.build_stream)
+        slot["event"] = self.ready
+        _lib.check(rc, "ttv_plan_rows_build")
+        self._offs = [int(o) for o in (sz.off_cu_seqlens, sz.off_latent_rows, sz.off_patch_rows, sz.off_clip_desc, sz.off_blocks64,
+                                       sz.off_row_seq, sz.off_rope_ids)]
+        self._attn = {}
+        self.reader_streams = {}
+
+    use_on_current_stream = BatchPlan.use_on_current_stream
+    retire = BatchPlan.retire
+    uniform_geometry = BatchPlan.uniform_geometry
+    table = BatchPlan.table
+    cu_dev = BatchPlan.cu_dev
+    latent_rows_dev = BatchPlan.latent_rows_dev
+    patch_rows_dev = BatchPlan.patch_rows_dev
+    clip_desc_dev = BatchPlan.clip_desc_dev
+
+    def _tables(self, q_heads: int, kv_heads: int, split: Optional[bool], tail_div: int) -> dict:
+        """The four attention work tables of these head counts on the device (one buffer), with the ttv_batch that points at them.
+        Copied on the building stream, whose pool owns every table of the plan (retire); any other stream waits for the copy's event."""
+        key = (int(q_heads), int(kv_heads), split, int(tail_div))
+        cur = torch.cuda.current_stream(self.device)
+        ent = self._attn.get(key)
+        if ent is None:
+            lib = _lib.lib()
+            az = _lib.PlanAttn()
+            args = (self._cu, self._counts, len(self.grids), key[0], key[1], _split_code(split), key[3])
+            _lib.check(lib.ttv_plan_attn_sizes(*args, C.byref(az)), "ttv_plan_attn_sizes")
+            slot = self._ring.take(int(az.words))
+            _lib.check(lib.ttv_plan_attn_fill(*args, slot["ptr"], slot["words"]), "ttv_plan_attn_fill")
+            build = self.build_stream
+            if cur == build:
+                dev = torch.empty(int(az.words), dtype=torch.int32, device=self.device)
+            else:
+                with torch.cuda.stream(build):
+                    dev = torch.empty(int(az.words), dtype=torch.int32, device=self.device)
+            batch = _lib.Batch.from_buffer_copy(self._base)
+            rc = lib.ttv_plan_attn_set(C.byref(az), slot["ptr"], dev.data_ptr(), C.byref(batch), build.cuda_stream)
+            done = torch.cuda.Event()
+            done.record(build)
+            slot["event"] = done
+            _lib.check(rc, "ttv_plan_attn_set")
+            ent = self._attn[key] = dict(dev=dev, sizes=az, batch=batch, done=done, seen={build.cuda_stream})
+        if cur.cuda_stream not in ent["seen"]:
+            cur.wait_event(ent["done"])
+            ent["seen"].add(cur.cuda_stream)
+        return ent
+
+    def _switched(self, q_heads: int, kv_heads: int) -> dict:
+        """The tables the diagnostics switches select (read here, passed down as arguments: the library reads no environment for this)."""
+        s = switches.text("TTV_ATTN_SPLIT")
+        return self._tables(q_heads, kv_heads, (s == "1") if s in ("0", "1") else None, switches.integer("TTV_ATTN_TAIL_DIV", 0))
+
+    @staticmethod
+    def _view(ent: dict, off: int, entries: int) -> Optional[torch.Tensor]:
+        return ent["dev"][off: off + 4 * entries].view(-1, 4) if entries else None
+
+    def attention_table(self, q_heads: int, kv_heads: int, split: Optional[bool] = None) -> torch.Tensor:
+        ent = self._switched(q_heads, kv_heads) if split is None else self._tables(q_heads, kv_heads, split, switches.integer("TTV_ATTN_TAIL_DIV", 0))
+        return self._view(ent, ent["sizes"].off_qblocks, ent["sizes"].n_qblocks)
+
+    def attention_table_latent(self, q_heads: int, kv_heads: int) -> Optional[torch.Tensor]:
+        ent = self._switched(q_heads, kv_heads)
+        return self._view(ent, ent["sizes"].off_qblocks_latent, ent["sizes"].n_qblocks_latent)
+
+    def attention_table_patch(self, q_heads: int, kv_heads: int) -> Optional[torch.Tensor]:
+        ent = self._switched(q_heads, kv_heads)
+        return self._view(ent, ent["sizes"].off_qblocks_patch, ent["sizes"].n_qblocks_patch)
+
+    def attention_table_l0(self, q_heads: int, kv_heads: int) -> torch.Tensor:
+        ent = self._switched(q_heads, kv_heads)
+        return self._view(ent, ent["sizes"].off_qblocks_l0, ent["sizes"].n_qblocks_l0)
+
+    def batch_for(self, q_heads: int, kv_heads: int) -> "_lib.Batch":
+        """ttv_batch struct whose attention work tables match the tower's head counts (ttv_plan_attn_set filled it)."""
+        return self._switched(q_heads, kv_heads)["batch"]
+
+    def clip0_patch_rope(self) -> Tuple[int, Optional[int], Optional[int]]:
+        k = self.token_counts[0]
+        ids = self._base.rope_ids
+        return (self.rope_cs.data_ptr() + 4 * self.rope_cs.shape[1] * k, ids + 8 * k if ids else None, self._base.rope_base if ids else None)
+
 
 _plan_cache = {}
 _PLAN_CACHE_MAX = 64
 
 
 def get_plan(pixel_grids, token_counts, patch, device) -> BatchPlan:
+    dev = torch.device(device)
+    # TTV_NATIVE_PLAN=1 (opt-in, read at call time and part of the key): the library builds the plan (NativeBatchPlan)
+    native = switches.flag("TTV_NATIVE_PLAN", False) and dev.type == "cuda" and len(patch) == 3
     key = (tuple(tuple(int(v) for v in g) for g in pixel_grids), tuple(int(k) for k in token_counts),
-           tuple(int(p) for p in patch), str(torch.device(device)))
+           tuple(int(p) for p in patch), str(dev), native)
     plan = _plan_cache.get(key)
     if plan is None:
         if len(_plan_cache) >= _PLAN_CACHE_MAX:
             _plan_cache.pop(next(iter(_plan_cache))).retire()
-        plan = BatchPlan(key[0], key[1], key[2], device)
+        plan = (NativeBatchPlan if native else BatchPlan)(key[0], key[1], key[2], device)
         _plan_cache[key] = plan
     plan.use_on_current_stream()
     return plan

@@ -233,6 +233,7 @@ def main():
         torch.empty = empty
         blocks_mod.get_plan = timed(blocks_mod.get_plan, "get_plan")
         plan_mod.BatchPlan.batch_for = timed(plan_mod.BatchPlan.batch_for, "batch_for")
+        plan_mod.NativeBatchPlan.batch_for = timed(plan_mod.NativeBatchPlan.batch_for, "batch_for")      # TTV_NATIVE_PLAN=1
         real_it = it
 
         def waited():
