@@ -605,6 +605,51 @@ int ttv_opt_adamw_step(const void* table, const int32_t* chunks, int n_chunks, i
                        float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay,
                        float bias_correction1, float bias_correction2_sqrt, float max_norm, float* out_norm, void* stream);
 
+/* The same step with its scalar state on the device (optim.HipAdamW(capturable=True) / (skip_nonfinite=True)): the update count, both
+ * bias corrections and the learning rate are formed by one tiny launch per parameter group and read by the update kernel from a
+ * 48-byte block, so a captured step replays with the count it finds, a schedule costs the host nothing per step, and a step whose
+ * gradient norm is not finite can be dropped without a host round trip.
+ * ttv_opt_state   : one per parameter group, device memory, 8-byte aligned, zero before the first update (or filled by the caller
+ *                   when training resumes).  `updates` counts the updates applied, `skipped` the calls dropped; the rest describes
+ *                   the last ttv_opt_prepare: skip_now (1: the update kernels of this step return at once), the floats the update
+ *                   uses and the schedule index they were formed at.
+ * ttv_opt_schedule: passed by value.  TTV_OPT_SCHEDULE_NONE: lr = lr_constant.  TTV_OPT_SCHEDULE_COSINE: the reference's
+ *                   get_cosine_schedule_with_warmup (train_utils/lr_schedulers.py:55-61) times LambdaLR's initial_lr, at
+ *                   index = max(0, first + stride * updates): index < warmup_steps ? index / max(1, warmup_steps) :
+ *                   (end_lr + (base_lr - end_lr) * max(0, 0.5 * (1 + cos(pi * num_cycles * 2 * progress)))) / base_lr with
+ *                   progress = (index - warmup_steps) / max(1, training_steps - warmup_steps); every operation in double, in that
+ *                   order, without contraction.
+ * ttv_opt_prepare : one block.  Sums partials[0 .. n_partials) in the order ttv_opt_adamw_step does (the same bits), writes the norm
+ *                   to out_norm (when not NULL and n_partials > 0) and forms the clip factor by the same rule (max_norm <= 0 or
+ *                   n_partials == 0: 1).  With TTV_OPT_SKIP_NONFINITE in flags and a norm that is NaN or infinite: skip_now = 1,
+ *                   skipped += 1; norm and clip_coef are written, updates and the other fields stay.  Otherwise skip_now = 0, t = updates + 1, bc1 = 1 - beta1^t,
+ *                   bc2_sqrt = sqrt(1 - beta2^t) and lr in double, each rounded to float once, and updates = t.
+ * ttv_opt_adamw_step_dev: ttv_opt_adamw_step's update of one tensor list with lr, bc1, bc2_sqrt and the clip factor read from
+ *                   the block; with skip_now set no block reads or writes a tensor.
+ * Both return TTV_ERR_INVALID and launch nothing for a NULL state (partials with n_partials > 0, table, chunks), an unknown
+ * schedule kind, training_steps < warmup_steps, stride < 1, n_partials < 0 or an unknown dtype. */
+typedef struct ttv_opt_state {
+  int64_t updates;
+  int64_t skipped;
+  int64_t schedule_index;
+  int32_t skip_now;
+  float lr, bc1, bc2_sqrt, clip_coef, norm;
+} ttv_opt_state;
+#define TTV_OPT_SCHEDULE_NONE 0
+#define TTV_OPT_SCHEDULE_COSINE 1
+typedef struct ttv_opt_schedule {
+  int32_t kind;
+  int32_t reserved;
+  int64_t warmup_steps, training_steps;
+  double base_lr, end_lr, num_cycles, initial_lr;
+  int64_t first, stride;
+} ttv_opt_schedule;
+#define TTV_OPT_SKIP_NONFINITE 1
+int ttv_opt_prepare(ttv_opt_state* state, ttv_opt_schedule schedule, double beta1, double beta2, double lr_constant, float max_norm,
+                    const float* partials, int n_partials, int flags, float* out_norm, void* stream);
+int ttv_opt_adamw_step_dev(const void* table, const int32_t* chunks, int n_chunks, int dtype, const ttv_opt_state* state, float beta1,
+                           float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay, void* stream);
+
 /* Per-parameter gradient norms of one tensor list (the log of reference train.py:78-79, :102-103: lightning.pytorch.utilities.grad_norm
  * with norm_type 2) from the partials ttv_opt_grad_sumsq has written for the same table, in one launch.  `chunks` (device, n_chunks x
  * (entry, first element)) lists every entry's chunks together and the entries in ascending order, as ttv_opt_grad_sumsq's caller builds

@@ -129,6 +129,20 @@ class TowerGrads(C.Structure):
                 ("proj_out_w", vp), ("proj_out_b", vp), ("layers", C.POINTER(LayerGrads)), ("layer_done_events", C.POINTER(vp))]
 
 
+TTV_OPT_SCHEDULE_NONE, TTV_OPT_SCHEDULE_COSINE = 0, 1
+TTV_OPT_SKIP_NONFINITE = 1
+
+
+class OptState(C.Structure):
+    _fields_ = [("updates", i64), ("skipped", i64), ("schedule_index", i64), ("skip_now", i32), ("lr", f32), ("bc1", f32),
+                ("bc2_sqrt", f32), ("clip_coef", f32), ("norm", f32)]
+
+
+class OptSchedule(C.Structure):
+    _fields_ = [("kind", i32), ("reserved", i32), ("warmup_steps", i64), ("training_steps", i64), ("base_lr", C.c_double),
+                ("end_lr", C.c_double), ("num_cycles", C.c_double), ("initial_lr", C.c_double), ("first", i64), ("stride", i64)]
+
+
 class LpipsWeights(C.Structure):
     _fields_ = [("w", vp * 13), ("wd", vp * 13), ("b", vp * 13), ("lin", vp * 5)]
 
@@ -233,6 +247,8 @@ SYMBOLS = {
                                               C.c_int, C.c_int, C.c_float, C.c_int, vp]),
     "ttv_opt_grad_sumsq": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
     "ttv_opt_adamw_step": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int] + [C.c_float] * 10 + [vp, vp]),
+    "ttv_opt_prepare": (C.c_int, [vp, OptSchedule, C.c_double, C.c_double, C.c_double, C.c_float, vp, C.c_int, C.c_int, vp, vp]),
+    "ttv_opt_adamw_step_dev": (C.c_int, [vp, vp, C.c_int, C.c_int, vp] + [C.c_float] * 6 + [vp]),
     "ttv_opt_param_norms": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp]),
     "ttv_opt_ema_update": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_float, vp]),
     "ttv_opt_ema_exchange": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),

@@ -544,6 +544,99 @@ __global__ __launch_bounds__(256) void k_opt_adamw(const OptEntry* __restrict__ 
   }
 }
 
+// The step with its scalar state on the device (include/titok_hip.h, ttv_opt_state): k_opt_prepare, one block, does once what every
+// block of k_opt_adamw does for itself - the norm from the partials in the same order (thread-strided sums, then opt_block_sum: the
+// same bits) and the clip factor - and what the host does for k_opt_adamw: t, both bias corrections and the learning rate in
+// double, each rounded to float once.  k_opt_adamw_dev is k_opt_adamw's update with those four floats read from the block.
+// The doubles are formed without contraction: the schedule is held bit for bit to the reference's Python, which has no fma.
+__device__ __forceinline__ double opt_schedule_lr(const ttv_opt_schedule& s, long long index) {
+#pragma clang fp contract(off)
+  double factor;
+  if (index < s.warmup_steps) {
+    factor = (double)index / (double)(s.warmup_steps > 1 ? s.warmup_steps : 1);
+  } else {
+    const long long span = s.training_steps - s.warmup_steps;
+    const double progress = (double)(index - s.warmup_steps) / (double)(span > 1 ? span : 1);
+    const double c = 0.5 * (1.0 + cos(3.141592653589793 * s.num_cycles * 2.0 * progress));
+    const double ratio = c > 0.0 ? c : 0.0;
+    factor = (s.end_lr + (s.base_lr - s.end_lr) * ratio) / s.base_lr;
+  }
+  return s.initial_lr * factor;
+}
+__global__ __launch_bounds__(256) void k_opt_prepare(ttv_opt_state* __restrict__ st, ttv_opt_schedule sched, double beta1, double beta2,
+                                                     double lr_constant, float max_norm, const float* __restrict__ partial, int n_partial,
+                                                     int flags, float* __restrict__ out_norm) {
+  __shared__ float red[4];
+  float coef = 1.0f, norm = 0.f;
+  if (n_partial > 0) {
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < n_partial; i += 256) acc += partial[i];
+    norm = sqrtf(opt_block_sum(acc, red));
+    if (max_norm > 0.f) {
+      const float r = max_norm / (norm + 1e-6f);          // k_opt_adamw's rule: a NaN norm gives a NaN factor
+      coef = r >= 1.0f ? 1.0f : r;
+    }
+  }
+  if (threadIdx.x != 0) return;
+  if (out_norm && n_partial > 0) out_norm[0] = norm;
+  st->norm = norm;
+  st->clip_coef = coef;
+  if ((flags & TTV_OPT_SKIP_NONFINITE) && !(fabsf(norm) <= 3.402823466e38f)) {          // NaN or infinite
+    st->skip_now = 1;
+    st->skipped += 1;
+    return;
+  }
+  const long long u = st->updates, t = u + 1;
+  long long index = 0;
+  double lr = lr_constant;
+  if (sched.kind == TTV_OPT_SCHEDULE_COSINE) {
+    index = sched.first + sched.stride * u;
+    if (index < 0) index = 0;
+    lr = opt_schedule_lr(sched, index);
+  }
+  st->skip_now = 0;
+  st->schedule_index = index;
+  st->lr = (float)lr;
+  st->bc1 = (float)(1.0 - pow(beta1, (double)t));
+  st->bc2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)t));
+  st->updates = t;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_opt_adamw_dev(const OptEntry* __restrict__ tab, const int2* __restrict__ chunks,
+                                                       const ttv_opt_state* __restrict__ st, OptHyper h) {
+  if (st->skip_now) return;          // the same word for every block: nobody touches a tensor
+  h.lr = st->lr; h.bc1 = st->bc1; h.bc2_sqrt = st->bc2_sqrt;
+  const float coef = st->clip_coef;
+  // from here on k_opt_adamw's text, kept apart so that the host-path kernel stays the code it was
+  const int2 c = chunks[blockIdx.x];
+  const OptEntry e = tab[c.x];
+  T* p = (T*)e.p; const T* g = (const T*)e.g; T* m = (T*)e.m; T* v = (T*)e.v;
+  const long long end = e.n < (long long)c.y + OPT_CHUNK ? e.n : (long long)c.y + OPT_CHUNK;
+  const float step_size = h.lr / h.bc1;
+  if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0) {
+    long long i = (long long)c.y + threadIdx.x * 8;
+    for (; i + 8 <= end; i += 256 * 8) {
+      float pv[8], gv[8], mv[8], vv[8];
+      OptVec<T>::load(p + i, pv); OptVec<T>::load(g + i, gv); OptVec<T>::load(m + i, mv); OptVec<T>::load(v + i, vv);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) opt_update(pv[k], gv[k] * coef, mv[k], vv[k], h, step_size);
+      OptVec<T>::store(p + i, pv); OptVec<T>::store(m + i, mv); OptVec<T>::store(v + i, vv);
+    }
+    if (i < end)
+      for (long long j = i; j < end; ++j) {
+        float pv = (float)p[j], mv = (float)m[j], vv = (float)v[j];
+        opt_update(pv, (float)g[j] * coef, mv, vv, h, step_size);
+        p[j] = (T)pv; m[j] = (T)mv; v[j] = (T)vv;
+      }
+  } else {
+    for (long long j = (long long)c.y + threadIdx.x; j < end; j += 256) {
+      float pv = (float)p[j], mv = (float)m[j], vv = (float)v[j];
+      opt_update(pv, (float)g[j] * coef, mv, vv, h, step_size);
+      p[j] = (T)pv; m[j] = (T)mv; v[j] = (T)vv;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ weight EMA
 // fp32 shadow weights of a parameter list (titok_video_amd/ema.py::WeightEMA; not a reference module: the reference validates its raw
 // weights).  The OptEntry table and chunk list of the optimizer step, one block per chunk, the same vector / element-wise split:
@@ -808,6 +901,39 @@ int ttv_opt_adamw_step(const void* table, const int32_t* chunks, int n_chunks, i
   if (dtype == TTV_BF16) hipLaunchKernelGGL((k_opt_adamw<bf16_t>), dim3(n_chunks), dim3(256), 0, s, (const OptEntry*)table, (const int2*)chunks, partials, n_partials, h, out_norm);
   else hipLaunchKernelGGL((k_opt_adamw<float>), dim3(n_chunks), dim3(256), 0, s, (const OptEntry*)table, (const int2*)chunks, partials, n_partials, h, out_norm);
   TTV_CHECK_LAUNCH("opt_adamw_step");
+  return TTV_OK;
+}
+
+int ttv_opt_prepare(ttv_opt_state* state, ttv_opt_schedule schedule, double beta1, double beta2, double lr_constant, float max_norm,
+                    const float* partials, int n_partials, int flags, float* out_norm, void* stream) {
+  TTV_CHECK_ARG(state, "opt_prepare: null state");
+  TTV_CHECK_ARG(n_partials >= 0, "opt_prepare: n_partials %d is negative", n_partials);
+  TTV_CHECK_ARG(n_partials == 0 || partials, "opt_prepare: null partials");
+  TTV_CHECK_ARG(schedule.kind == TTV_OPT_SCHEDULE_NONE || schedule.kind == TTV_OPT_SCHEDULE_COSINE, "opt_prepare: schedule kind %d is unknown",
+                schedule.kind);
+  if (schedule.kind == TTV_OPT_SCHEDULE_COSINE) {
+    TTV_CHECK_ARG(schedule.warmup_steps >= 0 && schedule.training_steps >= schedule.warmup_steps,
+                  "opt_prepare: training_steps %lld below warmup_steps %lld (or a negative warm-up)", (long long)schedule.training_steps,
+                  (long long)schedule.warmup_steps);
+    TTV_CHECK_ARG(schedule.stride >= 1, "opt_prepare: stride %lld is below 1", (long long)schedule.stride);
+  }
+  hipLaunchKernelGGL(k_opt_prepare, dim3(1), dim3(256), 0, (hipStream_t)stream, state, schedule, beta1, beta2, lr_constant, max_norm, partials,
+                     n_partials, flags, out_norm);
+  TTV_CHECK_LAUNCH("opt_prepare");
+  return TTV_OK;
+}
+
+int ttv_opt_adamw_step_dev(const void* table, const int32_t* chunks, int n_chunks, int dtype, const ttv_opt_state* state, float beta1,
+                           float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay, void* stream) {
+  TTV_CHECK_ARG(state, "opt_adamw_step_dev: null state");
+  TTV_CHECK_ARG(dtype == TTV_BF16 || dtype == TTV_F32, "opt_adamw_step_dev: dtype");
+  if (n_chunks == 0) return TTV_OK;
+  TTV_CHECK_ARG(n_chunks > 0 && table && chunks, "opt_adamw_step_dev: null buffer");
+  hipStream_t s = (hipStream_t)stream;
+  const OptHyper h = {0.f, beta1, beta2, one_minus_beta1, one_minus_beta2, eps, weight_decay, 1.f, 1.f, 0.f};          // lr, bc1, bc2_sqrt: from the block
+  if (dtype == TTV_BF16) hipLaunchKernelGGL((k_opt_adamw_dev<bf16_t>), dim3(n_chunks), dim3(256), 0, s, (const OptEntry*)table, (const int2*)chunks, state, h);
+  else hipLaunchKernelGGL((k_opt_adamw_dev<float>), dim3(n_chunks), dim3(256), 0, s, (const OptEntry*)table, (const int2*)chunks, state, h);
+  TTV_CHECK_LAUNCH("opt_adamw_step_dev");
   return TTV_OK;
 }
 

@@ -105,17 +105,37 @@ def limit_host_threads(max_threads: int = 4) -> int:
     return n
 
 
-def make_optimizer(model: torch.nn.Module, lr: float = 1e-4, beta1: float = 0.5, beta2: float = 0.96, weight_decay: float = 1e-4,
-                   capturable: bool = False):
-    """AdamW with the reference's hyper-parameters (configs/tiny.yaml:39-46, train.py:170-190).  capturable=True keeps the step
-    counter on the device so that the step can be recorded into a HIP graph (GraphedTrainingStep)."""
-    params = [p for p in model.parameters() if p.requires_grad]
+def _make_adamw(params, lr, beta1, beta2, weight_decay, capturable, hip_capturable, skip_nonfinite, schedule):
+    """The optimizer of make_optimizer / make_discriminator_optimizer; with `schedule` (a dict of schedule.CosineWarmupLR's
+    arguments) the pair (optimizer, scheduler)."""
+    device_path = hip_capturable or skip_nonfinite
+    if device_path and not (use_hip_adamw(params) and switches.flag("TTV_HIP_ADAMW", True)):
+        raise RuntimeError("make_optimizer: hip_capturable / skip_nonfinite are optim.HipAdamW's device path - parameters on one GPU and "
+                           "TTV_HIP_ADAMW not switched off")
     # parameters on the GPU: clip + AdamW as two HIP launches (optim.HipAdamW; TTV_HIP_ADAMW=0 keeps torch's multi-tensor kernels, and
-    # so does capturable=True - the HIP step takes its step count from the host)
-    if use_hip_adamw(params) and not capturable and switches.flag("TTV_HIP_ADAMW", True):
-        return HipAdamW(params, lr=lr, betas=(beta1, beta2), weight_decay=weight_decay)
-    fused = bool(params) and all(p.is_cuda for p in params)      # one multi-tensor kernel instead of a launch per parameter
-    return torch.optim.AdamW(params, lr=lr, betas=(beta1, beta2), weight_decay=weight_decay, fused=fused, capturable=capturable and fused)
+    # so does capturable=True - torch's capturable AdamW; hip_capturable=True is HipAdamW with its scalar state on the device)
+    if use_hip_adamw(params) and (device_path or not capturable) and switches.flag("TTV_HIP_ADAMW", True):
+        extra = dict(capturable=hip_capturable, skip_nonfinite=skip_nonfinite) if device_path else {}
+        opt = HipAdamW(params, lr=lr, betas=(beta1, beta2), weight_decay=weight_decay, **extra)
+    else:
+        fused = bool(params) and all(p.is_cuda for p in params)      # one multi-tensor kernel instead of a launch per parameter
+        opt = torch.optim.AdamW(params, lr=lr, betas=(beta1, beta2), weight_decay=weight_decay, fused=fused, capturable=capturable and fused)
+    if schedule is None:
+        return opt
+    from .schedule import CosineWarmupLR
+    return opt, CosineWarmupLR(opt, **schedule)
+
+
+def make_optimizer(model: torch.nn.Module, lr: float = 1e-4, beta1: float = 0.5, beta2: float = 0.96, weight_decay: float = 1e-4,
+                   capturable: bool = False, hip_capturable: bool = False, skip_nonfinite: bool = False, schedule: Optional[dict] = None):
+    """AdamW with the reference's hyper-parameters (configs/tiny.yaml:39-46, train.py:170-190).  capturable=True: torch's AdamW with
+    the step counter on the device, so that the step can be recorded into a HIP graph (GraphedTrainingStep).  hip_capturable=True:
+    `HipAdamW(capturable=True)`, which can be recorded too and runs a schedule on the device; skip_nonfinite=True: its
+    skip-and-count of steps with a NaN or infinite gradient norm.  `schedule`: a dict of `schedule.CosineWarmupLR`'s arguments
+    (warmup_steps, training_steps, base_lr, end_lr, optionally num_cycles, first, stride) - the call then returns
+    (optimizer, scheduler); the reference: get_scheduler('cosine', .., warmup_steps=1000, max_steps=600000, base_lr, end_lr)."""
+    params = [p for p in model.parameters() if p.requires_grad]
+    return _make_adamw(params, lr, beta1, beta2, weight_decay, capturable, hip_capturable, skip_nonfinite, schedule)
 
 
 def make_weight_ema(model: torch.nn.Module, config):
@@ -220,7 +240,7 @@ class GraphedTrainingStep:
     and weight packs are built during the warm-up steps, and the pack refresh after each optimizer step (parameter version -> new
     compute-dtype copies) is part of the captured sequence, so a replay is exact.  Constraints: one batch shape per instance (clip
     shapes and token counts fixed; ragged token-budget batches need one instance per shape signature), an optimizer created with
-    capturable=True, single process (the overlapped DP reducer launches collectives from Python callbacks).
+    capturable=True (torch's AdamW) or hip_capturable=True (HipAdamW with its step count on the device), single process (the overlapped DP reducer launches collectives from Python callbacks).
 
     Measured (tools/bench_train.py GRAPH=1): the replay runs at the speed of the eager step, 3.48 ms at 5 clips and 8.1 ms at 32 -
     with the Python garbage collector frozen the host issues the ~300 launches of a step faster than the GPU runs them (3.6 ms of
@@ -254,7 +274,9 @@ class GraphedTrainingStep:
             for p, q in zip(params, saved_params):
                 p.copy_(q)
             old = saved_opt["state"]
-            for i, p in enumerate(optimizer.param_groups[0]["params"]):
+            if isinstance(optimizer, HipAdamW):         # moments and the device block's counters (HipAdamW(capturable=True))
+                optimizer.restore_in_place(saved_opt)
+            for i, p in enumerate(optimizer.param_groups[0]["params"] if not isinstance(optimizer, HipAdamW) else ()):
                 st = optimizer.state.get(p, {})
                 for k, v in st.items():
                     if torch.is_tensor(v):
@@ -273,13 +295,12 @@ class GraphedTrainingStep:
 
 
 def make_discriminator_optimizer(loss_module: torch.nn.Module, lr: float = 1e-4, disc_lr_ratio: float = 0.15, beta1: float = 0.5,
-                                 beta2: float = 0.96, weight_decay: float = 1e-4):
-    """AdamW over `loss_module.disc_model` at lr * disc_lr_ratio (reference train.py:195-201, configs/tiny.yaml:46)."""
+                                 beta2: float = 0.96, weight_decay: float = 1e-4, hip_capturable: bool = False, skip_nonfinite: bool = False,
+                                 schedule: Optional[dict] = None):
+    """AdamW over `loss_module.disc_model` at lr * disc_lr_ratio (reference train.py:195-201, configs/tiny.yaml:46).  The three
+    last arguments as make_optimizer's; the reference gives this schedule base_lr = lr * disc_lr_ratio and end_lr scaled alike."""
     params = list(loss_module.disc_model.parameters())
-    if use_hip_adamw(params) and switches.flag("TTV_HIP_ADAMW", True):           # as make_optimizer
-        return HipAdamW(params, lr=lr * disc_lr_ratio, betas=(beta1, beta2), weight_decay=weight_decay)
-    fused = bool(params) and all(p.is_cuda for p in params)
-    return torch.optim.AdamW(params, lr=lr * disc_lr_ratio, betas=(beta1, beta2), weight_decay=weight_decay, fused=fused)
+    return _make_adamw(params, lr * disc_lr_ratio, beta1, beta2, weight_decay, False, hip_capturable, skip_nonfinite, schedule)
 
 
 def gan_training_step(model, loss_module, clips: List[torch.Tensor], token_counts, opt_g, opt_d=None, max_grad_norm: float = 1.0,

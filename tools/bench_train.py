@@ -3,7 +3,8 @@
 B= batch (5 = the reference's 6144-token budget), GRAPH=1: the whole step captured once in a HIP graph (torch.cuda.CUDAGraph) and
 replayed - the step is a fixed launch sequence for a fixed batch shape, and at small batches the host cannot issue ~280 launches
 as fast as the GPU runs them.  EMA=1: an ema.WeightEMA of the model (decay 0.9999) updated after every step (not with GRAPH=1: the update
-takes its weight from the host)."""
+takes its weight from the host).  OPT_DEVICE=1: optim.HipAdamW's device path (step count, bias corrections and rate formed by
+ttv_opt_prepare; three launches per bucket instead of two) - with GRAPH=1 it is the HIP optimizer that is captured, not torch's."""
 import json, os, sys, time
 from types import SimpleNamespace
 import torch
@@ -20,7 +21,8 @@ m = TiTok(cfg); m.load_state_dict(seeded_titok_state(0)); m = m.to("cuda:0", tor
 clips = synthetic_clips([(16, 128, 128)] * B, seed=1, dtype=torch.bfloat16, device="cuda:0")
 counts = [128] * B
 GRAPH = os.environ.get("GRAPH", "0") == "1"
-opt = make_optimizer(m, capturable=True) if GRAPH else make_optimizer(m)
+OPT_DEVICE = os.environ.get("OPT_DEVICE", "0") == "1"
+opt = make_optimizer(m, hip_capturable=True) if OPT_DEVICE else make_optimizer(m, capturable=True) if GRAPH else make_optimizer(m)
 if os.environ.get("GC_FREEZE", "1") == "1":
     freeze_python_gc()
     limit_host_threads()
@@ -52,4 +54,4 @@ else:
             ema.update()
     torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / n
-print(json.dumps({"train_ms_per_step": 1e3 * dt, "clips_per_s": B / dt, "batch": B, "loss": float(loss), "graph": GRAPH, "ema": EMA}))
+print(json.dumps({"train_ms_per_step": 1e3 * dt, "clips_per_s": B / dt, "batch": B, "loss": float(loss), "graph": GRAPH, "ema": EMA, "opt_device": OPT_DEVICE}))

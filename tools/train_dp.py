@@ -49,6 +49,14 @@ def main():
     ap.add_argument("--workers", type=int, default=2, help="loader worker processes per rank (the reference uses 3, video_dataset.py:211)")
     ap.add_argument("--backend", default="nccl")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--max-steps", type=int, default=0, help="> 0: the reference's cosine schedule with warm-up over this many optimizer steps "
+                    "(train.py:170-215: warmup_steps=1000, max_steps=600000); 0: a constant rate")
+    ap.add_argument("--warmup-steps", type=int, default=0, help="warm-up steps of the schedule (with --max-steps)")
+    ap.add_argument("--end-lr", type=float, default=1e-5, help="the generator's final rate (the discriminator's is scaled by its lr ratio)")
+    ap.add_argument("--skip-nonfinite", action="store_true", help="drop and count steps whose gradient norm is NaN or infinite (HipAdamW's device "
+                    "path: step count, schedule and skip decision on the GPU)")
+    ap.add_argument("--save", default="", help="rank 0 writes a checkpoint with optimizer and scheduler state here after the last step")
+    ap.add_argument("--resume", default="", help="continue from a checkpoint written by --save: weights, AdamW moments, step counts, schedule")
     ap.add_argument("--repeat-first-batch", action="store_true", help="diagnostics: every step trains on the first batch (plans cached, loader idle)")
     ap.add_argument("--preload", action="store_true", help="diagnostics: fetch every batch of the run before the first step (loader idle during the steps)")
     ap.add_argument("--torch-profile", default="", help="diagnostics: torch.profiler tables (CPU + GPU) of the timed steps of rank 0 -> this file")
@@ -164,8 +172,25 @@ def main():
     loss_module = ReconstructionLoss(cfg)
     loss_module.disc_model.load_state_dict(seeded_tower_state("encoder", "tiny", (4, 8, 8), 3, 1, seed=77), strict=True)
     loss_module = loss_module.to(device, dtype).train()
-    opt_g = make_optimizer(model)
-    opt_d = make_discriminator_optimizer(loss_module) if loss_module is not None else None
+    # Lightning counts global_step per optimizer step: beside a discriminator the generator's schedule sees the indices 0, 1, 3, 5, ..
+    # and the discriminator's 0, 2, 4, ...  --skip-nonfinite selects HipAdamW's device path, which runs the schedule
+    # on the GPU; otherwise the schedulers write group['lr'] from the host after every step.
+    lr, disc_ratio = 1e-4, 0.15
+    device_opt = dict(hip_capturable=True, skip_nonfinite=True) if args.skip_nonfinite else {}
+    sched_g = sched_d = None
+    if args.max_steps > 0:
+        sch = dict(warmup_steps=args.warmup_steps, training_steps=args.max_steps, stride=2)
+        opt_g, sched_g = make_optimizer(model, lr=lr, schedule=dict(sch, base_lr=lr, end_lr=args.end_lr, first=-1), **device_opt)
+        opt_d, sched_d = make_discriminator_optimizer(loss_module, lr=lr, disc_lr_ratio=disc_ratio, **device_opt,
+                                                      schedule=dict(sch, base_lr=lr * disc_ratio, end_lr=args.end_lr * disc_ratio, first=0))
+    else:
+        opt_g = make_optimizer(model, lr=lr, **device_opt)
+        opt_d = make_discriminator_optimizer(loss_module, lr=lr, disc_lr_ratio=disc_ratio, **device_opt)
+    optimizers, schedulers = [opt_g, opt_d], ([sched_g, sched_d] if sched_g is not None else None)
+    resumed_step = 0
+    if args.resume:
+        from titok_video_amd.checkpoint import load_checkpoint
+        resumed_step = load_checkpoint(args.resume, model, loss_module, optimizers=optimizers, schedulers=schedulers)
     logger = CodebookLogger(4375, world_size=world)
 
     freeze_python_gc()
@@ -176,6 +201,8 @@ def main():
         if loss_module is not None:
             d, idx = gan_training_step(model, loss_module, clips, counts, opt_g, opt_d, overlap=not args.no_overlap)
             loss = d.get("gen/total_loss", d.get("gen/loss", next(iter(d.values()))))
+            for s in schedulers or ():
+                s.step()
         else:
             from titok_video_amd.train import training_step
             loss, _g, idx = training_step(model, clips, counts, opt_g, overlap=not args.no_overlap)
@@ -304,13 +331,21 @@ def main():
                            "grad_allreduce": "after backward" if args.no_overlap else "overlapped with backward (per layer slice, communication stream)",
                            "allreduce_bytes_last_backward": int(red.bytes_reduced) if red is not None else 0,
                            "allreduce_slices_last_backward": int(red.slices) if red is not None else 0},
-                "loss_after_steps": float(loss), "codebook": scores}
+                "loss_after_steps": float(loss), "codebook": scores,
+                "lr": {"generator": sched_g.get_last_lr()[0] if sched_g is not None else opt_g.param_groups[0]["lr"],
+                       "discriminator": sched_d.get_last_lr()[0] if sched_d is not None else opt_d.param_groups[0]["lr"]},
+                "skipped": {"generator": opt_g.skipped_steps(), "discriminator": opt_d.skipped_steps()} if args.skip_nonfinite else None,
+                "resumed_step": resumed_step, "global_step": resumed_step + args.warmup + args.steps}
         if args.phase_times:
             line["host_ms_per_step"] = {k: round(1e3 * v / args.steps, 3) for k, v in phase.items()}
             mem1 = torch.cuda.memory_stats(device)
             line["allocator_per_step"] = {k: (mem1[k] - mem0[k]) / args.steps for k in ("num_device_alloc", "num_device_free", "num_alloc_retries")}
             line["allocator_reserved_MiB"] = mem1["reserved_bytes.all.current"] / 2**20
         print(json.dumps(line), flush=True)
+        if args.save:
+            from titok_video_amd.checkpoint import save_checkpoint
+            save_checkpoint(args.save, model, loss_module, global_step=resumed_step + args.warmup + args.steps, optimizers=optimizers,
+                            schedulers=schedulers)
     loader.close()
     if world > 1:
         dist.barrier()
