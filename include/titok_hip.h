@@ -566,6 +566,32 @@ typedef struct ttv_tower_grads {
 
 int64_t ttv_tower_tape_bytes(const ttv_tower_dims* dims, const ttv_batch* batch);
 int64_t ttv_tower_bwd_workspace_bytes(const ttv_tower_dims* dims, const ttv_batch* batch);
+/* Tape modes of the *_ex entry points below (each plain entry point is its _ex with TTV_TAPE_STORED; a forward and its backward take the
+ * same mode and the same tape).
+ * TTV_TAPE_STORED   : the forward writes, for every layer, every tensor the backward reads.
+ * TTV_TAPE_RECOMPUTE: the tape holds the tower's head / tail buffers, the residual stream at the layers + 1 layer boundaries and
+ *   min(2, layers) layer slots (each the size of one layer's region of the stored tape, for a layer > 0).  The forward runs the same
+ *   kernels with layer i writing slot i & 1; the backward rebuilds layer i's tape from boundary i with that same one-layer forward just
+ *   before it reads it (the two top layers are still in their slots), so every output has the bits of the stored mode wherever the
+ *   stored mode itself is reproducible.  Costs the forward of layers - 2 layers per backward; no allocation, synchronisation or host
+ *   read, so the step stays capturable into a HIP graph.  Not combinable with TTV_TRAIN_FUSED_NORMS=1 (there a layer's first norm is
+ *   written by the layer below, which a rebuilt layer cannot repeat): TTV_ERR_INVALID.
+ * Any other mode: TTV_ERR_INVALID from the entry points, -1 from the size functions.  The backward workspace is the same in both modes. */
+#define TTV_TAPE_STORED 0
+#define TTV_TAPE_RECOMPUTE 1
+int64_t ttv_tower_tape_bytes_ex(const ttv_tower_dims* dims, const ttv_batch* batch, int tape_mode);
+int64_t ttv_tower_bwd_workspace_bytes_ex(const ttv_tower_dims* dims, const ttv_batch* batch, int tape_mode);
+int ttv_encoder_forward_train_ex(const ttv_tower_dims* dims, const ttv_tower_weights* w, const ttv_batch* batch, const void* const* clips,
+                                 float* z, void* tape, int64_t tape_bytes, void* stream, int tape_mode);
+int ttv_encoder_backward_ex(const ttv_tower_dims* dims, const ttv_tower_weights* w, const ttv_tower_weights_t* wt, const ttv_batch* batch,
+                            const float* dz, void* tape, const ttv_tower_grads* grads, void* const* dclips, void* workspace,
+                            int64_t workspace_bytes, void* stream, int tape_mode);
+int ttv_decoder_forward_train_ex(const ttv_tower_dims* dims, const ttv_tower_weights* w, const ttv_batch* batch, const void* codes,
+                                 void* const* clips_out, void* tape, int64_t tape_bytes, void* workspace, int64_t workspace_bytes,
+                                 void* stream, int tape_mode);
+int ttv_decoder_backward_ex(const ttv_tower_dims* dims, const ttv_tower_weights* w, const ttv_tower_weights_t* wt, const ttv_batch* batch,
+                            const void* codes, const void* const* dclips_out, void* tape, const ttv_tower_grads* grads, float* dcodes,
+                            void* workspace, int64_t workspace_bytes, void* stream, int tape_mode);
 /* TiTokEncoder.forward recording a tape; z fp32 [sum_tokens, token_size] (FSQ is a separate differentiable op). */
 int ttv_encoder_forward_train(const ttv_tower_dims* dims, const ttv_tower_weights* w, const ttv_batch* batch, const void* const* clips,
                               float* z, void* tape, int64_t tape_bytes, void* stream);

@@ -19,6 +19,7 @@ TTV_MAX_FSQ = 8
 TTV_MAX_TOKEN = 64
 TTV_MAX_CLIPS_PER_LAUNCH = 64
 TTV_DISC_HEAD_GENERATOR, TTV_DISC_HEAD_DISCRIMINATOR = 0, 1
+TTV_TAPE_STORED, TTV_TAPE_RECOMPUTE = 0, 1          # tape modes of the training entry points (ttv_*_ex)
 
 # ttv_debug_set bits: the TTV_DBG_* enum of include/titok_hip.h under the same names (tests/test_cabi_cpu.py holds the two equal).
 # A value with two names is read by two kernels with two meanings; tools/README.md says what each bit forces.
@@ -242,6 +243,17 @@ SYMBOLS = {
                                             i64, vp, i64, vp]),
     "ttv_decoder_backward": (C.c_int, [C.POINTER(TowerDims), C.POINTER(TowerWeights), C.POINTER(TowerWeightsT), C.POINTER(Batch), vp,
                                        C.POINTER(vp), vp, C.POINTER(TowerGrads), vp, vp, i64, vp]),
+    # the six above with a tape mode (TTV_TAPE_*) as their last argument
+    "ttv_tower_tape_bytes_ex": (i64, [C.POINTER(TowerDims), C.POINTER(Batch), C.c_int]),
+    "ttv_tower_bwd_workspace_bytes_ex": (i64, [C.POINTER(TowerDims), C.POINTER(Batch), C.c_int]),
+    "ttv_encoder_forward_train_ex": (C.c_int, [C.POINTER(TowerDims), C.POINTER(TowerWeights), C.POINTER(Batch), C.POINTER(vp), vp, vp,
+                                               i64, vp, C.c_int]),
+    "ttv_encoder_backward_ex": (C.c_int, [C.POINTER(TowerDims), C.POINTER(TowerWeights), C.POINTER(TowerWeightsT), C.POINTER(Batch), vp,
+                                          vp, C.POINTER(TowerGrads), C.POINTER(vp), vp, i64, vp, C.c_int]),
+    "ttv_decoder_forward_train_ex": (C.c_int, [C.POINTER(TowerDims), C.POINTER(TowerWeights), C.POINTER(Batch), vp, C.POINTER(vp), vp,
+                                               i64, vp, i64, vp, C.c_int]),
+    "ttv_decoder_backward_ex": (C.c_int, [C.POINTER(TowerDims), C.POINTER(TowerWeights), C.POINTER(TowerWeightsT), C.POINTER(Batch), vp,
+                                          C.POINTER(vp), vp, C.POINTER(TowerGrads), vp, vp, i64, vp, C.c_int]),
     "ttv_fsq_backward": (C.c_int, [C.POINTER(FsqParams), vp, vp, C.c_int, vp, C.c_int, vp]),
     "ttv_rmsnorm_backward_chain": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_float, vp, C.c_int,
                                               C.c_int, C.c_int, C.c_float, C.c_int, vp]),

@@ -31,7 +31,11 @@ static int tape_y_dtype(int dt) {
   static const bool f32 = ttv_env_flag("TTV_TAPE_Y_F32", false);      // A/B: fp32 sums as before round 5
   return (dt == TTV_F32 || tape_fuse_norms() || f32) ? TTV_F32 : TTV_BF16;
 }
-static Tape carve_tape(const ttv_tower_dims* d, const ttv_batch* b, char* base) {
+// tape_mode TTV_TAPE_STORED: one region per layer (layer 0 has no y1 / y2).  TTV_TAPE_RECOMPUTE: min(2, layers) layer SLOTS of the size
+// of a layer > 0 instead; t.l[i] is slot i & 1 for every i, so the forward and the backward address a layer's tape the same way in both
+// modes and only WHEN a slot holds which layer differs (layers_forward_train, layers_backward).
+static bool tape_mode_ok(int tape_mode) { return tape_mode == TTV_TAPE_STORED || tape_mode == TTV_TAPE_RECOMPUTE; }
+static Tape carve_tape(const ttv_tower_dims* d, const ttv_batch* b, char* base, int tape_mode) {
   Tape t;
   const int64_t ye = dtype_bytes(tape_y_dtype(d->dtype));
   const int64_t e = dtype_bytes(d->dtype), L = b->total_rows, P = b->sum_patches, K = b->sum_tokens, dm = d->width;
@@ -45,13 +49,17 @@ static Tape carve_tape(const ttv_tower_dims* d, const ttv_batch* b, char* base) 
   if (d->kind == TTV_ENCODER) { t.patches = take(P * pd * e); t.pe = take(P * dm * e); t.agc = take(K * dm * e); t.xc = take(K * dm * e); }
   else { t.hpre = take(K * dm * e); t.pn = take(P * dm * e); }
   for (int i = 0; i <= d->layers; ++i) t.X[i] = take(L * dm * e);
-  for (int i = 0; i < d->layers; ++i) {
+  const bool slots = tape_mode == TTV_TAPE_RECOMPUTE;
+  const int regions = slots ? (d->layers < 2 ? d->layers : 2) : d->layers;
+  for (int i = 0; i < regions; ++i) {
     Tape::L& l = t.l[i];
+    const bool y = slots || i > 0;          // a slot takes any layer
     l.xn1 = take(L * dm * e); l.qkvg = take(L * nq * e); l.lse = (float*)take(L * d->q_heads * 4);
     l.a = take(L * dm * e); l.ag = take(L * dm * e);
-    l.y1 = take(i > 0 ? L * dm * ye : 0); l.x1 = take(L * dm * e); l.xn2 = take(L * dm * e);
-    l.u = take(L * 2 * d->inner * e); l.h = take(L * d->inner * e); l.y2 = take(i > 0 ? L * dm * ye : 0);
+    l.y1 = take(y ? L * dm * ye : 0); l.x1 = take(L * dm * e); l.xn2 = take(L * dm * e);
+    l.u = take(L * 2 * d->inner * e); l.h = take(L * d->inner * e); l.y2 = take(y ? L * dm * ye : 0);
   }
+  for (int i = regions; i < d->layers; ++i) t.l[i] = t.l[i & 1];
   t.total = off;
   return t;
 }
@@ -100,7 +108,10 @@ static BwdWs carve_bwd(const ttv_tower_dims* d, const ttv_batch* b, char* base) 
   return w;
 }
 
-static int check(const ttv_tower_dims* d, const ttv_batch* b) {
+static int check(const ttv_tower_dims* d, const ttv_batch* b, int tape_mode) {
+  TTV_CHECK_ARG(tape_mode_ok(tape_mode), "tape mode %d is neither TTV_TAPE_STORED nor TTV_TAPE_RECOMPUTE", tape_mode);
+  // the fused-norm forward writes a layer's xn1 from the GEMM of the layer below; a rebuilt layer would form its own, other bits
+  TTV_CHECK_ARG(tape_mode != TTV_TAPE_RECOMPUTE || !tape_fuse_norms(), "TTV_TAPE_RECOMPUTE does not combine with TTV_TRAIN_FUSED_NORMS=1");
   TTV_CHECK_ARG(d && b, "null dims/batch");
   TTV_CHECK_ARG(d->dtype == TTV_BF16 || d->dtype == TTV_F32, "bad dtype");
   TTV_CHECK_ARG(d->layers >= 1 && d->layers <= 64, "layers out of range");
@@ -126,95 +137,102 @@ static bool latent_attn(const ttv_tower_dims* d, const ttv_batch* b, int layer) 
 }
 
 // ------------------------------------------------------------------------------------------------ forward (tape)
-static int layers_forward_train(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_batch* b, Tape& t, hipStream_t s) {
+// One layer: reads X[i], writes layer i's tape entries into `l` and X[i + 1] (encoder, last layer: its latent rows, through t.agc / t.xc).
+// The stored tape calls it with t.l[i] once; the recompute tape calls it with the layer's slot in the forward (the slot is scratch there)
+// and again from the backward - the same kernels with the same launch arguments on the same inputs, hence the same bits.
+// xn1_ready (fused norms only): in, this layer's xn1 was written by the layer below; out, the next layer's was written by this one.
+static int layer_forward_train(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_batch* b, Tape& t, int i, Tape::L& l,
+                               bool& xn1_ready, hipStream_t s) {
   const int L = b->total_rows, dm = d->width, g = d->kv_heads * d->head_dim, dt = d->dtype, nq = 2 * dm + 2 * g, I = d->inner;
   // Round 4, OPT-IN (TTV_TRAIN_FUSED_NORMS=1): where the fused residual + KEEL-norm GEMM applies (bf16, width 256) the post-norm, the fp32
   // pre-norm sum the backward needs AND the following pre-norm come out of the GEMM kernel (GemmArgs.sum_f32 / y2): 5 launches per layer
   // instead of 9, same tape.  Measured neutral (same box, tools/bench_train.py: 8.234 vs 8.236 ms at 32 clips, 3.47 vs 3.44 ms at 5): the
   // row-owning GEMM kernels lose against the tiled GEMM + 160-token tiles what the four row kernels cost, and the step is GPU-bound, not
-  // launch-bound - so the proven sequence stays the default.
+  // launch-bound - so the proven sequence stays the default.  (It writes the NEXT layer's xn1, which a slot tape has no room for: the
+  // recompute entry points refuse it.)
   const bool fuse_norms = tape_fuse_norms();
   const int ydt = tape_y_dtype(dt);
   const int64_t row_bytes = (int64_t)dm * dtype_bytes(dt);
-  bool xn1_ready = false;          // this layer's xn1 was written by the layer below
-  for (int i = 0; i < d->layers; ++i) {
-    const ttv_layer_weights& lw = w->layers[i];
-    Tape::L& l = t.l[i];
-    const float alpha = keel_alpha(d, i);
-    if (!xn1_ready) TTV_TRY(ttvk_rmsnorm(t.X[i], dt, dm, nullptr, l.xn1, dt, dm, nullptr, lw.pre_ln, L, dm, d->eps, s));
-    xn1_ready = false;
-    GemmArgs a = gemm_rope_qk(gemm_args(dt, l.xn1, dm, lw.to_qkv, dm, L, nq, dm, l.qkvg, nq), b->rope_cs, dm, g);
-    a.rope_ids = b->rope_ids; a.rope_base = b->rope_ids ? b->rope_base : nullptr;
-    TTV_TRY(ttvk_gemm(EPI_QKV_ROPE, a, s));
-    // encoder, last layer: attention outputs are needed for the latent query rows only (latent_attn); the raw output of the other rows is
-    // zeroed (the gate backward reads it for every row, times a zero gradient) and the backward skips those query rows too
-    const bool lat_q = latent_attn(d, b, i);
-    const int32_t* qb = lat_q ? b->qblocks_latent : b->qblocks;
-    const int nqb = lat_q ? b->n_qblocks_latent : b->n_qblocks;
-    const int pair = (!lat_q && b->qblocks_paired) ? TTV_ATTN_PAIRED : 0;
-    if (lat_q) (void)hipMemsetAsync(l.a, 0, (size_t)L * dm * dtype_bytes(dt), s);
-    if (dt == TTV_BF16) {
-      // one launch writes the raw output a (tape) and the gated one ag = a * sigmoid(gate) (gate applied to the stored, rounded a)
-      TTV_TRY(ttvk_attention(l.qkvg, nq, l.ag, dm, b->cu_seqlens, qb, nqb, d->q_heads, d->kv_heads, d->head_dim, TTV_ATTN_GATE | pair, dt, s, l.lse, l.a));
-    } else {
-      TTV_TRY(ttvk_attention(l.qkvg, nq, l.a, dm, b->cu_seqlens, qb, nqb, d->q_heads, d->kv_heads, d->head_dim, pair, dt, s, l.lse));
-      TTV_TRY(ttvk_gate_fwd(l.a, dm, (const char*)l.qkvg + (size_t)dm * dtype_bytes(dt), nq, l.ag, dm, L, dm, dt, s));
-    }
-    // the rest of the layer on (Lc rows: ag_in, x_in): every row, or - encoder, last layer - the latent rows, compact
-    const bool lat = latent_tail(d, b, i);
-    const int Lc = lat ? b->sum_tokens : L;
-    char* ag_in = l.ag;
-    char* x_in = t.X[i];
-    char* x_out = t.X[i + 1];
-    if (lat) {
-      TTV_TRY(gather_rows(l.ag, t.agc, b->latent_rows, Lc, row_bytes, s));
-      TTV_TRY(gather_rows(t.X[i], t.xc, b->latent_rows, Lc, row_bytes, s));
-      ag_in = t.agc; x_in = t.xc; x_out = t.xc;          // the layer's output: compact in place of its input rows, scattered below
-    }
-    // out_proj + residual: the sum into x1 (layer 0, and the fused route which norms it in the kernel) or into the tape's y1
-    const bool o_fused = i > 0 && fuse_norms && ttvk_gemm_supports_resid_norm(dt, dm, dm);
-    GemmArgs o = gemm_resid(gemm_args(dt, ag_in, dm, lw.out_proj, dm, Lc, dm, dm, (i == 0 || o_fused) ? l.x1 : l.y1, dm), x_in, dm, alpha);
-    if (i == 0) {
-      TTV_TRY(ttvk_gemm(EPI_RESID_T, o, s));
-    } else if (o_fused) {
-      o.norm_gain = lw.attn_post_ln; o.eps = d->eps;
-      o.sum_f32 = (float*)l.y1; o.ld_sum = dm; o.y2 = l.xn2; o.ldy2 = dm; o.norm_gain2 = lw.ffd_norm;
-      TTV_TRY(ttvk_gemm(EPI_RESID_NORM, o, s));
-    } else {
-      TTV_TRY(ttvk_gemm(ydt == TTV_F32 ? EPI_RESID_F32 : EPI_RESID_T, o, s));
-      TTV_TRY(ttvk_rmsnorm(l.y1, ydt, dm, nullptr, l.x1, dt, dm, nullptr, lw.attn_post_ln, Lc, dm, d->eps, s));
-    }
-    if (!o_fused)
-      TTV_TRY(ttvk_rmsnorm(l.x1, dt, dm, nullptr, l.xn2, dt, dm, nullptr, lw.ffd_norm, Lc, dm, d->eps, s));
-    if (dt == TTV_BF16) {
-      // one launch: u = xn2 W12^T kept for the backward (through `resid`, no alpha) and h = gelu(gate) * x from the stored values
-      GemmArgs f = gemm_args(dt, l.xn2, dm, lw.w12, dm, Lc, I, dm, l.h, I);
-      f.resid = l.u; f.ldr = 2 * I;
-      TTV_TRY(ttvk_gemm(EPI_GEGLU, f, s));
-    } else {
-      TTV_TRY(ttvk_gemm(EPI_STORE, gemm_args(dt, l.xn2, dm, lw.w12, dm, Lc, 2 * I, dm, l.u, 2 * I), s));
-      TTV_TRY(ttvk_geglu_fwd(l.u, 2 * I, l.h, I, Lc, I, dt, s));
-    }
-    // w3 + residual: as out_proj above, into the layer's output rows or the tape's y2
-    const bool f3_fused = i > 0 && fuse_norms && ttvk_gemm_supports_resid_norm(dt, dm, I);
-    GemmArgs f3 = gemm_resid(gemm_args(dt, l.h, I, lw.w3, I, Lc, dm, I, (i == 0 || f3_fused) ? x_out : l.y2, dm), l.x1, dm, alpha);
-    if (i == 0) {
-      TTV_TRY(ttvk_gemm(EPI_RESID_T, f3, s));
-    } else if (f3_fused) {
-      f3.norm_gain = lw.ffd_post_ln; f3.eps = d->eps;
-      f3.sum_f32 = (float*)l.y2; f3.ld_sum = dm;
-      if (i + 1 < d->layers) {          // the next layer's pre-norm rides along
-        f3.y2 = t.l[i + 1].xn1; f3.ldy2 = dm; f3.norm_gain2 = w->layers[i + 1].pre_ln;
-        xn1_ready = true;
-      }
-      TTV_TRY(ttvk_gemm(EPI_RESID_NORM, f3, s));
-    } else {
-      TTV_TRY(ttvk_gemm(ydt == TTV_F32 ? EPI_RESID_F32 : EPI_RESID_T, f3, s));
-      TTV_TRY(ttvk_rmsnorm(l.y2, ydt, dm, nullptr, x_out, dt, dm, nullptr, lw.ffd_post_ln, Lc, dm, d->eps, s));
-    }
-    if (lat)     // the latent rows of the tower's output where the tail (and the backward) read them; its patch rows are never read
-      TTV_TRY(scatter_rows(t.xc, t.X[i + 1], b->latent_rows, Lc, row_bytes, s));
+  const ttv_layer_weights& lw = w->layers[i];
+  const float alpha = keel_alpha(d, i);
+  if (!xn1_ready) TTV_TRY(ttvk_rmsnorm(t.X[i], dt, dm, nullptr, l.xn1, dt, dm, nullptr, lw.pre_ln, L, dm, d->eps, s));
+  xn1_ready = false;
+  GemmArgs a = gemm_rope_qk(gemm_args(dt, l.xn1, dm, lw.to_qkv, dm, L, nq, dm, l.qkvg, nq), b->rope_cs, dm, g);
+  a.rope_ids = b->rope_ids; a.rope_base = b->rope_ids ? b->rope_base : nullptr;
+  TTV_TRY(ttvk_gemm(EPI_QKV_ROPE, a, s));
+  // encoder, last layer: attention outputs are needed for the latent query rows only (latent_attn); the raw output of the other rows is
+  // zeroed (the gate backward reads it for every row, times a zero gradient) and the backward skips those query rows too
+  const bool lat_q = latent_attn(d, b, i);
+  const int32_t* qb = lat_q ? b->qblocks_latent : b->qblocks;
+  const int nqb = lat_q ? b->n_qblocks_latent : b->n_qblocks;
+  const int pair = (!lat_q && b->qblocks_paired) ? TTV_ATTN_PAIRED : 0;
+  if (lat_q) (void)hipMemsetAsync(l.a, 0, (size_t)L * dm * dtype_bytes(dt), s);
+  if (dt == TTV_BF16) {
+    // one launch writes the raw output a (tape) and the gated one ag = a * sigmoid(gate) (gate applied to the stored, rounded a)
+    TTV_TRY(ttvk_attention(l.qkvg, nq, l.ag, dm, b->cu_seqlens, qb, nqb, d->q_heads, d->kv_heads, d->head_dim, TTV_ATTN_GATE | pair, dt, s, l.lse, l.a));
+  } else {
+    TTV_TRY(ttvk_attention(l.qkvg, nq, l.a, dm, b->cu_seqlens, qb, nqb, d->q_heads, d->kv_heads, d->head_dim, pair, dt, s, l.lse));
+    TTV_TRY(ttvk_gate_fwd(l.a, dm, (const char*)l.qkvg + (size_t)dm * dtype_bytes(dt), nq, l.ag, dm, L, dm, dt, s));
   }
+  // the rest of the layer on (Lc rows: ag_in, x_in): every row, or - encoder, last layer - the latent rows, compact
+  const bool lat = latent_tail(d, b, i);
+  const int Lc = lat ? b->sum_tokens : L;
+  char* ag_in = l.ag;
+  char* x_in = t.X[i];
+  char* x_out = t.X[i + 1];
+  if (lat) {
+    TTV_TRY(gather_rows(l.ag, t.agc, b->latent_rows, Lc, row_bytes, s));
+    TTV_TRY(gather_rows(t.X[i], t.xc, b->latent_rows, Lc, row_bytes, s));
+    ag_in = t.agc; x_in = t.xc; x_out = t.xc;          // the layer's output: compact in place of its input rows, scattered below
+  }
+  // out_proj + residual: the sum into x1 (layer 0, and the fused route which norms it in the kernel) or into the tape's y1
+  const bool o_fused = i > 0 && fuse_norms && ttvk_gemm_supports_resid_norm(dt, dm, dm);
+  GemmArgs o = gemm_resid(gemm_args(dt, ag_in, dm, lw.out_proj, dm, Lc, dm, dm, (i == 0 || o_fused) ? l.x1 : l.y1, dm), x_in, dm, alpha);
+  if (i == 0) {
+    TTV_TRY(ttvk_gemm(EPI_RESID_T, o, s));
+  } else if (o_fused) {
+    o.norm_gain = lw.attn_post_ln; o.eps = d->eps;
+    o.sum_f32 = (float*)l.y1; o.ld_sum = dm; o.y2 = l.xn2; o.ldy2 = dm; o.norm_gain2 = lw.ffd_norm;
+    TTV_TRY(ttvk_gemm(EPI_RESID_NORM, o, s));
+  } else {
+    TTV_TRY(ttvk_gemm(ydt == TTV_F32 ? EPI_RESID_F32 : EPI_RESID_T, o, s));
+    TTV_TRY(ttvk_rmsnorm(l.y1, ydt, dm, nullptr, l.x1, dt, dm, nullptr, lw.attn_post_ln, Lc, dm, d->eps, s));
+  }
+  if (!o_fused)
+    TTV_TRY(ttvk_rmsnorm(l.x1, dt, dm, nullptr, l.xn2, dt, dm, nullptr, lw.ffd_norm, Lc, dm, d->eps, s));
+  if (dt == TTV_BF16) {
+    // one launch: u = xn2 W12^T kept for the backward (through `resid`, no alpha) and h = gelu(gate) * x from the stored values
+    GemmArgs f = gemm_args(dt, l.xn2, dm, lw.w12, dm, Lc, I, dm, l.h, I);
+    f.resid = l.u; f.ldr = 2 * I;
+    TTV_TRY(ttvk_gemm(EPI_GEGLU, f, s));
+  } else {
+    TTV_TRY(ttvk_gemm(EPI_STORE, gemm_args(dt, l.xn2, dm, lw.w12, dm, Lc, 2 * I, dm, l.u, 2 * I), s));
+    TTV_TRY(ttvk_geglu_fwd(l.u, 2 * I, l.h, I, Lc, I, dt, s));
+  }
+  // w3 + residual: as out_proj above, into the layer's output rows or the tape's y2
+  const bool f3_fused = i > 0 && fuse_norms && ttvk_gemm_supports_resid_norm(dt, dm, I);
+  GemmArgs f3 = gemm_resid(gemm_args(dt, l.h, I, lw.w3, I, Lc, dm, I, (i == 0 || f3_fused) ? x_out : l.y2, dm), l.x1, dm, alpha);
+  if (i == 0) {
+    TTV_TRY(ttvk_gemm(EPI_RESID_T, f3, s));
+  } else if (f3_fused) {
+    f3.norm_gain = lw.ffd_post_ln; f3.eps = d->eps;
+    f3.sum_f32 = (float*)l.y2; f3.ld_sum = dm;
+    if (i + 1 < d->layers) {          // the next layer's pre-norm rides along
+      f3.y2 = t.l[i + 1].xn1; f3.ldy2 = dm; f3.norm_gain2 = w->layers[i + 1].pre_ln;
+      xn1_ready = true;
+    }
+    TTV_TRY(ttvk_gemm(EPI_RESID_NORM, f3, s));
+  } else {
+    TTV_TRY(ttvk_gemm(ydt == TTV_F32 ? EPI_RESID_F32 : EPI_RESID_T, f3, s));
+    TTV_TRY(ttvk_rmsnorm(l.y2, ydt, dm, nullptr, x_out, dt, dm, nullptr, lw.ffd_post_ln, Lc, dm, d->eps, s));
+  }
+  if (lat)     // the latent rows of the tower's output where the tail (and the backward) read them; its patch rows are never read
+    TTV_TRY(scatter_rows(t.xc, t.X[i + 1], b->latent_rows, Lc, row_bytes, s));
+  return TTV_OK;
+}
+static int layers_forward_train(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_batch* b, Tape& t, hipStream_t s) {
+  bool xn1_ready = false;
+  for (int i = 0; i < d->layers; ++i) TTV_TRY(layer_forward_train(d, w, b, t, i, t.l[i], xn1_ready, s));
   return TTV_OK;
 }
 
@@ -272,8 +290,10 @@ static int side_join(WgradSide* sd, hipStream_t s) {
 
 // ------------------------------------------------------------------------------------------------ backward (layers)
 // On entry ws.dxa holds dL/dX[layers] (fp32); on exit ws.dxa holds dL/dX[0].
+// TTV_TAPE_RECOMPUTE: t.l[i] is slot i & 1, and a layer's tape is rebuilt from X[i] by layer_forward_train before it is read.  The forward
+// left its two top layers in the slots (it used the same alternation), so the first layer rebuilt is layers - 3.
 static int layers_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_tower_weights_t* wt, const ttv_batch* b, Tape& t,
-                           const ttv_tower_grads* gr, BwdWs& ws, hipStream_t s) {
+                           const ttv_tower_grads* gr, BwdWs& ws, int tape_mode, hipStream_t s) {
   const int L = b->total_rows, dm = d->width, g = d->kv_heads * d->head_dim, dt = d->dtype, nq = 2 * dm + 2 * g, I = d->inner;
   const int ydt = tape_y_dtype(dt);
   float* dx = ws.dxa;     // gradient of the layer output
@@ -357,6 +377,14 @@ static int layers_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, 
     TTV_TRY(ttvk_gemm(EPI_STORE, gemm_args(dt, dqkvg, nq, lt.to_qkv_t, nq, L, dm, nq, ws.g_d2, dm), s));
     TTV_TRY(ttvk_wgrad(dqkvg, nq, l.xn1, dm, lg.to_qkv, dm, L, nq, dm, dt, ws.wg_part, ws.wg_part_bytes, sw, &wgb));
     TTV_TRY(ttvk_wgrad_flush(&wgb, sw));     // the layer's four weight gradients: one summing launch
+    // Recompute tape: the chain below reads y2 of layer i - 1, and the next iteration the rest of that layer's tape: rebuild it now, on
+    // the caller's stream, into the OTHER slot.  That slot held layer i + 1, whose weight-gradient GEMMs - the only readers outside this
+    // stream (h, xn2, ag, xn1) - were joined at the end of the previous iteration; this layer's own slot, which the second stream is
+    // still reading, is not touched.  X[i] is rewritten with the bits it holds.
+    if (tape_mode == TTV_TAPE_RECOMPUTE && i > 0 && i < d->layers - 1) {
+      bool xn1_ready = false;
+      TTV_TRY(layer_forward_train(d, w, b, t, i - 1, t.l[i - 1], xn1_ready, s));
+    }
     // dx += rmsnorm_bwd(X[i], pre_ln, dxn1) = dL/dX[i]; chained with the head of the layer below: through its feed-forward
     // post-norm (layers >= 1) and the bf16 copy df that its w3 products read
     if (i == 0) {
@@ -704,13 +732,19 @@ __global__ __launch_bounds__(256) void k_opt_ema_exchange(const OptEntry* __rest
 
 extern "C" {
 
+int64_t ttv_tower_tape_bytes_ex(const ttv_tower_dims* dims, const ttv_batch* batch, int tape_mode) {
+  if (!dims || !batch || !tape_mode_ok(tape_mode)) return -1;
+  return carve_tape(dims, batch, nullptr, tape_mode).total;
+}
+int64_t ttv_tower_bwd_workspace_bytes_ex(const ttv_tower_dims* dims, const ttv_batch* batch, int tape_mode) {
+  if (!dims || !batch || !tape_mode_ok(tape_mode)) return -1;
+  return carve_bwd(dims, batch, nullptr).total;          // the recompute writes the tape only: one workspace for both modes
+}
 int64_t ttv_tower_tape_bytes(const ttv_tower_dims* dims, const ttv_batch* batch) {
-  if (!dims || !batch) return -1;
-  return carve_tape(dims, batch, nullptr).total;
+  return ttv_tower_tape_bytes_ex(dims, batch, TTV_TAPE_STORED);
 }
 int64_t ttv_tower_bwd_workspace_bytes(const ttv_tower_dims* dims, const ttv_batch* batch) {
-  if (!dims || !batch) return -1;
-  return carve_bwd(dims, batch, nullptr).total;
+  return ttv_tower_bwd_workspace_bytes_ex(dims, batch, TTV_TAPE_STORED);
 }
 
 int ttv_fsq_backward(const ttv_fsq_params* p, const float* z, const void* dcodes, int dcodes_dtype, float* dz, int rows, void* stream) {
@@ -718,12 +752,12 @@ int ttv_fsq_backward(const ttv_fsq_params* p, const float* z, const void* dcodes
   return ttvk_fsq_bwd(p, z, dcodes, dcodes_dtype, dz, rows, (hipStream_t)stream);
 }
 
-int ttv_encoder_forward_train(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_batch* b, const void* const* clips, float* z,
-                              void* tape, int64_t tape_bytes, void* stream) {
-  TTV_TRY(check(d, b));
+int ttv_encoder_forward_train_ex(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_batch* b, const void* const* clips, float* z,
+                                 void* tape, int64_t tape_bytes, void* stream, int tape_mode) {
+  TTV_TRY(check(d, b, tape_mode));
   TTV_CHECK_ARG(d->kind == TTV_ENCODER && w && w->layers && clips && z && tape, "encoder_forward_train: bad argument");
   hipStream_t s = (hipStream_t)stream;
-  Tape t = carve_tape(d, b, (char*)tape);
+  Tape t = carve_tape(d, b, (char*)tape, tape_mode);
   TTV_CHECK_ARG(t.total <= tape_bytes, "encoder_forward_train: tape too small");
   const int dm = d->width, dt = d->dtype, P = b->sum_patches, pd = patch_dim(d);
   TTV_TRY(patch_copy_all(false, (void* const*)clips, d, b, t.patches, dt, s));
@@ -737,9 +771,15 @@ int ttv_encoder_forward_train(const ttv_tower_dims* d, const ttv_tower_weights* 
   return TTV_OK;
 }
 
-int ttv_encoder_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_tower_weights_t* wt, const ttv_batch* b, const float* dz,
-                         void* tape, const ttv_tower_grads* gr, void* const* dclips, void* workspace, int64_t workspace_bytes, void* stream) {
-  TTV_TRY(check(d, b));
+int ttv_encoder_forward_train(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_batch* b, const void* const* clips, float* z,
+                              void* tape, int64_t tape_bytes, void* stream) {
+  return ttv_encoder_forward_train_ex(d, w, b, clips, z, tape, tape_bytes, stream, TTV_TAPE_STORED);
+}
+
+int ttv_encoder_backward_ex(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_tower_weights_t* wt, const ttv_batch* b, const float* dz,
+                            void* tape, const ttv_tower_grads* gr, void* const* dclips, void* workspace, int64_t workspace_bytes, void* stream,
+                            int tape_mode) {
+  TTV_TRY(check(d, b, tape_mode));
   TTV_CHECK_ARG(d->kind == TTV_ENCODER && w && wt && wt->layers && (!gr || gr->layers) && dz && tape && workspace, "encoder_backward: bad argument");
   // grads == NULL: every parameter is frozen (generator step through the discriminator, loss_module.py:144-151) - only the
   // input-clip gradient is produced; all weight-gradient GEMMs, gain / bias reductions are skipped
@@ -750,7 +790,7 @@ int ttv_encoder_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, co
     gr = &no_grads;
   }
   hipStream_t s = (hipStream_t)stream;
-  Tape t = carve_tape(d, b, (char*)tape);
+  Tape t = carve_tape(d, b, (char*)tape, tape_mode);
   BwdWs ws = carve_bwd(d, b, (char*)workspace);
   TTV_CHECK_ARG(ws.total <= workspace_bytes, "encoder_backward: workspace too small");
   const int L = b->total_rows, dm = d->width, dt = d->dtype, P = b->sum_patches, K = b->sum_tokens, C = d->token_size, pd = patch_dim(d);
@@ -761,7 +801,7 @@ int ttv_encoder_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, co
   TTV_TRY(ttvk_expand_small(dz, TTV_F32, C, C, w->proj_out_w, dt, dm, 1, ws.g_d2, dt, dm, K, dm, s));                      // dn
   (void)hipMemsetAsync(ws.dxa, 0, (size_t)L * dm * sizeof(float), s);
   TTV_TRY(ttvk_rmsnorm_bwd(t.X[d->layers], dt, dm, b->latent_rows, ws.g_d2, dt, dm, nullptr, w->ln_post, ws.dxa, TTV_F32, dm, b->latent_rows, 0, gr->ln_post, K, dm, d->eps, s));
-  TTV_TRY(layers_backward(d, w, wt, b, t, gr, ws, s));
+  TTV_TRY(layers_backward(d, w, wt, b, t, gr, ws, tape_mode, s));
   // ---- head ----
   // latent rows are the constant vector ln_pre_t(mask_token * 1)
   (void)hipMemsetAsync(ws.colsum, 0, dm * sizeof(float), s);
@@ -779,12 +819,17 @@ int ttv_encoder_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, co
   return TTV_OK;
 }
 
-int ttv_decoder_forward_train(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_batch* b, const void* codes, void* const* clips_out,
-                              void* tape, int64_t tape_bytes, void* workspace, int64_t workspace_bytes, void* stream) {
-  TTV_TRY(check(d, b));
+int ttv_encoder_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_tower_weights_t* wt, const ttv_batch* b, const float* dz,
+                         void* tape, const ttv_tower_grads* gr, void* const* dclips, void* workspace, int64_t workspace_bytes, void* stream) {
+  return ttv_encoder_backward_ex(d, w, wt, b, dz, tape, gr, dclips, workspace, workspace_bytes, stream, TTV_TAPE_STORED);
+}
+
+int ttv_decoder_forward_train_ex(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_batch* b, const void* codes, void* const* clips_out,
+                                 void* tape, int64_t tape_bytes, void* workspace, int64_t workspace_bytes, void* stream, int tape_mode) {
+  TTV_TRY(check(d, b, tape_mode));
   TTV_CHECK_ARG(d->kind == TTV_DECODER && w && w->layers && codes && clips_out && tape && workspace, "decoder_forward_train: bad argument");
   hipStream_t s = (hipStream_t)stream;
-  Tape t = carve_tape(d, b, (char*)tape);
+  Tape t = carve_tape(d, b, (char*)tape, tape_mode);
   TTV_CHECK_ARG(t.total <= tape_bytes, "decoder_forward_train: tape too small");
   const int dm = d->width, dt = d->dtype, P = b->sum_patches, pd = patch_dim(d);
   TTV_CHECK_ARG((int64_t)P * pd * dtype_bytes(dt) <= workspace_bytes, "decoder_forward_train: workspace too small");
@@ -798,13 +843,18 @@ int ttv_decoder_forward_train(const ttv_tower_dims* d, const ttv_tower_weights* 
   return patch_copy_all(true, clips_out, d, b, workspace, dt, s);
 }
 
-int ttv_decoder_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_tower_weights_t* wt, const ttv_batch* b, const void* codes,
-                         const void* const* dclips_out, void* tape, const ttv_tower_grads* gr, float* dcodes, void* workspace,
-                         int64_t workspace_bytes, void* stream) {
-  TTV_TRY(check(d, b));
+int ttv_decoder_forward_train(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_batch* b, const void* codes, void* const* clips_out,
+                              void* tape, int64_t tape_bytes, void* workspace, int64_t workspace_bytes, void* stream) {
+  return ttv_decoder_forward_train_ex(d, w, b, codes, clips_out, tape, tape_bytes, workspace, workspace_bytes, stream, TTV_TAPE_STORED);
+}
+
+int ttv_decoder_backward_ex(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_tower_weights_t* wt, const ttv_batch* b, const void* codes,
+                            const void* const* dclips_out, void* tape, const ttv_tower_grads* gr, float* dcodes, void* workspace,
+                            int64_t workspace_bytes, void* stream, int tape_mode) {
+  TTV_TRY(check(d, b, tape_mode));
   TTV_CHECK_ARG(d->kind == TTV_DECODER && w && wt && wt->layers && gr && gr->layers && codes && dclips_out && tape && workspace, "decoder_backward: bad argument");
   hipStream_t s = (hipStream_t)stream;
-  Tape t = carve_tape(d, b, (char*)tape);
+  Tape t = carve_tape(d, b, (char*)tape, tape_mode);
   BwdWs ws = carve_bwd(d, b, (char*)workspace);
   TTV_CHECK_ARG(ws.total <= workspace_bytes, "decoder_backward: workspace too small");
   const int L = b->total_rows, dm = d->width, dt = d->dtype, P = b->sum_patches, K = b->sum_tokens, C = d->token_size, pd = patch_dim(d);
@@ -815,7 +865,7 @@ int ttv_decoder_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, co
   TTV_TRY(ttvk_gemm(EPI_STORE, gemm_args(dt, ws.g_pd, pd, wt->proj_out_t, pd, P, dm, pd, ws.g_d2, dm), s));   // dpn
   (void)hipMemsetAsync(ws.dxa, 0, (size_t)L * dm * sizeof(float), s);
   TTV_TRY(ttvk_rmsnorm_bwd(t.X[d->layers], dt, dm, b->patch_rows, ws.g_d2, dt, dm, nullptr, w->ln_post, ws.dxa, TTV_F32, dm, b->patch_rows, 0, gr->ln_post, P, dm, d->eps, s));
-  TTV_TRY(layers_backward(d, w, wt, b, t, gr, ws, s));
+  TTV_TRY(layers_backward(d, w, wt, b, t, gr, ws, tape_mode, s));
   // ---- head ----
   (void)hipMemsetAsync(ws.colsum, 0, dm * sizeof(float), s);
   TTV_TRY(ttvk_colsum(ws.dxa, TTV_F32, dm, b->patch_rows, P, dm, ws.colsum, s));
@@ -827,6 +877,12 @@ int ttv_decoder_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, co
   TTV_TRY(ttvk_outer_small(codes, dt, C, C, ws.small_f32, TTV_F32, dm, nullptr, gr->proj_in_w, C, 1, K, dm, s));
   if (dcodes) TTV_TRY(ttvk_reduce_small(ws.small_f32, TTV_F32, dm, nullptr, w->proj_in_w, dt, C, C, dcodes, C, K, dm, s));
   return TTV_OK;
+}
+
+int ttv_decoder_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_tower_weights_t* wt, const ttv_batch* b, const void* codes,
+                         const void* const* dclips_out, void* tape, const ttv_tower_grads* gr, float* dcodes, void* workspace,
+                         int64_t workspace_bytes, void* stream) {
+  return ttv_decoder_backward_ex(d, w, wt, b, codes, dclips_out, tape, gr, dcodes, workspace, workspace_bytes, stream, TTV_TAPE_STORED);
 }
 
 int64_t ttv_linear_wgrad_workspace_bytes(int L, int N, int K) { return ttvk_wgrad_ws_bytes(L, N, K); }

@@ -86,6 +86,10 @@ class _Tower(nn.Module):
         self._pack = None
         self._pack_key = None
         self._ws = {}
+        # Training tape: False (default) stores every layer's tensors for the backward; True keeps the layer boundaries and two layer
+        # slots and lets the backward rebuild each layer's tape from its boundary (TTV_TAPE_RECOMPUTE, include/titok_hip.h): the same
+        # gradients for one more forward of the layers, a fraction of the memory.  Read by each training forward, for its own backward too.
+        self.activation_recompute = False
         self.register_load_state_dict_post_hook(lambda module, incompatible: module.invalidate_packs())
         return mlp_ratio
 
@@ -688,8 +692,10 @@ def _train_ctx(tower: _Tower, pix, counts, device, dtype):
     batch = plan.batch_for(tower.heads[0], tower.heads[1])
     pack = tower._packed(dtype, device)
     lib = _lib.lib()
-    tape = torch.empty(int(lib.ttv_tower_tape_bytes(C.byref(dims), C.byref(batch))), dtype=torch.uint8, device=device)
-    return plan, dims, batch, pack, tape
+    # the tape mode is read once, here: the backward runs in the mode its forward recorded, whatever the attribute says by then
+    mode = _lib.TTV_TAPE_RECOMPUTE if tower.activation_recompute else _lib.TTV_TAPE_STORED
+    tape = torch.empty(int(lib.ttv_tower_tape_bytes_ex(C.byref(dims), C.byref(batch), mode)), dtype=torch.uint8, device=device)
+    return plan, dims, batch, pack, tape, mode
 
 
 class _EncoderTrainFn(torch.autograd.Function):
@@ -697,12 +703,12 @@ class _EncoderTrainFn(torch.autograd.Function):
     def forward(ctx, tower, counts, pix, n_clips, *tensors):
         clips = [c.contiguous() for c in tensors[:n_clips]]
         device, dtype = clips[0].device, clips[0].dtype
-        plan, dims, batch, pack, tape = _train_ctx(tower, pix, counts, device, dtype)
+        plan, dims, batch, pack, tape, mode = _train_ctx(tower, pix, counts, device, dtype)
         z = torch.empty((plan.sum_tokens, tower.token_size), dtype=torch.float32, device=device)
-        rc = _lib.lib().ttv_encoder_forward_train(C.byref(dims), C.byref(pack.struct), C.byref(batch), _lib.ptr_array(clips),
-                                                  z.data_ptr(), tape.data_ptr(), tape.numel(), _lib.stream_ptr(device))
+        rc = _lib.lib().ttv_encoder_forward_train_ex(C.byref(dims), C.byref(pack.struct), C.byref(batch), _lib.ptr_array(clips),
+                                                     z.data_ptr(), tape.data_ptr(), tape.numel(), _lib.stream_ptr(device), mode)
         _lib.check(rc, "ttv_encoder_forward_train")
-        ctx.tower, ctx.plan, ctx.dims, ctx.batch, ctx.pack, ctx.tape = tower, plan, dims, batch, pack, tape
+        ctx.tower, ctx.plan, ctx.dims, ctx.batch, ctx.pack, ctx.tape, ctx.tape_mode = tower, plan, dims, batch, pack, tape, mode
         ctx.clips = clips
         ctx.n_clips = n_clips
         ctx.clip_grad = [bool(t.requires_grad) for t in tensors[:n_clips]]
@@ -713,7 +719,8 @@ class _EncoderTrainFn(torch.autograd.Function):
     def backward(ctx, dz):
         tower, device = ctx.tower, dz.device
         lib = _lib.lib()
-        ws = torch.empty(int(lib.ttv_tower_bwd_workspace_bytes(C.byref(ctx.dims), C.byref(ctx.batch))), dtype=torch.uint8, device=device)
+        ws = torch.empty(int(lib.ttv_tower_bwd_workspace_bytes_ex(C.byref(ctx.dims), C.byref(ctx.batch), ctx.tape_mode)), dtype=torch.uint8,
+                         device=device)
         dclips = None
         if any(ctx.clip_grad):
             dclips = [torch.empty_like(c) for c in ctx.clips]
@@ -721,9 +728,10 @@ class _EncoderTrainFn(torch.autograd.Function):
         frozen = dclips is not None and not any(p.requires_grad for p in ctx.params)
         if not frozen:
             flat, gstruct, _lay = tower._grad_buffers(device)
-        rc = lib.ttv_encoder_backward(C.byref(ctx.dims), C.byref(ctx.pack.struct), C.byref(ctx.pack.transposed()), C.byref(ctx.batch),
-                                      dz.contiguous().float().data_ptr(), ctx.tape.data_ptr(), None if frozen else C.byref(gstruct),
-                                      _lib.ptr_array(dclips) if dclips else None, ws.data_ptr(), ws.numel(), _lib.stream_ptr(device))
+        rc = lib.ttv_encoder_backward_ex(C.byref(ctx.dims), C.byref(ctx.pack.struct), C.byref(ctx.pack.transposed()), C.byref(ctx.batch),
+                                         dz.contiguous().float().data_ptr(), ctx.tape.data_ptr(), None if frozen else C.byref(gstruct),
+                                         _lib.ptr_array(dclips) if dclips else None, ws.data_ptr(), ws.numel(), _lib.stream_ptr(device),
+                                         ctx.tape_mode)
         _lib.check(rc, "ttv_encoder_backward")
         by_id = {} if frozen else tower._reduce_and_finish(flat)
         clip_grads = [dclips[i] if (dclips and ctx.clip_grad[i]) else None for i in range(ctx.n_clips)]
@@ -737,16 +745,16 @@ class _DecoderTrainFn(torch.autograd.Function):
     def forward(ctx, tower, counts, pix, tokens, *params):
         device, dtype = tokens.device, tokens.dtype
         tokens = tokens.contiguous()
-        plan, dims, batch, pack, tape = _train_ctx(tower, pix, counts, device, dtype)
+        plan, dims, batch, pack, tape, mode = _train_ctx(tower, pix, counts, device, dtype)
         sizes = [tower.out_channels * t * h * w for (t, h, w) in pix]
         outs = [torch.empty((tower.out_channels, t, h, w), dtype=dtype, device=device) for (t, h, w) in pix]
         pd = tower.out_channels * math.prod(tower.patch)
         ws = torch.empty(plan.sum_patches * pd, dtype=dtype, device=device)
-        rc = _lib.lib().ttv_decoder_forward_train(C.byref(dims), C.byref(pack.struct), C.byref(batch), tokens.data_ptr(),
-                                                  _lib.ptr_array(outs), tape.data_ptr(), tape.numel(), ws.data_ptr(),
-                                                  ws.numel() * ws.element_size(), _lib.stream_ptr(device))
+        rc = _lib.lib().ttv_decoder_forward_train_ex(C.byref(dims), C.byref(pack.struct), C.byref(batch), tokens.data_ptr(),
+                                                     _lib.ptr_array(outs), tape.data_ptr(), tape.numel(), ws.data_ptr(),
+                                                     ws.numel() * ws.element_size(), _lib.stream_ptr(device), mode)
         _lib.check(rc, "ttv_decoder_forward_train")
-        ctx.tower, ctx.plan, ctx.dims, ctx.batch, ctx.pack, ctx.tape = tower, plan, dims, batch, pack, tape
+        ctx.tower, ctx.plan, ctx.dims, ctx.batch, ctx.pack, ctx.tape, ctx.tape_mode = tower, plan, dims, batch, pack, tape, mode
         ctx.tokens = tokens
         ctx.tokens_grad = bool(tokens.requires_grad)
         ctx.params = list(params)
@@ -757,14 +765,15 @@ class _DecoderTrainFn(torch.autograd.Function):
         tower, device = ctx.tower, ctx.tokens.device
         lib = _lib.lib()
         flat, gstruct, _lay = tower._grad_buffers(device)
-        ws = torch.empty(int(lib.ttv_tower_bwd_workspace_bytes(C.byref(ctx.dims), C.byref(ctx.batch))), dtype=torch.uint8, device=device)
+        ws = torch.empty(int(lib.ttv_tower_bwd_workspace_bytes_ex(C.byref(ctx.dims), C.byref(ctx.batch), ctx.tape_mode)), dtype=torch.uint8,
+                         device=device)
         shapes = [(tower.out_channels, t, h, w) for (t, h, w) in ctx.plan.pixel_grids]
         dcl = [(g if g is not None else torch.zeros(sh, dtype=ctx.tokens.dtype, device=device)).to(ctx.tokens.dtype).contiguous()
                for g, sh in zip(dclips, shapes)]
         dcodes = torch.empty((ctx.plan.sum_tokens, tower.token_size), dtype=torch.float32, device=device)
-        rc = lib.ttv_decoder_backward(C.byref(ctx.dims), C.byref(ctx.pack.struct), C.byref(ctx.pack.transposed()), C.byref(ctx.batch),
-                                      ctx.tokens.data_ptr(), _lib.ptr_array(dcl), ctx.tape.data_ptr(), C.byref(gstruct),
-                                      dcodes.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(device))
+        rc = lib.ttv_decoder_backward_ex(C.byref(ctx.dims), C.byref(ctx.pack.struct), C.byref(ctx.pack.transposed()), C.byref(ctx.batch),
+                                         ctx.tokens.data_ptr(), _lib.ptr_array(dcl), ctx.tape.data_ptr(), C.byref(gstruct),
+                                         dcodes.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(device), ctx.tape_mode)
         _lib.check(rc, "ttv_decoder_backward")
         by_id = tower._reduce_and_finish(flat)
         param_grads = [by_id.get(id(p)) if p.requires_grad else None for p in ctx.params]

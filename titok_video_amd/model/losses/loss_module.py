@@ -203,6 +203,8 @@ class ReconstructionLoss(nn.Module):
             self.disc_tokens = 4   # extra as register tokens (loss_module.py:42)
             self.disc_model = TiTokEncoder(model_size=model_d.model_size, patch_size=tuple(model_d.patch_size), in_channels=3,
                                            out_channels=1).apply(init_weights)
+            # build-defined, absent = off: the discriminator tower's training tape in recompute mode (TiTok.set_activation_recompute)
+            self.disc_model.activation_recompute = bool(getattr(model_d, "activation_recompute", False))
         self.gp_weight = float(loss_d.gp_weight)
         self.gp_noise = float(loss_d.gp_noise)
         self.centering_weight = float(loss_d.centering_weight)

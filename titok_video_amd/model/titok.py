@@ -11,7 +11,9 @@ types and state-dict keys (`encoder.*`, `decoder.*`; FSQ has no persistent keys)
     nearest-codebook-entry quantiser of BASELINE.json's configs #4 / #5 (8192 x 32, 16384 x 64) into the one quantiser slot the
     reference has (titok.py:37,47-52): encode -> L2 argmin + straight-through lookup -> decode.  The reference itself ships FSQ only;
     the default (`quantizer` absent or "fsq") is the reference's model.  Trainable (round 4): under autograd the towers record their
-    tape, the lookup is straight-through towards the encoder and passes the decoder's token gradient to the selected codebook rows.
+    tape, the lookup is straight-through towards the encoder and passes the decoder's token gradient to the selected codebook rows;
+  * BUILD-DEFINED: `config.tokenizer.model.activation_recompute = True` (absent: off) trains both towers on the recompute tape
+    (`set_activation_recompute`): same gradients, a fraction of the activation memory, one more forward of the layers.
 """
 from __future__ import annotations
 
@@ -65,6 +67,14 @@ class TiTok(nn.Module):
         # None (default): both towers follow the clips, as the reference's modules do.
         self.encoder_dtype = None
         self.decoder_dtype = None
+        self.set_activation_recompute(bool(getattr(m, "activation_recompute", False)))
+
+    def set_activation_recompute(self, flag: bool):
+        """Training memory: True makes both towers keep only the residual stream at the layer boundaries and rebuild one layer's
+        activations at a time during the backward (blocks._Tower.activation_recompute); False (default) stores them all.  Takes
+        effect with the next training forward; gradients are the stored tape's, bit for bit wherever those are reproducible."""
+        self.encoder.activation_recompute = self.decoder.activation_recompute = bool(flag)
+        return self
 
     def set_index_exact(self, mode):
         """Inference arithmetic that keeps the reference's fp32 token indices (parameters must be fp32 masters):
