@@ -1,4 +1,4 @@
-"""Float64 replay of one `HipAdamW` step (titok_video_amd/optim.py, `k_opt_gradsq` / `k_opt_adamw` in csrc/ttv_train.hip) and a counted
+"""Float64 replay of one `HipAdamW` step (titok_video_amd/optim.py, `k_opt_gradsq` / `k_opt_adamw` in csrc/ttv_optim.hip) and a counted
 bound on how far the kernels may be from it.  Plain numpy / torch, no GPU.  Used by tests/test_adamw_ref_cpu.py (the bound is valid and
 it bites) and tests/test_hip_adamw_f64.py (the kernels against the replay).
 

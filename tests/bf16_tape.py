@@ -49,7 +49,7 @@ class _Bwd(torch.autograd.Function):
 
 class Rounding:
     """Where the replay rounds.  on=False: a plain float64 autograd of the model (no rounding anywhere).  y_bf16=False: the KEEL sums
-    y1 / y2 stay unrounded (TTV_TAPE_Y_F32=1 or TTV_TRAIN_FUSED_NORMS=1, ttv_train.hip:39-42).  `record`: a dict that receives the
+    y1 / y2 stay unrounded (TTV_TAPE_Y_F32=1 or TTV_TRAIN_FUSED_NORMS=1, ttv_train.hip:30-33).  `record`: a dict that receives the
     forward value of every named F point (for the CPU tests)."""
 
     def __init__(self, on: bool = True, y_bf16: bool = True, record=None):
@@ -125,7 +125,7 @@ class _Attention64(torch.autograd.Function):
 
 
 def layers_replay(x, p, prefix, layers, heads, cos, sin, cu, r: Rounding):
-    """layers_forward_train (ttv_train.hip:140-234) on X[0] -> X[layers]; the backward's bf16 buffers from layers_backward (:290-405)."""
+    """layers_forward_train (ttv_train.hip:139-237) on X[0] -> X[layers]; the backward's bf16 buffers from layers_backward (:291-409)."""
     hq, hkv = heads
     d = x.shape[1]
     g = hkv * 64
@@ -133,36 +133,36 @@ def layers_replay(x, p, prefix, layers, heads, cos, sin, cu, r: Rounding):
     for i in range(layers):
         ap, fp = f"{prefix}attn_layer.{i}.", f"{prefix}ffd_layer.{i}."
         t = f"l{i}."
-        xn1 = r.FB(rmsnorm64(x, p[ap + "pre_ln.weight"]), t + "xn1")             # F :153 xn1 ; B :379 dxn1 (g_d2)
-        qkv = r.B(xn1 @ p[ap + "to_qkv.weight"].T)                               # B :372-376 dq / dk / dv (un-rotated) and dgate (g_nq)
+        xn1 = r.FB(rmsnorm64(x, p[ap + "pre_ln.weight"]), t + "xn1")             # F :158 xn1 ; B :377 dxn1 (g_d2)
+        qkv = r.B(xn1 @ p[ap + "to_qkv.weight"].T)                               # B :370-374 dq / dk / dv (un-rotated) and dgate (g_nq)
         q, gate, k, v = qkv.split([d, d, g, g], -1)
-        q = rotate64(q.unflatten(-1, (hq, 64)), cos, sin)                        # EPI_QKV_ROPE: rotary on the fp32 accumulator (:156-159)
+        q = rotate64(q.unflatten(-1, (hq, 64)), cos, sin)                        # EPI_QKV_ROPE: rotary on the fp32 accumulator (:160-162)
         k = rotate64(k.unflatten(-1, (hkv, 64)), cos, sin)
-        qkvg = r.F(torch.cat((q.flatten(-2), gate, k.flatten(-2), v), -1), t + "qkvg")   # F :159 qkvg
+        qkvg = r.F(torch.cat((q.flatten(-2), gate, k.flatten(-2), v), -1), t + "qkvg")   # F :162 qkvg
         q, gate, k, v = qkvg.split([d, d, g, g], -1)
         a = _Attention64.apply(q.unflatten(-1, (hq, 64)), k.unflatten(-1, (hkv, 64)), v.unflatten(-1, (hkv, 64)), cu, r.on)
-        a = r.FB(a.flatten(-2), t + "a")                                         # F :169 a (also delta's O) ; B :372 da (gate backward)
-        ag = r.FB(a * torch.sigmoid(gate), t + "ag")                             # F :169 ag from the rounded a ; B :356 dag (g_d2)
-        o = r.B(ag @ p[ap + "out_proj.weight"].T)                                # B :349-351 do (g_do)
+        a = r.FB(a.flatten(-2), t + "a")                                         # F :172 a (also delta's O) ; B :370 da (gate backward)
+        ag = r.FB(a * torch.sigmoid(gate), t + "ag")                             # F :172 ag from the rounded a ; B :355 dag (g_d2)
+        o = r.B(ag @ p[ap + "out_proj.weight"].T)                                # B :350-352 do (g_do)
         if i == 0:
-            x1 = r.F(x + o, t + "x1")                                            # F :188-189 x1 = X0 + ag Wo^T
+            x1 = r.F(x + o, t + "x1")                                            # F :190-192 x1 = X0 + ag Wo^T
         else:
             y1 = alpha * x + o
             if r.y_bf16:
-                y1 = r.F(y1, t + "y1")                                           # F :195-196 y1 (tape_y_dtype)
-            x1 = r.F(rmsnorm64(y1, p[f"{prefix}attn_post_ln.{i - 1}.weight"]), t + "x1")   # F :197 x1
-        xn2 = r.FB(rmsnorm64(x1, p[fp + "norm.weight"]), t + "xn2")              # F :200 xn2 ; B :344 dxn2 (g_d2)
-        u = r.FB(xn2 @ p[fp + "w12.weight"].T, t + "u")                          # F :204-206 u (EPI_GEGLU resid) ; B :339 du (g_2i)
+                y1 = r.F(y1, t + "y1")                                           # F :198 y1 (tape_y_dtype)
+            x1 = r.F(rmsnorm64(y1, p[f"{prefix}attn_post_ln.{i - 1}.weight"]), t + "x1")   # F :199 x1
+        xn2 = r.FB(rmsnorm64(x1, p[fp + "norm.weight"]), t + "xn2")              # F :202 xn2 ; B :345 dxn2 (g_d2)
+        u = r.FB(xn2 @ p[fp + "w12.weight"].T, t + "u")                          # F :205-207 u (EPI_GEGLU resid) ; B :342 du (g_2i)
         ux, ug = u.chunk(2, -1)
-        h = r.FB(F.gelu(ug) * ux, t + "h")                                       # F :204-206 h from the stored u ; B :337 dh (g_i)
-        f = r.B(h @ p[fp + "w3.weight"].T)                                       # B :327 / :392 df (the w3 product only)
+        h = r.FB(F.gelu(ug) * ux, t + "h")                                       # F :205-207 h from the stored u ; B :340 dh (g_i)
+        f = r.B(h @ p[fp + "w3.weight"].T)                                       # B :332 / :394-396 df (the w3 product only)
         if i == 0:
-            x = r.F(x1 + f, t + "X")                                             # F :215-216 X[1]
+            x = r.F(x1 + f, t + "X")                                             # F :214-216 X[1]
         else:
             y2 = alpha * x1 + f
             if r.y_bf16:
-                y2 = r.F(y2, t + "y2")                                           # F :226-227 y2 (tape_y_dtype)
-            x = r.F(rmsnorm64(y2, p[f"{prefix}ffd_post_ln.{i - 1}.weight"]), t + "X")   # F :228 X[i + 1]
+                y2 = r.F(y2, t + "y2")                                           # F :226 y2 (tape_y_dtype)
+            x = r.F(rmsnorm64(y2, p[f"{prefix}ffd_post_ln.{i - 1}.weight"]), t + "X")   # F :227 X[i + 1]
     return x
 
 
@@ -182,13 +182,13 @@ def encoder_replay(clips, counts, p, size="tiny", patch=(4, 8, 8), r: Rounding =
     mt = p[prefix + "mask_token"]
     patches = torch.cat([O.patchify(c, patch) for c in clips], 0)
     lin = r.F(patches @ p[prefix + "proj_in.weight"].T + p[prefix + "proj_in.bias"])   # Linear output rounded before + mask_token
-    pe = r.FB(lin + mt, "pe")                                    # (ttv_gemm.hip epilogue) ; F :561-562 pe ; B :602 dpe (g_d)
-    xt = rmsnorm64(mt.expand(-1, width), p[prefix + "ln_pre_t.weight"]).expand(int(mask.sum()), width)   # :564 constant latent rows
-    xp = rmsnorm64(pe, p[prefix + "ln_pre_p.weight"])            # :563
+    pe = r.FB(lin + mt, "pe")                                    # (ttv_gemm.hip epilogue) ; F :442-444 pe ; B :489 dpe (g_d)
+    xt = rmsnorm64(mt.expand(-1, width), p[prefix + "ln_pre_t.weight"]).expand(int(mask.sum()), width)   # :446 constant latent rows
+    xp = rmsnorm64(pe, p[prefix + "ln_pre_p.weight"])            # :445
     x = r.F(_rows(mask, xt, xp), "X0")                           # F X[0]
     x = layers_replay(x, p, prefix + "model_layers.", layers, heads, cos, sin, cu, r)
-    n = r.FB(rmsnorm64(x[mask], p[prefix + "ln_post.weight"]), "n")   # F :566 / :589 n ; B :592 dn (g_d2)
-    return n @ p[prefix + "proj_out.weight"].T + p[prefix + "proj_out.bias"]   # z: fp32 (:566), dz fp32
+    n = r.FB(rmsnorm64(x[mask], p[prefix + "ln_post.weight"]), "n")   # F :448 / :476 n ; B :479 dn (g_d2)
+    return n @ p[prefix + "proj_out.weight"].T + p[prefix + "proj_out.bias"]   # z: fp32 (:448), dz fp32
 
 
 def decoder_replay(codes, counts, pixel_grids, p, size="tiny", patch=(4, 8, 8), r: Rounding = None, prefix="decoder.", out_channels=3):
@@ -199,13 +199,13 @@ def decoder_replay(codes, counts, pixel_grids, p, size="tiny", patch=(4, 8, 8), 
     cos, sin = O.rope_table(grids, counts, width // heads[0])
     mt = p[prefix + "mask_token"]
     lin = r.F(codes @ p[prefix + "proj_in.weight"].T + p[prefix + "proj_in.bias"])   # k_dec_embed: Linear output rounded, then
-    hpre = r.F(lin + mt, "hpre")                                 # + mask_token rounded: F :628 hpre ; d(hpre) fp32 (:672 small_f32)
+    hpre = r.F(lin + mt, "hpre")                                 # + mask_token rounded: F :514 hpre ; d(hpre) fp32 (:552 small_f32)
     xt = rmsnorm64(hpre, p[prefix + "ln_pre_t.weight"])
-    xp = rmsnorm64(mt.expand(-1, width), p[prefix + "ln_pre_p.weight"]).expand(int((~mask).sum()), width)   # :629 constant patch rows
+    xp = rmsnorm64(mt.expand(-1, width), p[prefix + "ln_pre_p.weight"]).expand(int((~mask).sum()), width)   # :515 constant patch rows
     x = r.F(_rows(mask, xt, xp), "X0")                           # F X[0]
     x = layers_replay(x, p, prefix + "model_layers.", layers, heads, cos, sin, cu, r)
-    pn = r.FB(rmsnorm64(x[~mask], p[prefix + "ln_post.weight"]), "pn")   # F :631 pn ; B :662-663 dpn (g_d2)
-    out = r.FB(pn @ p[prefix + "proj_out.weight"].T + p[prefix + "proj_out.bias"], "recon")   # F :633-638 clips ; B: dclips arrive in bf16
+    pn = r.FB(rmsnorm64(x[~mask], p[prefix + "ln_post.weight"]), "pn")   # F :517 pn ; B :543 dpn (g_d2)
+    out = r.FB(pn @ p[prefix + "proj_out.weight"].T + p[prefix + "proj_out.bias"], "recon")   # F :518-521 clips ; B: dclips arrive in bf16
     return [O.unpatchify(c, g, patch, out_channels) for c, g in zip(torch.split(out, sizes, 0), grids)]
 
 

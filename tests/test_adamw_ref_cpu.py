@@ -1,5 +1,5 @@
 """The float64 replay of the optimizer step and its counted bound (tests/adamw_ref.py), without a GPU: a numpy restatement of
-`opt_update` and of the clip norm in float32 arithmetic (csrc/ttv_train.hip, both lerp branches, one rounding per operation - the
+`opt_update` and of the clip norm in float32 arithmetic (csrc/ttv_optim.hip, both lerp branches, one rounding per operation - the
 kernel's fma contractions only remove some) stays inside the bound on the GPU tests' own inputs and hyper-parameter grid, and each
 planted defect leaves it."""
 import math

@@ -1,4 +1,4 @@
-"""`HipAdamW` (titok_video_amd/optim.py; `k_opt_gradsq` / `k_opt_adamw`, csrc/ttv_train.hip) on the MI355X against a float64 replay of
+"""`HipAdamW` (titok_video_amd/optim.py; `k_opt_gradsq` / `k_opt_adamw`, csrc/ttv_optim.hip) on the MI355X against a float64 replay of
 every step, inside the bound counted in tests/adamw_ref.py.  `-m gpu`.
 
 Every step: clone p, g, m, v on the device, step, compare the stored p, m, v with the replay of the clones inside the bound, and go on

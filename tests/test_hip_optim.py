@@ -1,4 +1,4 @@
-"""HipAdamW (titok_video_amd/optim.py, csrc/ttv_train.hip k_opt_gradsq / k_opt_adamw) against torch.nn.utils.clip_grad_norm_ +
+"""HipAdamW (titok_video_amd/optim.py, csrc/ttv_optim.hip k_opt_gradsq / k_opt_adamw) against torch.nn.utils.clip_grad_norm_ +
 torch.optim.AdamW on the same parameters and gradients - the optimizer step of the reference's training loop (train.py:76-77, :183-190)."""
 import copy
 

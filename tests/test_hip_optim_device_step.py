@@ -1,4 +1,4 @@
-"""HipAdamW's device path (titok_video_amd/optim.py: capturable=True / skip_nonfinite=True; csrc/ttv_train.hip k_opt_prepare,
+"""HipAdamW's device path (titok_video_amd/optim.py: capturable=True / skip_nonfinite=True; csrc/ttv_optim.hip k_opt_prepare,
 k_opt_adamw_dev): the step count, both bias corrections, the learning rate and the skip decision live in a device block.
 
 The yardsticks: Python doubles rounded once (the block's floats, bit for bit), the host path on the same tensors and gradients (bit

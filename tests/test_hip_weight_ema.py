@@ -1,4 +1,4 @@
-"""`WeightEMA` (titok_video_amd/ema.py; `k_opt_ema_update` / `k_opt_ema_exchange`, csrc/ttv_train.hip) on the MI355X: the update against
+"""`WeightEMA` (titok_video_amd/ema.py; `k_opt_ema_update` / `k_opt_ema_exchange`, csrc/ttv_optim.hip) on the MI355X: the update against
 the float64 replay of tests/weight_ema_ref.py inside its counted bound, the exchange bit for bit, the tiny tokenizer trained with the
 average beside it (FSQ and the L2 quantiser), the state dict, and `ValidationLoop(..., ema=)`.  `-m gpu`.
 

@@ -1,4 +1,4 @@
-"""Float64 replay of one `WeightEMA` update (titok_video_amd/ema.py, `k_opt_ema_update` in csrc/ttv_train.hip) and a counted bound on
+"""Float64 replay of one `WeightEMA` update (titok_video_amd/ema.py, `k_opt_ema_update` in csrc/ttv_optim.hip) and a counted bound on
 how far the kernel may be from it.  Plain numpy / torch, no GPU.  Used by tests/test_weight_ema_cpu.py (the bound is valid and it
 bites) and tests/test_hip_weight_ema.py (the kernel against the replay).
 

@@ -1,5 +1,5 @@
 """Exponential moving average of the tokenizer's weights in fp32 shadow tensors (`ttv_opt_ema_update`, `ttv_opt_ema_exchange`;
-kernels beside the optimizer's in csrc/ttv_train.hip).
+kernels beside the optimizer's in csrc/ttv_optim.hip).
 
 Not a reference module: the reference validates and saves its raw weights.  Tokenizer recipes in the VQGAN line evaluate and export
 the average instead - with beta1 = 0.5 and a GAN term the raw weights move from step to step.  Built from eager `torch._foreach_*`

@@ -5,7 +5,7 @@ the reference's cosine schedule) and the skip decision formed on the device (`tt
 The reference steps `torch.optim.AdamW` after `clip_gradients` (train.py:76-77, :183-190).  On MI355X torch's multi-tensor path costs
 seven launches and ~230 us per step for the tiny tokenizer's 7 M parameters; `HipAdamW` keeps torch's interface, hyper-parameters and
 state layout (`step`, `exp_avg`, `exp_avg_sq` per parameter: a `state_dict()` loads into `torch.optim.AdamW` and back) and does the
-arithmetic in csrc/ttv_train.hip.  GPU only: there is no host fallback (parameters on the CPU raise)."""
+arithmetic in csrc/ttv_optim.hip.  GPU only: there is no host fallback (parameters on the CPU raise)."""
 import math
 import struct
 from typing import Iterable, List, Optional
@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 
-_CHUNK = 8192          # OPT_CHUNK of csrc/ttv_train.hip
+_CHUNK = 8192          # OPT_CHUNK of csrc/ttv_optim.hip
 _SLOTS = 4             # host / device table buffers in rotation: a slot is reused only after the step that read it has finished
 
 

@@ -8,7 +8,7 @@ properties of the reference are kept as they are: with a warm-up the rate at ind
 past `training_steps` the cosine goes on and the rate climbs again; `base_lr` is the formula's argument while the optimizer's own
 initial `lr` is the multiplier (the reference passes the same number for both).
 
-Pure host code; the device evaluation lives in csrc/ttv_train.hip (k_opt_prepare)."""
+Pure host code; the device evaluation lives in csrc/ttv_optim.hip (k_opt_prepare)."""
 from __future__ import annotations
 
 import math
