@@ -4,7 +4,10 @@ Four small shards are written; two ranks (both on cuda:0, gloo for the collectiv
 reference's generator step (train.py:65-83: forward, L1, backward, clip 1.0, AdamW) from their own shards through the process-based
 loader (titok_video_amd/loader.py: worker processes -> shared memory -> pinned staging -> GPU normalisation), gradients reduced
 behind the backward (dp.GradReducer), token indices logged (CodebookLogger).  One process then runs the same steps on the UNION of
-the two ranks' batches.  The first step's reduced gradients agree element by element (2e-5 of the tensor's largest); after N steps the parameters agree to 1e-4 (relative; an element is exempt only where its Adam second moment says its gradient is summation noise - see the test) and the
+the two ranks' batches, every step from the weights and optimizer state the two-rank run had before that step (rank 0 writes them to a
+file): each step reads the weights the step before it wrote, so two free runs drift apart from the first element whose update the
+summation noise decides, and only steps from one state can be held to each other tightly.  Every step's reduced gradients agree
+element by element (2e-5 of the tensor's largest); after N steps the parameters agree to 1e-4 (relative; an element is exempt only where its Adam second moment says its gradient is summation noise - see the test) and the
 codebook histogram exactly.  (The discriminator step of tools/train_dp.py draws fresh noise per rank, so the comparable quantity is
 the generator step.)  `-m gpu`."""
 import os
@@ -40,7 +43,7 @@ def _adam_v(model, opt):
     return {n: opt.state[p]["exp_avg_sq"].detach().cpu().numpy().copy() for n, p in model.named_parameters() if p in opt.state}
 
 
-def _rank_worker(rank, world, port, paths, q):
+def _rank_worker(rank, world, port, paths, q, sync_dir):
     from titok_video_amd.loader import ShardBatchLoader
     loader = ShardBatchLoader(paths, rank, world, seed=100 + rank, **LOADER).start()       # before the first GPU call
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -58,7 +61,11 @@ def _rank_worker(rank, world, port, paths, q):
         for st in range(STEPS):
             b = next(it)
             counts = b["token_counts"].tolist()
+            if rank == 0:                  # the state this step starts from, for the one-process run
+                torch.save({"model": model.state_dict(), "opt": opt.state_dict()}, os.path.join(sync_dir, f"before_{st}.pt"))
             loss, gnorm, idx = training_step(model, b["video"], counts, opt)
+            if rank == 0:
+                torch.save({n: p.grad.detach() for n, p in model.named_parameters() if p.grad is not None}, os.path.join(sync_dir, f"grads_{st}.pt"))
             if st == 0:
                 g0 = _grads(model)         # reduced + clipped gradients of the step both runs take from identical weights
             logger(torch.split(idx, counts))
@@ -71,8 +78,10 @@ def _rank_worker(rank, world, port, paths, q):
         dist.destroy_process_group()
 
 
-def _single_worker(paths, q):
-    """The union run in a fresh process (the loader workers must be forked before the process touches the GPU)."""
+def _single_worker(paths, q, sync_dir):
+    """The union run in a fresh process (the loader workers must be forked before the process touches the GPU).  Every step starts from
+    the state rank 0 had before that step; `grad_ratio[st]` is the largest |gradient difference| to rank 0's reduced gradients of that
+    step over 2e-5 of the tensor's largest gradient, over all tensors."""
     from titok_video_amd.loader import ShardBatchLoader
     loaders = [ShardBatchLoader(paths, r, 2, seed=100 + r, **LOADER).start() for r in range(2)]
     from titok_video_amd.codebook import CodebookLogger
@@ -81,19 +90,26 @@ def _single_worker(paths, q):
     opt = make_optimizer(model)
     logger = CodebookLogger(4375)
     its = [iter(ld.batches("cuda:0", torch.float32)) for ld in loaders]
-    keys, g0 = [], None
+    keys, g0, grad_ratio = [], None, []
     for st in range(STEPS):
         bs = [next(it) for it in its]
         clips = [c for b in bs for c in b["video"]]
         counts = [k for b in bs for k in b["token_counts"].tolist()]
+        before = torch.load(os.path.join(sync_dir, f"before_{st}.pt"), map_location="cuda:0", weights_only=False)
+        model.load_state_dict(before["model"], strict=True)
+        opt.load_state_dict(before["opt"])
         loss, gnorm, idx = training_step(model, clips, counts, opt)
+        theirs = torch.load(os.path.join(sync_dir, f"grads_{st}.pt"), map_location="cuda:0", weights_only=False)
+        mine = {n: p.grad for n, p in model.named_parameters() if p.grad is not None}
+        assert mine.keys() == theirs.keys()
+        grad_ratio.append(max(float((mine[n] - theirs[n]).abs().max() / (2e-5 * (mine[n].abs().max() + 1e-30))) for n in mine))
         if st == 0:
             g0 = _grads(model)
         logger(torch.split(idx, counts))
         keys.append([list(b["__key__"]) for b in bs])
     torch.cuda.synchronize()
     q.put(("single", {n: p.detach().cpu().numpy() for n, p in model.named_parameters()}, logger.histogram().cpu().numpy(), keys,
-           g0, _grads(model), _adam_v(model, opt)))
+           g0, _grads(model), _adam_v(model, opt), grad_ratio))
     for ld in loaders:
         ld.close()
 
@@ -104,7 +120,8 @@ def test_two_rank_shard_training_equals_one_process_on_the_union(tmp_path):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    procs = [ctx.Process(target=_rank_worker, args=(r, 2, port, paths, q)) for r in range(2)]
+    sync_dir = str(tmp_path)
+    procs = [ctx.Process(target=_rank_worker, args=(r, 2, port, paths, q, sync_dir)) for r in range(2)]
     for p in procs:
         p.start()
     res = {}
@@ -114,25 +131,30 @@ def test_two_rank_shard_training_equals_one_process_on_the_union(tmp_path):
     for p in procs:
         p.join(timeout=120)
         assert p.exitcode == 0
-    one = ctx.Process(target=_single_worker, args=(paths, q))
+    one = ctx.Process(target=_single_worker, args=(paths, q, sync_dir))
     one.start()
-    tag, params1, hist1, keys1, g0_1, glast_1, v_1 = q.get(timeout=600)
+    tag, params1, hist1, keys1, g0_1, glast_1, v_1, grad_ratio = q.get(timeout=600)
     one.join(timeout=120)
     assert one.exitcode == 0 and tag == "single"
     # the same clips went through both runs, step by step
     for st in range(STEPS):
         assert keys1[st] == [res[0][2][st], res[1][2][st]]
     assert set(res[0][2][0]).isdisjoint(res[1][2][0])                      # rank-disjoint shards
-    # (1) DP == single process, asserted where it can be asserted tightly: the first step starts from identical weights, so the reduced,
+    # (1) DP == single process, asserted where it can be asserted tightly: every step of the one-process run starts from the weights the
+    # two-rank run had before that step, so the reduced,
     # clipped gradients of the two-rank run (sum(count * grad) / sum(count) over the ranks, dp.GradReducer) must be the gradients of the
-    # one-process step on the union - every element, no exemption.  Tolerance 2e-5 of the tensor's largest gradient: the fp32 kernels
+    # one-process step on the union - every element, no exemption, at every step (the first step's compared here, all of them in
+    # _single_worker: grad_ratio).  Tolerance 2e-5 of the tensor's largest gradient: the fp32 kernels
     # accumulate in different orders (atomics, and two half-batches instead of one batch), ~1e-7 relative per sum.
     for n in g0_1:
         assert np.array_equal(res[0][3][n], res[1][3][n]), n
         gs = float(np.abs(g0_1[n]).max()) + 1e-30
         gd = np.abs(res[0][3][n] - g0_1[n])
         assert float(gd.max()) <= 2e-5 * gs, ("step-0 gradient", n, float(gd.max()), gs)
-    # (2) the weights after STEPS AdamW steps: both ranks identical, and equal to the single-process weights within 1e-4 of the tensor's
+    print("largest gradient difference per step, over 2e-5 of the tensor's largest gradient:", ["%.3g" % r for r in grad_ratio])
+    assert len(grad_ratio) == STEPS and all(r <= 1.0 for r in grad_ratio), grad_ratio
+    # (2) the weights after STEPS AdamW steps: both ranks identical, and equal to the single-process weights (its last step taken from the
+    # two-rank run's weights and moments before that step) within 1e-4 of the tensor's
     # scale - EXCEPT where AdamW's normalised update is noise: an element whose gradient is itself of the size of the summation noise
     # (|g| ~ 1e-7 of the tensor's gradients, sqrt(v) tiny) moves by up to lr (1 + wd |p|) per step in a direction the noise picks.  Such an
     # element is exempt only when the single-process second moment says so (sqrt(v) below 1e-4 of the tensor's largest); any other

@@ -229,18 +229,6 @@ def twin_of(kind, state):
     return m
 
 
-def rebuild_caches(model):
-    """`HipAdamW` writes the parameters with a kernel and does not bump their version counters, so after a training step the towers'
-    packs are still those of an earlier step (measured on the MI355X: after three fp32 steps the forward differs by up to 0.75 from
-    the forward behind `invalidate_packs()`).  That is the optimizer's, not the average's: the tests start from rebuilt packs, so that
-    what they compare before and after `applied()` is the exchange alone."""
-    for mod in model.modules():
-        if hasattr(mod, "invalidate_packs"):
-            mod.invalidate_packs()
-        if hasattr(mod, "invalidate_lookup_cache"):
-            mod.invalidate_lookup_cache()
-
-
 def forward(model, clips):
     with torch.no_grad():
         recon, info = model(clips, COUNTS)
@@ -281,7 +269,6 @@ def test_training_with_the_average_and_validation_on_it(kind):
         assert not fails, fails[:5]
         assert moved > len(names) // 2, "decay 0.5: the shadows move visibly"
     # the average in the model: the forward of a second model that loaded model_state_dict(), bit for bit
-    rebuild_caches(model)
     raw_state = {k: v.clone() for k, v in model.state_dict().items()}
     before = forward(model, clips)
     averaged = twin_of(kind, ema.model_state_dict())
@@ -398,7 +385,6 @@ def test_validation_loop_runs_on_the_average_and_leaves_the_weights():
     for _ in range(2):
         training_step(model, clips, COUNTS, opt)
         ema.update()
-    rebuild_caches(model)
     batches = [{"video": synthetic_clips(CLIP_SHAPES, seed=40 + k, dtype=torch.float32, device=DEV), "fps": [8, 12.5], "token_counts": COUNTS}
                for k in range(2)]
     averaged = twin_of("fsq", ema.model_state_dict())

@@ -113,7 +113,9 @@ class _Tower(nn.Module):
 
     def invalidate_packs(self) -> None:
         """Forget the packed weight copies.  The cache key is (storage pointer, tensor version, dtype) of every parameter, which
-        catches optimizer steps, load_state_dict and in-place ops under no_grad - but NOT writes through `.data` (they do not
+        catches optimizer steps (optim.HipAdamW, the step post-hook train.make_optimizer gives torch's fused AdamW, and
+        train.GraphedTrainingStep bump the counters behind the kernels; torch's foreach and single-tensor optimizers bump them
+        themselves; a fused torch optimizer built elsewhere does NOT), load_state_dict and in-place ops under no_grad - but NOT writes through `.data` (they do not
         bump the version counter: `p.data.mul_(2)`, `trunc_normal_(p.data)`, EMA by `p.data.copy_`).  Code that updates weights
         that way calls this afterwards; `init_weights` and `load_state_dict` do it themselves.  TTV_PACK_CHECK=1 (debugging)
         additionally compares a content checksum on every call."""

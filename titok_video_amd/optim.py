@@ -459,6 +459,11 @@ class HipAdamW(torch.optim.Optimizer):
                     sp["step"].fill_(t)
                 else:
                     sp["step"] = torch.tensor(t, dtype=torch.float32)
+        if update:
+            # the kernels wrote the parameters behind autograd's back: whatever caches on a parameter's version counter (the towers'
+            # weight packs, the L2 quantiser's norms) must see a new version.  A host-side counter: nothing is launched, and under
+            # capture the warm-up steps bump it too, so the captured forward builds its packs inside the graph.
+            torch.autograd.graph.increment_version(flat)
         if not capturing:          # a captured slot has left the rotation: nothing waits for it
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(dev))

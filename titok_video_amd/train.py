@@ -105,6 +105,14 @@ def limit_host_threads(max_threads: int = 4) -> int:
     return n
 
 
+def _bump_versions(optimizer, args, kwargs) -> None:
+    """Step post-hook of the torch AdamW `_make_adamw` builds.  torch's fused AdamW writes the parameters with one multi-tensor kernel
+    and leaves their version counters where they were (its foreach and single-tensor forms bump them), like any kernel behind
+    autograd's back: the towers' weight packs and the L2 quantiser's norms are keyed on the counters, so they are told here, whoever
+    called `step()`.  A host-side counter: nothing is launched, also under capture."""
+    torch.autograd.graph.increment_version([p for g in optimizer.param_groups for p in g["params"] if p.grad is not None])
+
+
 def _make_adamw(params, lr, beta1, beta2, weight_decay, capturable, hip_capturable, skip_nonfinite, schedule):
     """The optimizer of make_optimizer / make_discriminator_optimizer; with `schedule` (a dict of schedule.CosineWarmupLR's
     arguments) the pair (optimizer, scheduler)."""
@@ -120,6 +128,8 @@ def _make_adamw(params, lr, beta1, beta2, weight_decay, capturable, hip_capturab
     else:
         fused = bool(params) and all(p.is_cuda for p in params)      # one multi-tensor kernel instead of a launch per parameter
         opt = torch.optim.AdamW(params, lr=lr, betas=(beta1, beta2), weight_decay=weight_decay, fused=fused, capturable=capturable and fused)
+        if fused:
+            opt.register_step_post_hook(_bump_versions)
     if schedule is None:
         return opt
     from .schedule import CosineWarmupLR
@@ -236,9 +246,13 @@ class GraphedTrainingStep:
     """One generator training step (training_step: forward with tape, L1, backward, clip, AdamW) recorded ONCE into a HIP graph for a
     fixed batch shape and replayed per step ("HIP-graph capture of the training step").
 
-    The tower entry points only enqueue kernels on the current stream (no allocation, no synchronisation inside the library), plans
-    and weight packs are built during the warm-up steps, and the pack refresh after each optimizer step (parameter version -> new
-    compute-dtype copies) is part of the captured sequence, so a replay is exact.  Constraints: one batch shape per instance (clip
+    The tower entry points only enqueue kernels on the current stream (no allocation, no synchronisation inside the library) and the
+    plans are built during the warm-up steps.  Every optimizer step bumps the parameters' version counters (HipAdamW behind its
+    kernels, torch's fused AdamW through the step post-hook `_make_adamw` gives it), so the captured step starts from versions its towers have not seen: the weight packs
+    and the backward's W^T copies it reads are rebuilt inside the capture, from the graph's own memory pool, and every replay
+    rebuilds them from the weights the replay before it wrote - a replay is exact.  A replay runs no Python, so `__call__` bumps
+    the versions itself afterwards: an eager forward of the model between replays (validation) builds its packs from the current
+    weights.  Constraints: one batch shape per instance (clip
     shapes and token counts fixed; ragged token-budget batches need one instance per shape signature), an optimizer created with
     capturable=True (torch's AdamW) or hip_capturable=True (HipAdamW with its step count on the device), single process (the overlapped DP reducer launches collectives from Python callbacks).
 
@@ -284,13 +298,17 @@ class GraphedTrainingStep:
                             v.copy_(old[i][k])
                         else:
                             v.zero_()
-        for mod in model.modules():                     # the packed copies were made from the warm-up weights
+        # the packs the towers hold were made from the warm-up weights, inside the capture: dropping them here returns their memory
+        # to the graph's private pool, which only this graph allocates from, so the replays keep reading and rewriting it safely
+        for mod in model.modules():
             if hasattr(mod, "invalidate_packs"):
                 mod.invalidate_packs()
+        self._params = params
 
     def __call__(self, clips):
         torch._foreach_copy_(self.inputs, list(clips))
         self.graph.replay()
+        torch.autograd.graph.increment_version(self._params)          # the replayed optimizer kernels moved them; Python is told here
         return self.loss, self.gnorm, self.indices
 
 
