@@ -267,6 +267,16 @@ int ttv_attention64(const void* qkvg, int ld, void* out, int ldo, const int32_t*
  * reference's (pt,ph,pw,c) order is folded into the packed proj_in / proj_out weight (see weights.py). */
 int ttv_patch_gather(const void* const* clips, const int32_t* clip_desc, int clip0, int n_clips, int patch_t, int patch_h,
                      int patch_w, int channels, void* patches, int ld, int dtype, int max_patches_per_clip, void* stream);
+/* The encoder's front in one kernel (blocks.py:91-97): x[patch_rows[t]] = RMSNorm(bf16(bf16(patch t . w^T + bias) + mask_token)) * gain
+ * for the `rows` patches of n_clips clips (<= TTV_MAX_CLIPS_PER_LAUNCH), read straight from the clips - what ttv_patch_gather, ttv_linear
+ * (bias, mask token as add_scalar) and ttv_rmsnorm (dst_rows = patch_rows) compute as three launches, bit for bit (the k order of
+ * those GEMM kernels and the row kernel's summation order are kept).  w [width, C*pt*ph*pw] in (c,pt,ph,pw) order, bias [width] (dtype), gain fp32 [width];
+ * row_seq [L] = clip of every packed row (ttv_batch.row_seq).  bf16, width 256, patch_w 8, power-of-two patch_t / patch_h and a patch
+ * vector that is a multiple of 64; anything else returns TTV_ERR_UNSUPPORTED. */
+int ttv_patch_embed_norm(const void* const* clips, const int32_t* clip_desc, const int32_t* patch_rows, const int32_t* row_seq, int n_clips,
+                         int patch_t, int patch_h, int patch_w, int channels, const void* w, int ldw, const void* bias,
+                         const float* mask_token, const float* gain, float eps, void* x, int ldx, int rows, int width, int dtype,
+                         void* stream);
 /* unpatch_rearrange (model/base/utils.py:37-51); same descriptors, clips are written. */
 int ttv_patch_scatter(const void* patches, int ld, const int32_t* clip_desc, int clip0, int n_clips, int patch_t, int patch_h,
                       int patch_w, int channels, void* const* clips, int dtype, int max_patches_per_clip, void* stream);
@@ -397,6 +407,10 @@ typedef struct ttv_batch {
    * Ignored by the encoder and by the training entry points. */
   const int32_t* qblocks_patch;
   int32_t n_qblocks_patch;
+  /* optional (0: no such promise): K when EVERY clip of the batch has K_b = K latent tokens and the same number of patches.  With it,
+   * K and the patches per clip multiples of 128 and the width-256 bf16 kernels, the encoder's last layer - whose queries are the latent
+   * rows (qblocks_latent) - computes the q | gate columns of to_qkv for the latent token tiles only; k | v for every row, as before. */
+  int32_t tokens_per_clip;
 } ttv_batch;
 
 /* Fill ttv_batch.rope_cs [L,64] on the device: rows are gathered from base_cos/base_sin fp32 [n_ids, n_freqs] =
@@ -464,7 +478,8 @@ int ttv_plan_rows_build(const ttv_plan_sizes* sizes, const int32_t* host_segment
  * none).  qblocks_latent is absent (0 entries) when sum K_b = 0; qblocks_patch exists only beside a `qblocks` of full items, and only
  * when at least one latent-only block is dropped and at least one block remains.  cu_seqlens: HOST [n_clips+1]. */
 typedef struct ttv_plan_attn {
-  int32_t n_qblocks, qblocks_all_full, n_qblocks_latent, n_qblocks_patch, n_qblocks_l0, reserved;
+  int32_t n_qblocks, qblocks_all_full, n_qblocks_latent, n_qblocks_patch, n_qblocks_l0;
+  int32_t tokens_per_clip;   /* K when every clip has K_b = K and the same number of rows, else 0 (ttv_batch.tokens_per_clip) */
   int64_t words;                                                              /* int32 words of the four tables together */
   int64_t off_qblocks, off_qblocks_latent, off_qblocks_patch, off_qblocks_l0; /* word offsets (multiples of 4) */
 } ttv_plan_attn;
@@ -474,8 +489,8 @@ int ttv_plan_attn_sizes(const int32_t* cu_seqlens, const int32_t* token_counts, 
 int ttv_plan_attn_fill(const int32_t* cu_seqlens, const int32_t* token_counts, int n_clips, int q_heads, int kv_heads, int split,
                        int tail_div, int32_t* host_tables, int64_t host_words);
 /* Enqueues the copy of host_tables [sizes.words] (pinned, unchanged until the stream has passed it) to dev_tables (16-byte aligned) and
- * sets batch.qblocks / n_qblocks / qblocks_all_full / qblocks_latent / qblocks_patch and their counts; qblocks_paired = 0, items64 =
- * NULL.  The layer-0 table is at dev_tables + off_qblocks_l0 for ttv_dec_l0_const.qblocks. */
+ * sets batch.qblocks / n_qblocks / qblocks_all_full / qblocks_latent / qblocks_patch and their counts and tokens_per_clip;
+ * qblocks_paired = 0, items64 = NULL.  The layer-0 table is at dev_tables + off_qblocks_l0 for ttv_dec_l0_const.qblocks. */
 int ttv_plan_attn_set(const ttv_plan_attn* sizes, const int32_t* host_tables, int32_t* dev_tables, ttv_batch* batch, void* stream);
 
 /* base_cos / base_sin fp32 [n_ids, F], F = head_dim / (2 * nd): cos / sin of inv_freq[f] * n for every position id n < n_ids, evaluated
@@ -1079,7 +1094,9 @@ enum {
   TTV_DBG_ENC_ALL_ROWS = 524288,       /* encoder's last layer on every row, as TTV_ENC_LATENT_LAST=0 (ttv_api.hip, ttv_train.hip) */
   TTV_DBG_ATTN_NO_SWP = 1048576,       /* ttvk_attention keeps k_attn_bf16 where it would take k_attn_swp, as TTV_ATTN_SWP=0 (ttv_attn.hip) */
   TTV_DBG_DEC_ALL_BLOCKS = 2097152,    /* decoder's last attention on every query block, as TTV_DEC_PATCH_LAST=0 (ttv_api.hip) */
-  TTV_DBG_DEC_L0_NO_CONST = 4194304    /* decoder's layer 0 ignores the constant block, as TTV_DEC_L0_CONST=0 (ttv_api.hip) */
+  TTV_DBG_DEC_L0_NO_CONST = 4194304,   /* decoder's layer 0 ignores the constant block, as TTV_DEC_L0_CONST=0 (ttv_api.hip) */
+  TTV_DBG_ENC_LAST_QKV_ALL = 8388608,  /* encoder's last to_qkv computes every panel of every row, as TTV_ENC_LAST_QKV_SKIP=0 (ttv_api.hip) */
+  TTV_DBG_PATCH_EMBED_UNFUSED = 16777216 /* encoder's front as the gathering GEMM and the row kernel, as TTV_PATCH_EMBED_FUSED=0 (ttv_api.hip) */
 };
 int ttv_debug_set(int flags);
 /* Diagnostics: device buffer (>= 256 int64) that instrumented kernels fill with s_memtime stamps of block 0; NULL = off. */

@@ -48,6 +48,8 @@ DBG_ENC_ALL_ROWS = 524288
 DBG_ATTN_NO_SWP = 1048576
 DBG_DEC_ALL_BLOCKS = 2097152
 DBG_DEC_L0_NO_CONST = 4194304
+DBG_ENC_LAST_QKV_ALL = 8388608
+DBG_PATCH_EMBED_UNFUSED = 16777216
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # TTV_LIB_PATH: diagnostics only (an instrumented build of the same sources, tools/attn_stamps.py)
@@ -92,7 +94,7 @@ class Batch(C.Structure):
                 ("patch_rows", vp), ("clip_desc", vp), ("qblocks", vp), ("rope_cs", vp), ("blocks64", vp), ("row_seq", vp),
                 ("n_blocks64", i32), ("qblocks_paired", i32), ("qblocks_all_full", i32), ("items64", vp), ("n_items64", i32),
                 ("rope_ids", vp), ("rope_base", vp), ("qblocks_latent", vp), ("n_qblocks_latent", i32), ("qblocks_patch", vp),
-                ("n_qblocks_patch", i32)]
+                ("n_qblocks_patch", i32), ("tokens_per_clip", i32)]
 
 
 class PlanSizes(C.Structure):
@@ -104,7 +106,7 @@ class PlanSizes(C.Structure):
 
 class PlanAttn(C.Structure):
     _fields_ = [("n_qblocks", i32), ("qblocks_all_full", i32), ("n_qblocks_latent", i32), ("n_qblocks_patch", i32), ("n_qblocks_l0", i32),
-                ("reserved", i32), ("words", i64), ("off_qblocks", i64), ("off_qblocks_latent", i64), ("off_qblocks_patch", i64),
+                ("tokens_per_clip", i32), ("words", i64), ("off_qblocks", i64), ("off_qblocks_latent", i64), ("off_qblocks_patch", i64),
                 ("off_qblocks_l0", i64)]
 
 
@@ -222,6 +224,8 @@ SYMBOLS = {
     "ttv_attention64": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ttv_patch_gather": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
                                    C.c_int, C.c_int, vp]),
+    "ttv_patch_embed_norm": (C.c_int, [C.POINTER(vp), vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, f32,
+                                       vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ttv_patch_scatter": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp),
                                     C.c_int, C.c_int, vp]),
     "ttv_tower_workspace_bytes": (i64, [C.POINTER(TowerDims), C.POINTER(Batch)]),

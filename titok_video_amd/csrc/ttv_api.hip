@@ -29,6 +29,7 @@ bool ttv_sw_keel_f32sum() { static const bool v = ttv_env_flag("TTV_KEEL_F32SUM"
 bool ttv_sw_fused_patch() { static const bool v = ttv_env_flag("TTV_FUSED_PATCH", true); return v; }
 bool ttv_sw_attn_pipe() { static const bool v = ttv_env_flag("TTV_ATTN_PIPE", false); return v; }
 static bool sw_dec_l0_const() { static const bool v = ttv_env_flag("TTV_DEC_L0_CONST", true); return v; }
+static bool sw_enc_last_qkv_skip() { static const bool v = ttv_env_flag("TTV_ENC_LAST_QKV_SKIP", true); return v; }
 float ttv_sw_attn_thr() { static const float v = ttv_env_float("TTV_ATTN_THR", 8.0f); return v; }   // log2 units; 0 = exact running maximum
 thread_local int g_ttv_debug = 0;     // per host thread: a thread that forces a kernel variant (tests, A/B tools) does not change what another thread launches
 long long* g_ttv_stamps = nullptr;   // diagnostics: device buffer for in-kernel clock stamps (ttv_debug_stamps)
@@ -195,7 +196,7 @@ struct PreNormW { const float* gain; const void *w, *w_pn, *w_f8; const float* w
 // Split-bf16 towers: the normalised row is written as the projection's split image (its producer splits it once, the GEMM's staging
 // threads copy bytes); TTV_SPLIT3_IMAGES=0 keeps fp32 activations and the split in the GEMM (A/B).
 static int prenorm_proj(const LayerCtx& c, GemmEpilogue epi, const char* x, int rows, const PreNormW& p, int N, char* y, int y_image,
-                        bool rstd_valid, int tile_run = 0, int tile_period = 0) {
+                        bool rstd_valid, int tile_run = 0, int tile_period = 0, int panel_lo = 0) {
   const ttv_tower_dims* d = c.d;
   const TowerWs& ws = c.ws;
   const int dm = d->width, dt = d->dtype;
@@ -217,7 +218,7 @@ static int prenorm_proj(const LayerCtx& c, GemmEpilogue epi, const char* x, int 
   a.row_scale = fold_gen ? ws.rstd : nullptr;
   a.x = fold ? x : ws.xn; a.w = fold ? p.w_pn : p.w;
   if (epi == EPI_QKV_ROPE) { a.rope_ids = c.b->rope_ids; a.rope_base = c.b->rope_ids ? c.b->rope_base : nullptr; }
-  a.tile_run = tile_run; a.tile_period = tile_period;       // (the caller has asked ttvk_gemm_qkv_tiles_supported)
+  a.tile_run = tile_run; a.tile_period = tile_period; a.panel_lo = panel_lo;      // (the caller has asked ttvk_gemm_qkv_tiles_supported)
   return ttvk_gemm(epi, a, c.s);
 }
 
@@ -253,6 +254,18 @@ static int keel_tail(const LayerCtx& c, GemmArgs o, int layer, const float* post
   return TTV_OK;
 }
 
+// Can a to_qkv of this tower run k_qkv256 over a tile list that tells latent token tiles from patch token tiles?  Every clip K latent rows
+// and P patch rows (the caller's promise; the sums are checked), both multiples of the kernel's 128-row tiles, and the layer on the
+// width-256 bf16 kernel with the folded pre-norm and pre-scaled q.
+static bool qkv_tile_list_ok(const LayerCtx& c, const ttv_layer_weights& lw, int K, int P) {
+  const ttv_tower_dims* d = c.d;
+  const ttv_batch* b = c.b;
+  if (d->dtype != TTV_BF16 || d->width != 256 || d->head_dim != 64 || c.split3) return false;
+  if (K <= 0 || P <= 0 || K % 128 || P % 128 || (int64_t)b->n_clips * K != b->sum_tokens || (int64_t)b->n_clips * P != b->sum_patches) return false;
+  if (!lw.to_qkv_pn || !lw.qkv_q_prescaled) return false;
+  return ttvk_gemm_qkv_tiles_supported(d->width, d->kv_heads * d->head_dim, d->width);
+}
+
 // One ResidualAttentionBlock stack (reference transformer.py:126-146) on ws.x in place.
 // Can the decoder's layer 0 take its patch rows' q | gate | k | v from the constant block (ttv_dec_l0_const)?  The block's geometry must
 // be every clip's (the caller's promise; the sums are checked), rows and keys split at a multiple of the 128-row tiles of both kernels,
@@ -261,14 +274,18 @@ static bool dec_l0_const_ok(const LayerCtx& c, const ttv_tower_weights* w, const
   const ttv_tower_dims* d = c.d;
   const ttv_batch* b = c.b;
   if (!l0 || !l0->rows || !sw_dec_l0_const() || (g_ttv_debug & TTV_DBG_DEC_L0_NO_CONST)) return false;
-  if (d->kind != TTV_DECODER || d->dtype != TTV_BF16 || d->width != 256 || d->head_dim != 64 || c.split3) return false;
-  const int K = l0->latent_rows, P = l0->patch_rows;
-  if (K <= 0 || P <= 0 || K % 128 || P % 128 || (int64_t)b->n_clips * K != b->sum_tokens || (int64_t)b->n_clips * P != b->sum_patches) return false;
-  const ttv_layer_weights& lw = w->layers[0];
-  if (!lw.to_qkv_pn || !lw.qkv_q_prescaled) return false;
+  if (d->kind != TTV_DECODER || !qkv_tile_list_ok(c, w->layers[0], l0->latent_rows, l0->patch_rows)) return false;
   if (c.pair || c.pipe || !c.all_full || (b->items64 && b->n_items64 > 0)) return false;
-  return ttvk_gemm_qkv_tiles_supported(d->width, d->kv_heads * d->head_dim, d->width) &&
-         ttvk_attention_takes_swp(TTV_ATTN_GATE | TTV_ATTN_QSCALED | TTV_ATTN_ALLFULL);
+  return ttvk_attention_takes_swp(TTV_ATTN_GATE | TTV_ATTN_QSCALED | TTV_ATTN_ALLFULL);
+}
+
+// The encoder's last layer under lat_last queries its latent rows only: may its to_qkv skip the q | gate panels of the patch token tiles
+// (GemmArgs.panel_lo)?  The batch must promise one geometry for every clip (ttv_batch.tokens_per_clip; max_patches_per_clip then IS every
+// clip's P once the sums agree).  TTV_ENC_LAST_QKV_SKIP=0 / debug bit 23: every panel of every row (A/B, tests).
+static bool enc_last_qkv_skip_ok(const LayerCtx& c, const ttv_layer_weights& lw) {
+  const ttv_batch* b = c.b;
+  if (!sw_enc_last_qkv_skip() || (g_ttv_debug & TTV_DBG_ENC_LAST_QKV_ALL) || c.d->kind != TTV_ENCODER) return false;
+  return qkv_tile_list_ok(c, lw, b->tokens_per_clip, b->max_patches_per_clip);
 }
 
 static int run_layers(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_batch* b, const TowerWs& ws, hipStream_t s,
@@ -329,6 +346,10 @@ static int run_layers(const ttv_tower_dims* d, const ttv_tower_weights* w, const
       const void* w_plain = (dt == TTV_BF16 && lw.to_qkv_qs) ? lw.to_qkv_qs : lw.to_qkv;   // inference copy with scaled q rows, if packed
       const PreNormW qw = {lw.pre_ln, w_plain, lw.to_qkv_pn, lw.to_qkv_f8, lw.to_qkv_f8_scale, f8_qkv};
       if (l0c) TTV_TRY(prenorm_proj(ctx, EPI_QKV_ROPE, ws.x, L, qw, nq, ws.qkv, 0, rstd_valid, l0->latent_rows / 128, (l0->latent_rows + l0->patch_rows) / 128));
+      else if (lat_last && last && !f8_qkv && enc_last_qkv_skip_ok(ctx, lw))
+        // q | gate (the first 2 dm columns) for the latent token tiles only: the attention below reads those rows' queries and nothing else
+        TTV_TRY(prenorm_proj(ctx, EPI_QKV_ROPE, ws.x, L, qw, nq, ws.qkv, 0, rstd_valid, b->tokens_per_clip / 128,
+                             (b->tokens_per_clip + b->max_patches_per_clip) / 128, 2 * dm / 64));
       else TTV_TRY(prenorm_proj(ctx, EPI_QKV_ROPE, ws.x, L, qw, nq, ws.qkv, s3img ? 2 : 0, rstd_valid));
     }
     // q arrives pre-scaled when the projection used the folded weight whose q rows carry scale * log2(e)
@@ -649,6 +670,19 @@ int ttv_patch_gather(const void* const* clips, const int32_t* clip_desc, int cli
   return ttvk_patch_copy(false, (void* const*)clips, clip_desc, clip0, n_clips, patch_t, patch_h, patch_w, channels, patches, ld, dtype, max_patches_per_clip, (hipStream_t)stream);
 }
 
+int ttv_patch_embed_norm(const void* const* clips, const int32_t* clip_desc, const int32_t* patch_rows, const int32_t* row_seq, int n_clips,
+                         int patch_t, int patch_h, int patch_w, int channels, const void* w, int ldw, const void* bias, const float* mask_token,
+                         const float* gain, float eps, void* x, int ldx, int rows, int width, int dtype, void* stream) {
+  TTV_CHECK_ARG(rows == 0 || (clips && clip_desc && patch_rows && row_seq && w && bias && mask_token && gain && x), "patch_embed_norm: null buffer");
+  const int pd = channels * patch_t * patch_h * patch_w;
+  if (!ttvk_patch_embed_norm_supported(dtype, width, pd, patch_w)) {
+    ttv_set_error("patch_embed_norm: only bf16, width 256, patch_w 8 and a patch vector that is a multiple of 64");
+    return TTV_ERR_UNSUPPORTED;
+  }
+  return ttvk_patch_embed_norm((void* const*)clips, 0, n_clips, clip_desc, patch_rows, row_seq, patch_t, patch_h, patch_w, pd, w, ldw, bias,
+                               mask_token, gain, eps, x, ldx, rows, (hipStream_t)stream);
+}
+
 int ttv_patch_scatter(const void* patches, int ld, const int32_t* clip_desc, int clip0, int n_clips, int patch_t, int patch_h, int patch_w,
                       int channels, void* const* clips, int dtype, int max_patches_per_clip, void* stream) {
   TTV_CHECK_ARG(n_clips == 0 || (clips && clip_desc && patches), "patch_scatter: null buffer");
@@ -673,20 +707,30 @@ int ttv_encoder_forward(const ttv_tower_dims* d, const ttv_tower_weights* w, con
   TTV_CHECK_ARG(ws.total <= workspace_bytes, "encoder_forward: workspace too small (%lld < %lld)", (long long)workspace_bytes, (long long)ws.total);
   const int dm = d->width, dt = d->dtype, P = b->sum_patches, pd = patch_dim(d);
 
-  // patchify (utils.py:26-34) + proj_in (blocks.py:91-93); when the shapes allow it the GEMM reads its K = (c, pt, ph, pw)
-  // operand straight from the clips (16-byte pixel-row segments) instead of from a gathered [P, pd] copy
-  const bool gather = fused_patch_ok(d, b, dt) && pd != 256;
-  if (!gather) TTV_TRY(patch_copy_all(false, (void* const*)clips, d, b, ws.pa, dt, s));
-  GemmArgs a = gemm_args(dt, ws.pa, pd, w->proj_in_w, pd, P, dm, pd, ws.pb, dm);
-  a.bias = w->proj_in_b; a.add_scalar = w->mask_token;
-  a.split3 = (dt == TTV_F32 && w->f32_split3) ? 1 : 0;
-  if (gather) {
-    a.gather = 1; a.clips = (void* const*)clips; a.n_clips = b->n_clips; a.clip_desc = b->clip_desc; a.patch_rows = b->patch_rows;
-    a.row_seq = b->row_seq; a.patch_t = d->patch_t; a.patch_h = d->patch_h; a.patch_w = d->patch_w;
+  // patchify (utils.py:26-34) + proj_in (blocks.py:91-93) + ln_pre_p of the patch rows (blocks.py:95-97).  Width 256 bf16: one kernel
+  // that keeps a patch's whole row in a block, so neither a gathered copy nor the sums pass through memory (k_patch_embed256).
+  // TTV_PATCH_EMBED_FUSED=0 / debug bit 24: the GEMM and the row kernel below (A/B, tests)
+  static const bool embed_env = ttv_env_flag("TTV_PATCH_EMBED_FUSED", true);
+  if (embed_env && !(g_ttv_debug & TTV_DBG_PATCH_EMBED_UNFUSED) && fused_patch_ok(d, b, dt) && w->proj_in_b && w->mask_token &&
+      ttvk_patch_embed_norm_supported(dt, dm, pd, d->patch_w)) {
+    TTV_TRY(ttvk_patch_embed_norm((void* const*)clips, 0, b->n_clips, b->clip_desc, b->patch_rows, b->row_seq, d->patch_t, d->patch_h, d->patch_w,
+                                  pd, w->proj_in_w, pd, w->proj_in_b, w->mask_token, w->ln_pre_p, d->eps, ws.x, dm, P, s));
+  } else {
+    // when the shapes allow it the GEMM reads its K = (c, pt, ph, pw) operand straight from the clips (16-byte pixel-row segments)
+    // instead of from a gathered [P, pd] copy
+    const bool gather = fused_patch_ok(d, b, dt) && pd != 256;
+    if (!gather) TTV_TRY(patch_copy_all(false, (void* const*)clips, d, b, ws.pa, dt, s));
+    GemmArgs a = gemm_args(dt, ws.pa, pd, w->proj_in_w, pd, P, dm, pd, ws.pb, dm);
+    a.bias = w->proj_in_b; a.add_scalar = w->mask_token;
+    a.split3 = (dt == TTV_F32 && w->f32_split3) ? 1 : 0;
+    if (gather) {
+      a.gather = 1; a.clips = (void* const*)clips; a.n_clips = b->n_clips; a.clip_desc = b->clip_desc; a.patch_rows = b->patch_rows;
+      a.row_seq = b->row_seq; a.patch_t = d->patch_t; a.patch_h = d->patch_h; a.patch_w = d->patch_w;
+    }
+    TTV_TRY(ttvk_gemm(EPI_STORE, a, s));
+    TTV_TRY(ttvk_rmsnorm(ws.pb, dt, dm, nullptr, ws.x, dt, dm, b->patch_rows, w->ln_pre_p, P, dm, d->eps, s));
   }
-  TTV_TRY(ttvk_gemm(EPI_STORE, a, s));
-  // x[patch rows] = ln_pre_p(patches + mask_token); x[latent rows] = ln_pre_t(mask_token * 1) (blocks.py:95-97)
-  TTV_TRY(ttvk_rmsnorm(ws.pb, dt, dm, nullptr, ws.x, dt, dm, b->patch_rows, w->ln_pre_p, P, dm, d->eps, s));
+  // x[latent rows] = ln_pre_t(mask_token * 1) (blocks.py:95-97)
   TTV_TRY(ttvk_fill_const_rows(ws.x, dt, dm, b->latent_rows, b->sum_tokens, dm, w->mask_token, w->ln_pre_t, d->eps, s));
 
   TTV_TRY(run_layers(d, w, b, ws, s));

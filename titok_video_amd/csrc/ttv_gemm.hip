@@ -55,6 +55,7 @@ struct GemmDev {
   long long* stamps;               // diagnostic builds only (-DQKV_STAMPS): g_ttv_stamps
   int resid_rows;                  // EPI_BIAS_RESID_F32R: residual row = token % resid_rows (0: token)
   int tile_run, tile_period;       // k_qkv256: item tile t is token tile (t / tile_run) * tile_period + t % tile_run (tile_period 0: t)
+  int panel_lo;                    // k_qkv256 with a tile list, > 0: every token tile is computed, those behind the first tile_run of a period from panel panel_lo on
 };
 
 // per-token part of a patch destination (EPI_STORE_PATCH), computed once per token tile
@@ -2082,8 +2083,10 @@ static int launch(const GemmDev& d, int dtype, bool prenorm, hipStream_t s) {
     const int fo = (EPI == EPI_GEGLU) ? 32 : 64;
     // (a tile list - GemmArgs.tile_run / tile_period - counts the listed tiles only: with one item per block below 512 items, the 32 x 12
     // items of the decoder's latent tiles at the benchmark batch are 384 co-resident blocks on the 256 CUs)
+    // (with a panel floor - GemmArgs.panel_lo - the other tiles of a period count too, n_panels - panel_lo items each: the encoder's last
+    // layer at the benchmark batch, 32 x 12 + 256 x 4 = 1 408 items instead of 3 456)
     const int n_panels = ttv_cdiv(d.N, fo), n_tiles = d.tile_period ? d.M / K256_TT / d.tile_period * d.tile_run : ttv_cdiv(d.M, K256_TT);
-    const int total = n_panels * n_tiles;
+    const int total = n_panels * n_tiles + (d.panel_lo ? d.M / K256_TT / d.tile_period * (d.tile_period - d.tile_run) * (n_panels - d.panel_lo) : 0);
     // 2 co-resident blocks per CU = 512 slots.  Blocks take contiguous (tile, panel) item ranges and reload their token rows
     // whenever a range crosses into the next tile (-5 us of 34.6 with that reload knocked out).  With an item count per block that
     // is an integer, the ranges repeat with a short period against the panels of a tile and fewer of them straddle: QKV at the
@@ -2094,7 +2097,14 @@ static int launch(const GemmDev& d, int dtype, bool prenorm, hipStream_t s) {
     static const int grid_env = ttv_env_int("TTV_K256_GRID", 0);
     int grid = total < 512 ? total : 512;
     if (grid_env > 0) grid = total < grid_env ? total : grid_env;
-    else if (total > 512)
+    else if (d.panel_lo && total > 512) {
+      // a panel floor: tiles hold n_panels or n_panels - panel_lo items, so blocks of ipb items, ipb a common divisor of the two, never
+      // straddle a tile: the encoder's last layer at the benchmark batch, 1 408 items as 352 blocks x 4 (one patch tile, a third of a
+      // latent tile) 17.9 us against 21.8 us for 512 blocks x 2.75 (profiles/encoder_edges_ab.txt).  The smallest such ipb that fits the slots.
+      const int w = n_panels - d.panel_lo;
+      for (int ipb = 2; ipb <= w; ++ipb)
+        if (w % ipb == 0 && n_panels % ipb == 0 && total / ipb <= 512) { grid = total / ipb; break; }
+    } else if (total > 512)
       for (int g = 512; g >= 416; --g)
         if (total % g == 0) { grid = g; break; }
     // to_qkv: the wave-pipelined streaming kernel k_qkv256 (ttv_qkv256.inc) unless the call needs something only the general epilogue
@@ -2117,8 +2127,11 @@ static int launch(const GemmDev& d, int dtype, bool prenorm, hipStream_t s) {
           TTV_CHECK_LAUNCH("qkv256ws");
           return TTV_OK;
         }
-        if (prenorm) hipLaunchKernelGGL((k_qkv256<true>), dim3(grid), dim3(256), 0, s, d, n_panels, total);
-        else hipLaunchKernelGGL((k_qkv256<false>), dim3(grid), dim3(256), 0, s, d, n_panels, total);
+        if (d.panel_lo) {
+          if (prenorm) hipLaunchKernelGGL((k_qkv256<true, true>), dim3(grid), dim3(256), 0, s, d, n_panels, total);
+          else hipLaunchKernelGGL((k_qkv256<false, true>), dim3(grid), dim3(256), 0, s, d, n_panels, total);
+        } else if (prenorm) hipLaunchKernelGGL((k_qkv256<true, false>), dim3(grid), dim3(256), 0, s, d, n_panels, total);
+        else hipLaunchKernelGGL((k_qkv256<false, false>), dim3(grid), dim3(256), 0, s, d, n_panels, total);
         TTV_CHECK_LAUNCH("qkv256");
         return TTV_OK;
       }
@@ -2281,11 +2294,13 @@ int ttvk_gemm(GemmEpilogue epi, const GemmArgs& a, hipStream_t s) {
   d.row_scale = a.row_scale;
   d.stamps = g_ttv_stamps;
   d.resid_rows = a.resid_rows;
-  d.tile_run = d.tile_period = 0;
+  d.tile_run = d.tile_period = d.panel_lo = 0;
+  TTV_CHECK_ARG(a.panel_lo >= 0 && (!a.panel_lo || (a.tile_period && a.N % 64 == 0 && a.panel_lo < a.N / 64)),
+                "gemm: a panel floor goes with a tile list and leaves at least one 64-feature panel");
   if (a.tile_period) {
     TTV_CHECK_ARG(epi == EPI_QKV_ROPE && a.dtype == TTV_BF16 && a.K == 256 && a.tile_run > 0 && a.tile_run < a.tile_period &&
                   a.M % (K256_TT * a.tile_period) == 0, "gemm: a tile list is a to_qkv option of the bf16 K=256 kernel, M a whole number of periods");
-    d.tile_run = a.tile_run; d.tile_period = a.tile_period;
+    d.tile_run = a.tile_run; d.tile_period = a.tile_period; d.panel_lo = a.panel_lo;
   }
   TTV_CHECK_ARG(!a.row_scale || ((a.dtype == TTV_BF16 || a.split3) && (epi == EPI_STORE || epi == EPI_QKV_ROPE || epi == EPI_GEGLU)),
                 "gemm: row_scale is a STORE / QKV_ROPE / GEGLU option of the bf16 and the split-bf16 kernels");

@@ -103,6 +103,9 @@ struct GemmArgs {
   // optional (EPI_QKV_ROPE on k_qkv256 only): of every tile_period consecutive 128-row token tiles only the first tile_run are computed
   // and stored, rows and outputs in place; the other rows of y are not touched.  0 / 0: every tile.  M % (128 * tile_period) == 0.
   int tile_run, tile_period;
+  // optional, with a tile list: panel_lo > 0 computes the other tiles of a period as well, but only their 64-feature panels panel_lo ..
+  // N / 64 - 1 (columns [64 * panel_lo, N)); the columns in front of those rows of y are not touched.  0: today's tile list.
+  int panel_lo;
 };
 struct ClipPtrs { void* p[TTV_MAX_CLIPS_PER_LAUNCH]; };
 int ttvk_gemm(GemmEpilogue epi, const GemmArgs& a, hipStream_t s);
@@ -110,7 +113,14 @@ int ttvk_gemm(GemmEpilogue epi, const GemmArgs& a, hipStream_t s);
 int ttvk_gemm_fp8(GemmEpilogue epi, const GemmArgs& a, const float* x_scale, const float* w_scale, hipStream_t s, const void* x_mx = nullptr,
                   const void* w_mx = nullptr);
 bool ttvk_gemm_supports_resid_norm(int dtype, int N, int K);
-bool ttvk_gemm_qkv_tiles_supported(int d_model, int gqa_dim, int ldw);   // GemmArgs.tile_run / tile_period: will this to_qkv take them?
+bool ttvk_gemm_qkv_tiles_supported(int d_model, int gqa_dim, int ldw);
+
+// ---- ttv_patch_embed.hip: the encoder's front in one kernel (gather + proj_in + mask token + ln_pre_p), width 256 bf16 ----
+bool ttvk_patch_embed_norm_supported(int dtype, int width, int patch_dim, int patch_w);
+int ttvk_patch_embed_norm(void* const* clips, int clip0, int n_clips, const int* clip_desc, const int* patch_rows, const int* row_seq,
+                          int patch_t, int patch_h, int patch_w, int patch_dim, const void* w, int ldw, const void* bias,
+                          const float* mask_token, const float* gain, float eps, void* x, int ldx, int M, hipStream_t s);
+   // GemmArgs.tile_run / tile_period: will this to_qkv take them?
 
 // ---- ttv_attn.hip ----
 int ttvk_attention(const void* qkvg, int ld, void* out, int ldo, const int* cu_seqlens, const int* qblocks, int n_qblocks,

@@ -193,5 +193,6 @@ extern "C" int ttv_plan_attn_set(const ttv_plan_attn* sz, const int32_t* host_ta
   batch->n_qblocks_latent = sz->n_qblocks_latent;
   batch->qblocks_patch = sz->n_qblocks_patch ? dev_tables + sz->off_qblocks_patch : nullptr;
   batch->n_qblocks_patch = sz->n_qblocks_patch;
+  batch->tokens_per_clip = sz->tokens_per_clip;
   return TTV_OK;
 }

@@ -238,6 +238,9 @@ int attn_build(const int32_t* cu, const int32_t* token_counts, int n_clips, int 
   z.n_qblocks_latent = a.has_latent ? (int32_t)a.latent.n_entries : 0;
   z.n_qblocks_patch = a.has_patch ? (int32_t)a.patch.n_entries : 0;
   z.n_qblocks_l0 = (int32_t)a.l0.n_entries;
+  bool uniform = true;
+  for (int b = 1; b < n_clips; ++b) uniform = uniform && token_counts[b] == token_counts[0] && cu[b + 1] - cu[b] == cu[1] - cu[0];
+  z.tokens_per_clip = uniform ? token_counts[0] : 0;
   int64_t o = 0;
   z.off_qblocks = o;        o += 4 * (int64_t)z.n_qblocks;
   z.off_qblocks_latent = o; o += 4 * (int64_t)z.n_qblocks_latent;

@@ -54,7 +54,10 @@
 #endif
 typedef unsigned qk_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned qk_u32x2 __attribute__((ext_vector_type(2)));
-template <bool PRENORM>
+// FLOOR (GemmDev.panel_lo > 0, with a tile list): EVERY token tile is an item tile, and the tiles behind the first tile_run of a period
+// get the panels panel_lo .. n_panels - 1 only - the k | v columns of rows whose q | gate nobody reads (the encoder's last layer: queries
+// are the latent rows).  Only the item -> (token tile, panel) map differs: it is stepped, not divided, from the block's first item on.
+template <bool PRENORM, bool FLOOR>
 __global__ __launch_bounds__(256, 2) void k_qkv256(GemmDev p, int n_panels, int total_items) {
   __shared__ uint4 wl[2][K256_ROWS * 32];  // [stage][row * 32 + swizzled 16-byte chunk]
 
@@ -246,13 +249,24 @@ __global__ __launch_bounds__(256, 2) void k_qkv256(GemmDev p, int n_panels, int 
   do {                                                                                                       \
     const int it__ = (it_);                                                                                  \
     const int buf__ = (it__ - it0) & 1;                                                                      \
-    const int tile__ = it__ / n_panels, panel__ = it__ - tile__ * n_panels;                                  \
+    int tile__, panel__;                                                                                     \
+    if (FLOOR) {                                                                                             \
+      /* this item is (fl_tile, fl_panel); step to the next one: its panel is what the body stages */        \
+      tile__ = fl_tile; panel__ = fl_panel;                                                                  \
+      if (++fl_panel == n_panels) {                                                                          \
+        ++fl_tile;                                                                                           \
+        if (++fl_pos == p.tile_period) fl_pos = 0;                                                           \
+        fl_panel = fl_pos < p.tile_run ? 0 : p.panel_lo;                                                     \
+      }                                                                                                      \
+    } else {                                                                                                 \
+      tile__ = it__ / n_panels; panel__ = it__ - tile__ * n_panels;                                          \
+    }                                                                                                        \
     if (tile__ != cur_tile) {                                                                                \
       cur_tile = tile__;                                                                                     \
       /* the new rows are requested first: the epilogue owed to the previous tile (it needs that tile's factors and addresses) */ \
       /* runs under their latency */                                                                         \
       /* a tile list (GemmDev.tile_run / tile_period): item tile -> token tile, rows and outputs in place */  \
-      const int ttile__ = p.tile_period ? (tile__ / p.tile_run) * p.tile_period + tile__ % p.tile_run : tile__; \
+      const int ttile__ = FLOOR ? tile__ : p.tile_period ? (tile__ / p.tile_run) * p.tile_period + tile__ % p.tile_run : tile__; \
       const int t0__ = ttile__ * K256_TT + wave * 32;                                                        \
       int ntk__ = t0__ + r;                                                                                  \
       const bool nok__ = ntk__ < p.M;                                                                        \
@@ -279,7 +293,7 @@ __global__ __launch_bounds__(256, 2) void k_qkv256(GemmDev p, int n_panels, int 
     }                                                                                                        \
     QK_STAMP(1);                                                                                             \
     const bool has_next__ = it__ + 1 < it1;                                                                  \
-    const char* nsrc__ = QK_PANEL_SRC((it__ + 1) % n_panels);                                                \
+    const char* nsrc__ = QK_PANEL_SRC(FLOOR ? fl_panel : (it__ + 1) % n_panels);                             \
     const uint32_t ndst__ = QK_PANEL_DST(buf__ ^ 1);                                                         \
     const int f_first__ = panel__ * 64;                                                                      \
     const int rot__ = (f_first__ < p.rope_q_end || (f_first__ >= p.rope_k_begin && f_first__ < p.rope_k_end)) ? 2 : 1; \
@@ -308,8 +322,20 @@ __global__ __launch_bounds__(256, 2) void k_qkv256(GemmDev p, int n_panels, int 
 
   f32x16 accA[2], accB[2];
   QK_STAMP_DECL;
+  // FLOOR: the block's first item.  A period of tile_period token tiles holds tile_run * n_panels + (tile_period - tile_run) * (n_panels -
+  // panel_lo) items: the full tiles first, panel-major inside a tile.  fl_pos = the tile's place in its period.
+  int fl_tile = 0, fl_panel = 0, fl_pos = 0;
+  if (FLOOR) {
+    const int full = p.tile_run * n_panels, wide = n_panels - p.panel_lo;
+    const int per = full + (p.tile_period - p.tile_run) * wide;
+    const int q = it0 / per;
+    int rem = it0 - q * per;
+    if (rem < full) { fl_pos = rem / n_panels; fl_panel = rem - fl_pos * n_panels; }
+    else { rem -= full; fl_pos = p.tile_run + rem / wide; fl_panel = p.panel_lo + rem % wide; }
+    fl_tile = q * p.tile_period + fl_pos;
+  }
   {
-    const char* src0 = QK_PANEL_SRC(it0 % n_panels);
+    const char* src0 = QK_PANEL_SRC(FLOOR ? fl_panel : it0 % n_panels);
     const uint32_t dst0 = QK_PANEL_DST(0);
     QK_DMA_PIECE(dchunk0, 0, src0, dst0); QK_DMA_PIECE(dchunk0, 1, src0, dst0); QK_DMA_PIECE(dchunk0, 2, src0, dst0); QK_DMA_PIECE(dchunk0, 3, src0, dst0);
     QK_DMA_PIECE(dchunk0, 4, src0, dst0); QK_DMA_PIECE(dchunk0, 5, src0, dst0); QK_DMA_PIECE(dchunk0, 6, src0, dst0); QK_DMA_PIECE(dchunk0, 7, src0, dst0);

@@ -233,6 +233,8 @@ class BatchPlan:
         self._base_fields = dict(
             n_clips=B, total_rows=self.total_rows, sum_tokens=self.sum_tokens, sum_patches=self.sum_patches,
             max_patches_per_clip=max(sizes),
+            # (ttv_batch.tokens_per_clip: the promise that every clip has this K and the same number of patches)
+            tokens_per_clip=self.token_counts[0] if len(set(self.token_counts)) == 1 and len(set(sizes)) == 1 else 0,
             cu_seqlens=base + 4 * offs[0], latent_rows=base + 4 * offs[1], patch_rows=base + 4 * offs[2],
             clip_desc=base + 4 * offs[3], rope_cs=self.rope_cs.data_ptr(),
             blocks64=base + 4 * offs[4], row_seq=base + 4 * offs[5], n_blocks64=self.n_blocks64)
