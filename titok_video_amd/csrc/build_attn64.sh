@@ -3,13 +3,14 @@
 # a wave's 256 registers as VGPRs.  hipcc splits 128 / 128 by default whenever AGPRs are in use (and then spills); the backend honours
 # the function attribute "amdgpu-agpr-alloc"="96", which has no source-level spelling - so the device IR is emitted, the attribute is
 # added to the kernels' attribute group, and the device object, its fat binary and the host object are produced by the same tools
-# hipcc itself runs (hipcc -### shows the sequence).       usage: build_attn64.sh <out.o> [extra -D flags]
+# hipcc itself runs (hipcc -### shows the sequence).       usage (from build.sh, which exports FLAGS): build_attn64.sh <out.o> [extra -D flags]
+# Temporaries are named after the output object: two builds of one tree give the same bytes, builds of different outputs do not collide.
 set -e
 cd "$(dirname "$0")"
 OUT=$1; shift
 LLVM=/opt/rocm/lib/llvm/bin
-FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=on -fno-slp-vectorize -Wall -Wno-unused-function"
-T=build/attn64_$$
+: "${FLAGS:?build_attn64.sh: FLAGS is not set (build.sh exports it)}"
+T=build/attn64_$(basename $OUT)
 hipcc $FLAGS "$@" --cuda-device-only -emit-llvm -S ttv_attn64.hip -o $T.ll 2>/dev/null
 grep -q '^attributes #0 = { .*"amdgpu-waves-per-eu"="2"' $T.ll || { echo "build_attn64.sh: kernel attribute group not found"; exit 1; }
 sed -i 's/^attributes #0 = { /attributes #0 = { "amdgpu-agpr-alloc"="96" /' $T.ll

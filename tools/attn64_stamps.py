@@ -3,7 +3,7 @@
 loop, prologue and epilogue (diagnostic build tools/attn64_stamps.sh, loaded through TTV_LIB_PATH).  Shares are meaningful, the run
 time of this build is not (the stamps fence the scheduler and cost ~10 %).
 
-    bash tools/attn64_stamps.sh && TTV_LIB_PATH=titok_video_amd/csrc/build/libtitok_hip_stamps64.so python3 tools/attn64_stamps.py"""
+    bash tools/attn64_stamps.sh && TTV_LIB_PATH=titok_video_amd/csrc/variants/libtitok_hip_stamps64.so python3 tools/attn64_stamps.py"""
 import os
 import sys
 

@@ -2,7 +2,7 @@
 """Where a wave of the bf16 attention kernel spends its cycles: per-segment s_memtime sums of the key loop (diagnostic build
 tools/attn_stamps.sh, loaded through TTV_LIB_PATH).  Shares are meaningful, the run time of this build is not.
 
-    bash tools/attn_stamps.sh && TTV_LIB_PATH=titok_video_amd/csrc/build/libtitok_hip_stamps.so python3 tools/attn_stamps.py"""
+    bash tools/attn_stamps.sh && TTV_LIB_PATH=titok_video_amd/csrc/variants/libtitok_hip_stamps.so python3 tools/attn_stamps.py"""
 import os
 import sys
 

@@ -3,7 +3,7 @@
 loaded through TTV_LIB_PATH): per table entry the 100 MHz constant clock and the shader clock at entry start / loop start / loop end
 / entry end, and the CU the block ran on.
 
-    bash tools/attn_timeline.sh && TTV_LIB_PATH=titok_video_amd/csrc/build/libtitok_hip_timeline.so python3 tools/attn_timeline.py
+    bash tools/attn_timeline.sh && TTV_LIB_PATH=titok_video_amd/csrc/variants/libtitok_hip_timeline.so python3 tools/attn_timeline.py
     B=64 ... (clips)   TTV_ATTN_PERS=1 ... (persistent walk)"""
 import os
 import sys

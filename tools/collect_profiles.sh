@@ -11,11 +11,11 @@ step() { echo "[collect $PART] $*"; }
 if [ $PART = tiny2 ]; then
   step rocprof two chains; rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_if2 -o p -- python3 $R/bench.py --no-cpu-baseline --no-fp32-leg > $O/tiny_bench_under_rocprof.json 2> $O/prof_if2.log
   step rocprof one chain; rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_if1 -o p -- python3 $R/bench.py --in-flight 1 --no-cpu-baseline --no-fp32-leg > $O/tiny_bench_inflight1_under_rocprof.json 2> $O/prof_if1.log
-  step stamps; TTV_LIB_PATH=$R/titok_video_amd/csrc/build/libtitok_hip_stamps.so python3 $R/tools/attn_stamps.py > $O/attn_stamps.txt 2>&1
-  TTV_LIB_PATH=$R/titok_video_amd/csrc/build/libtitok_hip_stamps64.so python3 $R/tools/attn64_stamps.py > $O/attn64_stamps.txt 2>&1
+  step stamps; TTV_LIB_PATH=$R/titok_video_amd/csrc/variants/libtitok_hip_stamps.so python3 $R/tools/attn_stamps.py > $O/attn_stamps.txt 2>&1
+  TTV_LIB_PATH=$R/titok_video_amd/csrc/variants/libtitok_hip_stamps64.so python3 $R/tools/attn64_stamps.py > $O/attn64_stamps.txt 2>&1
   step attention alone; FP32=0 python3 $R/tools/attn_bench.py 1.5 6 > $O/attn_bench.txt 2>&1
   B=4 CLIP=32,256,256 K=1024 HQ=12 HKV=4 FP32=0 python3 $R/tools/attn_bench.py 1.5 >> $O/attn_bench.txt 2>&1
-  step knock-outs of the 64-row kernel; for n in dma lds max exp all; do echo "== knock-out $n" >> $O/attn64_knockouts.txt; TTV_LIB_PATH=$R/titok_video_amd/csrc/build/libtitok_hip_ko64_$n.so FP32=0 python3 $R/tools/attn_bench.py 1.5 2>&1 | grep "w64" >> $O/attn64_knockouts.txt; done
+  step knock-outs of the 64-row kernel; for n in dma lds max exp all; do echo "== knock-out $n" >> $O/attn64_knockouts.txt; TTV_LIB_PATH=$R/titok_video_amd/csrc/variants/libtitok_hip_ko64_$n.so FP32=0 python3 $R/tools/attn_bench.py 1.5 2>&1 | grep "w64" >> $O/attn64_knockouts.txt; done
   step loss probe; TAG=default python3 $R/tools/loss_probe.py > $O/loss_probe.txt 2>&1; TAG=thr0 TTV_ATTN_THR=0 python3 $R/tools/loss_probe.py >> $O/loss_probe.txt 2>&1
 fi
 if [ $PART = r04 ]; then       # round 4 evidence set: the driver's command, both modes under rocprof, traffic counters, base / base5, exact index
@@ -39,8 +39,8 @@ if [ $PART = r05 ]; then       # round 5 evidence set: the driver's command, bot
   step attention alone; FP32=0 timeout -k 10 200 python3 $R/tools/attn_bench.py 1.5 6 > $O/attn_bench.txt 2>&1
   for b in 48 64; do echo "== B=$b" >> $O/attn_bench.txt; B=$b timeout -k 10 200 python3 $R/tools/attn_bench.py 1.5 2>&1 | grep qscaled >> $O/attn_bench.txt; done
   echo "== base shape" >> $O/attn_bench.txt; B=4 CLIP=32,256,256 K=1024 HQ=12 HKV=4 FP32=0 timeout -k 10 200 python3 $R/tools/attn_bench.py 1.5 >> $O/attn_bench.txt 2>&1
-  step stamps + clock; TTV_LIB_PATH=$R/titok_video_amd/csrc/build/libtitok_hip_swpstamps.so timeout -k 10 200 python3 $R/tools/swp_stamps.py > $O/swp_stamps.txt 2>&1
-  echo "== all-zero operands" >> $O/swp_stamps.txt; ZERO=1 TTV_LIB_PATH=$R/titok_video_amd/csrc/build/libtitok_hip_swpstamps.so timeout -k 10 200 python3 $R/tools/swp_stamps.py >> $O/swp_stamps.txt 2>&1
+  step stamps + clock; TTV_LIB_PATH=$R/titok_video_amd/csrc/variants/libtitok_hip_swpstamps.so timeout -k 10 200 python3 $R/tools/swp_stamps.py > $O/swp_stamps.txt 2>&1
+  echo "== all-zero operands" >> $O/swp_stamps.txt; ZERO=1 TTV_LIB_PATH=$R/titok_video_amd/csrc/variants/libtitok_hip_swpstamps.so timeout -k 10 200 python3 $R/tools/swp_stamps.py >> $O/swp_stamps.txt 2>&1
   step power probe; timeout -k 10 200 python3 $R/tools/power_probe.py > $O/power_probe.txt 2>&1
   for z in 0 1; do echo "== attn_bench B=64 ZERO=$z" >> $O/power_probe.txt; ZERO=$z B=64 timeout -k 10 200 python3 $R/tools/attn_bench.py 1.5 2>&1 | grep qscaled >> $O/power_probe.txt; done
   for i in 1 2; do
@@ -58,8 +58,8 @@ if [ $PART = r04base ]; then
   find $O -name "*kernel_trace.csv" -delete
 fi
 if [ $PART = r04attn ]; then   # the attention kernel alone: stamps, timeline, both shapes, three SQ counter passes (diagnostic builds: tools/attn_stamps.sh, attn_timeline.sh)
-  step stamps; TTV_LIB_PATH=$R/titok_video_amd/csrc/build/libtitok_hip_stamps.so timeout -k 10 200 python3 $R/tools/attn_stamps.py > $O/attn_stamps.txt 2>&1
-  step timeline; TTV_LIB_PATH=$R/titok_video_amd/csrc/build/libtitok_hip_timeline.so timeout -k 10 200 python3 $R/tools/attn_timeline.py > $O/attn_timeline.txt 2>&1
+  step stamps; TTV_LIB_PATH=$R/titok_video_amd/csrc/variants/libtitok_hip_stamps.so timeout -k 10 200 python3 $R/tools/attn_stamps.py > $O/attn_stamps.txt 2>&1
+  step timeline; TTV_LIB_PATH=$R/titok_video_amd/csrc/variants/libtitok_hip_timeline.so timeout -k 10 200 python3 $R/tools/attn_timeline.py > $O/attn_timeline.txt 2>&1
   step attention alone; FP32=0 timeout -k 10 200 python3 $R/tools/attn_bench.py 1.5 6 > $O/attn_bench.txt 2>&1
   B=4 CLIP=32,256,256 K=1024 HQ=12 HKV=4 FP32=0 timeout -k 10 200 python3 $R/tools/attn_bench.py 1.5 >> $O/attn_bench.txt 2>&1
   for i in 1 2 3; do
@@ -73,8 +73,8 @@ if [ $PART = tiny ]; then
   step rocprof two chains; rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_if2 -o p -- python3 $R/bench.py --no-cpu-baseline --no-fp32-leg > $O/tiny_bench_under_rocprof.json 2> $O/prof_if2.log
   step rocprof one chain; rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_if1 -o p -- python3 $R/bench.py --in-flight 1 --no-cpu-baseline --no-fp32-leg > $O/tiny_bench_inflight1_under_rocprof.json 2> $O/prof_if1.log
   step ubench; $R/tools/ubench/valu_rates > $O/ubench_valu_rates.txt 2>&1
-  step stamps; TTV_LIB_PATH=$R/titok_video_amd/csrc/build/libtitok_hip_stamps.so python3 $R/tools/attn_stamps.py > $O/attn_stamps.txt 2>&1
-  TTV_LIB_PATH=$R/titok_video_amd/csrc/build/libtitok_hip_stamps64.so python3 $R/tools/attn64_stamps.py > $O/attn64_stamps.txt 2>&1
+  step stamps; TTV_LIB_PATH=$R/titok_video_amd/csrc/variants/libtitok_hip_stamps.so python3 $R/tools/attn_stamps.py > $O/attn_stamps.txt 2>&1
+  TTV_LIB_PATH=$R/titok_video_amd/csrc/variants/libtitok_hip_stamps64.so python3 $R/tools/attn64_stamps.py > $O/attn64_stamps.txt 2>&1
   step attention alone; FP32=0 python3 $R/tools/attn_bench.py 1.5 6 > $O/attn_bench.txt 2>&1
   B=4 CLIP=32,256,256 K=1024 HQ=12 HKV=4 FP32=0 python3 $R/tools/attn_bench.py 1.5 >> $O/attn_bench.txt 2>&1
 fi

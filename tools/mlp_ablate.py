@@ -1,5 +1,6 @@
 # In-kernel stamps of the layer-tail kernel.  Needs the diagnostic build:
-#   bash tools/attn_stamps.sh && TTV_LIB_PATH=titok_video_amd/csrc/build/libtitok_hip_stamps.so python tools/mlp_ablate.py
+#   bash tools/attn_stamps.sh && TTV_LIB_PATH=titok_video_amd/csrc/variants/libtitok_hip_stamps.so python tools/mlp_ablate.py
+# Other builds of the kernel: bash titok_video_amd/csrc/build.sh --variant depth2 ttv_mlp -DMLP_STAMPS -DMLP_P1_DEPTH=2   (-> csrc/variants/libtitok_hip_depth2.so)
 import os, sys, torch, ctypes as C
 sys.path.insert(0, os.getcwd())
 from titok_video_amd import _lib

@@ -1,12 +1,9 @@
 #!/bin/bash
-# Diagnostic build of the to_qkv kernel with -DQKV_STAMPS (ttv_qkv256.inc) -> build/libtitok_hip_qkvstamps.so, then tools/qkv256_stamps.py.
-# The object files do not travel to the GPU box (.gpurunignore): the product objects are rebuilt there first.
+# Diagnostic build of the to_qkv kernel with -DQKV_STAMPS (ttv_qkv256.inc) -> csrc/variants/libtitok_hip_qkvstamps.so, then tools/qkv256_stamps.py.
+#   tools/qkv256_stamps.sh build   (cross-compile only; the library travels to the GPU box)
+#   tools/qkv256_stamps.sh run     (GPU box: the reader under the library built before)         no argument: both
 set -e
 R="$(cd "$(dirname "$0")/.." && pwd)"
-cd "$R/titok_video_amd/csrc"
-[ -f build/ttv_api.o ] || bash build.sh > /dev/null 2>&1
-FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=on -fno-slp-vectorize -Wno-unused-function -Wno-unused-variable"
-hipcc $FLAGS -DQKV_STAMPS $QKV_EXTRA -c ttv_gemm.hip -o build/ttv_gemm_qkvstamps.o
-hipcc --offload-arch=gfx950 -shared -fPIC build/ttv_elem.o build/ttv_gemm_qkvstamps.o build/ttv_attn.o build/ttv_attn_swp.o build/ttv_attn64.o build/ttv_mlp.o build/ttv_bwd.o build/ttv_train.o build/ttv_vq.o build/ttv_api.o -o build/libtitok_hip_qkvstamps.so
+[ "$1" = run ] || bash $R/titok_video_amd/csrc/build.sh --variant qkvstamps ttv_gemm -DQKV_STAMPS -Wno-unused-variable $QKV_EXTRA
 cd "$R"
-TTV_LIB_PATH=$R/titok_video_amd/csrc/build/libtitok_hip_qkvstamps.so python3 tools/qkv256_stamps.py
+[ "$1" = build ] || TTV_LIB_PATH=$R/titok_video_amd/csrc/variants/libtitok_hip_qkvstamps.so python3 tools/qkv256_stamps.py

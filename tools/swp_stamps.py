@@ -2,7 +2,7 @@
 """Where a wave of k_attn_swp spends its cycles: per-segment s_memtime sums of the key loop plus prologue / epilogue (diagnostic build
 tools/swp_stamps.sh, loaded through TTV_LIB_PATH).  Shares are meaningful, the run time of this build is not.
 
-    bash tools/swp_stamps.sh && TTV_LIB_PATH=titok_video_amd/csrc/build/libtitok_hip_swpstamps.so python3 tools/swp_stamps.py"""
+    bash tools/swp_stamps.sh && TTV_LIB_PATH=titok_video_amd/csrc/variants/libtitok_hip_swpstamps.so python3 tools/swp_stamps.py"""
 import os
 import sys
 

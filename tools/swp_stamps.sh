@@ -1,8 +1,3 @@
 #!/bin/bash
-# Diagnostic build: ttv_attn_swp.hip with -DSWP_STAMPS (+ extra -D flags) linked against the product objects -> build/libtitok_hip_swpstamps.so
-set -e
-cd "$(dirname "$0")/../titok_video_amd/csrc"
-FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=on -fno-slp-vectorize -Wall -Wno-unused-function"
-hipcc $FLAGS -DSWP_STAMPS "$@" -c ttv_attn_swp.hip -o build/ttv_attn_swp_stamps.o
-hipcc --offload-arch=gfx950 -shared -fPIC build/ttv_elem.o build/ttv_gemm.o build/ttv_attn.o build/ttv_attn_swp_stamps.o build/ttv_attn64.o build/ttv_mlp.o build/ttv_bwd.o build/ttv_train.o build/ttv_vq.o build/ttv_api.o -o build/libtitok_hip_swpstamps.so
-echo "built $(realpath build/libtitok_hip_swpstamps.so)"
+# Diagnostic build: ttv_attn_swp.hip with -DSWP_STAMPS (+ extra -D flags) -> csrc/variants/libtitok_hip_swpstamps.so
+exec bash "$(dirname "$0")/../titok_video_amd/csrc/build.sh" --variant swpstamps ttv_attn_swp -DSWP_STAMPS "$@"

@@ -2,7 +2,7 @@
 """Where the waves of k_wgrad128_bf16 spend their cycles (diagnostic build tools/wgrad_stamps.sh, loaded through TTV_LIB_PATH): s_memtime
 sums per 64-token stage of the compute waves (barrier | sub-step 0 | sub-step 1) and of the loader waves (wait for the stage | barrier | issue).
 
-    bash tools/wgrad_stamps.sh && TTV_LIB_PATH=titok_video_amd/csrc/build/libtitok_hip_wgstamps.so python3 tools/wgrad_stamps.py"""
+    bash tools/wgrad_stamps.sh && TTV_LIB_PATH=titok_video_amd/csrc/variants/libtitok_hip_wgstamps.so python3 tools/wgrad_stamps.py"""
 import os
 import sys
 
