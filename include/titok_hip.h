@@ -261,6 +261,22 @@ int ttv_attention(const void* qkvg, int ld, void* out, int ldo, const int32_t* c
 int ttv_attention64(const void* qkvg, int ld, void* out, int ldo, const int32_t* cu_seqlens, const int32_t* items, int n_items,
                     int q_heads, int kv_heads, int head_dim, int flags, int dtype, void* stream);
 
+/* The three producers of the block-scaled fp8 layers that write the next linear's operand themselves, each on its own.  FOR TESTS
+ * ONLY (tests/test_hip_fp8_blocks.py): the towers reach the same kernels inside ttv_encoder_forward / ttv_decoder_forward; no caller
+ * needs them one by one.  Each image must equal ttv_quant_mx_fp8 of the bf16 rows its plain twin stores, bit for bit: elements
+ * [rows, width] bytes (leading dimension = width), scales ttv_mx_scale_bytes_per_row(width) bytes per row in ttv_quant_mx_fp8's layout.
+ *   ttv_rmsnorm_mx: ttv_rmsnorm without row maps; next_rstd fp32 [rows] (may be NULL) receives rsqrt(mean(out^2) + eps) of the rows as
+ *     stored; mx_q / mx_s (both or neither; width % 128 == 0) the image of the rows as stored.
+ *   ttv_attention_mxout: ttv_attention (bf16, head_dim 64, TTV_ATTN_GATE | TTV_ATTN_QSCALED, unpaired table) whose output leaves only
+ *     as the image out_q / out_mx (ld_mx = ttv_mx_scale_bytes_per_row(64 * q_heads)).
+ *   ttv_linear_fp8_mx_geglu_q: ttv_linear_fp8_mx with epilogue 2 whose output h [M, N] leaves only as the image hq / hq_mx (N % 128 == 0). */
+int ttv_rmsnorm_mx(const void* in, int in_dtype, int ld_in, void* out, int out_dtype, int ld_out, const float* gain, int rows, int width,
+                   float eps, float* next_rstd, void* mx_q, void* mx_s, void* stream);
+int ttv_attention_mxout(const void* qkvg, int ld, void* out_q, void* out_mx, int ld_mx, const int32_t* cu_seqlens, const int32_t* qblocks,
+                        int n_qblocks, int q_heads, int kv_heads, void* stream);
+int ttv_linear_fp8_mx_geglu_q(const void* xq, int ldx, const void* x_mx, const float* x_row_scale, const void* wq, int ldw, const void* w_mx,
+                              const float* w_row_scale, void* hq, void* hq_mx, int M, int N, int K, void* stream);
+
 /* patch_rearrange (model/base/utils.py:26-34) for up to TTV_MAX_CLIPS_PER_LAUNCH clips per call.
  * clips: HOST array of device pointers [n_clips] to [C,T,H,W] tensors; clip_desc: DEVICE int32 [n_clips,8] =
  * (T,H,W, gt,gh,gw, first patch row, C).  Output rows hold the patch vector in (c,pt,ph,pw) order - the

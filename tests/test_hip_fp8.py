@@ -303,13 +303,26 @@ def test_base_towers_with_mx_fp8_linears_stay_within_the_stated_tolerance():
     assert float((res["mx"][2] - ref_flat).norm() / ref_flat.norm()) < 0.15
 
 
-def test_mx_quantisation_fused_into_the_producers_is_bit_identical():
-    """run_layer_mx writes the block-scaled image of x from the KEEL post-norm kernel and of h from the w12 GEMM's GEGLU epilogue; with
-    ttv_debug_set bit 11 every operand is quantised by a pass of its own.  Same values, same blocks, same rounding: the towers' outputs
-    must be equal bit for bit."""
+# 84 rows: one partial token tile per GEMM, one query block and one key tile per sequence.  4 112 rows: to_qkv and w12 take the 160-token
+# tile of k_gemm_fp8_dma, out_proj and w3 the 128-token tile; the sequences span nine query blocks and eighteen key tiles.  2 120 rows:
+# only w12 takes the 160-token tile; a sequence of 968 rows ends inside a query block.
+FUSED_BATCHES = {
+    "84rows": ([(4, 16, 16), (8, 16, 24), (4, 32, 16)], [16, 24, 20]),
+    "4112rows": ([(16, 128, 128)] * 3 + [(16, 64, 64)], [128] * 3 + [400]),
+    "2120rows": ([(16, 128, 128), (16, 128, 96)], [128, 200]),
+}
+
+
+@pytest.mark.parametrize("batch", list(FUSED_BATCHES))
+def test_mx_quantisation_fused_into_the_producers_is_bit_identical(batch):
+    """run_layer_mx writes the block-scaled image of x from the KEEL post-norm kernel, of the attention output from the attention
+    epilogue and of h from the w12 GEMM's GEGLU epilogue; with ttv_debug_set bit 11 every operand is quantised by a pass of its own.
+    Same values, same blocks, same rounding: the towers' outputs must be equal bit for bit - z, indices and reconstructions, and the
+    encoder's z with its last layer on the MX path as well (DBG_ENC_ALL_ROWS)."""
     levels = [8, 8, 8, 6, 5]
     sd = seeded_titok_state(3, "base", "base", gain=3.0)
-    shapes, counts = [(4, 16, 16), (8, 16, 24), (4, 32, 16)], [16, 24, 20]
+    shapes, counts = FUSED_BATCHES[batch]
+    assert sum(k + (t // 4) * (h // 8) * (w // 8) for (t, h, w), k in zip(shapes, counts)) == int(batch[:-4])
     clips = [c.to(DEV, torch.bfloat16) for c in synthetic_clips(shapes, seed=13)]
     m = TiTok(_base_cfg(levels))
     m.load_state_dict(sd, strict=True)
@@ -322,12 +335,16 @@ def test_mx_quantisation_fused_into_the_producers_is_bit_identical():
             with torch.no_grad():
                 z = m.encoder.run(clips, counts, None, None, want_z=True)["z"].clone()
                 recon, info = m(clips, counts)
+                _lib.lib().ttv_debug_set(bit | _lib.DBG_ENC_ALL_ROWS)
+                z_all = m.encoder.run(clips, counts, None, None, want_z=True)["z"].clone()
             torch.cuda.synchronize()
         finally:
             _lib.lib().ttv_debug_set(0)
-        outs.append((z, [r.clone() for r in recon], info["indices"].clone()))
+        outs.append((z, [r.clone() for r in recon], info["indices"].clone(), z_all))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][2], outs[1][2])
     assert all(torch.equal(a, b) for a, b in zip(outs[0][1], outs[1][1]))
+    assert torch.equal(outs[0][3], outs[1][3])
+    assert not torch.equal(outs[0][0], outs[0][3])      # the all-rows forward really took the MX kernels in the last layer
 
 
 def test_mx_tower_layer_off_the_mx_path_reads_the_folded_bf16_weights_not_the_mx_images():

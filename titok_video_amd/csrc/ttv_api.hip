@@ -664,6 +664,28 @@ int ttv_attention64(const void* qkvg, int ld, void* out, int ldo, const int32_t*
   return ttvk_attention64(qkvg, ld, out, ldo, cu_seqlens, items, n_items, q_heads, kv_heads, flags, (hipStream_t)stream);
 }
 
+// The three fused MX producers of run_layer_mx, one by one (tests only: tests/test_hip_fp8_blocks.py)
+int ttv_rmsnorm_mx(const void* in, int in_dtype, int ld_in, void* out, int out_dtype, int ld_out, const float* gain, int rows, int width,
+                   float eps, float* next_rstd, void* mx_q, void* mx_s, void* stream) {
+  TTV_CHECK_ARG(rows >= 0 && (rows == 0 || (in && out && gain)), "rmsnorm_mx: null buffer");
+  TTV_CHECK_ARG(!mx_q == !mx_s, "rmsnorm_mx: the image needs both its element and its scale buffer");
+  return ttvk_rmsnorm(in, in_dtype, ld_in, nullptr, out, out_dtype, ld_out, nullptr, gain, rows, width, eps, (hipStream_t)stream, next_rstd, mx_q, mx_s);
+}
+
+int ttv_attention_mxout(const void* qkvg, int ld, void* out_q, void* out_mx, int ld_mx, const int32_t* cu_seqlens, const int32_t* qblocks,
+                        int n_qblocks, int q_heads, int kv_heads, void* stream) {
+  TTV_CHECK_ARG(n_qblocks >= 0 && (n_qblocks == 0 || (qkvg && out_q && out_mx && cu_seqlens && qblocks)), "attention_mxout: null buffer");
+  return ttvk_attention_mxout(qkvg, ld, out_q, out_mx, ld_mx, cu_seqlens, qblocks, n_qblocks, q_heads, kv_heads, (hipStream_t)stream);
+}
+
+int ttv_linear_fp8_mx_geglu_q(const void* xq, int ldx, const void* x_mx, const float* x_row_scale, const void* wq, int ldw, const void* w_mx,
+                              const float* w_row_scale, void* hq, void* hq_mx, int M, int N, int K, void* stream) {
+  TTV_CHECK_ARG(M == 0 || (xq && wq && x_mx && w_mx && hq && hq_mx), "linear_fp8_mx_geglu_q: null buffer");
+  GemmArgs a = gemm_args(TTV_BF16, xq, ldx, wq, ldw, M, N, K, hq, N);      // no bf16 output: y is the image buffer, as in run_layer_mx
+  a.yq = hq; a.yq_mx = hq_mx;
+  return ttvk_gemm_fp8(EPI_GEGLU, a, x_row_scale, w_row_scale, (hipStream_t)stream, x_mx, w_mx);
+}
+
 int ttv_patch_gather(const void* const* clips, const int32_t* clip_desc, int clip0, int n_clips, int patch_t, int patch_h, int patch_w,
                      int channels, void* patches, int ld, int dtype, int max_patches_per_clip, void* stream) {
   TTV_CHECK_ARG(n_clips == 0 || (clips && clip_desc && patches), "patch_gather: null buffer");
