@@ -277,6 +277,17 @@ int ttv_attention_mxout(const void* qkvg, int ld, void* out_q, void* out_mx, int
 int ttv_linear_fp8_mx_geglu_q(const void* xq, int ldx, const void* x_mx, const float* x_row_scale, const void* wq, int ldw, const void* w_mx,
                               const float* w_row_scale, void* hq, void* hq_mx, int M, int N, int K, void* stream);
 
+/* The folded pre-norm of the wide bf16 layer (widths other than 256: the gain lives in the weight, the row statistic multiplies the
+ * GEMM's output rows), launch by launch.  FOR TESTS ONLY (tests/test_hip_wide_layer.py): the towers make the same launches inside
+ * ttv_encoder_forward / ttv_decoder_forward; the public linears carry no row scale.
+ *   ttv_row_rstd: rstd[r] = rsqrt(mean(x[r, :width]^2) + eps), fp32 [rows]; x bf16 or fp32, ldx >= width, width % 8 == 0.
+ *   ttv_linear_rowscale: y = epilogue((x @ w^T) * row_scale[:, None]); epilogue 0 = store, 1 = to_qkv + rotary (ttv_linear_qkv_rope:
+ *     N = 2 d_model + 2 gqa_dim, K = d_model), 2 = GEGLU (ttv_linear_geglu: w holds 2N rows, y [M, N]).  row_scale fp32 [M] or NULL
+ *     (then the launch is the public linear's).  The kernel is chosen as for the public linears (ttv_debug_set forces one). */
+int ttv_row_rstd(const void* x, int dtype, int ldx, float* rstd, int rows, int width, float eps, void* stream);
+int ttv_linear_rowscale(const void* x, int ldx, const void* w, int ldw, const float* row_scale, int epilogue, const float* rope_cs, int d_model,
+                        int gqa_dim, void* y, int ldy, int M, int N, int K, int dtype, void* stream);
+
 /* patch_rearrange (model/base/utils.py:26-34) for up to TTV_MAX_CLIPS_PER_LAUNCH clips per call.
  * clips: HOST array of device pointers [n_clips] to [C,T,H,W] tensors; clip_desc: DEVICE int32 [n_clips,8] =
  * (T,H,W, gt,gh,gw, first patch row, C).  Output rows hold the patch vector in (c,pt,ph,pw) order - the

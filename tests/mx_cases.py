@@ -16,6 +16,9 @@ restates it; every case names the height it expects, so a changed rule fails lou
   qkv + rotary       d = 768, g = 256 (N = 2048), K = 768: M = 4097 (160) and M = 300 (128); the rotary table belongs to QKV_PLANS
   GEGLU              N = I = 2048, K = 768: M = 2049 (32 x 17 = 544 blocks -> 160, last tile 129 rows), M = 300 and M = 1 (128)
   long K (MX only)   (129, 768, 2048), store and residual: 16 k-tiles = four scale dwords per lane
+
+The layer restatement at the end (mx_layer_weights / mx_stack / encoder_front) also serves the plain bf16 wide layer: with the quantiser
+off, bf16 weights and the fold switch it is what tests/wide_cases.py compares the truncated towers with.
 """
 import functools
 from typing import NamedTuple
@@ -234,51 +237,69 @@ def bf16_round(t):
     return t.to(torch.bfloat16).double()
 
 
-def mx_layer_weights(sd, prefix, layers, width, quant: bool, last_plain: bool):
+def mx_layer_weights(sd, prefix, layers, width, quant: bool, last_plain: bool, bf16_all: bool = False, fold: bool = True):
     """Per layer the four float64 weights run_layer_mx multiplies by: W' = to_qkv * pre_ln gain with the q rows times
     head_dim^-0.5 * log2(e), w12 * ffd_norm gain, out_proj, w3 - formed in fp32 as the weight pack forms them (blocks.py f8_mx), then
     quant: the values of their block-scaled images with row factors (tests/test_hip_fp8_blocks.py pins those images to the pack's);
     the last layer under `last_plain` (the encoder's, which runs off the MX path on its latent rows): rounded to bf16 instead - the
-    folded weights to_qkv_pn / w12_pn and the plain out_proj / w3.  quant False: W' itself (the oracle's stack, re-associated)."""
+    folded weights to_qkv_pn / w12_pn and the plain out_proj / w3.  quant False: W' itself (the oracle's stack, re-associated).
+    bf16_all (the plain bf16 wide layer, tests/wide_cases.py): every layer's weights rounded to bf16, no image anywhere.  fold False
+    (TTV_FOLD_NORMS=0): the gains stay out of the weights - to_qkv with the q factor on its q rows (to_qkv_qs) and w12 as they are,
+    the gains under "g_qkv" / "g_w12" for the stand-alone norms."""
     out = []
     for i in range(layers):
         ap, fp = f"{prefix}attn_layer.{i}.", f"{prefix}ffd_layer.{i}."
-        wqkv = sd[ap + "to_qkv.weight"].float() * sd[ap + "pre_ln.weight"].float()[None, :]
+        gq, gf = sd[ap + "pre_ln.weight"].float(), sd[fp + "norm.weight"].float()
+        wqkv = sd[ap + "to_qkv.weight"].float() * gq[None, :] if fold else sd[ap + "to_qkv.weight"].float().clone()
         wqkv[:width] *= FC.C_EXP
-        w = {"qkv": wqkv, "wo": sd[ap + "out_proj.weight"].float(), "w12": sd[fp + "w12.weight"].float() * sd[fp + "norm.weight"].float()[None, :],
+        w = {"qkv": wqkv, "wo": sd[ap + "out_proj.weight"].float(), "w12": sd[fp + "w12.weight"].float() * gf[None, :] if fold else sd[fp + "w12.weight"].float(),
              "w3": sd[fp + "w3.weight"].float()}
-        plain = last_plain and i == layers - 1
-        if quant and plain:
+        plain = bf16_all or (last_plain and i == layers - 1)
+        if (quant or bf16_all) and plain:
             w = {k: v.to(torch.bfloat16).double() for k, v in w.items()}
         elif quant:
             w = {k: F.mx_dequantize(*F.mx_quantize(v, True)) for k, v in w.items()}
         else:
             w = {k: v.double() for k, v in w.items()}
         w["plain"] = plain or not quant
+        if not fold:
+            w["g_qkv"], w["g_w12"] = gq.double(), gf.double()
         out.append(w)
     return out
 
 
-def mx_stack(x, weights, sd, prefix, layers, heads, cos, sin, cu, rnd):
+def mx_stack(x, weights, sd, prefix, layers, heads, cos, sin, cu, rnd, alpha=None):
     """run_layer_mx (csrc/ttv_api.hip) layer by layer in float64: every linear on mx(operand) x image, rstd applied AFTER the product,
     the q factor inside the image and the softmax 2^(q . k), layer 0 without post-norms.  `rnd` (identity or bf16_round) stands at each
-    point where the HIP path stores bf16; the ttv_api.hip line of the launch that stores is named."""
+    point where the HIP path stores bf16; the ttv_api.hip line of the launch that stores is named.
+    With plain weights (mx_layer_weights quant False or bf16_all) this is the plain bf16 wide layer of run_layers: prenorm_proj's
+    folded route (the statistic is that of x as it stands - under bf16_round the stored row, which is what k_row_rstd reads and what
+    k_rmsnorm's next_rstd is taken from) and keel_tail.  Weights without the fold ("g_qkv" / "g_w12" present): the stand-alone pre-norm
+    writes the normalised copy xn (one more store), then the plain weight.  alpha: what keel_alpha sees for layers >= 1 (the module's
+    2 x its full depth, whatever depth runs); None: 2 x layers."""
     from tests.blockwise import attention_forward_reference
     hq, hkv = heads
     d = x.shape[1]
     g = d // hq * hkv
+    a_keel = 2.0 * layers if alpha is None else float(alpha)
     for i, w in enumerate(weights):
         q8 = identity if w["plain"] else _mx
-        alpha = 1.0 if i == 0 else 2.0 * layers
-        rstd = torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + O.RMS_EPS)
-        u = (q8(x) @ w["qkv"].T) * rstd
+        alpha = 1.0 if i == 0 else a_keel
+        if "g_qkv" in w:
+            u = rnd(_norm64(x, w["g_qkv"])) @ w["qkv"].T                                 # prenorm_proj, no fold: ws.xn
+        else:
+            rstd = torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + O.RMS_EPS)
+            u = (q8(x) @ w["qkv"].T) * rstd
         qkv = rnd(torch.cat([rotary64(u[:, :d], cos, sin), u[:, d:2 * d], rotary64(u[:, 2 * d:2 * d + g], cos, sin), u[:, 2 * d + g:]], 1))  # :138 ws.qkv
         ao = rnd(attention_forward_reference(qkv, cu, hq, hkv, c_exp=FC.C_EXP)[1])       # :142 / :147 the gated output, before its quantisation
         x = rnd(alpha * x + q8(ao) @ w["wo"].T)                                          # :151 in place on ws.x
         if i > 0:
             x = rnd(_norm64(x, sd[f"{prefix}attn_post_ln.{i - 1}.weight"].double()))     # :153
-        rstd = torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + O.RMS_EPS)
-        u = (q8(x) @ w["w12"].T) * rstd
+        if "g_w12" in w:
+            u = rnd(_norm64(x, w["g_w12"])) @ w["w12"].T
+        else:
+            rstd = torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + O.RMS_EPS)
+            u = (q8(x) @ w["w12"].T) * rstd
         inner = u.shape[1] // 2
         h = rnd(torch.nn.functional.gelu(u[:, inner:]) * u[:, :inner])                   # :165 h, before its quantisation
         x = rnd(alpha * x + q8(h) @ w["w3"].T)                                           # :168 in place on ws.x
@@ -287,9 +308,9 @@ def mx_stack(x, weights, sd, prefix, layers, heads, cos, sin, cu, rnd):
     return x
 
 
-def mx_encoder_forward(videos, token_counts, sd, size="base", rnd=identity, quant=True, patch=FC.PATCH, prefix="encoder."):
-    """oracle encoder_forward with the stack replaced by mx_stack (the last layer on plain weights), float64.  Returns z [sum K, C]."""
-    width, layers, heads = O.model_dims(size)
+def encoder_front(videos, token_counts, sd, size="base", rnd=identity, patch=FC.PATCH, prefix="encoder."):
+    """The oracle's encoder up to the stack, float64: (x [L, width], cos, sin, cu_seqlens, latent-row mask)."""
+    width, _layers, heads = O.model_dims(size)
     grids, sizes, counts, cu, mask = O.batch_metadata([v.shape[1:] for v in videos], token_counts, patch)
     cos, sin = O.rope_table(grids, counts, width // heads[0])
     D = lambda name: sd[prefix + name].double()
@@ -299,6 +320,14 @@ def mx_encoder_forward(videos, token_counts, sd, size="base", rnd=identity, quan
     x = torch.zeros(mask.shape[0], width, dtype=torch.float64)
     x[mask] = rnd(_norm64(mt.expand(-1, width), D("ln_pre_t.weight")))            # :756
     x[~mask] = rnd(_norm64(p, D("ln_pre_p.weight")))                              # :753
+    return x, cos, sin, cu, mask
+
+
+def mx_encoder_forward(videos, token_counts, sd, size="base", rnd=identity, quant=True, patch=FC.PATCH, prefix="encoder."):
+    """oracle encoder_forward with the stack replaced by mx_stack (the last layer on plain weights), float64.  Returns z [sum K, C]."""
+    width, layers, heads = O.model_dims(size)
+    x, cos, sin, cu, mask = encoder_front(videos, token_counts, sd, size, rnd, patch, prefix)
+    D = lambda name: sd[prefix + name].double()
     w = mx_layer_weights(sd, prefix + "model_layers.", layers, width, quant, last_plain=True)
     x = mx_stack(x, w, sd, prefix + "model_layers.", layers, heads, cos, sin, cu, rnd)
     t = rnd(_norm64(x[mask], D("ln_post.weight")))                                # :761 k_enc_tail: ln_post output in dtype, z stays fp32

@@ -226,6 +226,9 @@ SYMBOLS = {
     "ttv_rmsnorm_mx": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, f32, vp, vp, vp, vp]),
     "ttv_attention_mxout": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "ttv_linear_fp8_mx_geglu_q": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    # the folded pre-norm of the wide bf16 layer launch by launch (tests only)
+    "ttv_row_rstd": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, f32, vp]),
+    "ttv_linear_rowscale": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ttv_patch_gather": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
                                    C.c_int, C.c_int, vp]),
     "ttv_patch_embed_norm": (C.c_int, [C.POINTER(vp), vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, f32,

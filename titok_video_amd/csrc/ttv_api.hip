@@ -686,6 +686,27 @@ int ttv_linear_fp8_mx_geglu_q(const void* xq, int ldx, const void* x_mx, const f
   return ttvk_gemm_fp8(EPI_GEGLU, a, x_row_scale, w_row_scale, (hipStream_t)stream, x_mx, w_mx);
 }
 
+// The folded pre-norm of the wide bf16 layer (prenorm_proj's fold_gen route), one launch at a time (tests only:
+// tests/test_hip_wide_layer.py): the light statistic pass, and a to_qkv / w12 / plain GEMM whose output rows take a row scale
+int ttv_row_rstd(const void* x, int dtype, int ldx, float* rstd, int rows, int width, float eps, void* stream) {
+  TTV_CHECK_ARG(rows >= 0 && (rows == 0 || (x && rstd)), "row_rstd: null buffer");
+  TTV_CHECK_ARG(ldx >= width, "row_rstd: leading dim smaller than the width");
+  return ttvk_row_rstd(x, dtype, ldx, rstd, rows, width, eps, (hipStream_t)stream);
+}
+
+int ttv_linear_rowscale(const void* x, int ldx, const void* w, int ldw, const float* row_scale, int epilogue, const float* rope_cs, int d_model,
+                        int gqa_dim, void* y, int ldy, int M, int N, int K, int dtype, void* stream) {
+  TTV_CHECK_ARG(M == 0 || (x && w && y), "linear_rowscale: null buffer");
+  TTV_CHECK_ARG(epilogue >= 0 && epilogue <= 2, "linear_rowscale: epilogue 0 (store), 1 (qkv + rotary) or 2 (GEGLU)");
+  GemmArgs a = gemm_args(dtype, x, ldx, w, ldw, M, N, K, y, ldy);
+  if (epilogue == 1) {
+    TTV_CHECK_ARG(rope_cs && N == 2 * d_model + 2 * gqa_dim && K == d_model, "linear_rowscale: qkv epilogue needs rope_cs, N = 2 d_model + 2 gqa_dim and K = d_model");
+    a = gemm_rope_qk(a, rope_cs, d_model, gqa_dim);
+  }
+  a.row_scale = row_scale;
+  return ttvk_gemm(epilogue == 0 ? EPI_STORE : epilogue == 1 ? EPI_QKV_ROPE : EPI_GEGLU, a, (hipStream_t)stream);
+}
+
 int ttv_patch_gather(const void* const* clips, const int32_t* clip_desc, int clip0, int n_clips, int patch_t, int patch_h, int patch_w,
                      int channels, void* patches, int ld, int dtype, int max_patches_per_clip, void* stream) {
   TTV_CHECK_ARG(n_clips == 0 || (clips && clip_desc && patches), "patch_gather: null buffer");
