@@ -172,6 +172,30 @@ def test_attention_table64_covers_every_row_slice_once():
     assert big.shape[0] == 576 and (big[:, 2:6] >= 0).all()
 
 
+def test_deal_xcd_is_stable_greedy_and_complete():
+    """plan._deal_xcd, the one dealing rule of every work table: heaviest first, equal weights in index order, each unit to the first
+    list of minimum load."""
+    from titok_video_amd.plan import _deal_xcd
+    # equal weights: index order over lists 0..7, then wrap
+    assert _deal_xcd([3] * 19) == [[x, x + 8, x + 16] if x < 3 else [x, x + 8] for x in range(8)]
+    # one heavy unit (index 5, weight 10) among light ones (weight 3): it opens list 0, which gets nothing more until every other list
+    # has reached its load - three rounds of lights over lists 1..7 bring those to 9 < 10, the fourth to 12, only then is list 0 minimal
+    weights = [3] * 5 + [10] + [3] * 30
+    lists = _deal_xcd(weights)
+    lights = [i for i in range(len(weights)) if i != 5]
+    assert lists[0][0] == 5
+    assert [l[:4] for l in lists[1:]] == [lights[x::7][:4] for x in range(7)]
+    assert lists[0][1:] == [lights[28]]                # the 29th light unit is the first to find list 0 (load 10) below the others (12)
+    load = [0] * 8
+    for i in sorted(range(len(weights)), key=lambda i: -weights[i]):      # replay: whenever list 0 takes a unit, no list is lighter
+        x = next(x for x in range(8) if i in lists[x])
+        assert load[x] == min(load) and x == load.index(min(load))
+        load[x] += weights[i]
+    # every index exactly once, whatever the weights (zero weights and ties included)
+    for weights in ([], [0, 0, 0], [7], [5, 1, 5, 0, 2, 5, 9, 9, 1, 1, 3, 5, 8, 2, 2, 4, 4, 0, 6, 5, 1]):
+        assert sorted(i for l in _deal_xcd(weights) for i in l) == list(range(len(weights)))
+
+
 def test_attention_backward_blocks_are_a_permutation_grouped_by_xcd():
     """plan._xcd_interleave: every (sequence, first row) block appears exactly once; for a uniform batch every sequence's blocks sit in
     one residue class of the table index modulo 8 (one XCD under round-robin dispatch); ragged batches keep the permutation property."""

@@ -15,8 +15,8 @@ from typing import List, Optional, Sequence
 import torch
 import torch.nn as nn
 
-from ... import _lib, switches
-from ...plan import BatchPlan, get_plan, host_ints
+from ... import _lib, streams, switches
+from ...plan import _PlanBase, get_plan, host_ints
 from .utils import LinearWeight, RMSNormWeight, geglu_inner_dim, get_model_dims
 
 
@@ -124,19 +124,11 @@ class _Tower(nn.Module):
 
     def _retire_pack(self) -> None:
         """The old pack's memory goes back to the allocator of the stream that built it: every other stream that read it (forwards
-        in flight in a ForwardPipeline) must be finished from that stream's point of view first."""
+        in flight in a ForwardPipeline) must be finished from that stream's point of view first, and from the point of view of the
+        stream that releases it when that is another one (a version change noticed inside a ForwardPipeline side stream)."""
         old, self._pack = self._pack, None
-        if old is not None and old.device.type == "cuda":
-            cur = torch.cuda.current_stream(old.device)
-            build = getattr(old, "build_stream", None)
-            for st in old.reader_streams.values():
-                if st != cur:
-                    cur.wait_stream(st)
-                # the freed buffers return to the BUILD stream's pool: when that is not the current stream (a version change noticed
-                # inside a ForwardPipeline side stream) it must see the readers as finished too, or it could hand the memory out
-                # again while another stream is still reading the old pack (ADVICE round 2)
-                if build is not None and build != cur and st != build:
-                    build.wait_stream(st)
+        if old is not None and old._owned is not None:
+            old._owned.retire(torch.cuda.current_stream(old.device))
 
     def _packed(self, dtype: torch.dtype, device) -> "_WeightPack":
         params = self._param_list()
@@ -157,7 +149,7 @@ class _Tower(nn.Module):
                               pix_channels=self.pix_channels, token_size=self.token_size, eps=1e-5,
                               alpha=float(self.model_layers.alpha))
 
-    def _workspace(self, dims: _lib.TowerDims, plan: BatchPlan, device) -> torch.Tensor:
+    def _workspace(self, dims: _lib.TowerDims, plan: _PlanBase, device) -> torch.Tensor:
         need = _lib.lib().ttv_tower_workspace_bytes(C.byref(dims), C.byref(plan.batch_for(self.heads[0], self.heads[1])))
         if need < 0:
             _lib.check(1, "ttv_tower_workspace_bytes")
@@ -171,7 +163,7 @@ class _Tower(nn.Module):
             self._ws[key] = ws
         return ws
 
-    def _plan(self, pixel_grids, token_counts, device) -> BatchPlan:
+    def _plan(self, pixel_grids, token_counts, device) -> _PlanBase:
         return get_plan(pixel_grids, token_counts, self.patch, device)
 
     # ---- training (autograd) support -------------------------------------------------------------
@@ -314,8 +306,7 @@ class _WeightPack:
         keep: List[torch.Tensor] = []
         self.dtype, self.device = dtype, torch.device(device)
         self.lin_tensors: List[torch.Tensor] = []     # compute-dtype linear weights in creation order (see transposed())
-        self.ready = None                              # event recorded on the building stream once every copy / pack kernel is queued
-        self.reader_streams = {}                       # stream id -> stream, of every stream a forward read this pack on
+        self._owned = None                             # streams.StreamOwned once every copy / pack kernel is queued (host packs: None)
 
         # fp32 towers in split-bf16 mode (tower.f32_split3, inference): the GEMM weights are handed over as split images
         # (ttv_split3_pack: per four k values hi0..3 | lo0..3 in bf16), same bytes and leading dimension as the fp32 matrix
@@ -491,21 +482,16 @@ class _WeightPack:
         self._t = None
         self._l0_const = {}                            # clip geometry -> the decoder's constant block (dec_l0_const)
         if self.device.type == "cuda":
-            self.build_stream = torch.cuda.current_stream(self.device)
-            self.ready = torch.cuda.Event()
-            self.ready.record(self.build_stream)
+            build = torch.cuda.current_stream(self.device)
+            self._owned = streams.StreamOwned(build, build.record_event())
 
     def use_on_current_stream(self) -> None:
         """Called by every forward: a stream other than the one that built the pack waits for the build (casts, folds, the
         ttv_mlp_pack kernel) before its kernels read the buffers, and is remembered as a reader (see _Tower._retire_pack)."""
-        if self.ready is None:
-            return
-        cur = torch.cuda.current_stream(self.device)
-        if cur != self.build_stream and cur.cuda_stream not in self.reader_streams:
-            cur.wait_event(self.ready)
-        self.reader_streams[cur.cuda_stream] = cur
+        if self._owned is not None:
+            self._owned.use(torch.cuda.current_stream(self.device))
 
-    def dec_l0_const(self, dims: "_lib.TowerDims", plan: BatchPlan) -> Optional["_lib.DecL0Const"]:
+    def dec_l0_const(self, dims: "_lib.TowerDims", plan: _PlanBase) -> Optional["_lib.DecL0Const"]:
         """The decoder's constant block for this plan's clip geometry (ttv_dec_l0_const: layer 0's q | gate | k | v of the patch rows,
         which enter the tower as ln_pre_p(mask_token) whatever the input, and the attention kernel's raw sums over those keys), or
         None where there is none: clips of several geometries, a latent or patch count that is no multiple of 128, a tower without the
@@ -521,7 +507,8 @@ class _WeightPack:
             need = _lib.lib().ttv_dec_l0_const_bytes(C.byref(dims), p) if (k > 0 and k % 128 == 0 and p % 128 == 0 and self.q_prescaled) else -1
             ent = None
             if need > 0:
-                with torch.cuda.stream(self.build_stream):       # behind `ready`: the folded weights are queued on this stream
+                build = self._owned.build_stream
+                with torch.cuda.stream(build):                   # behind the pack's build: the folded weights are queued on this stream
                     plan.use_on_current_stream()
                     block = torch.empty(int(need), dtype=torch.uint8, device=self.device)
                     iota = torch.arange(p, dtype=torch.int32, device=self.device)
@@ -531,17 +518,13 @@ class _WeightPack:
                                                            block.data_ptr(), block.numel(), C.byref(so), C.byref(fo), _lib.stream_ptr(self.device))
                     _lib.check(rc, "ttv_dec_l0_const_build")
                     out_of_window = int(block[fo.value:fo.value + 4].view(torch.int32).item()) != 0      # (waits for the builder)
-                    done = torch.cuda.Event()
-                    done.record(self.build_stream)
+                    done = streams.EventOnce(build, build.record_event())
                 state = None if out_of_window else block.data_ptr() + so.value
-                ent = dict(rows=block.data_ptr(), latent_rows=k, patch_rows=p, state=state, keep=(block, iota), done=done, seen=set(), structs={})
+                ent = dict(rows=block.data_ptr(), latent_rows=k, patch_rows=p, state=state, keep=(block, iota), done=done, structs={})
             self._l0_const[geo] = ent
         if ent is None:
             return None
-        cur = torch.cuda.current_stream(self.device)
-        if cur != self.build_stream and cur.cuda_stream not in ent["seen"]:
-            cur.wait_event(ent["done"])
-            ent["seen"].add(cur.cuda_stream)
+        ent["done"].wait_once(torch.cuda.current_stream(self.device))
         hit = ent["structs"].get(id(plan))       # (per plan: the work table's clip count is the plan's; the entry keeps the plan alive)
         if hit is None:
             table = plan.attention_table_l0(int(dims.q_heads), int(dims.kv_heads))

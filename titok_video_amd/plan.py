@@ -13,12 +13,12 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import math
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib, switches
+from . import _lib, streams, switches
 
 QBLOCK = 128  # query rows per attention workgroup (csrc/ttv_attn.hip QB)
 ATTN_SLOTS = 1024  # table size below which the last third of every sequence's blocks become half items (set when the kernel held 4 blocks per CU; it holds 3 = 768 since round 2 - the rule was re-measured, not re-derived: see attention_table)
@@ -127,6 +127,18 @@ def _clip_rope_ids(grid: Tuple[int, ...], k: int, n_ids: int) -> np.ndarray:
     return ids
 
 
+def _deal_xcd(weights) -> List[List[int]]:
+    """Greedy deal of weighted units over the 8 XCD lists (`deal` of csrc/ttv_plan_host.cpp): units in descending order of their
+    integer weight (stable: equal weights keep index order), each to the first list of minimum load.  Returns the unit indices of
+    every list in the order they were dealt."""
+    lists, load = [[] for _ in range(8)], [0] * 8
+    for i in sorted(range(len(weights)), key=weights.__getitem__, reverse=True):
+        x = min(range(8), key=load.__getitem__)
+        lists[x].append(i)
+        load[x] += weights[i]
+    return lists
+
+
 def _xcd_interleave(units) -> np.ndarray:
     """(sequence, first row) entries of the attention backward's 64-row blocks, ordered for the 8 XCDs: block b of a launch runs on XCD
     b % 8 under round-robin dispatch (a speed assumption only), and every block of a sequence streams that sequence's Q / dO (key
@@ -136,12 +148,7 @@ def _xcd_interleave(units) -> np.ndarray:
     short lists run out the rest follows in list order (no padding entries: the kernels take the table as it is)."""
     if not switches.flag("TTV_BWD_XCD", True):       # A/B: sequence-major order
         return np.asarray([e for u in units for e in u], dtype=np.int32).reshape(-1, 2)
-    order = sorted(range(len(units)), key=lambda i: len(units[i]), reverse=True)
-    lists, weight = [[] for _ in range(8)], [0] * 8
-    for i in order:
-        x = min(range(8), key=lambda j: weight[j])
-        lists[x].extend(units[i])
-        weight[x] += len(units[i])
+    lists = [[e for i in dealt for e in units[i]] for dealt in _deal_xcd([len(u) for u in units])]
     depth = min(len(l) for l in lists)
     out = [lists[x][k] for k in range(depth) for x in range(8)]
     for l in lists:
@@ -149,8 +156,57 @@ def _xcd_interleave(units) -> np.ndarray:
     return np.asarray(out, dtype=np.int32).reshape(-1, 2)
 
 
-class BatchPlan:
-    """Device tables + the ttv_batch struct for one (clip shapes, token counts) combination."""
+PAD4 = (-1, -1, -1, -1)     # padding entry of the 4-wide attention work tables: sequence -1, the kernel returns at once
+
+
+def _xcd_table(lists, pad_row, device) -> torch.Tensor:
+    """Eight per-list entry sequences -> the flat int32 [n, len(pad_row)] table on `device`: entry i comes from list i % 8, shorter
+    lists are padded with `pad_row`, and only the padding entries behind the last real one are dropped (interior padding keeps the
+    i % 8 alignment).  Table::write of the port."""
+    depth = max(len(l) for l in lists)
+    table = np.empty((depth, 8, len(pad_row)), dtype=np.int32)
+    table[:] = pad_row
+    for x, l in enumerate(lists):
+        if l:
+            table[: len(l), x, :] = np.asarray(l, dtype=np.int32)
+    last = max((len(l) - 1) * 8 + x + 1 for x, l in enumerate(lists) if l)
+    return _upload(np.ascontiguousarray(table.reshape(-1, len(pad_row))[:last]), device)
+
+
+class _Unit(NamedTuple):
+    """One (sequence, kv-head) unit of a 4-wide attention work table, as the port's Unit: full items of the query blocks [f0, f1) first;
+    behind ALL first parts of its XCD list the blocks [s0, s1), as full items or (second_half) as half items: two per block and q-head,
+    the second only where its 64 rows begin inside the sequence."""
+    b: int
+    kvh: int
+    length: int
+    f0: int
+    f1: int
+    s0: int
+    s1: int
+    second_half: bool
+
+
+def _attn_units_table(units: List[_Unit], rep: int, device) -> torch.Tensor:
+    """int32 [n,4] attention work table (sequence, first query row, q-head, mode) of these units on `device`.  A unit keeps one XCD list
+    for both its parts and weighs 2 * full + half items (Table::finish of the port: the order of full + half / 2, in integers)."""
+    first, second = [], []
+    for u in units:
+        heads = range(u.kvh * rep, u.kvh * rep + rep)
+        first.append([(u.b, qb * QBLOCK, hd, 0) for qb in range(u.f0, u.f1) for hd in heads])
+        if u.second_half:
+            second.append([(u.b, q0, hd, 1) for qb in range(u.s0, u.s1) for hd in heads for q0 in (qb * QBLOCK, qb * QBLOCK + 64) if q0 < u.length])
+        else:
+            second.append([(u.b, qb * QBLOCK, hd, 0) for qb in range(u.s0, u.s1) for hd in heads])
+    dealt = _deal_xcd([2 * len(f) + (1 if u.second_half else 2) * len(h) for u, f, h in zip(units, first, second)])
+    return _xcd_table([[e for part in (first, second) for i in l for e in part[i]] for l in dealt], PAD4, device)
+
+
+class _PlanBase:
+    """What the two builders of a plan share: the normalised arguments and the patch grids, the stream ownership of the device tables
+    (streams.py), and the views into `int_tables`.  A builder checks its arguments in `_check_arguments`, then fills `int_tables`,
+    `_offs` (word offsets of cu_seqlens, latent_rows, patch_rows, clip_desc, blocks64, row_seq, rope_ids), `rope_cs`, `_rope_by_id`
+    and, on a GPU, `_owned`."""
 
     def __init__(self, pixel_grids: Sequence[Sequence[int]], token_counts: Sequence[int], patch: Sequence[int],
                  device: torch.device, head_dim: int = 64):
@@ -160,18 +216,78 @@ class BatchPlan:
         self.patch = tuple(int(p) for p in patch)
         self.pixel_grids = [tuple(int(v) for v in g) for g in pixel_grids]
         self.token_counts = [int(k) for k in token_counts]
+        self._check_arguments()
+        self.grids = [tuple(v // p for v, p in zip(pg, self.patch)) for pg in self.pixel_grids]
+        self.grid_sizes = [math.prod(g) for g in self.grids]
+        self._attn = {}
+        self._owned: Optional[streams.StreamOwned] = None       # host plans own no stream
+        self._rope_by_id = (None, None)                         # device pointers (ttv_batch.rope_ids, rope_base), or None twice
+
+    def _check_arguments(self) -> None:
+        """ValueError, in the builder's own words, unless every clip shape is a positive multiple of the patch and has a count >= 0."""
+        raise NotImplementedError
+
+    def use_on_current_stream(self) -> None:
+        """Stream safety of the cached plan (see ForwardPipeline): wait for the build on foreign streams, remember the readers."""
+        if self._owned is not None:
+            self._owned.use(torch.cuda.current_stream(self.device))
+
+    def retire(self) -> None:
+        """Before the tables are released (cache eviction): the releasing stream and the build stream wait for every stream that read them."""
+        if self._owned is not None:
+            self._owned.retire(torch.cuda.current_stream(self.device))
+
+    def uniform_geometry(self) -> Optional[tuple]:
+        """(patch grid, latent count, rotary id table size) when every clip of the batch has the same patch grid and latent count, else
+        None: what the rows of a decoder's constant block (ttv_dec_l0_const) depend on besides the weights."""
+        g, k = self.grids[0], self.token_counts[0]
+        if any(gb != g for gb in self.grids) or any(kb != k for kb in self.token_counts):
+            return None
+        return (g, k, self.n_rope_ids)
+
+    def clip0_patch_rope(self) -> Tuple[int, Optional[int], Optional[int]]:
+        """Device pointers to the rotary tables of the FIRST clip's patch rows: (rope_cs rows, rope_ids rows or None, rope_base or None)."""
+        k = self.token_counts[0]
+        ids, base = self._rope_by_id
+        return (self.rope_cs.data_ptr() + 4 * self.rope_cs.shape[1] * k, ids + 8 * k if ids else None, base if ids else None)
+
+    # views used by tests that call single ops
+    def table(self, i: int, n: int) -> torch.Tensor:
+        return self.int_tables[self._offs[i]: self._offs[i] + n]
+
+    @property
+    def cu_dev(self):
+        return self.table(0, len(self.cu_seqlens))
+
+    @property
+    def latent_rows_dev(self):
+        return self.table(1, self.sum_tokens)
+
+    @property
+    def patch_rows_dev(self):
+        return self.table(2, self.sum_patches)
+
+    @property
+    def clip_desc_dev(self):
+        return self.table(3, 8 * len(self.grids))
+
+
+class BatchPlan(_PlanBase):
+    """Device tables + the ttv_batch struct for one (clip shapes, token counts) combination."""
+
+    def _check_arguments(self) -> None:
         if len(self.pixel_grids) != len(self.token_counts) or not self.pixel_grids:
             raise ValueError("need one token count per clip and at least one clip")
-        grids, sizes = [], []
         for pg in self.pixel_grids:
             if len(pg) != len(self.patch) or any(v <= 0 or v % p for v, p in zip(pg, self.patch)):
                 raise ValueError(f"clip shape {pg} is not a positive multiple of patch size {self.patch}")
-            g = tuple(v // p for v, p in zip(pg, self.patch))
-            grids.append(g)
-            sizes.append(math.prod(g))
         if any(k < 0 for k in self.token_counts):
             raise ValueError("token counts must be >= 0")
-        self.grids, self.grid_sizes = grids, sizes
+
+    def __init__(self, pixel_grids: Sequence[Sequence[int]], token_counts: Sequence[int], patch: Sequence[int],
+                 device: torch.device, head_dim: int = 64):
+        super().__init__(pixel_grids, token_counts, patch, device, head_dim)
+        grids, sizes = self.grids, self.grid_sizes
         B = len(grids)
         cu = [0]
         for k, p in zip(self.token_counts, sizes):
@@ -223,9 +339,8 @@ class BatchPlan:
                                                  _lib.stream_ptr(self.device))
             _lib.check(rc, "ttv_rope_table_build")
             # the table is written by a kernel on the building stream: other streams wait for this event before their first use
-            self.build_stream = torch.cuda.current_stream(self.device)
-            self.ready = torch.cuda.Event()
-            self.ready.record(self.build_stream)
+            build = torch.cuda.current_stream(self.device)
+            self._owned = streams.StreamOwned(build, build.record_event())
         else:   # host tensors (CPU-side tests of the plan): same table, gathered with numpy
             rope = np.concatenate([_rope_clip_table(g, k, head_dim) for g, k in zip(grids, self.token_counts)], axis=0)
             self.rope_cs = torch.from_numpy(rope).to(self.device)
@@ -242,33 +357,17 @@ class BatchPlan:
         # from the cached base table instead of streaming the 256-byte fp32 row of rope_cs (TTV_ROPE_IDS=0: the table path, A/B)
         if self.device.type == "cuda" and len(self.patch) == 3 and switches.flag("TTV_ROPE_IDS", True):
             self._rope_base_cs = _rope_base_interleaved(head_dim, len(self.patch), n_ids, str(self.device))
-            self._base_fields.update(rope_ids=base + 4 * offs[6], rope_base=self._rope_base_cs.data_ptr())
+            self._rope_by_id = (base + 4 * offs[6], self._rope_base_cs.data_ptr())
+            self._base_fields.update(rope_ids=self._rope_by_id[0], rope_base=self._rope_by_id[1])
         self._offs = offs
-        self._attn = {}
         self._attn_all_full = {}
         self._batch_structs = {}
-        self.reader_streams = {}
 
-    def use_on_current_stream(self) -> None:
-        """Stream safety of the cached plan (see ForwardPipeline): wait for the build on foreign streams, remember the readers."""
-        if self.device.type != "cuda":
-            return
-        cur = torch.cuda.current_stream(self.device)
-        if cur != self.build_stream and cur.cuda_stream not in self.reader_streams:
-            cur.wait_event(self.ready)
-        self.reader_streams[cur.cuda_stream] = cur
-
-    def retire(self) -> None:
-        """Before the tables are released (cache eviction): the releasing stream waits for every stream that read them."""
-        if self.device.type != "cuda":
-            return
-        cur = torch.cuda.current_stream(self.device)
-        build = getattr(self, "build_stream", None)
-        for st in self.reader_streams.values():
-            if st != cur:
-                cur.wait_stream(st)
-            if build is not None and build != cur and st != build:      # the tables return to the build stream's pool (see _Tower._retire_pack)
-                build.wait_stream(st)
+    def _sequences(self):
+        """(b, length, query blocks, query blocks that hold latent rows only) of every sequence."""
+        for b, k in enumerate(self.token_counts):
+            s = self.cu_seqlens[b + 1] - self.cu_seqlens[b]
+            yield b, s, -(-s // QBLOCK), k // QBLOCK
 
     def attention_table(self, q_heads: int, kv_heads: int, split: Optional[bool] = None) -> torch.Tensor:
         """int32 [n,4] attention work table (sequence, first query row, q-head, mode) for this batch, XCD-aware.
@@ -293,41 +392,14 @@ class BatchPlan:
         key = (int(q_heads), int(kv_heads), split)
         t = self._attn.get(key)
         if t is None:
-            rep = q_heads // kv_heads
-            n_items = sum(-(-(self.cu_seqlens[b + 1] - self.cu_seqlens[b]) // QBLOCK) for b in range(len(self.grids))) * q_heads
-            small_grid = n_items < ATTN_SLOTS
-            units_full, units_half = [], []
-            for b in range(len(self.grids)):
-                s = self.cu_seqlens[b + 1] - self.cu_seqlens[b]
-                nq = -(-s // QBLOCK)
-                tail_div = 3 if small_grid else switches.integer("TTV_ATTN_TAIL_DIV", 0)
+            n_items = sum(nq for _b, _s, nq, _lat in self._sequences()) * q_heads
+            tail_div = 3 if n_items < ATTN_SLOTS else switches.integer("TTV_ATTN_TAIL_DIV", 0)
+            units = []
+            for b, s, nq, _lat in self._sequences():
                 first_half = 0 if split else (nq if (split is False or tail_div <= 0) else nq - nq // tail_div)
-                for kvh in range(kv_heads):
-                    heads = [kvh * rep + r for r in range(rep)]
-                    units_full.append([(b, qb * QBLOCK, hd, 0) for qb in range(first_half) for hd in heads])
-                    units_half.append([(b, q0, hd, 1) for qb in range(first_half, nq) for hd in heads
-                                       for q0 in (qb * QBLOCK, qb * QBLOCK + 64) if q0 < s])
-            # a (sequence, kv-head) unit keeps one XCD list for its full and its half items
-            order = sorted(range(len(units_full)), key=lambda i: len(units_full[i]) + len(units_half[i]) / 2, reverse=True)
-            lists, weight, halves = [[] for _ in range(8)], [0.0] * 8, [[] for _ in range(8)]
-            for i in order:
-                x = min(range(8), key=lambda j: weight[j])
-                lists[x].extend(units_full[i])
-                halves[x].extend(units_half[i])
-                weight[x] += len(units_full[i]) + len(units_half[i]) / 2
-            for x in range(8):
-                lists[x].extend(halves[x])
-            depth = max(len(l) for l in lists)
-            table = np.full((depth, 8, 4), -1, dtype=np.int32)
-            for x, l in enumerate(lists):
-                if l:
-                    table[: len(l), x, :] = np.asarray(l, dtype=np.int32)
-            # drop trailing all-padding rows only (interior padding keeps the i % 8 alignment)
-            flat = table.reshape(-1, 4)
-            last = int(np.max(np.nonzero(flat[:, 0] >= 0)[0])) + 1
-            t = _upload(np.ascontiguousarray(flat[:last]), self.device)
-            self._attn[key] = t
-            self._attn_all_full[t.data_ptr()] = not bool((flat[:last, 3] > 0).any())
+                units += [_Unit(b, kvh, s, 0, first_half, first_half, nq, True) for kvh in range(kv_heads)]
+            t = self._attn[key] = _attn_units_table(units, q_heads // kv_heads, self.device)
+            self._attn_all_full[t.data_ptr()] = all(u.s0 == u.s1 for u in units)      # no half item
         return t
 
     def attention_table_latent(self, q_heads: int, kv_heads: int) -> torch.Tensor:
@@ -338,27 +410,9 @@ class BatchPlan:
         key = ("latent", int(q_heads), int(kv_heads))
         t = self._attn.get(key)
         if t is None:
-            rep = q_heads // kv_heads
-            units = []
-            for b in range(len(self.grids)):
-                nq = -(-int(self.token_counts[b]) // QBLOCK)
-                for kvh in range(kv_heads):
-                    units.append([(b, qb * QBLOCK, kvh * rep + r, 0) for qb in range(nq) for r in range(rep)])
-            order = sorted(range(len(units)), key=lambda i: len(units[i]), reverse=True)
-            lists, weight = [[] for _ in range(8)], [0] * 8
-            for i in order:
-                x = min(range(8), key=lambda j: weight[j])
-                lists[x].extend(units[i])
-                weight[x] += len(units[i])
-            depth = max(len(l) for l in lists)
-            table = np.full((depth, 8, 4), -1, dtype=np.int32)
-            for x, l in enumerate(lists):
-                if l:
-                    table[: len(l), x, :] = np.asarray(l, dtype=np.int32)
-            flat = table.reshape(-1, 4)
-            last = int(np.max(np.nonzero(flat[:, 0] >= 0)[0])) + 1
-            t = _upload(np.ascontiguousarray(flat[:last]), self.device)
-            self._attn[key] = t
+            # blocks [0, ceil(K_b / 128)) hold latent rows
+            units = [_Unit(b, kvh, s, 0, -(-self.token_counts[b] // QBLOCK), 0, 0, False) for b, s, _nq, _lat in self._sequences() for kvh in range(kv_heads)]
+            t = self._attn[key] = _attn_units_table(units, q_heads // kv_heads, self.device)
         return t
 
     def attention_table_patch(self, q_heads: int, kv_heads: int) -> Optional[torch.Tensor]:
@@ -368,32 +422,10 @@ class BatchPlan:
         (`ttv_batch.qblocks_patch`): at the benchmark shape 1024 entries instead of 1152.  Same XCD interleaving as the full table."""
         key = ("patch", int(q_heads), int(kv_heads))
         if key not in self._attn:
-            rep = q_heads // kv_heads
-            units, dropped = [], 0
-            for b in range(len(self.grids)):
-                s = self.cu_seqlens[b + 1] - self.cu_seqlens[b]
-                nq = -(-s // QBLOCK)
-                first = int(self.token_counts[b]) // QBLOCK          # blocks [0, first) hold latent rows only
-                dropped += first
-                for kvh in range(kv_heads):
-                    units.append([(b, qb * QBLOCK, kvh * rep + r, 0) for qb in range(first, nq) for r in range(rep)])
-            t = None
-            if dropped and any(units):
-                order = sorted(range(len(units)), key=lambda i: len(units[i]), reverse=True)
-                lists, weight = [[] for _ in range(8)], [0] * 8
-                for i in order:
-                    x = min(range(8), key=lambda j: weight[j])
-                    lists[x].extend(units[i])
-                    weight[x] += len(units[i])
-                depth = max(len(l) for l in lists)
-                table = np.full((depth, 8, 4), -1, dtype=np.int32)
-                for x, l in enumerate(lists):
-                    if l:
-                        table[: len(l), x, :] = np.asarray(l, dtype=np.int32)
-                flat = table.reshape(-1, 4)
-                last = int(np.max(np.nonzero(flat[:, 0] >= 0)[0])) + 1
-                t = _upload(np.ascontiguousarray(flat[:last]), self.device)
-            self._attn[key] = t
+            # blocks [0, lat) hold latent rows only; a table only when a block was dropped and one remains
+            units = [_Unit(b, kvh, s, lat, nq, 0, 0, False) for b, s, nq, lat in self._sequences() for kvh in range(kv_heads)]
+            dropped, remains = any(u.f0 > 0 for u in units), any(u.f0 < u.f1 for u in units)
+            self._attn[key] = _attn_units_table(units, q_heads // kv_heads, self.device) if dropped and remains else None
         return self._attn[key]
 
     def attention_table_l0(self, q_heads: int, kv_heads: int) -> torch.Tensor:
@@ -403,31 +435,8 @@ class BatchPlan:
         key = ("l0", int(q_heads), int(kv_heads))
         t = self._attn.get(key)
         if t is None:
-            rep = q_heads // kv_heads
-            lat, pat = [], []
-            for b in range(len(self.grids)):
-                s = self.cu_seqlens[b + 1] - self.cu_seqlens[b]
-                nq, first = -(-s // QBLOCK), int(self.token_counts[b]) // QBLOCK
-                for kvh in range(kv_heads):
-                    lat.append([(b, qb * QBLOCK, kvh * rep + r, 0) for qb in range(first) for r in range(rep)])
-                    pat.append([(b, qb * QBLOCK, kvh * rep + r, 0) for qb in range(first, nq) for r in range(rep)])
-            order = sorted(range(len(lat)), key=lambda i: len(lat[i]) + len(pat[i]), reverse=True)
-            first_l, then_l, weight = [[] for _ in range(8)], [[] for _ in range(8)], [0] * 8
-            for i in order:
-                x = min(range(8), key=lambda j: weight[j])
-                first_l[x].extend(lat[i])
-                then_l[x].extend(pat[i])
-                weight[x] += len(lat[i]) + len(pat[i])
-            lists = [a + b for a, b in zip(first_l, then_l)]
-            depth = max(len(l) for l in lists)
-            table = np.full((depth, 8, 4), -1, dtype=np.int32)
-            for x, l in enumerate(lists):
-                if l:
-                    table[: len(l), x, :] = np.asarray(l, dtype=np.int32)
-            flat = table.reshape(-1, 4)
-            last = int(np.max(np.nonzero(flat[:, 0] >= 0)[0])) + 1
-            t = _upload(np.ascontiguousarray(flat[:last]), self.device)
-            self._attn[key] = t
+            units = [_Unit(b, kvh, s, 0, lat, lat, nq, False) for b, s, nq, lat in self._sequences() for kvh in range(kv_heads)]
+            t = self._attn[key] = _attn_units_table(units, q_heads // kv_heads, self.device)
         return t
 
     def attention_table64(self, q_heads: int, kv_heads: int) -> torch.Tensor:
@@ -444,29 +453,14 @@ class BatchPlan:
         if t is None:
             rep = q_heads // kv_heads
             units = []
-            for b in range(len(self.grids)):
-                s = self.cu_seqlens[b + 1] - self.cu_seqlens[b]
+            for b, s, _nq, _lat in self._sequences():
                 n64 = -(-s // 64)
                 for kvh in range(kv_heads):
                     items = [(kvh * rep + r) | (q << 8) for q in range(n64) for r in range(rep)]
                     items += [-1] * (-len(items) % 4)
                     units.append([(b, kvh, *items[i:i + 4], self.cu_seqlens[b], s) for i in range(0, len(items), 4)])
-            order = sorted(range(len(units)), key=lambda i: len(units[i]), reverse=True)
-            lists, weight = [[] for _ in range(8)], [0] * 8
-            for i in order:
-                x = min(range(8), key=lambda j: weight[j])
-                lists[x].extend(units[i])
-                weight[x] += len(units[i])
-            depth = max(len(l) for l in lists)
-            table = np.zeros((depth, 8, 8), dtype=np.int32)
-            table[:, :, 0] = -1
-            for x, l in enumerate(lists):
-                if l:
-                    table[: len(l), x, :] = np.asarray(l, dtype=np.int32)
-            flat = table.reshape(-1, 8)
-            last = int(np.max(np.nonzero(flat[:, 0] >= 0)[0])) + 1
-            t = _upload(np.ascontiguousarray(flat[:last]), self.device)
-            self._attn[key] = t
+            dealt = _deal_xcd([len(u) for u in units])
+            t = self._attn[key] = _xcd_table([[e for i in l for e in units[i]] for l in dealt], (-1, 0, 0, 0, 0, 0, 0, 0), self.device)
         return t
 
     def batch_for(self, q_heads: int, kv_heads: int) -> "_lib.Batch":
@@ -500,41 +494,6 @@ class BatchPlan:
                           qblocks_patch=tp.data_ptr() if tp is not None else None, n_qblocks_patch=int(tp.shape[0]) if tp is not None else 0,
                           **self._base_fields)
         return out
-
-    def uniform_geometry(self) -> Optional[tuple]:
-        """(patch grid, latent count, rotary id table size) when every clip of the batch has the same patch grid and latent count, else
-        None: what the rows of a decoder's constant block (ttv_dec_l0_const) depend on besides the weights."""
-        g, k = self.grids[0], self.token_counts[0]
-        if any(gb != g for gb in self.grids) or any(kb != k for kb in self.token_counts):
-            return None
-        return (g, k, self.n_rope_ids)
-
-    def clip0_patch_rope(self) -> Tuple[int, Optional[int], Optional[int]]:
-        """Device pointers to the rotary tables of the FIRST clip's patch rows: (rope_cs rows, rope_ids rows or None, rope_base or None)."""
-        k = self.token_counts[0]
-        ids = self._base_fields.get("rope_ids")
-        return (self.rope_cs.data_ptr() + 4 * self.rope_cs.shape[1] * k, ids + 8 * k if ids else None,
-                self._base_fields.get("rope_base") if ids else None)
-
-    # views used by tests that call single ops
-    def table(self, i: int, n: int) -> torch.Tensor:
-        return self.int_tables[self._offs[i]: self._offs[i] + n]
-
-    @property
-    def cu_dev(self):
-        return self.table(0, len(self.cu_seqlens))
-
-    @property
-    def latent_rows_dev(self):
-        return self.table(1, self.sum_tokens)
-
-    @property
-    def patch_rows_dev(self):
-        return self.table(2, self.sum_patches)
-
-    @property
-    def clip_desc_dev(self):
-        return self.table(3, 8 * len(self.grids))
 
 
 # ---- the same plan built by the library (ttv_plan_* of include/titok_hip.h): TTV_NATIVE_PLAN=1 -------------------------------------------
@@ -621,7 +580,7 @@ def _stage_ring(device) -> _StageRing:
     return ring
 
 
-class NativeBatchPlan:
+class NativeBatchPlan(_PlanBase):
     """BatchPlan's device tables and ttv_batch structs, built by the library: the host writes cu_seqlens, the clip descriptors, the
     backward blocks and the attention work tables in C++ (csrc/ttv_plan_host.cpp) into pinned staging, the copies are queued on the
     building stream without waiting for them, and the per-row tables (latent_rows, patch_rows, row_seq, rope_ids) are written on the
@@ -629,27 +588,24 @@ class NativeBatchPlan:
     (tests/test_native_plan_cpu.py, tests/test_hip_native_plan.py); GPU only, three patch axes.  items64 and the paired flag (opt-in
     kernels, TTV_ATTN64 / TTV_ATTN_PAIRED) are not built: the struct leaves them NULL / 0."""
 
-    def __init__(self, pixel_grids: Sequence[Sequence[int]], token_counts: Sequence[int], patch: Sequence[int],
-                 device: torch.device, head_dim: int = 64):
-        if head_dim != 64:
-            raise ValueError("head_dim is fixed at 64 (reference model/base/utils.py:8)")
-        self.device = torch.device(device)
-        self.patch = tuple(int(p) for p in patch)
+    def _check_arguments(self) -> None:
+        """The library's checks and message (ttv_plan_rows_sizes); its sizes and the ctypes arrays of the arguments are kept."""
         if self.device.type != "cuda" or len(self.patch) != 3:
             raise ValueError("NativeBatchPlan: GPU plans with three patch axes only (BatchPlan builds the others)")
-        self.pixel_grids = [tuple(int(v) for v in g) for g in pixel_grids]
-        self.token_counts = [int(k) for k in token_counts]
         if len(self.pixel_grids) != len(self.token_counts) or not self.pixel_grids or any(len(g) != 3 for g in self.pixel_grids):
             raise ValueError("need one token count per clip, at least one clip, and three dimensions per clip")
         lib = _lib.lib()
-        B = len(self.pixel_grids)
         self._counts = _i32s(self.token_counts)
-        dims, pt = _i32s([v for g in self.pixel_grids for v in g]), _i32s(self.patch)
-        sz = self._sizes = _lib.PlanSizes()
-        if lib.ttv_plan_rows_sizes(dims, self._counts, B, pt, C.byref(sz)) != 0:
+        self._dims, self._pt = _i32s([v for g in self.pixel_grids for v in g]), _i32s(self.patch)
+        self._sizes = _lib.PlanSizes()
+        if lib.ttv_plan_rows_sizes(self._dims, self._counts, len(self.pixel_grids), self._pt, C.byref(self._sizes)) != 0:
             raise ValueError(lib.ttv_error_string().decode("utf-8", "replace"))
-        self.grids = [tuple(v // p for v, p in zip(g, self.patch)) for g in self.pixel_grids]
-        self.grid_sizes = [g[0] * g[1] * g[2] for g in self.grids]
+
+    def __init__(self, pixel_grids: Sequence[Sequence[int]], token_counts: Sequence[int], patch: Sequence[int],
+                 device: torch.device, head_dim: int = 64):
+        super().__init__(pixel_grids, token_counts, patch, device, head_dim)
+        lib, sz, dims, pt = _lib.lib(), self._sizes, self._dims, self._pt
+        B = len(self.pixel_grids)
         self.total_rows, self.sum_tokens, self.sum_patches = int(sz.total_rows), int(sz.sum_tokens), int(sz.sum_patches)
         self.max_seqlen, self.n_rope_ids, self.n_blocks64 = int(sz.max_seqlen), int(sz.n_rope_ids), int(sz.n_blocks64)
         self._ring = _stage_ring(self.device)
@@ -664,28 +620,17 @@ class NativeBatchPlan:
         # rotary factors by position id beside the table, as in BatchPlan (TTV_ROPE_IDS=0: the table path alone, A/B)
         self._rope_base_cs = _rope_base_interleaved(head_dim, 3, self.n_rope_ids, str(self.device)) if switches.flag("TTV_ROPE_IDS", True) else None
         self._base = _lib.Batch()
-        self.build_stream = torch.cuda.current_stream(self.device)
+        build = torch.cuda.current_stream(self.device)
         rc = lib.ttv_plan_rows_build(C.byref(sz), slot["ptr"], self.int_tables.data_ptr(), bc.data_ptr(), bs.data_ptr(), bc.shape[1],
-                                     self.rope_cs.data_ptr(), _lib.ptr(self._rope_base_cs), C.byref(self._base), self.build_stream.cuda_stream)
+                                     self.rope_cs.data_ptr(), _lib.ptr(self._rope_base_cs), C.byref(self._base), build.cuda_stream)
         # the tables are written by a copy and two kernels on the building stream: other streams wait for this event before their
         # first use, and the staging slot is rewritten only once it has completed
-        self.ready = torch.cuda.Event()
-        self.ready.record(self.build_stream)
-        slot["event"] = self.ready
+        self._owned = streams.StreamOwned(build, build.record_event())
+        slot["event"] = self._owned.ready
         _lib.check(rc, "ttv_plan_rows_build")
+        self._rope_by_id = (self._base.rope_ids, self._base.rope_base)
         self._offs = [int(o) for o in (sz.off_cu_seqlens, sz.off_latent_rows, sz.off_patch_rows, sz.off_clip_desc, sz.off_blocks64,
                                        sz.off_row_seq, sz.off_rope_ids)]
-        self._attn = {}
-        self.reader_streams = {}
-
-    use_on_current_stream = BatchPlan.use_on_current_stream
-    retire = BatchPlan.retire
-    uniform_geometry = BatchPlan.uniform_geometry
-    table = BatchPlan.table
-    cu_dev = BatchPlan.cu_dev
-    latent_rows_dev = BatchPlan.latent_rows_dev
-    patch_rows_dev = BatchPlan.patch_rows_dev
-    clip_desc_dev = BatchPlan.clip_desc_dev
 
     def _tables(self, q_heads: int, kv_heads: int, split: Optional[bool], tail_div: int) -> dict:
         """The four attention work tables of these head counts on the device (one buffer), with the ttv_batch that points at them.
@@ -700,7 +645,7 @@ class NativeBatchPlan:
             _lib.check(lib.ttv_plan_attn_sizes(*args, C.byref(az)), "ttv_plan_attn_sizes")
             slot = self._ring.take(int(az.words))
             _lib.check(lib.ttv_plan_attn_fill(*args, slot["ptr"], slot["words"]), "ttv_plan_attn_fill")
-            build = self.build_stream
+            build = self._owned.build_stream
             if cur == build:
                 dev = torch.empty(int(az.words), dtype=torch.int32, device=self.device)
             else:
@@ -708,14 +653,10 @@ class NativeBatchPlan:
                     dev = torch.empty(int(az.words), dtype=torch.int32, device=self.device)
             batch = _lib.Batch.from_buffer_copy(self._base)
             rc = lib.ttv_plan_attn_set(C.byref(az), slot["ptr"], dev.data_ptr(), C.byref(batch), build.cuda_stream)
-            done = torch.cuda.Event()
-            done.record(build)
-            slot["event"] = done
+            slot["event"] = build.record_event()
             _lib.check(rc, "ttv_plan_attn_set")
-            ent = self._attn[key] = dict(dev=dev, sizes=az, batch=batch, done=done, seen={build.cuda_stream})
-        if cur.cuda_stream not in ent["seen"]:
-            cur.wait_event(ent["done"])
-            ent["seen"].add(cur.cuda_stream)
+            ent = self._attn[key] = dict(dev=dev, sizes=az, batch=batch, done=streams.EventOnce(build, slot["event"]))
+        ent["done"].wait_once(cur)
         return ent
 
     def _switched(self, q_heads: int, kv_heads: int) -> dict:
@@ -747,17 +688,12 @@ class NativeBatchPlan:
         """ttv_batch struct whose attention work tables match the tower's head counts (ttv_plan_attn_set filled it)."""
         return self._switched(q_heads, kv_heads)["batch"]
 
-    def clip0_patch_rope(self) -> Tuple[int, Optional[int], Optional[int]]:
-        k = self.token_counts[0]
-        ids = self._base.rope_ids
-        return (self.rope_cs.data_ptr() + 4 * self.rope_cs.shape[1] * k, ids + 8 * k if ids else None, self._base.rope_base if ids else None)
-
 
 _plan_cache = {}
 _PLAN_CACHE_MAX = 64
 
 
-def get_plan(pixel_grids, token_counts, patch, device) -> BatchPlan:
+def get_plan(pixel_grids, token_counts, patch, device) -> _PlanBase:
     dev = torch.device(device)
     # TTV_NATIVE_PLAN=1 (opt-in, read at call time and part of the key): the library builds the plan (NativeBatchPlan)
     native = switches.flag("TTV_NATIVE_PLAN", False) and dev.type == "cuda" and len(patch) == 3
