@@ -261,6 +261,27 @@ int ttv_attention(const void* qkvg, int ld, void* out, int ldo, const int32_t* c
 int ttv_attention64(const void* qkvg, int ld, void* out, int ldo, const int32_t* cu_seqlens, const int32_t* items, int n_items,
                     int q_heads, int kv_heads, int head_dim, int flags, int dtype, void* stream);
 
+/* OPT-IN, INFERENCE: the same operator with its second product in 8 bits (bf16 rows, head_dim 64, q pre-scaled).  S = Q K^T and the
+ * softmax are ttv_attention's (bf16 operands, fp32); P enters P.V as e4m3_rne(p * 2^6) against a running reference that lags the row
+ * maximum by at most 2 log2 units (never saturated), V as an OCP-MX e4m3 image - one E8M0 scale per 32 keys (the natural halves of a
+ * 64-key tile counted from the sequence's first row) and head-dim column, scale rule of ttv_quant_mx_fp8 - and the product runs on
+ * v_mfma_scale_f32_32x32x64_f8f6f4 with fp32 accumulation; row sums add the fp32 p.  Accuracy price: ~2^-5 relative per p (e4m3's three
+ * mantissa bits) and per v instead of bf16's 2^-9 - DESIGN.md section 4z has the bound and the measured figures.
+ *   ttv_attention_pv8_bytes: size of the image for a packed batch ((total_rows / 64 + n_seqs) * kv_heads tiles of 4 224 bytes); -1 for
+ *     negative sizes.
+ *   ttv_quant_v_pv8: writes the image of the v columns of qkvg [total_rows, ld] (layout: csrc/ttv_attn_pv8.hip, restated in
+ *     tests/pv8_ref.py); `image` 16-byte aligned; cu_seqlens device int32 [n_seqs + 1] with cu_seqlens[n_seqs] == total_rows.
+ *   ttv_attention_pv8: ttv_attention's arguments and work tables (mode-1 entries run without the key split; a paired table is walked
+ *     entry by entry); flags MUST carry TTV_ATTN_QSCALED (the caller's statement that q is pre-scaled) and may carry TTV_ATTN_GATE,
+ *     nothing else; `image` is what ttv_quant_v_pv8 wrote for the same qkvg, cu_seqlens and head counts.  TTV_ERR_INVALID with a
+ *     message and nothing launched: head_dim other than 64, q not pre-scaled, any other flag, qkvg / out / image not 16-byte aligned,
+ *     ld or ldo not a multiple of 8 or too small. */
+int64_t ttv_attention_pv8_bytes(int total_rows, int n_seqs, int kv_heads);
+int ttv_quant_v_pv8(const void* qkvg, int ld, const int32_t* cu_seqlens, int n_seqs, int total_rows, int q_heads, int kv_heads, void* image,
+                    void* stream);
+int ttv_attention_pv8(const void* qkvg, int ld, void* out, int ldo, const int32_t* cu_seqlens, const int32_t* qblocks, int n_qblocks,
+                      int q_heads, int kv_heads, int head_dim, int flags, const void* image, void* stream);
+
 /* The three producers of the block-scaled fp8 layers that write the next linear's operand themselves, each on its own.  FOR TESTS
  * ONLY (tests/test_hip_fp8_blocks.py): the towers reach the same kernels inside ttv_encoder_forward / ttv_decoder_forward; no caller
  * needs them one by one.  Each image must equal ttv_quant_mx_fp8 of the bf16 rows its plain twin stores, bit for bit: elements
@@ -384,6 +405,12 @@ typedef struct ttv_tower_weights {
    * residual stream, the encoder tail and FSQ stay exact fp32.  Measured: every token index of the reference's fp32 run is kept on the
    * benchmark fixture (max |pre-rounding FSQ value error| ~6e-4) at about a third of the exact-fp32 MFMA kernels' time. */
   int32_t f32_split3;
+  /* bf16 towers, inference: 1 = every layer's attention runs ttv_quant_v_pv8 + ttv_attention_pv8 (e4m3 P.V, see there) in place of the
+   * bf16 kernels - the plain, the wide and the block-scaled fp8 layer paths alike; the image lives in the workspace's GEGLU buffer,
+   * which is dead during attention (ttv_tower_workspace_bytes is unchanged; a batch whose image does not fit is refused).  The decoder's
+   * layer-0 constant block and the software-pipelined kernel stay off.  TTV_ERR_INVALID: fp32 and split-bf16 towers, a layer whose q is
+   * not pre-scaled.  The *_forward_train* entry points ignore the field.  (Sits in the struct's tail padding: sizeof is unchanged.) */
+  int32_t attn_pv8;
 } ttv_tower_weights;
 
 /* Per-batch metadata, built on the host from Python ints (replaces the device-side bookkeeping and its

@@ -85,7 +85,7 @@ class LayerWeights(C.Structure):
 class TowerWeights(C.Structure):
     _fields_ = [("proj_in_w", vp), ("proj_in_b", vp), ("mask_token", vp), ("ln_pre_t", vp), ("ln_pre_p", vp),
                 ("ln_post", vp), ("proj_out_w", vp), ("proj_out_b", vp), ("layers", C.POINTER(LayerWeights)), ("proj_out_pn", vp),
-                ("f32_split3", i32)]
+                ("f32_split3", i32), ("attn_pv8", i32)]
 
 
 class Batch(C.Structure):
@@ -224,6 +224,9 @@ SYMBOLS = {
     "ttv_attention64": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     # the fused MX producers one by one (tests only)
     "ttv_rmsnorm_mx": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, f32, vp, vp, vp, vp]),
+    "ttv_attention_pv8_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "ttv_quant_v_pv8": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "ttv_attention_pv8": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "ttv_attention_mxout": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "ttv_linear_fp8_mx_geglu_q": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     # the folded pre-norm of the wide bf16 layer launch by launch (tests only)

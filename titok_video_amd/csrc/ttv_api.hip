@@ -103,12 +103,25 @@ struct LayerCtx {
   int split3, s3img;   // fp32 tower on the three-pass bf16 kernels / its activations travel as split images
   bool gen_ok;         // a folded pre-norm may take its row statistic as the GEMM's row scale (wide bf16 towers, split-bf16 towers)
   int pair, all_full, pipe;   // TTV_ATTN_PAIRED / _ALLFULL / _PIPE where the batch's own table (pair, all_full) or the switch (pipe) says so, else 0
+  bool pv8;            // ttv_tower_weights.attn_pv8: every attention of the tower is ttvk_quant_v_pv8 + ttvk_attention_pv8
 };
 
 // The towers' attention: ws.qkv -> ws.ao over one work table.  The gate, the q pre-scale and the split-bf16 formats are the same at
 // every site; `site` holds the TTV_ATTN_PAIRED / _ALLFULL / _PIPE bits that this table and this site may take (see the callers).
 static int tower_attention(const LayerCtx& c, bool q_scaled, const int32_t* table, int n_table, int site) {
   const ttv_tower_dims* d = c.d;
+  if (c.pv8) {
+    // e4m3 P.V (opt-in): the image of this layer's v columns goes into the GEGLU buffer, which nobody reads before the w12 GEMM writes
+    // it again; the table is walked entry by entry whatever `site` says about it
+    const ttv_batch* b = c.b;
+    const int nq = 2 * d->width + 2 * d->kv_heads * d->head_dim;
+    TTV_CHECK_ARG(q_scaled, "attn_pv8: a layer's q is not pre-scaled (pack the towers with qkv_q_prescaled / to_qkv_qs)");
+    TTV_CHECK_ARG(ttvk_attention_pv8_bytes(b->total_rows, b->n_clips, d->kv_heads) <= (int64_t)b->total_rows * d->inner * dtype_bytes(d->dtype),
+                  "attn_pv8: the V image (%lld bytes) does not fit the workspace's GEGLU buffer", (long long)ttvk_attention_pv8_bytes(b->total_rows, b->n_clips, d->kv_heads));
+    TTV_TRY(ttvk_quant_v_pv8(c.ws.qkv, nq, b->cu_seqlens, b->n_clips, b->total_rows, d->q_heads, d->kv_heads, c.ws.h, c.s));
+    return ttvk_attention_pv8(c.ws.qkv, nq, c.ws.ao, d->width, b->cu_seqlens, table, n_table, d->q_heads, d->kv_heads, d->head_dim,
+                              TTV_ATTN_GATE | TTV_ATTN_QSCALED, c.ws.h, c.s);
+  }
   const int flags = TTV_ATTN_GATE | (q_scaled ? TTV_ATTN_QSCALED : 0) | (c.split3 ? TTV_ATTN_SPLIT3 : 0) |
                     (c.s3img ? (TTV_ATTN_SPLIT_OUT | TTV_ATTN_SPLIT_IN) : 0) | site;
   return ttvk_attention(c.ws.qkv, 2 * d->width + 2 * d->kv_heads * d->head_dim, c.ws.ao, d->width, c.b->cu_seqlens, table, n_table, d->q_heads,
@@ -137,7 +150,7 @@ static int run_layer_mx(const LayerCtx& c, const ttv_layer_weights& lw, int i, b
   const GemmArgs a = gemm_rope_qk(gemm_args(dt, ws.f8, dm, lw.to_qkv_f8, dm, L, nq, dm, ws.qkv, nq), b->rope_cs, dm, g);
   TTV_TRY(ttvk_gemm_fp8(EPI_QKV_ROPE, a, ws.rstd, lw.to_qkv_f8_scale, s, ws.f8mx, lw.to_qkv_mx));
   const bool q_scaled = lw.qkv_q_prescaled != 0;
-  if (fused_q && q_scaled && !c.pair && !c.pipe && d->head_dim == 64) {
+  if (fused_q && q_scaled && !c.pair && !c.pipe && d->head_dim == 64 && !c.pv8) {
     // the attention epilogue writes out_proj's operand itself (no bf16 output, no pass over it); ws.f8 is free: the qkv GEMM has read it
     TTV_TRY(ttvk_attention_mxout(ws.qkv, nq, ws.f8, ws.f8mx, (int)ttvk_mx_scale_ld(dm), b->cu_seqlens, b->qblocks, b->n_qblocks, d->q_heads,
                                  d->kv_heads, s));
@@ -275,7 +288,7 @@ static bool dec_l0_const_ok(const LayerCtx& c, const ttv_tower_weights* w, const
   const ttv_batch* b = c.b;
   if (!l0 || !l0->rows || !sw_dec_l0_const() || (g_ttv_debug & TTV_DBG_DEC_L0_NO_CONST)) return false;
   if (d->kind != TTV_DECODER || !qkv_tile_list_ok(c, w->layers[0], l0->latent_rows, l0->patch_rows)) return false;
-  if (c.pair || c.pipe || !c.all_full || (b->items64 && b->n_items64 > 0)) return false;
+  if (c.pair || c.pipe || c.pv8 || !c.all_full || (b->items64 && b->n_items64 > 0)) return false;
   return ttvk_attention_takes_swp(TTV_ATTN_GATE | TTV_ATTN_QSCALED | TTV_ATTN_ALLFULL);
 }
 
@@ -314,8 +327,10 @@ static int run_layers(const ttv_tower_dims* d, const ttv_tower_weights* w, const
   const bool pat_last = pat_env && !(g_ttv_debug & TTV_DBG_DEC_ALL_BLOCKS) && d->kind == TTV_DECODER && d->layers >= 2 && b->qblocks_patch &&
                         b->n_qblocks_patch > 0 && !split3 && !b->qblocks_paired;
   bool compacted = false;
+  const bool pv8 = w->attn_pv8 != 0;       // opt-in e4m3 P.V (ttv_tower_weights.attn_pv8)
+  TTV_CHECK_ARG(!pv8 || (dt == TTV_BF16 && !split3), "attn_pv8 is a bf16 inference option (not for fp32 or split-bf16 towers)");
   const LayerCtx ctx = {d, b, ws, s, split3, s3img, gen_ok, b->qblocks_paired ? TTV_ATTN_PAIRED : 0, b->qblocks_all_full ? TTV_ATTN_ALLFULL : 0,
-                        ttv_sw_attn_pipe() ? TTV_ATTN_PIPE : 0};       // (pipe: the opt-in pipelined attention kernel)
+                        ttv_sw_attn_pipe() ? TTV_ATTN_PIPE : 0, pv8};       // (pipe: the opt-in pipelined attention kernel)
   // The decoder's patch rows enter layer 0 as one constant vector (blocks.py:165-167), so their q | gate | k | v depend on the weights
   // and the rows' positions only: with the block built for this (weight pack, clip geometry) layer 0's to_qkv computes the token tiles
   // that hold latent rows and its attention reads the patch rows from the block - one copy for every clip, L2-resident - instead of
@@ -371,7 +386,7 @@ static int run_layers(const ttv_tower_dims* d, const ttv_tower_weights* w, const
                                  d->kv_heads, 1, s, l0->rows, l0->latent_rows, l0->state));
     } else if (pat_last && last && dt == TTV_BF16 && !ctx.pipe)     // (pat_last: the batch's table is unpaired)
       TTV_TRY(tower_attention(ctx, q_scaled, b->qblocks_patch, b->n_qblocks_patch, ctx.all_full));
-    else if (q_scaled && b->items64 && b->n_items64 > 0 && d->head_dim == 64)
+    else if (q_scaled && b->items64 && b->n_items64 > 0 && d->head_dim == 64 && !pv8)
       TTV_TRY(ttvk_attention64(ws.qkv, nq, ws.ao, dm, b->cu_seqlens, b->items64, b->n_items64, d->q_heads, d->kv_heads,
                                TTV_ATTN_GATE | TTV_ATTN_QSCALED, s));
     else
@@ -662,6 +677,16 @@ int ttv_attention64(const void* qkvg, int ld, void* out, int ldo, const int32_t*
                     int kv_heads, int head_dim, int flags, int dtype, void* stream) {
   TTV_CHECK_ARG(dtype == TTV_BF16 && head_dim == 64, "attention64: bf16, head_dim 64 only");
   return ttvk_attention64(qkvg, ld, out, ldo, cu_seqlens, items, n_items, q_heads, kv_heads, flags, (hipStream_t)stream);
+}
+
+int64_t ttv_attention_pv8_bytes(int total_rows, int n_seqs, int kv_heads) { return ttvk_attention_pv8_bytes(total_rows, n_seqs, kv_heads); }
+int ttv_quant_v_pv8(const void* qkvg, int ld, const int32_t* cu_seqlens, int n_seqs, int total_rows, int q_heads, int kv_heads, void* image,
+                    void* stream) {
+  return ttvk_quant_v_pv8(qkvg, ld, cu_seqlens, n_seqs, total_rows, q_heads, kv_heads, image, (hipStream_t)stream);
+}
+int ttv_attention_pv8(const void* qkvg, int ld, void* out, int ldo, const int32_t* cu_seqlens, const int32_t* qblocks, int n_qblocks,
+                      int q_heads, int kv_heads, int head_dim, int flags, const void* image, void* stream) {
+  return ttvk_attention_pv8(qkvg, ld, out, ldo, cu_seqlens, qblocks, n_qblocks, q_heads, kv_heads, head_dim, flags, image, (hipStream_t)stream);
 }
 
 // The three fused MX producers of run_layer_mx, one by one (tests only: tests/test_hip_fp8_blocks.py)

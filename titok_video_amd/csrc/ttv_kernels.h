@@ -139,6 +139,13 @@ int ttvk_attention_swp_dump(const void* rows, int ld, int n_rows, int q_heads, i
 int ttvk_attention_mxout(const void* qkvg, int ld, void* out_q, void* out_mx, int ld_mx, const int* cu_seqlens, const int* qblocks,
                          int n_qblocks, int q_heads, int kv_heads, hipStream_t s);
 
+// ---- ttv_attn_pv8.hip: opt-in inference attention with an e4m3 P.V product (see the file's header) ----
+int64_t ttvk_attention_pv8_bytes(int total_rows, int n_seqs, int kv_heads);
+int ttvk_quant_v_pv8(const void* qkvg, int ld, const int* cu_seqlens, int n_seqs, int total_rows, int q_heads, int kv_heads, void* image,
+                     hipStream_t s);
+int ttvk_attention_pv8(const void* qkvg, int ld, void* out, int ldo, const int* cu_seqlens, const int* qblocks, int n_qblocks, int q_heads,
+                       int kv_heads, int head_dim, int flags, const void* image, hipStream_t s);
+
 // ---- ttv_attn64.hip ----
 int ttvk_attention64(const void* qkvg, int ld, void* out, int ldo, const int* cu_seqlens, const int* items, int n_items, int q_heads,
                      int kv_heads, int flags, hipStream_t s);

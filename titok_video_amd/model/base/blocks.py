@@ -90,6 +90,9 @@ class _Tower(nn.Module):
         # slots and lets the backward rebuild each layer's tape from its boundary (TTV_TAPE_RECOMPUTE, include/titok_hip.h): the same
         # gradients for one more forward of the layers, a fraction of the memory.  Read by each training forward, for its own backward too.
         self.activation_recompute = False
+        # Inference arithmetic of the attention's second product: None (default) bf16 P.V; "fp8" = e4m3 P and block-scaled e4m3 V on the
+        # 32x32x64 scaled MFMA (ttv_tower_weights.attn_pv8; bf16 inference forwards only, TiTok.set_attention_pv).  Part of the pack key.
+        self.attention_pv = None
         self.register_load_state_dict_post_hook(lambda module, incompatible: module.invalidate_packs())
         return mlp_ratio
 
@@ -132,7 +135,8 @@ class _Tower(nn.Module):
 
     def _packed(self, dtype: torch.dtype, device) -> "_WeightPack":
         params = self._param_list()
-        key = (dtype, str(device), _versions(params), str(getattr(self, "fp8_linears", False)), bool(getattr(self, "f32_split3", False)))
+        key = (dtype, str(device), _versions(params), str(getattr(self, "fp8_linears", False)), bool(getattr(self, "f32_split3", False)),
+               str(getattr(self, "attention_pv", None)))
         if _PACK_CHECK:
             key = key + (float(sum(p.detach().double().sum() for p in params)),)
         if self._pack is None or self._pack_key != key:
@@ -340,6 +344,14 @@ class _WeightPack:
         q_scale = 0.125 * 1.4426950408889634 if use_qs else None
         self.q_prescaled = 1 if ((fold or fold_gen) and use_qs) else 0
 
+        # e4m3 P.V attention (tower.attention_pv = "fp8"): the struct carries it for the packs the C side accepts it with (bf16, pre-scaled
+        # q); the inference forwards refuse the others (check_attention_pv), the training forwards ignore the field either way
+        pv = getattr(tower, "attention_pv", None)
+        if pv not in (None, "fp8"):
+            raise ValueError(f"attention_pv must be None or 'fp8', got {pv!r}")
+        self.attn_pv8 = pv == "fp8" and dtype == torch.bfloat16 and use_qs
+        self.attn_pv8_refused = pv == "fp8" and not self.attn_pv8
+
         def lin_qs(w):
             """Inference copy of to_qkv with the factor on its q rows, for towers whose QKV GEMM does not take the folded weight."""
             if fold or fold_gen or not use_qs:
@@ -475,7 +487,7 @@ class _WeightPack:
             proj_in_w=lin(w_in, tower.kind == _lib.TTV_ENCODER), proj_in_b=lin(tower.proj_in.bias), mask_token=gain(tower.mask_token),
             ln_pre_t=gain(tower.ln_pre_t.weight), ln_pre_p=gain(tower.ln_pre_p.weight), ln_post=gain(tower.ln_post.weight),
             proj_out_w=lin(w_out, tower.kind == _lib.TTV_DECODER), proj_out_b=lin(b_out), layers=self.layers,
-            f32_split3=1 if self.f32_split3 else 0,
+            f32_split3=1 if self.f32_split3 else 0, attn_pv8=1 if self.attn_pv8 else 0,
             proj_out_pn=folded(w_out, tower.ln_post.weight) if (tower.kind == _lib.TTV_DECODER and fold) else None)
         self.keep = keep
         self.kind, self.n_layers = tower.kind, n
@@ -484,6 +496,12 @@ class _WeightPack:
         if self.device.type == "cuda":
             build = torch.cuda.current_stream(self.device)
             self._owned = streams.StreamOwned(build, build.record_event())
+
+    def check_attention_pv(self) -> None:
+        """Inference forwards: raise where ttv_encoder_forward / ttv_decoder_forward would refuse the mode."""
+        if self.attn_pv8_refused:
+            raise ValueError("attention_pv='fp8' is a bf16 inference mode with pre-scaled q: not for fp32 clips, set_index_exact modes "
+                             "or TTV_ATTN_QSCALE=0")
 
     def use_on_current_stream(self) -> None:
         """Called by every forward: a stream other than the one that built the pack waits for the build (casts, folds, the
@@ -498,7 +516,7 @@ class _WeightPack:
         width-256 bf16 kernels.  One per geometry, built on first use by the forward's own kernels on the pack's stream (one host sync
         there, for the builder's range flag) and dropped with the pack, i.e. on any weight-version change."""
         geo = plan.uniform_geometry()
-        if geo is None or self.kind != _lib.TTV_DECODER or self.device.type != "cuda":
+        if geo is None or self.kind != _lib.TTV_DECODER or self.device.type != "cuda" or self.attn_pv8:      # (attn_pv8: layer 0 runs no k_attn_swp)
             return None
         if geo in self._l0_const:
             ent = self._l0_const[geo]
@@ -585,6 +603,7 @@ class TiTokEncoder(_Tower):
         plan = self._plan(pix, counts, device)
         dims = self._dims(code)
         pack = self._packed(dtype, device)
+        pack.check_attention_pv()
         ws = self._workspace(dims, plan, device)
         clips = [v if v.is_contiguous() else v.contiguous() for v in videos]
         n, c = plan.sum_tokens, self.token_size
@@ -648,6 +667,7 @@ class TiTokDecoder(_Tower):
             raise ValueError(f"tokens must be [{plan.sum_tokens}, {self.token_size}], got {tuple(tokens.shape)}")
         dims = self._dims(code)
         pack = self._packed(dtype, device)
+        pack.check_attention_pv()
         ws = self._workspace(dims, plan, device)
         tokens = tokens.contiguous()
         sizes = [self.out_channels * t * h * w for (t, h, w) in pix]

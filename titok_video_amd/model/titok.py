@@ -14,6 +14,9 @@ types and state-dict keys (`encoder.*`, `decoder.*`; FSQ has no persistent keys)
     tape, the lookup is straight-through towards the encoder and passes the decoder's token gradient to the selected codebook rows;
   * BUILD-DEFINED: `config.tokenizer.model.activation_recompute = True` (absent: off) trains both towers on the recompute tape
     (`set_activation_recompute`): same gradients, a fraction of the activation memory, one more forward of the layers.
+  * BUILD-DEFINED: `config.tokenizer.model.attention_pv = "fp8"` (absent / None: off) runs the attention's P.V product of both towers'
+    bf16 inference forwards in e4m3 on the block-scaled 32x32x64 MFMA (`set_attention_pv`): an accuracy-for-arithmetic trade whose
+    price INTEGRATION.md states; never a default, training forwards are unaffected.
 """
 from __future__ import annotations
 
@@ -68,12 +71,25 @@ class TiTok(nn.Module):
         self.encoder_dtype = None
         self.decoder_dtype = None
         self.set_activation_recompute(bool(getattr(m, "activation_recompute", False)))
+        self.set_attention_pv(getattr(m, "attention_pv", None))
 
     def set_activation_recompute(self, flag: bool):
         """Training memory: True makes both towers keep only the residual stream at the layer boundaries and rebuild one layer's
         activations at a time during the backward (blocks._Tower.activation_recompute); False (default) stores them all.  Takes
         effect with the next training forward; gradients are the stored tape's, bit for bit wherever those are reproducible."""
         self.encoder.activation_recompute = self.decoder.activation_recompute = bool(flag)
+        return self
+
+    def set_attention_pv(self, mode):
+        """Inference arithmetic of the attention's second product in both towers: None (default) - bf16 P.V, today's kernels and bits;
+        "fp8" - P as e4m3 and V as a block-scaled (OCP MX) e4m3 image on v_mfma_scale_f32_32x32x64_f8f6f4 (scores, softmax and row sums
+        stay bf16 / fp32; ~2^-5 relative per probability and value instead of bf16's 2^-9).  bf16 inference forwards
+        only: fp32 clips and the `set_index_exact` modes raise ValueError; forwards under autograd run as without it."""
+        if mode not in (None, "fp8"):
+            raise ValueError("attention_pv must be None or 'fp8'")
+        if mode is not None and self.encoder_dtype is not None:
+            raise ValueError("attention_pv='fp8' does not combine with set_index_exact modes (fp32 / split-bf16 encoder)")
+        self.encoder.attention_pv = self.decoder.attention_pv = mode
         return self
 
     def set_index_exact(self, mode):
@@ -84,6 +100,8 @@ class TiTok(nn.Module):
                    bit-for-bit guarantee), decoder bf16.  About 2.5x the throughput of "fp32"."""
         if mode not in (None, "fp32", "split3"):
             raise ValueError("mode must be None, 'fp32' or 'split3'")
+        if mode is not None and self.encoder.attention_pv is not None:
+            raise ValueError("set_index_exact modes do not combine with attention_pv='fp8' (a bf16 inference mode)")
         self.encoder_dtype = None if mode is None else torch.float32
         self.decoder_dtype = None if mode is None else torch.bfloat16
         self.encoder.f32_split3 = mode == "split3"

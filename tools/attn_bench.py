@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Attention kernel alone at the benchmark shape (32 sequences x 1152 rows, 4 q-heads / 2 kv-heads, head_dim 64): launch time by
 torch events over back-to-back launches, TFLOP/s against the MFMA peak, and the error against an fp64 reference on two sequences.
-GPU box only.    python tools/attn_bench.py [spread ...]   (spread = std of the score exponents; default 1.5 6)"""
+GPU box only.    python tools/attn_bench.py [spread ...]   (spread = std of the score exponents; default 1.5 6)
+PV8=1 adds the opt-in e4m3 P.V kernel (ttv_attention_pv8) as three rows - its V pre-pass alone, the attention launch alone, the two
+back to back - and ROUNDS=n repeats the whole variant list n times in this process (alternations of one box, same inputs)."""
 import math
 import os
 import sys
@@ -25,6 +27,8 @@ ld = 2 * dm + 2 * g
 table = plan.attention_table(HQ, HKV)
 table64 = plan.attention_table64(HQ, HKV)
 W64 = 1 << 20          # tool-local marker: run ttv_attention64 (the 64-rows-per-wave kernel)
+PV8_QUANT, PV8_ATTN = 1 << 21, 1 << 22      # tool-local markers: ttv_quant_v_pv8 / ttv_attention_pv8 (either or both)
+pv8_image = torch.empty(max(int(lib.ttv_attention_pv8_bytes(L, B, HKV)), 16), dtype=torch.uint8, device=DEV)
 C_EXP = 0.125 * 1.4426950408889634
 
 
@@ -48,6 +52,13 @@ def run(dtype, flags, qkv, iters=30):
     code = _lib.dtype_code(dtype)
 
     def call():
+        if flags & (PV8_QUANT | PV8_ATTN):
+            if flags & PV8_QUANT:
+                _lib.check(lib.ttv_quant_v_pv8(qkv.data_ptr(), ld, plan.cu_dev.data_ptr(), B, L, HQ, HKV, pv8_image.data_ptr(), ST), "quant_v_pv8")
+            if flags & PV8_ATTN:
+                _lib.check(lib.ttv_attention_pv8(qkv.data_ptr(), ld, out.data_ptr(), dm, plan.cu_dev.data_ptr(), table.data_ptr(), table.shape[0],
+                                                 HQ, HKV, D, 1 | 4, pv8_image.data_ptr(), ST), "attention_pv8")
+            return
         if flags & W64:
             _lib.check(lib.ttv_attention64(qkv.data_ptr(), ld, out.data_ptr(), dm, plan.cu_dev.data_ptr(), table64.data_ptr(),
                                            table64.shape[0], HQ, HKV, D, flags & ~W64, code, ST), "attention64")
@@ -88,12 +99,18 @@ for spread in spreads:
             variants.append((torch.bfloat16, "bf16 gate+qscaled pipe", 1 | 4 | 8 | 16, True))
     if os.environ.get("FP32", "0") == "1":
         variants.append((torch.float32, "fp32 gate", 1, False))
-    for dtype, name, flags, pre in variants:
+    if os.environ.get("PV8", "0") == "1":
+        variants += [(torch.bfloat16, "pv8 V pre-pass alone", PV8_QUANT, True), (torch.bfloat16, "pv8 pre-pass + attention", PV8_QUANT | PV8_ATTN, True),
+                     (torch.bfloat16, "pv8 attention alone", PV8_ATTN, True)]       # (alone: on the image the row above left)
+    for dtype, name, flags, pre in variants * int(os.environ.get("ROUNDS", "1")):
         x = base.clone()
         if pre:
             x[:, :dm] *= C_EXP
         qkv = x.to(DEV, dtype).contiguous()
         us, out = run(dtype, flags, qkv, iters=30 if dtype == torch.bfloat16 else 8)
+        if flags & PV8_QUANT and not flags & PV8_ATTN:
+            print(f"spread {spread:4.1f} {name:24s} {us:8.1f} us", flush=True)
+            continue
         ref = reference(qkv, (0, B - 1), pre)
         err = max(float((out[b * S:(b + 1) * S].double() - r).abs().max()) for b, r in ref.items())
         rel = max(float((out[b * S:(b + 1) * S].double() - r).norm() / r.norm()) for b, r in ref.items())
