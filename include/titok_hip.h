@@ -1105,6 +1105,58 @@ int ttv_vjepa_linear(const void* x, int ldx, const void* w, int ldw, const void*
                      const float* resid, int ldr, int resid_rows, void* y, int ldy, void* stream);
 int ttv_vjepa_pool_attention(const void* q, const void* kv, int n, int rows, void* out, void* stream);
 
+/* ---- FID / IS / MMD: frame preprocessing and the Inception-v3 feature extractor (model/metrics/metrics.py MetricCalculator) ------
+ * torchvision's Inception-v3 trunk (no transform_input, no AuxLogits) up to the 2048 activations after the 8 x 8 average pool, the fc
+ * logits and their softmax, in fp32 with activations channels-last.  94 units (bias-free convolution, eval BatchNorm eps 1e-3, ReLU)
+ * in torchvision's module order: 0 .. 4 the stem (Conv2d_1a_3x3, 2a_3x3, 2b_3x3, 3b_1x1, 4a_3x3); 5 .. 25 Mixed_5b, 5c, 5d, 7 each
+ * (branch1x1, branch5x5_1, _2, branch3x3dbl_1, _2, _3, branch_pool); 26 .. 29 Mixed_6a (branch3x3, branch3x3dbl_1, _2, _3);
+ * 30 .. 69 Mixed_6b .. 6e, 10 each (branch1x1, branch7x7_1, _2, _3, branch7x7dbl_1 .. _5, branch_pool); 70 .. 75 Mixed_7a
+ * (branch3x3_1, _2, branch7x7x3_1 .. _4); 76 .. 93 Mixed_7b, 7c, 9 each (branch1x1, branch3x3_1, _2a, _2b, branch3x3dbl_1, _2, _3a,
+ * _3b, branch_pool).
+ * unit[i].w: fp32 weight image [K][Cout], K = (dh kW + dw) Cin + ci, i.e. W[co][ci][dh][dw] -> [dh][dw][ci][co], 16-byte aligned.
+ * unit[i].scale, .shift: fp32 [Cout], the folded BatchNorm (y = conv * scale + shift, then ReLU).  fc_w: fp32 [2048][1000] (the
+ * transpose of fc.weight), fc_b: fp32 [1000].  Every output is a fixed-order fp32 chain: an image's features are bit-identical
+ * whatever other images share the launch. */
+#define TTV_INCEPTION_UNITS 94
+#define TTV_INCEPTION_FEATURES 2048
+#define TTV_INCEPTION_CLASSES 1000
+#define TTV_INCEPTION_INPUT 299
+#define TTV_INCEPTION_POOL_AVG3 0
+#define TTV_INCEPTION_POOL_MAX3S2 1
+typedef struct ttv_inception_unit {
+  const float* w;
+  const float* scale;
+  const float* shift;
+} ttv_inception_unit;
+typedef struct ttv_inception_weights {
+  ttv_inception_unit unit[TTV_INCEPTION_UNITS];
+  const float* fc_w;
+  const float* fc_b;
+} ttv_inception_weights;
+
+/* Workspace of ttv_inception_features for n images (1 .. TTV_MAX_CLIPS_PER_LAUNCH), -1 on a bad n. */
+int64_t ttv_inception_workspace_bytes(int n);
+
+/* Up to TTV_MAX_CLIPS_PER_LAUNCH images [3][H][W] (host array of device pointers, `dtype`; dims = n x (H, W, channel stride in
+ * elements), host: rows are contiguous, and a frame t of a contiguous clip [3][T][H][W] is the image at clip + t H W with channel
+ * stride T H W) -> out [n][299][299][3] fp32: clamped to [-1, 1] when `clamp` is set, resized bilinearly with torch's
+ * align_corners=True rule (nn.Upsample(size=(299, 299), mode='bilinear', align_corners=True)). */
+int ttv_inception_preprocess(void* const* images, const int64_t* dims, int n, int dtype, int clamp, float* out, void* stream);
+
+/* x: [n][299][299][3] fp32 (ttv_inception_preprocess) -> acts [n][2048] fp32 and, unless probs is NULL, probs [n][1000] fp32 (the
+ * softmax of fc(acts)).  x and the workspace are 256-byte aligned. */
+int ttv_inception_features(const ttv_inception_weights* w, const float* x, int n, float* acts, float* probs, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+
+/* Single operations (tests).  ttv_inception_conv2d: x [N][H][W][Cin] -> channels [c_off, c_off + Cout) of y [N][Ho][Wo][ldc], a
+ * kh x kw convolution (1 .. 7 each) with strides sh x sw (1 or 2) and zero padding ph x pw (Ho = (H + 2 ph - kh) / sh + 1),
+ * y = conv * scale + shift (scale / shift NULL: 1 / 0), ReLU when `relu`; w is a weight image as above, Cout % 4 == 0.
+ * ttv_inception_pool2d: TTV_INCEPTION_POOL_AVG3 (3 x 3, stride 1, padding 1, always divided by 9) or TTV_INCEPTION_POOL_MAX3S2
+ * (3 x 3, stride 2, no padding) of x [N][H][W][C] -> channels [c_off, c_off + C) of y [N][Ho][Wo][ldc]. */
+int ttv_inception_conv2d(const float* x, int N, int H, int W, int Cin, int kh, int kw, int sh, int sw, int ph, int pw, const float* w,
+                         const float* scale, const float* shift, int Cout, int relu, float* y, int ldc, int c_off, void* stream);
+int ttv_inception_pool2d(const float* x, int N, int H, int W, int C, int mode, float* y, int ldc, int c_off, void* stream);
+
 /* ---- measurement hook (bench.py roofline leg) ---------------------------------------------------------- */
 /* Kernel classes whose launches can be bracketed by HIP events on the stream they are launched on. */
 #define TTV_KC_ATTENTION 1

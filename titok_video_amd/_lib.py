@@ -158,6 +158,21 @@ class I3dWeights(C.Structure):
     _fields_ = [("w", vp * TTV_I3D_CONVS), ("scale", vp * TTV_I3D_CONVS), ("shift", vp * TTV_I3D_CONVS)]
 
 
+TTV_INCEPTION_UNITS = 94
+TTV_INCEPTION_FEATURES = 2048
+TTV_INCEPTION_CLASSES = 1000
+TTV_INCEPTION_INPUT = 299
+TTV_INCEPTION_POOL_AVG3, TTV_INCEPTION_POOL_MAX3S2 = 0, 1
+
+
+class InceptionUnit(C.Structure):
+    _fields_ = [("w", vp), ("scale", vp), ("shift", vp)]
+
+
+class InceptionWeights(C.Structure):
+    _fields_ = [("unit", InceptionUnit * TTV_INCEPTION_UNITS), ("fc_w", vp), ("fc_b", vp)]
+
+
 TTV_VJEPA_WIDTH = 1024
 TTV_VJEPA_TOKENS = 1568
 TTV_VJEPA_PATCH_K = 1536
@@ -320,7 +335,12 @@ SYMBOLS = {
     "ttv_i3d_features": (C.c_int, [C.POINTER(I3dWeights), vp, C.c_int, vp, vp, C.c_int64, vp]),
     "ttv_i3d_conv3d": (C.c_int, [vp] + [C.c_int] * 7 + [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]),
     "ttv_i3d_maxpool3d": (C.c_int, [vp] + [C.c_int] * 11 + [vp, vp]),
-    "ttv_jedi_preprocess": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
+    "ttv_inception_workspace_bytes": (C.c_int64, [C.c_int]),
+    "ttv_inception_preprocess": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "ttv_inception_features": (C.c_int, [C.POINTER(InceptionWeights), vp, C.c_int, vp, vp, vp, C.c_int64, vp]),
+    "ttv_inception_conv2d": (C.c_int, [vp] + [C.c_int] * 10 + [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]),
+    "ttv_inception_pool2d": (C.c_int, [vp] + [C.c_int] * 5 + [vp, C.c_int, C.c_int, vp]),
+    "ttv_jedi_preprocess":(C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
     "ttv_vjepa_workspace_bytes": (C.c_int64, [C.c_int]),
     "ttv_vjepa_features": (C.c_int, [C.POINTER(VjepaWeights), vp, C.c_int, vp, C.c_int, vp, C.c_int64, vp]),
     "ttv_vjepa_layernorm": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_float, vp, vp, C.c_float, vp, C.c_int, vp, C.c_int, vp]),

@@ -1008,6 +1008,26 @@ int ttv_i3d_maxpool3d(const float* x, int N, int T, int H, int W, int C, int kt,
   return ttvk_i3d_maxpool3d(x, N, T, H, W, C, kt, kh, kw, st, sh, sw, y, (hipStream_t)stream);
 }
 
+int64_t ttv_inception_workspace_bytes(int n) { return ttvk_inception_workspace_bytes(n); }
+
+int ttv_inception_preprocess(void* const* images, const int64_t* dims, int n, int dtype, int clamp, float* out, void* stream) {
+  return ttvk_inception_preprocess(images, dims, n, dtype, clamp, out, (hipStream_t)stream);
+}
+
+int ttv_inception_features(const ttv_inception_weights* w, const float* x, int n, float* acts, float* probs, void* workspace,
+                           int64_t workspace_bytes, void* stream) {
+  return ttvk_inception_features(w, x, n, acts, probs, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ttv_inception_conv2d(const float* x, int N, int H, int W, int Cin, int kh, int kw, int sh, int sw, int ph, int pw, const float* w,
+                         const float* scale, const float* shift, int Cout, int relu, float* y, int ldc, int c_off, void* stream) {
+  return ttvk_inception_conv2d(x, N, H, W, Cin, kh, kw, sh, sw, ph, pw, w, scale, shift, Cout, relu, y, ldc, c_off, (hipStream_t)stream);
+}
+
+int ttv_inception_pool2d(const float* x, int N, int H, int W, int C, int mode, float* y, int ldc, int c_off, void* stream) {
+  return ttvk_inception_pool2d(x, N, H, W, C, mode, y, ldc, c_off, (hipStream_t)stream);
+}
+
 int ttv_jedi_preprocess(void* const* clips, const int32_t* dims, int n_clips, int dtype, void* out, void* stream) {
   return ttvk_jedi_preprocess(clips, dims, n_clips, dtype, out, (hipStream_t)stream);
 }

@@ -287,6 +287,15 @@ int ttvk_vjepa_linear(const void* x, int ldx, const void* w, int ldw, const void
                       const float* resid, int ldr, int resid_rows, void* y, int ldy, hipStream_t s);
 int ttvk_vjepa_pool_attention(const void* q, const void* kv, int n, int rows, void* out, hipStream_t s);
 
+// ---- ttv_inception.hip ----
+int64_t ttvk_inception_workspace_bytes(int n);
+int ttvk_inception_preprocess(void* const* images, const int64_t* dims, int n, int dtype, int clamp, float* out, hipStream_t s);
+int ttvk_inception_features(const ttv_inception_weights* w, const float* x, int n, float* acts, float* probs, void* ws, int64_t ws_bytes,
+                            hipStream_t s);
+int ttvk_inception_conv2d(const float* x, int N, int H, int W, int Cin, int kh, int kw, int sh, int sw, int ph, int pw, const float* w,
+                          const float* scale, const float* shift, int Cout, int relu, float* y, int ldc, int c_off, hipStream_t s);
+int ttvk_inception_pool2d(const float* x, int N, int H, int W, int C, int mode, float* y, int ldc, int c_off, hipStream_t s);
+
 // ---- host helpers of the launch sequences (ttv_api.hip, ttv_train.hip, the feature extractors) ----
 #define TTV_TRY(expr)                \
   do {                               \

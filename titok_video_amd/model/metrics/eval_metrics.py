@@ -28,6 +28,12 @@ them `x.clamp(-1, 1)` per clip, CTHW -> TCHW (eval_metrics.py:19-21, 32-37).
   (eval_metrics.py:33-37), each frame pair is a batch entry of its own.  State: a running sum of per-frame values and a frame
   count (double, on the device), so compute() is a mean of per-frame values like SSIM; no cross-rank sum in compute(), as for PSNR
   and SSIM.  The weights are not part of state_dict().
+- FID / IS / MMD (the 'fid', 'is' and 'mmd' entries, reference metrics.MetricCalculator): frame metrics on Inception-v3, which
+  needs torchvision's `inception_v3` weights from a local file or state dict, given as `EvalMetrics(config, inception_weights=...)`
+  or the optional config key `training.eval.inception_weights`; without them the three raise as before.  Every frame of every clip is
+  one image, read in place; the reconstruction is clamped, the target is not, and the reconstructions are the "generated" set.  One
+  extractor and one feature store serve the three entries (metrics.py InceptionStats); features stay on the device until compute(),
+  which runs the float64 statistics on the host.  The weights are not part of state_dict().
 No host sync until compute().
 """
 from __future__ import annotations
@@ -46,13 +52,14 @@ AVAILABLE = ("psnr", "ssim")
 
 class EvalMetrics(nn.Module):
     def __init__(self, config=None, eval_prefix: str = "eval", fvd_detector=None, jedi_weights=None, jedi_probe=None,
-                 lpips_weights=None, lpips_model=None):
+                 lpips_weights=None, lpips_model=None, inception_weights=None):
         super().__init__()
         self.eval_prefix = eval_prefix
         names = ["psnr"]
         self._fvd = None
         self._jedi = None
         self._lpips = None
+        self._inception = None
         if config is not None:
             names = [m for m in config.training.eval.log_metrics]
             if fvd_detector is None:
@@ -63,6 +70,8 @@ class EvalMetrics(nn.Module):
                 jedi_probe = getattr(config.training.eval, "jedi_probe", None)
             if lpips_weights is None and lpips_model is None:
                 lpips_weights = getattr(config.training.eval, "lpips_weights", None)
+            if inception_weights is None:
+                inception_weights = getattr(config.training.eval, "inception_weights", None)
             for m in names:
                 if m == "lpips" and (lpips_model is not None or lpips_weights is not None):
                     from .lpips_gram import LPIPS
@@ -81,6 +90,10 @@ class EvalMetrics(nn.Module):
                     from .jedi import JEDiMetric
                     model_name = getattr(config.training.eval, "jedi_jepa_model", "vit_large")
                     self.__dict__["_jedi"] = JEDiMetric(model_name=model_name, weights=jedi_weights, probe=jedi_probe)
+                elif m in ("fid", "is", "mmd") and inception_weights is not None:
+                    if self._inception is None:      # one extractor and one feature store for the three entries
+                        from .metrics import InceptionStats, make_extractor
+                        self.__dict__["_inception"] = InceptionStats(make_extractor(inception_weights), names)
                 elif m not in AVAILABLE:
                     raise NotImplementedError(f"metric '{m}' is not built: FVD / JEDi need weights fetched over the network "
                                               f"(reference model/metrics/); the available metrics are {', '.join(AVAILABLE)}")
@@ -140,6 +153,10 @@ class EvalMetrics(nn.Module):
             self._fvd.update_clips(recon, target, clamp_recon=True)
         if self._jedi is not None:
             self._jedi.update_clips(recon, target)
+        if self._inception is not None:
+            def frames(clips):
+                return [c[:, t] for c in (c.contiguous() for c in clips) for t in range(c.shape[1])]
+            self._inception.update(frames(target), frames(recon), clamp_generated=True)
 
     def compute(self) -> dict:
         out = {}
@@ -157,6 +174,8 @@ class EvalMetrics(nn.Module):
                 out[f"{self.eval_prefix}/fvd"] = self._fvd.compute()
             elif name == "jedi" and self._jedi is not None:
                 out[f"{self.eval_prefix}/jedi"] = self._jedi.compute()
+            elif name in ("fid", "is", "mmd") and self._inception is not None:
+                out[f"{self.eval_prefix}/{name}"] = self._inception.compute(name)
         return out
 
     def reset(self) -> None:
@@ -167,3 +186,5 @@ class EvalMetrics(nn.Module):
             self._fvd.reset()
         if self._jedi is not None:
             self._jedi.reset()
+        if self._inception is not None:
+            self._inception.reset()

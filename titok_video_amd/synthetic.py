@@ -135,6 +135,29 @@ def seeded_i3d_state(seed: int = 0) -> Dict[str, torch.Tensor]:
     return out
 
 
+def seeded_inception_state(seed: int = 0) -> Dict[str, torch.Tensor]:
+    """torchvision-keyed Inception-v3 state dict (model/metrics/metrics.py canonical_shapes) of seeded values: He-normal
+    convolutions and BatchNorm statistics near identity (weight 1 +- 0.05, running_var in [0.9, 1.1], bias and running_mean
+    N(0, 0.05^2)), so that activations neither die nor blow up through the 47 convolutions of the deepest path; fc N(0, 0.02^2)
+    with a small bias, which keeps the softmax away from one-hot."""
+    from .model.metrics.metrics import canonical_shapes
+
+    g = torch.Generator().manual_seed(seed)
+    out = OrderedDict()
+    for key, shape in canonical_shapes().items():
+        if len(shape) == 4:
+            out[key] = torch.randn(shape, generator=g) * math.sqrt(2.0 / (shape[1] * shape[2] * shape[3]))
+        elif key == "fc.weight":
+            out[key] = 0.02 * torch.randn(shape, generator=g)
+        elif key.endswith("bn.weight"):
+            out[key] = 1.0 + 0.05 * torch.randn(shape, generator=g)
+        elif key.endswith("running_var"):
+            out[key] = 0.9 + 0.2 * torch.rand(shape, generator=g)
+        else:   # bn.bias, bn.running_mean, fc.bias
+            out[key] = 0.05 * torch.randn(shape, generator=g)
+    return out
+
+
 def _vjepa_values(shapes, g: torch.Generator) -> Dict[str, torch.Tensor]:
     out = OrderedDict()
     for key, shape in shapes.items():
