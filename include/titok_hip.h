@@ -44,6 +44,28 @@ extern "C" {
 const char* ttv_error_string(void);
 int ttv_version(void);
 
+/* ---- deterministic mode: fixed-order sums in place of every float atomic onto a shared address ----------------------------------------
+ * Process-wide, off by default; ttv_set_deterministic returns the previous value.  Launchers read it when they launch, so under a
+ * graph capture it is the value at capture.  Off: nothing changes - the same kernels, launch geometry and workspace sizes.  On: two
+ * runs of a training step on the same inputs give the same bits (the order of a cross-rank all-reduce is outside this mode).
+ *   Row reductions into a vector or scalar (RMSNorm gain gradients, bias / column sums, the mask-token sum, the d <-> token_size
+ *   projection gradients, ttv_l1_loss, ttv_sq_err_accumulate): every block writes its partial to scratch as [block][element] with
+ *   plain stores; a second kernel, one thread per element, adds the partials of an element in ascending block index starting from
+ *   block 0's (fp32; double for the squared-error sums) and adds that total onto the destination with a plain load / add / store.
+ *   The block's own arithmetic is what it is with the mode off.
+ *   Weight gradients (ttv_linear_wgrad and the towers): the split partial tiles with their fixed-order sum where the workspace has
+ *   room; otherwise (no or too little workspace, an operand off 16 bytes, TTV_WGRAD_TILE64, fp32) one token range per output tile:
+ *   a single writer per address.
+ *   fp32 attention backward: dK / dV by an owner per (key row, kv-head) that adds over the sequence's query rows, and for each over
+ *   the q-heads of its group, in ascending order.  Codebook gradient: an owner per codebook entry adds its token rows in ascending order.
+ * Scratch: the tower backward entry points take the partials from their workspace - ttv_tower_bwd_workspace_bytes[_ex] returns the
+ * larger size while the mode is on.  The four ops without a workspace argument have a sibling *_det that takes (scratch,
+ * scratch_bytes) - device memory, 16-byte aligned, at least the size function beside it - and with the mode on the plain entry point
+ * returns TTV_ERR_INVALID before any launch, naming the sibling.  A sibling called with the mode off runs the plain path and
+ * ignores its scratch.  Size functions return -1 (message set) on refused input. */
+int ttv_set_deterministic(int on);
+int ttv_get_deterministic(void);
+
 /* ---- FSQ (model/quantizer/fsq.py) -------------------------------------------------------------------- */
 typedef struct ttv_fsq_params {
   int32_t n;                        /* codebook_dim = len(levels)                         fsq.py:69 */
@@ -81,6 +103,12 @@ int ttv_vq_lookup(const void* codebook, int dtype, int ldc, const int32_t* indic
  * straight-through quantiser named by BASELINE.json's north_star; the encoder's is the identity (FSQ's round_ste, fsq.py:48-51, is the
  * reference's instance of the same estimator). */
 int ttv_vq_lookup_backward(const void* dcodes, int dtype, int ld, const int32_t* indices, int rows, int C, float* dcodebook, int ldc, void* stream);
+/* Deterministic sibling (see ttv_set_deterministic): N = codebook entries; an owner per entry walks the token rows in ascending order
+ * and adds the rows that chose it one after the other in fp32, then adds that sum onto dcodebook[entry] (an entry no row chose is not
+ * written; an index outside [0, N) contributes nothing).  No partials: the size function returns 0 and scratch may be NULL. */
+int64_t ttv_vq_lookup_backward_det_scratch_bytes(int rows, int N, int C);
+int ttv_vq_lookup_backward_det(const void* dcodes, int dtype, int ld, const int32_t* indices, int rows, int N, int C, float* dcodebook, int ldc,
+                               void* scratch, int64_t scratch_bytes, void* stream);
 
 /* ---- training the L2 quantiser: commitment term, EMA codebook, restart of dead entries (ttv_vq_train.hip) ----------------------------
  * Not reference components (the reference trains FSQ, which has no codebook).  Every sum below has a fixed order and no float atomic:
@@ -789,6 +817,38 @@ int ttv_rmsnorm_backward_chain(const void* x, int ldx, const void* dy, int lddy,
 /* RMSNorm backward: dx (dtype), dgain fp32 [width] (accumulated; may be NULL). */
 int ttv_rmsnorm_backward(const void* x, int ldx, const void* dy, int lddy, const float* gain, void* dx, int lddx, float* dgain, int rows,
                          int width, float eps, int dtype, void* stream);
+/* Deterministic siblings of the two above (see ttv_set_deterministic).  Partial layout: fp32 [blocks][width], blocks =
+ * scratch_bytes / (4 * width) of ttv_rmsnorm_backward_det_scratch_bytes(rows, width); block b holds the sum over its rows of dy * xhat.
+ * The chain takes two such arrays, gain 1's at the scratch's start and gain 2's right behind it (at half of
+ * ttv_rmsnorm_backward_chain_det_scratch_bytes).  ttv_rmsnorm_backward_det also takes the row maps of the tower backward (int32
+ * [rows] each, NULL = row r): row r reads x[x_rows[r]], dy[dy_rows[r]] and writes dx[dx_rows[r]]. */
+int64_t ttv_rmsnorm_backward_det_scratch_bytes(int rows, int width);
+int64_t ttv_rmsnorm_backward_chain_det_scratch_bytes(int rows, int width);
+int ttv_rmsnorm_backward_chain_det(const void* x, int ldx, const void* dy, int lddy, const float* gain1, float* dgain1, float* dx, int lddx,
+                                   const float* y, int ldy, const float* gain2, float* dgain2, float out_scale, void* cast_out, int ldc, int rows,
+                                   int width, float eps, int dtype, void* scratch, int64_t scratch_bytes, void* stream);
+int ttv_rmsnorm_backward_det(const void* x, int ldx, const void* dy, int lddy, const float* gain, void* dx, int lddx, float* dgain, int rows,
+                             int width, float eps, int dtype, const int32_t* x_rows, const int32_t* dy_rows, const int32_t* dx_rows, void* scratch,
+                             int64_t scratch_bytes, void* stream);
+/* The tower backward's three small reductions on their own, for tests (either mode; the scratch is looked at with the deterministic
+ * mode on only).  All accumulate into fp32 destinations.
+ *   ttv_colsum_accumulate      out[c] += sum_r a[rows_map ? rows_map[r] : r][c], c < n (bias gradients).  Partials: fp32 [row blocks][n],
+ *                              64 rows per block (the last one short): ttv_colsum_det_scratch_bytes(rows, n) = blocks * n * 4.
+ *   ttv_sumall_accumulate      out[0] += scale * sum of a[rows, 0:n] (mask-token gradient).  Partials: fp32 [blocks], block b's sum already
+ *                              scaled: ttv_sumall_det_scratch_bytes(rows, n) = blocks * 4.
+ *   ttv_outer_small_accumulate dw[c][f] (transpose_out: dw[f][c]) += sum_r a[r][c] * b[r][f], c < C <= TTV_MAX_TOKEN, f < d (the
+ *                              d <-> token_size projections).  Partials: fp32 [row blocks][cn][d], 32 rows per block, for one chunk of
+ *                              cn <= TTV_MAX_FSQ columns c at a time (the chunks reuse the scratch; after the call it holds the last
+ *                              chunk's): ttv_outer_small_det_scratch_bytes(rows, C, d) = blocks * min(C, TTV_MAX_FSQ) * d * 4. */
+int64_t ttv_colsum_det_scratch_bytes(int rows, int n);
+int64_t ttv_sumall_det_scratch_bytes(int rows, int n);
+int64_t ttv_outer_small_det_scratch_bytes(int rows, int C, int d);
+int ttv_colsum_accumulate(const void* a, int dtype, int lda, const int32_t* rows_map, int rows, int n, float* out, void* scratch,
+                          int64_t scratch_bytes, void* stream);
+int ttv_sumall_accumulate(const void* a, int dtype, int lda, int rows, int n, float scale, float* out, void* scratch, int64_t scratch_bytes,
+                          void* stream);
+int ttv_outer_small_accumulate(const void* a, int a_dtype, int lda, int C, const void* b, int b_dtype, int ldb, float* dw, int lddw,
+                               int transpose_out, int rows, int d, void* scratch, int64_t scratch_bytes, void* stream);
 /* Attention backward (flash-style recompute from the forward's LSE): qkvg as in ttv_attention, o / dout [L,d], lse fp32
  * [L,q_heads] -> dqkvg [L,2d+2g] (q, k, v column ranges written; gate range untouched).  delta: fp32 [L,q_heads] scratch;
  * dkv_scratch: fp32 [L,2g] scratch (fp32 dtype only). blocks64 / row_seq as in ttv_batch.  rope_cs (fp32 [L,64] cos|sin as in
@@ -798,6 +858,15 @@ int ttv_attention_backward(const void* qkvg, int ld, const void* o, int ldo, con
                            const int32_t* cu_seqlens, const int32_t* blocks64, int n_blocks64, const int32_t* row_seq, void* dqkvg,
                            int ldg, float* dkv_scratch, int total_rows, int q_heads, int kv_heads, int dtype, const float* rope_cs,
                            void* stream);
+/* ttv_attention_backward with the towers' rule for query rows the forward did not compute (the encoder's last layer, whose attention
+ * runs for the latent query rows only), for tests.  clip_desc: int32 [n_seqs][8] as in ttv_batch (entries 3 - 5 of a clip: its patch
+ * grid gt, gh, gw; the latent tokens are the K = S - gt * gh * gw rows in front of the patches); NULL = every row.  Of a sequence
+ * only the query rows [0, min(S, ceil(K / 128) * 128)) take part: the rows behind get dq = 0 and add nothing to dk / dv (their lse
+ * and dout are not read). */
+int ttv_attention_backward_qlim(const void* qkvg, int ld, const void* o, int ldo, const void* dout, int ldd, const float* lse, float* delta,
+                                const int32_t* cu_seqlens, const int32_t* blocks64, int n_blocks64, const int32_t* row_seq, void* dqkvg,
+                                int ldg, float* dkv_scratch, int total_rows, int q_heads, int kv_heads, int dtype, const float* rope_cs,
+                                const int32_t* clip_desc, void* stream);
 /* ttv_attention with an extra fp32 [L,q_heads] log-sum-exp output (training forward). */
 int ttv_attention_lse(const void* qkvg, int ld, void* out, int ldo, const int32_t* cu_seqlens, const int32_t* qblocks, int n_qblocks,
                       int q_heads, int kv_heads, int head_dim, int flags, int dtype, float* lse, void* stream);
@@ -811,6 +880,12 @@ int ttv_codebook_histogram(const int32_t* indices, int n, int64_t* counts, int c
  * grad_c[i] = sign(recon - target) / (sizes[c] * n_clips) in `dtype` (grad NULL = value only).  Host arrays of device pointers. */
 int ttv_l1_loss(void* const* recon, void* const* target, void* const* grad, const int32_t* sizes, int n_clips, int dtype, float* loss,
                 void* stream);
+/* Deterministic sibling (see ttv_set_deterministic).  Partial layout: fp32 [clip][block], blocks per clip = scratch bytes / (4 * n_clips)
+ * for n_clips <= TTV_MAX_CLIPS_PER_LAUNCH; a partial is the block's sum of |recon - target| times 1 / (sizes[clip] * n_clips).  More
+ * clips run in groups of TTV_MAX_CLIPS_PER_LAUNCH that reuse the scratch (the size is the largest group's). */
+int64_t ttv_l1_loss_det_scratch_bytes(const int32_t* sizes, int n_clips);
+int ttv_l1_loss_det(void* const* recon, void* const* target, void* const* grad, const int32_t* sizes, int n_clips, int dtype, float* loss,
+                    void* scratch, int64_t scratch_bytes, void* stream);
 
 /* The loader's tail on the device (dataset/video_dataset.py:116-119: ToDtype(scale=True) + Normalize(0.5, 0.5) on channel-first
  * frames): decoded frames uint8 [T,H,W,3] (device memory, what the decoder / a shard hands over) -> clip [3,T,H,W] in `dtype`,
@@ -855,6 +930,12 @@ int ttv_recon_panels_u8(void* const* target, void* const* recon, const int32_t* 
  * PSNR = 10 log10(4 * acc[1] / acc[0]) is finished on the host (one read when the score is wanted, none per step). */
 int ttv_sq_err_accumulate(void* const* recon, void* const* target, const int32_t* sizes, int n_clips, int dtype, int clamp, double* acc,
                           void* stream);
+/* Deterministic sibling (see ttv_set_deterministic).  Partial layout: double [clip][block][2] = (the block's sum of squared errors,
+ * formed in fp32 as with the mode off; the clip's element count in its block 0 and zero in its other blocks), blocks per clip =
+ * scratch bytes / (16 * n_clips) for n_clips <= TTV_MAX_CLIPS_PER_LAUNCH; groups as for ttv_l1_loss_det. */
+int64_t ttv_sq_err_accumulate_det_scratch_bytes(const int32_t* sizes, int n_clips);
+int ttv_sq_err_accumulate_det(void* const* recon, void* const* target, const int32_t* sizes, int n_clips, int dtype, int clamp, double* acc,
+                              void* scratch, int64_t scratch_bytes, void* stream);
 
 /* SSIM statistic of the evaluation loop (model/metrics/eval_metrics.py:20-21,32-37: x.clamp(-1, 1), CTHW -> TCHW, torchmetrics
  * StructuralSimilarityIndexMeasure(data_range=2) = running sum of per-frame SSIM + frame count): for up to

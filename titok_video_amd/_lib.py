@@ -298,6 +298,8 @@ SYMBOLS = {
     "ttv_rmsnorm_backward": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, f32, C.c_int, vp]),
     "ttv_attention_backward": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int,
                                          C.c_int, C.c_int, C.c_int, vp, vp]),
+    "ttv_attention_backward_qlim": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int,
+                                              C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "ttv_attention_lse": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "ttv_codebook_histogram": (C.c_int, [vp, C.c_int, vp, C.c_int, vp]),
     "ttv_rope_table_build": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp]),
@@ -346,6 +348,29 @@ SYMBOLS = {
     "ttv_vjepa_layernorm": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_float, vp, vp, C.c_float, vp, C.c_int, vp, C.c_int, vp]),
     "ttv_vjepa_linear": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp]),
     "ttv_vjepa_pool_attention": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
+    # deterministic mode: the process-wide switch, the siblings with scratch of the ops that have no workspace argument, and the tower
+    # backward's three small reductions on their own (tests)
+    "ttv_set_deterministic": (C.c_int, [C.c_int]),
+    "ttv_get_deterministic": (C.c_int, []),
+    "ttv_vq_lookup_backward_det_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "ttv_vq_lookup_backward_det": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int64, vp]),
+    "ttv_rmsnorm_backward_det_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "ttv_rmsnorm_backward_chain_det_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "ttv_rmsnorm_backward_chain_det": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_float, vp, C.c_int,
+                                                  C.c_int, C.c_int, C.c_float, C.c_int, vp, C.c_int64, vp]),
+    "ttv_rmsnorm_backward_det": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, f32, C.c_int, vp, vp, vp, vp,
+                                            C.c_int64, vp]),
+    "ttv_colsum_det_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "ttv_sumall_det_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "ttv_outer_small_det_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "ttv_colsum_accumulate": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int64, vp]),
+    "ttv_sumall_accumulate": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp, vp, C.c_int64, vp]),
+    "ttv_outer_small_accumulate": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp,
+                                              C.c_int64, vp]),
+    "ttv_l1_loss_det_scratch_bytes": (C.c_int64, [vp, C.c_int]),
+    "ttv_l1_loss_det": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int64, vp]),
+    "ttv_sq_err_accumulate_det_scratch_bytes": (C.c_int64, [vp, C.c_int]),
+    "ttv_sq_err_accumulate_det": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int64, vp]),
     "ttv_debug_set": (C.c_int, [C.c_int]),
     "ttv_debug_stamps": (C.c_int, [vp]),
     "ttv_prof_begin": (C.c_int, [C.c_int, C.c_int]),
@@ -370,8 +395,41 @@ def lib():
                 for name, (res, args) in SYMBOLS.items():
                     fn = getattr(handle, name)
                     fn.restype, fn.argtypes = res, args
+                # TTV_DETERMINISTIC=1: the process starts in deterministic mode (set_deterministic() changes it later)
+                if switches.flag("TTV_DETERMINISTIC", False):
+                    handle.ttv_set_deterministic(1)
                 _lib = handle
     return _lib
+
+
+def set_deterministic(flag: bool) -> bool:
+    """Fixed-order sums in place of every float atomic of the training path (ttv_set_deterministic); returns the previous setting."""
+    return bool(lib().ttv_set_deterministic(1 if flag else 0))
+
+
+def is_deterministic() -> bool:
+    return bool(lib().ttv_get_deterministic())
+
+
+class DetScratch:
+    """Device scratch for the block partials of a *_det entry point: one tensor per (device, stream), grown as needed and kept.
+    A launch and its fold are ordered on their stream, so calls on one stream share a buffer safely and calls on two streams never
+    do.  While a graph is being captured nothing is kept: the tensor comes from the graph's own pool and stays there, so an eager
+    call never writes into memory a replay uses."""
+
+    def __init__(self):
+        self._bufs = {}
+
+    def get(self, nbytes: int, device) -> torch.Tensor:
+        device = torch.device(device)
+        stream = torch.cuda.current_stream(device)
+        if torch.cuda.is_current_stream_capturing():
+            return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+        key = (device.index if device.index is not None else torch.cuda.current_device(), stream.cuda_stream)
+        buf = self._bufs.get(key)
+        if buf is None or buf.numel() < nbytes:
+            buf = self._bufs[key] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+        return buf
 
 
 def check(rc: int, what: str) -> None:

@@ -31,6 +31,9 @@ bool ttv_sw_attn_pipe() { static const bool v = ttv_env_flag("TTV_ATTN_PIPE", fa
 static bool sw_dec_l0_const() { static const bool v = ttv_env_flag("TTV_DEC_L0_CONST", true); return v; }
 static bool sw_enc_last_qkv_skip() { static const bool v = ttv_env_flag("TTV_ENC_LAST_QKV_SKIP", true); return v; }
 float ttv_sw_attn_thr() { static const float v = ttv_env_float("TTV_ATTN_THR", 8.0f); return v; }   // log2 units; 0 = exact running maximum
+// deterministic mode: process-wide (not per thread: a training step's launches come from whichever thread runs it), read at launch time
+static int g_ttv_det = 0;
+bool ttv_det() { return __atomic_load_n(&g_ttv_det, __ATOMIC_RELAXED) != 0; }
 thread_local int g_ttv_debug = 0;     // per host thread: a thread that forces a kernel variant (tests, A/B tools) does not change what another thread launches
 long long* g_ttv_stamps = nullptr;   // diagnostics: device buffer for in-kernel clock stamps (ttv_debug_stamps)
 static hipEvent_t* g_prof_start = nullptr;
@@ -479,9 +482,25 @@ int ttv_vq_lookup(const void* codebook, int dtype, int ldc, const int32_t* indic
 }
 
 int ttv_vq_lookup_backward(const void* dcodes, int dtype, int ld, const int32_t* indices, int rows, int C, float* dcodebook, int ldc, void* stream) {
+  TTV_CHECK_ARG(!ttv_det(), "vq_lookup_backward: deterministic mode is on and this entry point adds with atomics: call ttv_vq_lookup_backward_det");
   TTV_CHECK_ARG(rows == 0 || (dcodes && indices && dcodebook), "vq_lookup_backward: null buffer");
   TTV_CHECK_ARG(ld >= C && ldc >= C, "vq_lookup_backward: leading dims smaller than the codebook dim");
   return ttvk_vq_lookup_bwd(dcodes, dtype, ld, indices, rows, C, dcodebook, ldc, (hipStream_t)stream);
+}
+
+int64_t ttv_vq_lookup_backward_det_scratch_bytes(int rows, int N, int C) {
+  if (rows < 0 || N < 1 || C < 1 || C > 256) { ttv_set_error("vq_lookup_backward_det_scratch_bytes: %d rows, %d entries of dim %d", rows, N, C); return -1; }
+  return 0;      // an owner per codebook entry: no partials
+}
+
+int ttv_vq_lookup_backward_det(const void* dcodes, int dtype, int ld, const int32_t* indices, int rows, int N, int C, float* dcodebook, int ldc,
+                               void* scratch, int64_t scratch_bytes, void* stream) {
+  (void)scratch;
+  TTV_CHECK_ARG(scratch_bytes >= 0, "vq_lookup_backward_det: negative scratch size");
+  TTV_CHECK_ARG(rows == 0 || (dcodes && indices && dcodebook), "vq_lookup_backward_det: null buffer");
+  TTV_CHECK_ARG(ld >= C && ldc >= C, "vq_lookup_backward_det: leading dims smaller than the codebook dim");
+  if (!ttv_det()) return ttvk_vq_lookup_bwd(dcodes, dtype, ld, indices, rows, C, dcodebook, ldc, (hipStream_t)stream);
+  return ttvk_vq_lookup_bwd_det(dcodes, dtype, ld, indices, rows, N, C, dcodebook, ldc, (hipStream_t)stream);
 }
 
 int64_t ttv_vq_train_workspace_bytes(int rows, int N) {
@@ -909,9 +928,68 @@ int ttv_rope_table_build(const float* base_cos, const float* base_sin, int n_ids
 int ttv_l1_loss(void* const* recon, void* const* target, void* const* grad, const int32_t* sizes, int n_clips, int dtype, float* loss,
                 void* stream) {
   // loss must be zeroed by the caller; clips are processed in groups of TTV_MAX_CLIPS_PER_LAUNCH
+  TTV_CHECK_ARG(!ttv_det(), "l1_loss: deterministic mode is on and this entry point has no scratch for the block partials: call ttv_l1_loss_det");
   return for_clip_groups(n_clips, [&](int c0, int n) {
-    return ttvk_l1_loss(recon + c0, target + c0, grad ? grad + c0 : nullptr, sizes + c0, n, n_clips, dtype, loss, (hipStream_t)stream);
+    return ttvk_l1_loss(recon + c0, target + c0, grad ? grad + c0 : nullptr, sizes + c0, n, n_clips, dtype, loss, (hipStream_t)stream, nullptr);
   });
+}
+
+static int64_t clips_det_bytes(const int32_t* sizes, int n_clips, bool l1, const char* what) {
+  if (n_clips < 0 || (n_clips > 0 && !sizes)) { ttv_set_error("%s: bad argument", what); return -1; }
+  for (int i = 0; i < n_clips; ++i)
+    if (sizes[i] <= 0) { ttv_set_error("%s: empty clip", what); return -1; }
+  return ttvk_det_clips_bytes(sizes, n_clips, l1);
+}
+int64_t ttv_l1_loss_det_scratch_bytes(const int32_t* sizes, int n_clips) { return clips_det_bytes(sizes, n_clips, true, "l1_loss_det_scratch_bytes"); }
+int64_t ttv_sq_err_accumulate_det_scratch_bytes(const int32_t* sizes, int n_clips) { return clips_det_bytes(sizes, n_clips, false, "sq_err_accumulate_det_scratch_bytes"); }
+
+int ttv_l1_loss_det(void* const* recon, void* const* target, void* const* grad, const int32_t* sizes, int n_clips, int dtype, float* loss,
+                    void* scratch, int64_t scratch_bytes, void* stream) {
+  const DetScratch det = {scratch, scratch_bytes};
+  return for_clip_groups(n_clips, [&](int c0, int n) {
+    return ttvk_l1_loss(recon + c0, target + c0, grad ? grad + c0 : nullptr, sizes + c0, n, n_clips, dtype, loss, (hipStream_t)stream, &det);
+  });
+}
+
+int ttv_sq_err_accumulate_det(void* const* recon, void* const* target, const int32_t* sizes, int n_clips, int dtype, int clamp, double* acc,
+                              void* scratch, int64_t scratch_bytes, void* stream) {
+  const DetScratch det = {scratch, scratch_bytes};
+  return for_clip_groups(n_clips, [&](int c0, int n) {
+    return ttvk_sq_err(recon + c0, target + c0, sizes + c0, n, dtype, clamp, acc, (hipStream_t)stream, &det);
+  });
+}
+
+// The tower backward's three small reductions on their own (tests: both modes; the scratch is looked at in deterministic mode only)
+int64_t ttv_colsum_det_scratch_bytes(int rows, int n) {
+  if (rows < 0 || n < 1) { ttv_set_error("colsum_det_scratch_bytes: %d rows, %d columns", rows, n); return -1; }
+  return ttvk_det_colsum_bytes(rows, n);
+}
+int64_t ttv_sumall_det_scratch_bytes(int rows, int n) {
+  if (rows < 0 || n < 1) { ttv_set_error("sumall_det_scratch_bytes: %d rows, %d columns", rows, n); return -1; }
+  return ttvk_det_sumall_bytes((long)rows * n);
+}
+int64_t ttv_outer_small_det_scratch_bytes(int rows, int C, int d) {
+  if (rows < 0 || C < 1 || C > TTV_MAX_TOKEN || d < 1) { ttv_set_error("outer_small_det_scratch_bytes: %d rows, C %d, d %d", rows, C, d); return -1; }
+  return ttvk_det_outer_small_bytes(rows, C, d);
+}
+int ttv_colsum_accumulate(const void* a, int dtype, int lda, const int32_t* rows_map, int rows, int n, float* out, void* scratch,
+                          int64_t scratch_bytes, void* stream) {
+  TTV_CHECK_ARG(rows >= 0 && n >= 1 && lda >= n && (rows == 0 || (a && out)), "colsum_accumulate: bad argument");
+  const DetScratch det = {scratch, scratch_bytes};
+  return ttvk_colsum(a, dtype, lda, rows_map, rows, n, out, (hipStream_t)stream, &det);
+}
+int ttv_sumall_accumulate(const void* a, int dtype, int lda, int rows, int n, float scale, float* out, void* scratch, int64_t scratch_bytes,
+                          void* stream) {
+  TTV_CHECK_ARG(rows >= 0 && n >= 1 && lda >= n && (rows == 0 || (a && out)), "sumall_accumulate: bad argument");
+  const DetScratch det = {scratch, scratch_bytes};
+  return ttvk_sumall(a, dtype, lda, nullptr, rows, n, nullptr, scale, out, (hipStream_t)stream, &det);
+}
+int ttv_outer_small_accumulate(const void* a, int a_dtype, int lda, int C, const void* b, int b_dtype, int ldb, float* dw, int lddw,
+                               int transpose_out, int rows, int d, void* scratch, int64_t scratch_bytes, void* stream) {
+  TTV_CHECK_ARG(rows >= 0 && d >= 1 && d <= 1024 && lda >= C && ldb >= d && (rows == 0 || (a && b && dw)), "outer_small_accumulate: bad argument");
+  TTV_CHECK_ARG(lddw >= (transpose_out ? C : d), "outer_small_accumulate: leading dim of dw");
+  const DetScratch det = {scratch, scratch_bytes};
+  return ttvk_outer_small(a, a_dtype, lda, C, b, b_dtype, ldb, nullptr, dw, lddw, transpose_out, rows, d, (hipStream_t)stream, &det);
 }
 
 int ttv_clip_from_u8(const void* frames_thwc, int T, int H, int W, void* clip_cthw, int dtype, void* stream) {
@@ -925,7 +1003,8 @@ int ttv_clip_resample_u8(void* const* frames_thwc, void* const* clips_cthw, cons
 
 int ttv_sq_err_accumulate(void* const* recon, void* const* target, const int32_t* sizes, int n_clips, int dtype, int clamp, double* acc,
                           void* stream) {
-  return for_clip_groups(n_clips, [&](int c0, int n) { return ttvk_sq_err(recon + c0, target + c0, sizes + c0, n, dtype, clamp, acc, (hipStream_t)stream); });
+  TTV_CHECK_ARG(!ttv_det(), "sq_err_accumulate: deterministic mode is on and this entry point has no scratch for the block partials: call ttv_sq_err_accumulate_det");
+  return for_clip_groups(n_clips, [&](int c0, int n) { return ttvk_sq_err(recon + c0, target + c0, sizes + c0, n, dtype, clamp, acc, (hipStream_t)stream, nullptr); });
 }
 
 int64_t ttv_ssim_workspace_bytes(const int32_t* dims, int n_clips) { return ttvk_ssim_workspace_bytes(dims, n_clips); }
@@ -1057,6 +1136,9 @@ int ttv_debug_set(int flags) {
   g_ttv_debug = flags;
   return TTV_OK;
 }
+
+int ttv_set_deterministic(int on) { return __atomic_exchange_n(&g_ttv_det, on ? 1 : 0, __ATOMIC_RELAXED); }
+int ttv_get_deterministic(void) { return ttv_det() ? 1 : 0; }
 
 int ttv_debug_stamps(void* device_buffer) {
   g_ttv_stamps = (long long*)device_buffer;

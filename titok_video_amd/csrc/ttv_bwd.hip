@@ -19,8 +19,44 @@
 
 #define BW_MAX_ITERS 4
 
+// ------------------------------------------------------------------------------------------------ deterministic mode: the fold
+// Second stage of every fixed-order row reduction: part is [nblocks][n] (T = float, double for the PSNR sums), written by the
+// DET form of the reducing kernel with plain stores.  One thread per element adds its partials in ascending block index, starting from
+// block 0's, and then the total onto the destination with a plain load / add / store (the destination is accumulated into).
+// Element e lives at dst[(e / inner) * stride_outer + (e % inner) * stride_inner].
+template <typename T>
+__global__ __launch_bounds__(256) void k_det_fold(const T* __restrict__ part, int nblocks, int n, int inner, long stride_outer,
+                                                  long stride_inner, T* __restrict__ dst) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  T sum = part[e];
+  int b = 1;
+  for (; b + 8 <= nblocks; b += 8) {      // eight loads in flight, added one after the other
+    T v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = part[(size_t)(b + u) * n + e];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) sum += v[u];
+  }
+  for (; b < nblocks; ++b) sum += part[(size_t)b * n + e];
+  T* p = dst + (long)(e / inner) * stride_outer + (long)(e % inner) * stride_inner;
+  *p = *p + sum;
+}
+template <typename T>
+static int det_fold(const void* part, int nblocks, int n, int inner, long stride_outer, long stride_inner, T* dst, hipStream_t s) {
+  hipLaunchKernelGGL((k_det_fold<T>), dim3(ttv_cdiv(n, 256)), dim3(256), 0, s, (const T*)part, nblocks, n, inner, stride_outer, stride_inner, dst);
+  TTV_CHECK_LAUNCH("det_fold");
+  return TTV_OK;
+}
+// the scratch a deterministic launch needs: present, 16-byte aligned, large enough - checked before anything is launched
+#define TTV_CHECK_DET(det_, need_, what_)                                                                                         \
+  TTV_CHECK_ARG((det_) && (det_)->p && ((uintptr_t)(det_)->p % 16 == 0) && (det_)->bytes >= (int64_t)(need_),                      \
+                what_ ": deterministic mode needs %lld bytes of 16-byte aligned scratch for its block partials, the caller handed over %lld", \
+                (long long)(need_), (long long)((det_) ? (det_)->bytes : 0))
+
 // ------------------------------------------------------------------------------------------------ rmsnorm backward
-template <typename TX, typename TG, typename TO>
+// DET: the block's gain partial goes to dgain[block][d] (the caller passes the scratch) instead of one atomicAdd per column
+template <typename TX, typename TG, typename TO, bool DET>
 __global__ __launch_bounds__(256) void k_rmsnorm_bwd(const TX* __restrict__ x, int ldx, const int* __restrict__ x_rows,
                                                      const TG* __restrict__ dy, int lddy, const int* __restrict__ dy_rows,
                                                      const float* __restrict__ gain, TO* __restrict__ dx, int lddx,
@@ -109,18 +145,35 @@ __global__ __launch_bounds__(256) void k_rmsnorm_bwd(const TX* __restrict__ x, i
       if (c < d) *reinterpret_cast<f32x4*>(&red[wave][c]) = (f32x4){dg[it][0], dg[it][1], dg[it][2], dg[it][3]};
     }
     __syncthreads();
-    for (int c = threadIdx.x; c < d; c += 256) atomicAdd(dgain + c, red[0][c] + red[1][c] + red[2][c] + red[3][c]);
+    for (int c = threadIdx.x; c < d; c += 256) {
+      const float v = red[0][c] + red[1][c] + red[2][c] + red[3][c];
+      if (DET) dgain[(size_t)blockIdx.x * d + c] = v; else atomicAdd(dgain + c, v);
+    }
   }
 }
 
+// rows per wave and blocks of the two norm-backward kernels (one geometry for both modes)
+static inline int rms_bwd_rpw(int rows) {
+  const int rpw = ttv_cdiv(rows, 4 * 512);   // ~2 blocks per CU: the row loop is latency-bound, two waves per SIMD overlap it
+  return rpw < 1 ? 1 : rpw;
+}
+static inline int rms_bwd_blocks(int rows) { return ttv_cdiv(rows, 4 * rms_bwd_rpw(rows)); }
+int64_t ttvk_det_rms_bytes(int rows, int d) { return rows > 0 && d > 0 ? (int64_t)rms_bwd_blocks(rows) * d * 4 : 0; }
+
 template <typename TX, typename TG, typename TO>
 static int launch_rms_bwd(const void* x, int ldx, const int* xr, const void* dy, int lddy, const int* dyr, const float* gain, void* dx,
-                          int lddx, const int* dxr, int acc, float* dgain, int rows, int d, float eps, hipStream_t s) {
+                          int lddx, const int* dxr, int acc, float* dgain, int rows, int d, float eps, hipStream_t s, const DetScratch* det) {
   // few, fat blocks: the gain gradient is one atomicAdd per column per BLOCK onto the same `d` addresses, so the block count
   // (not the row count) sets the contention; ~256 blocks keep every CU busy
-  int rpw = ttv_cdiv(rows, 4 * 512);   // ~2 blocks per CU: the row loop is latency-bound, two waves per SIMD overlap it
-  if (rpw < 1) rpw = 1;
-  hipLaunchKernelGGL((k_rmsnorm_bwd<TX, TG, TO>), dim3(ttv_cdiv(rows, 4 * rpw)), dim3(256), 0, s, (const TX*)x, ldx, xr, (const TG*)dy,
+  const int rpw = rms_bwd_rpw(rows), nb = rms_bwd_blocks(rows);
+  if (dgain && ttv_det()) {
+    TTV_CHECK_DET(det, ttvk_det_rms_bytes(rows, d), "rmsnorm_bwd");
+    hipLaunchKernelGGL((k_rmsnorm_bwd<TX, TG, TO, true>), dim3(nb), dim3(256), 0, s, (const TX*)x, ldx, xr, (const TG*)dy,
+                       lddy, dyr, gain, (TO*)dx, lddx, dxr, acc, (float*)det->p, rows, d, eps, rpw);
+    TTV_CHECK_LAUNCH("rmsnorm_bwd");
+    return det_fold<float>(det->p, nb, d, d, 0, 1, dgain, s);
+  }
+  hipLaunchKernelGGL((k_rmsnorm_bwd<TX, TG, TO, false>), dim3(nb), dim3(256), 0, s, (const TX*)x, ldx, xr, (const TG*)dy,
                      lddy, dyr, gain, (TO*)dx, lddx, dxr, acc, dgain, rows, d, eps, rpw);
   TTV_CHECK_LAUNCH("rmsnorm_bwd");
   return TTV_OK;
@@ -153,7 +206,8 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
   return quad16_sum(v);        // lanes ^ 16, then ^ 32, on v_permlane16_swap / v_permlane32_swap (same association as the two ds_bpermute steps it replaces)
 }
 
-template <typename T, typename YT, int ITERS>
+// DET: dgain1 / dgain2 are the [block][d] partial arrays of the two gains
+template <typename T, typename YT, int ITERS, bool DET>
 __global__ __launch_bounds__(256) void k_rmsnorm_bwd_chain(const T* __restrict__ x, int ldx, const T* __restrict__ dy, int lddy,
                                                            const float* __restrict__ gain1, float* __restrict__ dgain1, float* dx, int lddx,
                                                            const YT* __restrict__ y, int ldy, const float* __restrict__ gain2,
@@ -287,31 +341,48 @@ __global__ __launch_bounds__(256) void k_rmsnorm_bwd_chain(const T* __restrict__
       if (c < d) *reinterpret_cast<f32x4*>(&red[wave][c]) = pass ? dg2[it] : dg1[it];
     }
     __syncthreads();
-    for (int c = threadIdx.x; c < d; c += 256) atomicAdd(dgain + c, red[0][c] + red[1][c] + red[2][c] + red[3][c]);
+    for (int c = threadIdx.x; c < d; c += 256) {
+      const float v = red[0][c] + red[1][c] + red[2][c] + red[3][c];
+      if (DET) dgain[(size_t)blockIdx.x * d + c] = v; else atomicAdd(dgain + c, v);
+    }
   }
 }
 
 template <typename T, typename YT, int ITERS>
 static void launch_rms_chain(const void* x, int ldx, const void* dy, int lddy, const float* gain1, float* dgain1, float* dx, int lddx,
                              const void* y, int ldy, const float* gain2, float* dgain2, float out_scale, void* cast_out, int ldc, int rows,
-                             int d, float eps, hipStream_t s) {
-  int rpw = ttv_cdiv(rows, 4 * 512);
-  if (rpw < 1) rpw = 1;
-  hipLaunchKernelGGL((k_rmsnorm_bwd_chain<T, YT, ITERS>), dim3(ttv_cdiv(rows, 4 * rpw)), dim3(256), 0, s, (const T*)x, ldx, (const T*)dy, lddy,
-                     gain1, dgain1, dx, lddx, (const YT*)y, ldy, gain2, dgain2, out_scale, (T*)cast_out, ldc, rows, d, eps, rpw);
+                             int d, float eps, hipStream_t s, bool det) {
+  const int rpw = rms_bwd_rpw(rows);
+  if (det)
+    hipLaunchKernelGGL((k_rmsnorm_bwd_chain<T, YT, ITERS, true>), dim3(rms_bwd_blocks(rows)), dim3(256), 0, s, (const T*)x, ldx, (const T*)dy, lddy,
+                       gain1, dgain1, dx, lddx, (const YT*)y, ldy, gain2, dgain2, out_scale, (T*)cast_out, ldc, rows, d, eps, rpw);
+  else
+    hipLaunchKernelGGL((k_rmsnorm_bwd_chain<T, YT, ITERS, false>), dim3(rms_bwd_blocks(rows)), dim3(256), 0, s, (const T*)x, ldx, (const T*)dy, lddy,
+                       gain1, dgain1, dx, lddx, (const YT*)y, ldy, gain2, dgain2, out_scale, (T*)cast_out, ldc, rows, d, eps, rpw);
 }
 
 // y_dt: dtype of the second norm's input y (TTV_F32, or TTV_BF16 with dt == TTV_BF16: the bf16 towers' tape keeps the KEEL sums in bf16)
-int ttvk_rmsnorm_bwd_chain(const void* x, int ldx, const void* dy, int lddy, const float* gain1, float* dgain1, float* dx, int lddx,
-                           const void* y, int y_dt, int ldy, const float* gain2, float* dgain2, float out_scale, void* cast_out, int ldc, int rows,
-                           int d, float eps, int dt, hipStream_t s) {
+int ttvk_rmsnorm_bwd_chain(const void* x, int ldx, const void* dy, int lddy, const float* gain1, float* dgain1_dst, float* dx, int lddx,
+                           const void* y, int y_dt, int ldy, const float* gain2, float* dgain2_dst, float out_scale, void* cast_out, int ldc, int rows,
+                           int d, float eps, int dt, hipStream_t s, const DetScratch* scratch) {
   if (rows == 0) return TTV_OK;
   TTV_CHECK_ARG(d % 4 == 0 && d <= 1024, "rmsnorm_bwd_chain: width");
   TTV_CHECK_ARG(dt == TTV_BF16 || dt == TTV_F32, "rmsnorm_bwd_chain: dtype");
   TTV_CHECK_ARG(!y || gain2, "rmsnorm_bwd_chain: second norm needs its gain");
   TTV_CHECK_ARG(!y || y_dt == TTV_F32 || (y_dt == TTV_BF16 && dt == TTV_BF16), "rmsnorm_bwd_chain: y is fp32, or bf16 beside bf16 rows");
   const int iters = ttv_cdiv(d, 256);
-#define RC(T, YT, I) launch_rms_chain<T, YT, I>(x, ldx, dy, lddy, gain1, dgain1, dx, lddx, y, ldy, gain2, dgain2, out_scale, cast_out, ldc, rows, d, eps, s)
+  // deterministic mode: the kernel writes the block partials of gain 1 to the scratch's first ttvk_det_rms_bytes(), those of gain 2
+  // behind them; two folds add them onto the gain gradients
+  const bool want2 = y && dgain2_dst;
+  const bool det = (dgain1_dst || want2) && ttv_det();
+  float *dgain1 = dgain1_dst, *dgain2 = dgain2_dst;
+  const int64_t one = ttvk_det_rms_bytes(rows, d);
+  if (det) {
+    TTV_CHECK_DET(scratch, 2 * one, "rmsnorm_bwd_chain");
+    dgain1 = dgain1_dst ? (float*)scratch->p : nullptr;
+    dgain2 = want2 ? (float*)((char*)scratch->p + one) : nullptr;
+  }
+#define RC(T, YT, I) launch_rms_chain<T, YT, I>(x, ldx, dy, lddy, gain1, dgain1, dx, lddx, y, ldy, gain2, dgain2, out_scale, cast_out, ldc, rows, d, eps, s, det)
   if (dt == TTV_BF16 && y && y_dt == TTV_BF16) {
     if (iters == 1) RC(bf16_t, bf16_t, 1); else if (iters == 2) RC(bf16_t, bf16_t, 2); else RC(bf16_t, bf16_t, 4);
   } else if (dt == TTV_BF16) {
@@ -321,16 +392,21 @@ int ttvk_rmsnorm_bwd_chain(const void* x, int ldx, const void* dy, int lddy, con
   }
 #undef RC
   TTV_CHECK_LAUNCH("rmsnorm_bwd_chain");
+  if (det) {
+    const int nb = rms_bwd_blocks(rows);
+    if (dgain1) TTV_TRY(det_fold<float>(dgain1, nb, d, d, 0, 1, dgain1_dst, s));
+    if (dgain2) TTV_TRY(det_fold<float>(dgain2, nb, d, d, 0, 1, dgain2_dst, s));
+  }
   return TTV_OK;
 }
 
 // x dtype, dy dtype, dx dtype codes: TTV_BF16 / TTV_F32
 int ttvk_rmsnorm_bwd(const void* x, int x_dt, int ldx, const int* xr, const void* dy, int dy_dt, int lddy, const int* dyr,
                      const float* gain, void* dx, int dx_dt, int lddx, const int* dxr, int acc, float* dgain, int rows, int d, float eps,
-                     hipStream_t s) {
+                     hipStream_t s, const DetScratch* det) {
   if (rows == 0) return TTV_OK;
   TTV_CHECK_ARG(d % 4 == 0 && d <= 1024, "rmsnorm_bwd: width");
-#define RB(TX, TG, TO) return launch_rms_bwd<TX, TG, TO>(x, ldx, xr, dy, lddy, dyr, gain, dx, lddx, dxr, acc, dgain, rows, d, eps, s)
+#define RB(TX, TG, TO) return launch_rms_bwd<TX, TG, TO>(x, ldx, xr, dy, lddy, dyr, gain, dx, lddx, dxr, acc, dgain, rows, d, eps, s, det)
   const int key = x_dt * 4 + dy_dt * 2 + dx_dt;
   switch (key) {
     case 0: RB(bf16_t, bf16_t, bf16_t);
@@ -350,7 +426,8 @@ int ttvk_rmsnorm_bwd(const void* x, int x_dt, int ldx, const int* xr, const void
 // thread -> column (grid.y tiles of 256 columns), block -> row range.  Eight rows in flight per thread (independent partial sums):
 // with one running sum the 128 rows of a block were 128 dependent load -> add steps and the launch took ~30 us whatever the batch
 // (latency, not bytes: 6 launches per training step); the partial sums are combined in a fixed order, rows past the end add zero.
-template <typename T>
+// DET: out is the [row block][n] partial array
+template <typename T, bool DET>
 __global__ __launch_bounds__(256) void k_colsum(const T* __restrict__ a, int lda, const int* __restrict__ rows_map, int rows, int n,
                                                 float* __restrict__ out, int rows_per_block) {
   const int c = blockIdx.y * 256 + threadIdx.x;
@@ -368,22 +445,35 @@ __global__ __launch_bounds__(256) void k_colsum(const T* __restrict__ a, int lda
 #pragma unroll
     for (int u = 0; u < 8; ++u) acc[u] += r + u < r1 ? v[u] : 0.f;
   }
-  atomicAdd(out + c, ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7])));
+  const float v = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+  if (DET) out[(size_t)blockIdx.x * n + c] = v; else atomicAdd(out + c, v);
 }
 
-int ttvk_colsum(const void* a, int dt, int lda, const int* rows_map, int rows, int n, float* out, hipStream_t s) {
+#define COLSUM_RPB 64
+int64_t ttvk_det_colsum_bytes(int rows, int n) { return rows > 0 && n > 0 ? (int64_t)ttv_cdiv(rows, COLSUM_RPB) * n * 4 : 0; }
+
+int ttvk_colsum(const void* a, int dt, int lda, const int* rows_map, int rows, int n, float* out, hipStream_t s, const DetScratch* det) {
   if (rows == 0 || n == 0 || !out) return TTV_OK;   // out == NULL: this parameter's gradient is not wanted
   // narrow matrices (n <= 256: one column tile) are latency-bound per block: shorter row ranges, more blocks
-  const int rpb = 64;
+  const int rpb = COLSUM_RPB;
   dim3 grid(ttv_cdiv(rows, rpb), ttv_cdiv(n, 256));
-  if (dt == TTV_BF16) hipLaunchKernelGGL((k_colsum<bf16_t>), grid, dim3(256), 0, s, (const bf16_t*)a, lda, rows_map, rows, n, out, rpb);
-  else hipLaunchKernelGGL((k_colsum<float>), grid, dim3(256), 0, s, (const float*)a, lda, rows_map, rows, n, out, rpb);
+  if (ttv_det()) {
+    TTV_CHECK_DET(det, ttvk_det_colsum_bytes(rows, n), "colsum");
+    float* part = (float*)det->p;
+    if (dt == TTV_BF16) hipLaunchKernelGGL((k_colsum<bf16_t, true>), grid, dim3(256), 0, s, (const bf16_t*)a, lda, rows_map, rows, n, part, rpb);
+    else hipLaunchKernelGGL((k_colsum<float, true>), grid, dim3(256), 0, s, (const float*)a, lda, rows_map, rows, n, part, rpb);
+    TTV_CHECK_LAUNCH("colsum");
+    return det_fold<float>(part, (int)grid.x, n, n, 0, 1, out, s);
+  }
+  if (dt == TTV_BF16) hipLaunchKernelGGL((k_colsum<bf16_t, false>), grid, dim3(256), 0, s, (const bf16_t*)a, lda, rows_map, rows, n, out, rpb);
+  else hipLaunchKernelGGL((k_colsum<float, false>), grid, dim3(256), 0, s, (const float*)a, lda, rows_map, rows, n, out, rpb);
   TTV_CHECK_LAUNCH("colsum");
   return TTV_OK;
 }
 
 // sum of ALL elements (mask_token gradient pieces): out[0] += scale * sum(a[rows, 0:n])
-template <typename T>
+// DET: out is the [block] partial array
+template <typename T, bool DET>
 __global__ __launch_bounds__(256) void k_sumall(const T* __restrict__ a, int lda, const int* __restrict__ rows_map, int rows, int n,
                                                 const float* __restrict__ colw, float scale, float* __restrict__ out) {
   __shared__ float red[4];
@@ -397,17 +487,33 @@ __global__ __launch_bounds__(256) void k_sumall(const T* __restrict__ a, int lda
   acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, scale * (red[0] + red[1] + red[2] + red[3]));
+  if (threadIdx.x == 0) {
+    const float v = scale * (red[0] + red[1] + red[2] + red[3]);
+    if (DET) out[blockIdx.x] = v; else atomicAdd(out, v);
+  }
 }
 
+static inline int sumall_blocks(long total) {
+  const long b = (total + 255) / 256;
+  return (int)(b > 1024 ? 1024 : b);
+}
+int64_t ttvk_det_sumall_bytes(long total) { return total > 0 ? (int64_t)sumall_blocks(total) * 4 : 0; }
+
 int ttvk_sumall(const void* a, int dt, int lda, const int* rows_map, int rows, int n, const float* colw, float scale, float* out,
-                hipStream_t s) {
+                hipStream_t s, const DetScratch* det) {
   if (rows == 0 || n == 0 || !out) return TTV_OK;
-  long total = (long)rows * n;
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 1024) blocks = 1024;
-  if (dt == TTV_BF16) hipLaunchKernelGGL((k_sumall<bf16_t>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)a, lda, rows_map, rows, n, colw, scale, out);
-  else hipLaunchKernelGGL((k_sumall<float>), dim3(blocks), dim3(256), 0, s, (const float*)a, lda, rows_map, rows, n, colw, scale, out);
+  const long total = (long)rows * n;
+  const int blocks = sumall_blocks(total);
+  if (ttv_det()) {
+    TTV_CHECK_DET(det, ttvk_det_sumall_bytes(total), "sumall");
+    float* part = (float*)det->p;
+    if (dt == TTV_BF16) hipLaunchKernelGGL((k_sumall<bf16_t, true>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)a, lda, rows_map, rows, n, colw, scale, part);
+    else hipLaunchKernelGGL((k_sumall<float, true>), dim3(blocks), dim3(256), 0, s, (const float*)a, lda, rows_map, rows, n, colw, scale, part);
+    TTV_CHECK_LAUNCH("sumall");
+    return det_fold<float>(part, blocks, 1, 1, 0, 0, out, s);
+  }
+  if (dt == TTV_BF16) hipLaunchKernelGGL((k_sumall<bf16_t, false>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)a, lda, rows_map, rows, n, colw, scale, out);
+  else hipLaunchKernelGGL((k_sumall<float, false>), dim3(blocks), dim3(256), 0, s, (const float*)a, lda, rows_map, rows, n, colw, scale, out);
   TTV_CHECK_LAUNCH("sumall");
   return TTV_OK;
 }
@@ -1173,6 +1279,7 @@ int ttvk_wgrad(const void* dy, int lddy, const void* x, int ldx, float* dw, int 
   if (L == 0 || N == 0 || K == 0 || !dw) return TTV_OK;   // dw == NULL: frozen weight
   static const bool batch_env = ttv_env_flag("TTV_WGRAD_BATCHED", true);   // A/B
   if (!batch_env && batch) { TTV_TRY(ttvk_wgrad_flush(batch, s)); batch = nullptr; }
+  const bool det = ttv_det();
   if (dt == TTV_BF16 && N % 8 == 0 && K % 8 == 0 && lddy % 8 == 0 && ldx % 8 == 0) {
     // TTV_WGRAD_TILE64 is on when merely present, whatever its value: only a set variable reads the same under two defaults
     static const int wg_tile64 = ttv_env_int("TTV_WGRAD_TILE64", 0) == ttv_env_int("TTV_WGRAD_TILE64", 1) ? 1 : 0;
@@ -1210,6 +1317,10 @@ int ttvk_wgrad(const void* dy, int lddy, const void* x, int ldx, float* dw, int 
         hipLaunchKernelGGL(k_wgrad128_bf16<true>, grid, dim3(256 + 64 * WG_NL), WG_RING * WG_STAGE_BYTES, s, (const bf16_t*)dy, lddy, (const bf16_t*)x, ldx, dw, lddw, L, N, K,
                            tpb, part, tn, tk, splits);
         hipLaunchKernelGGL(k_wgrad_reduce, dim3(tn * tk * 64), dim3(256), 0, s, part, splits, dw, lddw, N, K, tn);
+      } else if (det) {
+        // no room for partial tiles: one token range per output tile, so that the kernel's atomicAdd is the address's only writer
+        hipLaunchKernelGGL(k_wgrad128_bf16<false>, dim3(tn * tk),dim3(256 + 64 * WG_NL), WG_RING * WG_STAGE_BYTES, s, (const bf16_t*)dy, lddy, (const bf16_t*)x, ldx, dw, lddw, L, N, K,
+                           ttv_cdiv(L, 64) * 64, nullptr, tn, tk, 1);
       } else {
         hipLaunchKernelGGL(k_wgrad128_bf16<false>, grid, dim3(256 + 64 * WG_NL), WG_RING * WG_STAGE_BYTES, s, (const bf16_t*)dy, lddy, (const bf16_t*)x, ldx, dw, lddw, L, N, K,
                            tpb, nullptr, tn, tk, splits);
@@ -1218,13 +1329,13 @@ int ttvk_wgrad(const void* dy, int lddy, const void* x, int ldx, float* dw, int 
       const int nb = ttv_cdiv(N, 64) * ttv_cdiv(K, 64);
       int splits = ttv_cdiv(2048, nb);   // aim at >= 2048 blocks
       if (splits > ttv_cdiv(L, 64)) splits = ttv_cdiv(L, 64);
-      if (splits < 1) splits = 1;
+      if (splits < 1 || det) splits = 1;   // deterministic mode: a single writer per address
       const int tpb = ttv_cdiv(ttv_cdiv(L, splits), 64) * 64;
       dim3 grid(ttv_cdiv(N, 64), ttv_cdiv(K, 64), ttv_cdiv(L, tpb));
       hipLaunchKernelGGL(k_wgrad_bf16, grid, dim3(256), 0, s, (const bf16_t*)dy, lddy, (const bf16_t*)x, ldx, dw, lddw, L, N, K, tpb);
     }
   } else if (dt == TTV_F32) {
-    const int tpb = 1024;
+    const int tpb = det ? L : 1024;      // deterministic mode: grid.z = 1, a single writer per address
     dim3 grid(ttv_cdiv(N, 16), ttv_cdiv(K, 16), ttv_cdiv(L, tpb));
     hipLaunchKernelGGL(k_wgrad_f32, grid, dim3(256), 0, s, (const float*)dy, lddy, (const float*)x, ldx, dw, lddw, L, N, K, tpb);
   } else {
@@ -1237,7 +1348,8 @@ int ttvk_wgrad(const void* dy, int lddy, const void* x, int ldx, float* dw, int 
 
 // small-N / small-K linear backward helpers for the d <-> token_size projections (encoder proj_out [C,d], decoder proj_in [d,C])
 // dW[c, f] += sum_r a[r, c] * b[r, f]  (a: [rows, C] fp32 or T with C <= 8;  b: [rows, d]) ; one wave per row chunk
-template <typename TA, typename TB>
+// DET: dw is the [row block][C][d] partial array (lddw and transpose_out are the fold's business)
+template <typename TA, typename TB, bool DET>
 __global__ __launch_bounds__(256) void k_outer_small(const TA* __restrict__ a, int lda, int C, const TB* __restrict__ b, int ldb,
                                                      const int* __restrict__ b_rows, float* __restrict__ dw, int lddw, int transpose_out,
                                                      int rows, int d, int rows_per_block) {
@@ -1266,26 +1378,45 @@ __global__ __launch_bounds__(256) void k_outer_small(const TA* __restrict__ a, i
     }
 #pragma unroll
     for (int c = 0; c < TTV_MAX_FSQ; ++c)
-      if (c < C) atomicAdd(transpose_out ? dw + (size_t)f * lddw + c : dw + (size_t)c * lddw + f, acc[c]);
+      if (c < C) {
+        if (DET) dw[((size_t)blockIdx.x * C + c) * d + f] = acc[c];
+        else atomicAdd(transpose_out ? dw + (size_t)f * lddw + c : dw + (size_t)c * lddw + f, acc[c]);
+      }
   }
 }
 
+#define OUTER_SMALL_RPB 32
+int64_t ttvk_det_outer_small_bytes(int rows, int C, int d) {
+  if (rows <= 0 || C <= 0 || d <= 0) return 0;
+  return (int64_t)ttv_cdiv(rows, OUTER_SMALL_RPB) * (C < TTV_MAX_FSQ ? C : TTV_MAX_FSQ) * d * 4;
+}
+
 int ttvk_outer_small(const void* a, int a_dt, int lda, int C, const void* b, int b_dt, int ldb, const int* b_rows, float* dw, int lddw,
-                     int transpose_out, int rows, int d, hipStream_t s) {
+                     int transpose_out, int rows, int d, hipStream_t s, const DetScratch* scratch) {
   if (rows == 0 || !dw) return TTV_OK;
   TTV_CHECK_ARG(C >= 1 && C <= TTV_MAX_TOKEN, "outer_small: C");
-  const int rpb = 32;
+  const int rpb = OUTER_SMALL_RPB;
   dim3 grid(ttv_cdiv(rows, rpb));
+  const bool det = ttv_det();
+  if (det) TTV_CHECK_DET(scratch, ttvk_det_outer_small_bytes(rows, C, d), "outer_small");
   // the kernel keeps TTV_MAX_FSQ partial sums per thread: wider tokens (the L2 quantiser's, up to TTV_MAX_TOKEN) go in column chunks
+  // (deterministic mode: each chunk's partials through the same scratch, its fold in front of the next chunk's launch)
   for (int c0 = 0; c0 < C; c0 += TTV_MAX_FSQ) {
     const int cn = C - c0 < TTV_MAX_FSQ ? C - c0 : TTV_MAX_FSQ;
     float* dwc = transpose_out ? dw + c0 : dw + (size_t)c0 * lddw;
-#define OS(TA, TB) hipLaunchKernelGGL((k_outer_small<TA, TB>), grid, dim3(256), 0, s, (const TA*)a + c0, lda, cn, (const TB*)b, ldb, b_rows, dwc, lddw, transpose_out, rows, d, rpb)
+#define OS_(TA, TB, DET_, dst_) hipLaunchKernelGGL((k_outer_small<TA, TB, DET_>), grid, dim3(256), 0, s, (const TA*)a + c0, lda, cn, (const TB*)b, ldb, b_rows, dst_, lddw, transpose_out, rows, d, rpb)
+#define OS(TA, TB) do { if (det) OS_(TA, TB, true, (float*)scratch->p); else OS_(TA, TB, false, dwc); } while (0)
     if (a_dt == TTV_F32 && b_dt == TTV_F32) OS(float, float);
     else if (a_dt == TTV_F32 && b_dt == TTV_BF16) OS(float, bf16_t);
     else if (a_dt == TTV_BF16 && b_dt == TTV_F32) OS(bf16_t, float);
     else OS(bf16_t, bf16_t);
 #undef OS
+#undef OS_
+    if (det) {
+      TTV_CHECK_LAUNCH("outer_small");
+      // element (c, f) of the chunk: dw[c][f], or dw[f][c] when the output is transposed
+      TTV_TRY(det_fold<float>(scratch->p, (int)grid.x, cn * d, d, transpose_out ? 1 : lddw, transpose_out ? lddw : 1, dwc, s));
+    }
   }
   TTV_CHECK_LAUNCH("outer_small");
   return TTV_OK;
@@ -1375,7 +1506,9 @@ __device__ __forceinline__ int attn_bwd_query_rows(const int* __restrict__ qlim_
 }
 
 // naive fp32 backward: one wave per (query row, q-head); lane = head dim.  dk/dv accumulate with fp32 atomics into
-// [L, g] scratch (zeroed by the caller), dq is written directly.
+// [L, g] scratch (zeroed by the caller), dq is written directly.  ATOMIC_DKV = false (deterministic mode): dq only, the same
+// arithmetic; dk / dv then come from k_attn_bwd_f32_dkv below.
+template <bool ATOMIC_DKV>
 __global__ __launch_bounds__(256) void k_attn_bwd_f32(const float* __restrict__ qkvg, int ld, const float* __restrict__ dout, int ldd,
                                                       const float* __restrict__ lse, const float* __restrict__ delta,
                                                       const int* __restrict__ cu, const int* __restrict__ row_seq,
@@ -1404,10 +1537,47 @@ __global__ __launch_bounds__(256) void k_attn_bwd_f32(const float* __restrict__ 
     const float dp = wave_sum(dov * vv);
     const float ds = p * (dp - dl) * scale;
     dq += ds * kv;
-    atomicAdd(dkv + (size_t)j * 2 * gqa + kvh * 64 + lane, ds * q);
-    atomicAdd(dkv + (size_t)j * 2 * gqa + gqa + kvh * 64 + lane, p * dov);
+    if (ATOMIC_DKV) {
+      atomicAdd(dkv + (size_t)j * 2 * gqa + kvh * 64 + lane, ds * q);
+      atomicAdd(dkv + (size_t)j * 2 * gqa + gqa + kvh * 64 + lane, p * dov);
+    }
   }
   dqkvg[(size_t)t * ldg + h * 64 + lane] = dq;
+}
+
+// Deterministic dk / dv of the naive fp32 backward: one wave OWNS a (key row, kv-head) and adds the terms of the kernel above in a fixed
+// order - the sequence's query rows ascending, and for each the q-heads of the GQA group ascending (the rows attn_bwd_query_rows
+// leaves out are skipped, as there).  Same inputs, lse and delta; every term is formed by the same expressions.  dkv [L, 2g] is written,
+// not added to.
+__global__ __launch_bounds__(256) void k_attn_bwd_f32_dkv(const float* __restrict__ qkvg, int ld, const float* __restrict__ dout, int ldd,
+                                                          const float* __restrict__ lse, const float* __restrict__ delta,
+                                                          const int* __restrict__ cu, const int* __restrict__ row_seq, float* __restrict__ dkv,
+                                                          int total_rows, int hq, int hkv, float scale, const int* __restrict__ qlim_desc) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int idx = blockIdx.x * 4 + wave;
+  if (idx >= total_rows * hkv) return;
+  const int j = idx / hkv, kvh = idx % hkv;
+  const int d_model = hq * 64, gqa = hkv * 64, rep = hq / hkv;
+  const int seq = row_seq[j];
+  const int s0 = cu[seq], S = cu[seq + 1] - s0;
+  const int nq = attn_bwd_query_rows(qlim_desc, seq, s0, S);
+  const float kv = qkvg[(size_t)j * ld + 2 * d_model + kvh * 64 + lane];
+  const float vv = qkvg[(size_t)j * ld + 2 * d_model + gqa + kvh * 64 + lane];
+  float dk = 0.f, dv = 0.f;
+  for (int t = s0; t < s0 + nq; ++t)
+    for (int h = kvh * rep; h < (kvh + 1) * rep; ++h) {
+      const float q = qkvg[(size_t)t * ld + h * 64 + lane];
+      const float dov = dout[(size_t)t * ldd + h * 64 + lane];
+      const float l = lse[(size_t)t * hq + h], dl = delta[(size_t)t * hq + h];
+      const float sdot = wave_sum(q * kv) * scale;
+      const float p = expf(sdot - l);
+      const float dp = wave_sum(dov * vv);
+      const float ds = p * (dp - dl) * scale;
+      dk += ds * q;
+      dv += p * dov;
+    }
+  dkv[(size_t)j * 2 * gqa + kvh * 64 + lane] = dk;
+  dkv[(size_t)j * 2 * gqa + gqa + kvh * 64 + lane] = dv;
 }
 
 // ---- bf16 MFMA kernels.  LDS tiles are row-major [64 rows][64 cols] bf16 with 128-byte rows; the 16-byte chunk c of row r
@@ -1801,6 +1971,7 @@ int ttvk_attention_bwd(const void* qkvg, int ld, const void* o, int ldo, const v
                        const int* cu, const int* blocks64, int n_blocks64, const int* row_seq, void* dqkvg, int ldg, float* dkv_scratch,
                        int total_rows, int hq, int hkv, int dt, const float* rope_cs, hipStream_t s, int delta_ready, const int* qlim_desc) {
   if (total_rows == 0) return TTV_OK;
+  TTV_CHECK_ARG(hq >= 1 && hkv >= 1 && hq % hkv == 0, "attention_bwd: %d q-heads on %d kv-heads", hq, hkv);
   const float scale = 0.125f;
   const int d_model = hq * 64, gqa = hkv * 64;
   if (delta_ready) {
@@ -1814,8 +1985,14 @@ int ttvk_attention_bwd(const void* qkvg, int ld, const void* o, int ldo, const v
     TTV_CHECK_LAUNCH("attn_bwd");
   } else {
     TTV_CHECK_ARG(dkv_scratch && row_seq, "attention_bwd: fp32 path needs scratch and row map");
-    (void)hipMemsetAsync(dkv_scratch, 0, (size_t)total_rows * 2 * gqa * sizeof(float), s);
-    hipLaunchKernelGGL(k_attn_bwd_f32, dim3(ttv_cdiv(total_rows * hq, 4)), dim3(256), 0, s, (const float*)qkvg, ld, (const float*)dout, ldd, lse, delta, cu, row_seq, (float*)dqkvg, ldg, dkv_scratch, total_rows, hq, hkv, scale, qlim_desc);
+    if (ttv_det()) {
+      // dq as ever, dk / dv by an owner per (key row, kv-head): the same [L, 2g] scratch, written whole
+      hipLaunchKernelGGL(k_attn_bwd_f32<false>, dim3(ttv_cdiv(total_rows * hq, 4)), dim3(256), 0, s, (const float*)qkvg, ld, (const float*)dout, ldd, lse, delta, cu, row_seq, (float*)dqkvg, ldg, dkv_scratch, total_rows, hq, hkv, scale, qlim_desc);
+      hipLaunchKernelGGL(k_attn_bwd_f32_dkv, dim3(ttv_cdiv(total_rows * hkv, 4)), dim3(256), 0, s, (const float*)qkvg, ld, (const float*)dout, ldd, lse, delta, cu, row_seq, dkv_scratch, total_rows, hq, hkv, scale, qlim_desc);
+    } else {
+      (void)hipMemsetAsync(dkv_scratch, 0, (size_t)total_rows * 2 * gqa * sizeof(float), s);
+      hipLaunchKernelGGL(k_attn_bwd_f32<true>, dim3(ttv_cdiv(total_rows * hq, 4)), dim3(256), 0, s, (const float*)qkvg, ld, (const float*)dout, ldd, lse, delta, cu, row_seq, (float*)dqkvg, ldg, dkv_scratch, total_rows, hq, hkv, scale, qlim_desc);
+    }
     TTV_CHECK_LAUNCH("attn_bwd_f32");
     // copy dk|dv scratch [L, 2g] into the k, v columns of dqkvg
     (void)hipMemcpy2DAsync((float*)dqkvg + 2 * d_model, (size_t)ldg * sizeof(float), dkv_scratch, (size_t)2 * gqa * sizeof(float),
@@ -1837,7 +2014,8 @@ int ttvk_attention_bwd(const void* qkvg, int ld, const void* o, int ldo, const v
 struct L1Clips { const void* recon[TTV_MAX_CLIPS_PER_LAUNCH]; const void* target[TTV_MAX_CLIPS_PER_LAUNCH]; void* grad[TTV_MAX_CLIPS_PER_LAUNCH];
                  int n[TTV_MAX_CLIPS_PER_LAUNCH]; };
 
-template <typename T>
+// DET: loss is the [clip][block] partial array
+template <typename T, bool DET>
 __global__ __launch_bounds__(256) void k_l1_loss(L1Clips c, float inv_clips, float* __restrict__ loss) {
   __shared__ float red[4];
   const int ci = blockIdx.y, n = c.n[ci];
@@ -1880,13 +2058,17 @@ __global__ __launch_bounds__(256) void k_l1_loss(L1Clips c, float inv_clips, flo
   acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(loss, (red[0] + red[1] + red[2] + red[3]) * w);
+  if (threadIdx.x == 0) {
+    const float v = (red[0] + red[1] + red[2] + red[3]) * w;
+    if (DET) loss[blockIdx.y * gridDim.x + blockIdx.x] = v; else atomicAdd(loss, v);
+  }
 }
 
 // Squared error of clamp(recon, -1, 1) against target, summed over the clips of a call into a double accumulator (the statistic
 // behind the reference's PSNR: model/metrics/eval_metrics.py:19,32-36 = torchmetrics PeakSignalNoiseRatio(data_range=2), which keeps
 // the running sum of squared errors and the element count over all update() calls).  acc[0] += sum (clamp(r) - t)^2, acc[1] += count.
-template <typename T>
+// DET: acc2 is the [clip][block][2] partial array (sum of squares, element count - the count in a clip's block 0, zero in the others)
+template <typename T, bool DET>
 __global__ __launch_bounds__(256) void k_sq_err(L1Clips c, int clamp, double* __restrict__ acc2) {
   __shared__ float red[4];
   const int ci = blockIdx.y, n = c.n[ci];
@@ -1918,49 +2100,90 @@ __global__ __launch_bounds__(256) void k_sq_err(L1Clips c, int clamp, double* __
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {
-    atomicAdd(&acc2[0], (double)(red[0] + red[1] + red[2] + red[3]));
-    if (blockIdx.x == 0) atomicAdd(&acc2[1], (double)n);
+    const double v = (double)(red[0] + red[1] + red[2] + red[3]);
+    if (DET) {
+      double* mine = acc2 + 2 * (size_t)(blockIdx.y * gridDim.x + blockIdx.x);
+      mine[0] = v;
+      mine[1] = blockIdx.x == 0 ? (double)n : 0.0;
+    } else {
+      atomicAdd(&acc2[0], v);
+      if (blockIdx.x == 0) atomicAdd(&acc2[1], (double)n);
+    }
   }
 }
 
-int ttvk_sq_err(void* const* recon, void* const* target, const int* sizes, int n_clips, int dtype, int clamp, double* acc2, hipStream_t s) {
+// blocks per clip of the two launches above (one geometry for both modes)
+static inline int sq_err_bx(const int* sizes, int n_clips) {
+  int mx = 0;
+  for (int i = 0; i < n_clips; ++i) mx = sizes[i] > mx ? sizes[i] : mx;
+  const int bx = ttv_cdiv(mx, 256 * 8);
+  return bx < 1 ? 1 : (bx > 256 ? 256 : bx);
+}
+static inline int l1_loss_bx(const int* sizes, int n_clips) {
+  int mx = 0;
+  for (int i = 0; i < n_clips; ++i) mx = sizes[i] > mx ? sizes[i] : mx;
+  // ~1024 blocks in all: every block ends in ONE atomicAdd on the loss scalar, and same-address atomics retire one after the other
+  // at the memory side - with 256 blocks per clip (8192 at the benchmark batch) that tail was most of the launch (110 -> ~45 us)
+  const int bx = ttv_cdiv(mx, 256 * 8);
+  const int cap = 1024 / n_clips > 8 ? 1024 / n_clips : 8;
+  return bx < 1 ? 1 : (bx > cap ? cap : bx);
+}
+int64_t ttvk_det_clips_bytes(const int* sizes, int n_clips, bool l1) {
+  int64_t most = 0;
+  for (int c0 = 0; c0 < n_clips; c0 += TTV_MAX_CLIPS_PER_LAUNCH) {
+    const int n = n_clips - c0 < TTV_MAX_CLIPS_PER_LAUNCH ? n_clips - c0 : TTV_MAX_CLIPS_PER_LAUNCH;
+    const int64_t v = l1 ? (int64_t)l1_loss_bx(sizes + c0, n) * n * 4 : (int64_t)sq_err_bx(sizes + c0, n) * n * 16;
+    most = v > most ? v : most;
+  }
+  return most;
+}
+
+int ttvk_sq_err(void* const* recon, void* const* target, const int* sizes, int n_clips, int dtype, int clamp, double* acc2, hipStream_t s,
+                const DetScratch* det) {
   TTV_CHECK_ARG(n_clips >= 0 && n_clips <= TTV_MAX_CLIPS_PER_LAUNCH, "sq_err: at most %d clips per call", TTV_MAX_CLIPS_PER_LAUNCH);
   if (n_clips == 0) return TTV_OK;
   TTV_CHECK_ARG(recon && target && sizes && acc2, "sq_err: null argument");
   L1Clips c;
-  int mx = 0;
   for (int i = 0; i < n_clips; ++i) {
     c.recon[i] = recon[i]; c.target[i] = target[i]; c.grad[i] = nullptr; c.n[i] = sizes[i];
     TTV_CHECK_ARG(sizes[i] > 0 && recon[i] && target[i], "sq_err: empty clip");
-    mx = sizes[i] > mx ? sizes[i] : mx;
   }
-  int bx = ttv_cdiv(mx, 256 * 8);
-  bx = bx < 1 ? 1 : (bx > 256 ? 256 : bx);
-  if (dtype == TTV_BF16) hipLaunchKernelGGL((k_sq_err<bf16_t>), dim3(bx, n_clips), dim3(256), 0, s, c, clamp, acc2);
-  else hipLaunchKernelGGL((k_sq_err<float>), dim3(bx, n_clips), dim3(256), 0, s, c, clamp, acc2);
+  const int bx = sq_err_bx(sizes, n_clips);
+  if (ttv_det()) {
+    TTV_CHECK_DET(det, (int64_t)bx * n_clips * 16, "sq_err");
+    double* part = (double*)det->p;
+    if (dtype == TTV_BF16) hipLaunchKernelGGL((k_sq_err<bf16_t, true>), dim3(bx, n_clips), dim3(256), 0, s, c, clamp, part);
+    else hipLaunchKernelGGL((k_sq_err<float, true>), dim3(bx, n_clips), dim3(256), 0, s, c, clamp, part);
+    TTV_CHECK_LAUNCH("sq_err");
+    return det_fold<double>(part, bx * n_clips, 2, 2, 0, 1, acc2, s);
+  }
+  if (dtype == TTV_BF16) hipLaunchKernelGGL((k_sq_err<bf16_t, false>), dim3(bx, n_clips), dim3(256), 0, s, c, clamp, acc2);
+  else hipLaunchKernelGGL((k_sq_err<float, false>), dim3(bx, n_clips), dim3(256), 0, s, c, clamp, acc2);
   TTV_CHECK_LAUNCH("sq_err");
   return TTV_OK;
 }
 
 int ttvk_l1_loss(void* const* recon, void* const* target, void* const* grad, const int* sizes, int n_clips, int total_clips, int dtype,
-                 float* loss, hipStream_t s) {
+                 float* loss, hipStream_t s, const DetScratch* det) {
   TTV_CHECK_ARG(n_clips >= 0 && n_clips <= TTV_MAX_CLIPS_PER_LAUNCH && total_clips >= n_clips, "l1_loss: at most %d clips per call", TTV_MAX_CLIPS_PER_LAUNCH);
   if (n_clips == 0) return TTV_OK;
   TTV_CHECK_ARG(recon && target && sizes && loss, "l1_loss: null argument");
   L1Clips c;
-  int mx = 0;
   for (int i = 0; i < n_clips; ++i) {
     c.recon[i] = recon[i]; c.target[i] = target[i]; c.grad[i] = grad ? grad[i] : nullptr; c.n[i] = sizes[i];
     TTV_CHECK_ARG(sizes[i] > 0 && recon[i] && target[i], "l1_loss: empty clip");
-    mx = sizes[i] > mx ? sizes[i] : mx;
   }
-  // ~1024 blocks in all: every block ends in ONE atomicAdd on the loss scalar, and same-address atomics retire one after the other
-  // at the memory side - with 256 blocks per clip (8192 at the benchmark batch) that tail was most of the launch (110 -> ~45 us)
-  int bx = ttv_cdiv(mx, 256 * 8);
-  const int cap = 1024 / n_clips > 8 ? 1024 / n_clips : 8;
-  bx = bx < 1 ? 1 : (bx > cap ? cap : bx);
-  if (dtype == TTV_BF16) hipLaunchKernelGGL((k_l1_loss<bf16_t>), dim3(bx, n_clips), dim3(256), 0, s, c, 1.0f / (float)total_clips, loss);
-  else hipLaunchKernelGGL((k_l1_loss<float>), dim3(bx, n_clips), dim3(256), 0, s, c, 1.0f / (float)total_clips, loss);
+  const int bx = l1_loss_bx(sizes, n_clips);
+  if (ttv_det()) {
+    TTV_CHECK_DET(det, (int64_t)bx * n_clips * 4, "l1_loss");
+    float* part = (float*)det->p;
+    if (dtype == TTV_BF16) hipLaunchKernelGGL((k_l1_loss<bf16_t, true>), dim3(bx, n_clips), dim3(256), 0, s, c, 1.0f / (float)total_clips, part);
+    else hipLaunchKernelGGL((k_l1_loss<float, true>), dim3(bx, n_clips), dim3(256), 0, s, c, 1.0f / (float)total_clips, part);
+    TTV_CHECK_LAUNCH("l1_loss");
+    return det_fold<float>(part, bx * n_clips, 1, 1, 0, 0, loss, s);
+  }
+  if (dtype == TTV_BF16) hipLaunchKernelGGL((k_l1_loss<bf16_t, false>), dim3(bx, n_clips), dim3(256), 0, s, c, 1.0f / (float)total_clips, loss);
+  else hipLaunchKernelGGL((k_l1_loss<float, false>), dim3(bx, n_clips), dim3(256), 0, s, c, 1.0f / (float)total_clips, loss);
   TTV_CHECK_LAUNCH("l1_loss");
   return TTV_OK;
 }

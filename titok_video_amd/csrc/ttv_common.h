@@ -221,6 +221,11 @@ bool ttv_sw_fused_patch();           // TTV_FUSED_PATCH (default on): the encode
 bool ttv_sw_attn_pipe();             // TTV_ATTN_PIPE (default off): the opt-in pipelined attention kernel
 float ttv_sw_attn_thr();            // TTV_ATTN_THR (default 8): deferred-rescale threshold of k_attn_bf16 / k_attn64 (0 = exact running maximum)
 
+// ---- deterministic mode (ttv_set_deterministic, ttv_api.hip): process-wide, read by the launchers at launch time ------------------
+// On: every float sum onto an address that more than one block adds to takes its fixed-order form (per-block partials in scratch and
+// a fold in ascending block index, or a single writer per address); off: the atomics.  Under graph capture: the value at capture.
+bool ttv_det();
+
 // ---- torch's bicubic taps without antialiasing (aten/src/ATen/native/UpSample.h, upsample_bicubic2d, align_corners=False) ----------
 // Along one axis n_in -> n_out: src = scale * (dst + 0.5) - 0.5 with no clamp at 0 for cubic, i = floor(src), t = src - i, taps
 // i - 1 .. i + 2 clamped to [0, n_in - 1], Keys weights with A = -0.75.  ttv_cubic_floor is the i of an output index on its own

@@ -157,6 +157,8 @@ int ttvk_vq_l2_argmin(const void* z, int dtype, int ldz, const void* cb, int ldc
                       float* best_dist, void* workspace, int64_t workspace_bytes, hipStream_t s);
 int ttvk_vq_lookup(const void* cb, int dtype, int ldc, const int* indices, int rows, int C, void* codes, int ldo, hipStream_t s);
 int ttvk_vq_lookup_bwd(const void* dcodes, int dtype, int ld, const int* indices, int rows, int C, float* dcb, int ldc, hipStream_t s);
+// deterministic form: an owner per codebook entry adds its rows in ascending row order (no partials, no scratch); N = codebook entries
+int ttvk_vq_lookup_bwd_det(const void* dcodes, int dtype, int ld, const int* indices, int rows, int N, int C, float* dcb, int ldc, hipStream_t s);
 
 // ---- ttv_vq_train.hip (commitment term, EMA codebook update, dead-entry restart) ----
 int64_t ttvk_vq_train_workspace_bytes(int rows, int N);
@@ -186,19 +188,34 @@ int ttvk_mlp_fused(const void* ao, int ldao, const float* front_gain, float fron
                    int inner, void* y, int ldy, const float* post_gain, float alpha, float eps, int M, const MlpNextQkv* nq, hipStream_t s);
 
 // ---- ttv_bwd.hip (backward kernels) ----
+// Deterministic mode (ttv_det()): the reductions below that add block partials onto shared addresses write them to `det` instead, as
+// [block][element] (the layouts: include/titok_hip.h beside the ttv_*_det_scratch_bytes functions), and k_det_fold adds the partials of
+// an element in ascending block index and the total onto the destination.  One scratch serves every launch of one stream in turn (the
+// fold of a launch is ordered in front of the next launch's partials); with the mode on a launch that needs partials and has no
+// scratch, or too little, is TTV_ERR_INVALID before anything runs.  Mode off: `det` is not looked at.
+// The argument is not optional: a call site says where its partials go (NULL only behind a public entry point that has refused the mode).
+struct DetScratch { void* p; int64_t bytes; };
+int64_t ttvk_det_rms_bytes(int rows, int d);                 // one gain: [blocks][d] fp32; the chain kernel takes two of these side by side
+int64_t ttvk_det_colsum_bytes(int rows, int n);              // [row blocks][n] fp32
+int64_t ttvk_det_sumall_bytes(long total);                   // [blocks] fp32
+int64_t ttvk_det_outer_small_bytes(int rows, int C, int d);  // [row blocks][min(C, TTV_MAX_FSQ)][d] fp32 (one column chunk at a time)
+int64_t ttvk_det_clips_bytes(const int* sizes, int n_clips, bool l1);   // l1_loss: [clip][block] fp32; sq_err: [clip][block][2] double; any n_clips: the largest launch group
 int ttvk_l1_loss(void* const* recon, void* const* target, void* const* grad, const int* sizes, int n_clips, int total_clips, int dtype,
-                 float* loss, hipStream_t s);
-int ttvk_sq_err(void* const* recon, void* const* target, const int* sizes, int n_clips, int dtype, int clamp, double* acc2, hipStream_t s);
+                 float* loss, hipStream_t s, const DetScratch* det);
+int ttvk_sq_err(void* const* recon, void* const* target, const int* sizes, int n_clips, int dtype, int clamp, double* acc2, hipStream_t s,
+                const DetScratch* det);
 // dx (fp32, in/out) = out_scale * B(A), cast_out = (T) B(A) with A = dx + rmsnorm_bwd(x, gain1, dy), B = rmsnorm_bwd(y, gain2, .) or
-// identity when y == NULL; gain gradients accumulated with atomics (dgain1 / dgain2 may be NULL); cast_out may be NULL
+// identity when y == NULL; gain gradients accumulated (dgain1 / dgain2 may be NULL): one atomicAdd per block and column, or - deterministic
+// mode - block partials in `det` (gain 1's array, gain 2's behind it) and two folds; cast_out may be NULL
 int ttvk_rmsnorm_bwd_chain(const void* x, int ldx, const void* dy, int lddy, const float* gain1, float* dgain1, float* dx, int lddx,
                            const void* y, int y_dt, int ldy, const float* gain2, float* dgain2, float out_scale, void* cast_out, int ldc, int rows,
-                           int d, float eps, int dt, hipStream_t s);
+                           int d, float eps, int dt, hipStream_t s, const DetScratch* det);
 int ttvk_rmsnorm_bwd(const void* x, int x_dt, int ldx, const int* xr, const void* dy, int dy_dt, int lddy, const int* dyr,
                      const float* gain, void* dx, int dx_dt, int lddx, const int* dxr, int acc, float* dgain, int rows, int d, float eps,
-                     hipStream_t s);
-int ttvk_colsum(const void* a, int dt, int lda, const int* rows_map, int rows, int n, float* out, hipStream_t s);
-int ttvk_sumall(const void* a, int dt, int lda, const int* rows_map, int rows, int n, const float* colw, float scale, float* out, hipStream_t s);
+                     hipStream_t s, const DetScratch* det);
+int ttvk_colsum(const void* a, int dt, int lda, const int* rows_map, int rows, int n, float* out, hipStream_t s, const DetScratch* det);
+int ttvk_sumall(const void* a, int dt, int lda, const int* rows_map, int rows, int n, const float* colw, float scale, float* out, hipStream_t s,
+                const DetScratch* det);
 int ttvk_gate_fwd(const void* a, int lda, const void* gate, int ldg, void* ag, int ldo, int rows, int d, int dt, hipStream_t s);
 int ttvk_gate_bwd(const void* dag, int ldd, const void* a, int lda, const void* gate, int ldg, void* da, int ldda, void* dgate, int lddg,
                   int rows, int d, int dt, float* delta, hipStream_t s);
@@ -208,6 +225,8 @@ int ttvk_scale_cast(const float* a, float alpha, float* b, void* c, int dt, long
 int ttvk_to_f32(const void* a, int dt, float* b, long n, int accumulate, hipStream_t s);
 int ttvk_fsq_bwd(const ttv_fsq_params* fp, const float* z, const void* dcodes, int dt, float* dz, int rows, hipStream_t s);
 // part / part_bytes: optional scratch for the split partial tiles (ttvk_wgrad_ws_bytes); without it the bf16 path uses fp32 atomics
+// (deterministic mode: the paths that use atomics - no or too little scratch, an unaligned operand, TTV_WGRAD_TILE64, fp32 - run with
+// ONE token range per output tile instead, so that every address has a single writer)
 // `batch` (optional): the split partial tiles of several weight gradients are summed by ONE launch (ttvk_wgrad_flush) instead of one
 // k_wgrad_reduce per weight: the call takes its partial tiles from part + batch->used_bytes, records what to sum and returns; the
 // gradients are complete only behind the flush.  A call that does not fit (more than TTV_WGRAD_BATCH entries, scratch exhausted,
@@ -223,7 +242,7 @@ int ttvk_wgrad(const void* dy, int lddy, const void* x, int ldx, float* dw, int 
 int ttvk_wgrad_flush(WgradBatch* batch, hipStream_t s);
 int64_t ttvk_wgrad_ws_bytes(int L, int N, int K);
 int ttvk_outer_small(const void* a, int a_dt, int lda, int C, const void* b, int b_dt, int ldb, const int* b_rows, float* dw, int lddw,
-                     int transpose_out, int rows, int d, hipStream_t s);
+                     int transpose_out, int rows, int d, hipStream_t s, const DetScratch* det);
 int ttvk_expand_small(const void* a, int a_dt, int lda, int C, const void* w, int w_dt, int ldw, int w_cf, void* out, int o_dt, int ldo,
                       int rows, int d, hipStream_t s);
 int ttvk_reduce_small(const void* a, int a_dt, int lda, const int* a_rows, const void* w, int w_dt, int ldw, int C, float* out, int ldo,

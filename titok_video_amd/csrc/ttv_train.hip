@@ -71,6 +71,7 @@ struct BwdWs {
   char *g_df2, *g_do;   // [L, width]: the second df buffer (layers alternate) and do - operands the weight-gradient stream may still read
   float* wg_part;
   int64_t wg_part_bytes;
+  DetScratch det;   // deterministic mode only: the block partials of the row reductions (every launch of the caller's stream in turn)
   int64_t total;
 };
 static BwdWs carve_bwd(const ttv_tower_dims* d, const ttv_batch* b, char* base) {
@@ -104,6 +105,23 @@ static BwdWs carve_bwd(const ttv_tower_dims* d, const ttv_batch* b, char* base) 
     wgb = layer_sum > wgb ? layer_sum : wgb;
   }
   w.wg_part = (float*)take(wgb); w.wg_part_bytes = wgb;
+  // Deterministic mode: room for the largest partial array among the backward's reductions.  They all run on the caller's stream (the
+  // weight-gradient stream adds into the four weight matrices of a layer and nothing else), one after the other, and each launch's fold
+  // is ordered in front of the next launch's partials.  Mode off: no bytes, the size is what it was.
+  int64_t db = 0;
+  if (ttv_det()) {
+    const int C = d->token_size, K = b->sum_tokens;
+    const int rows3[3] = {(int)L, (int)P, K};
+    for (int i = 0; i < 3; ++i) {
+      const int64_t v = 2 * ttvk_det_rms_bytes(rows3[i], (int)dm);      // the chain kernel: two gains
+      db = v > db ? v : db;
+    }
+    const int64_t nmax = pd > dm ? pd : dm;
+    const int64_t cand[3] = {ttvk_det_colsum_bytes((int)L, (int)(nmax > C ? nmax : C)), ttvk_det_sumall_bytes((long)L * dm),
+                             ttvk_det_outer_small_bytes(K, C, (int)dm)};
+    for (int i = 0; i < 3; ++i) db = cand[i] > db ? cand[i] : db;
+  }
+  w.det.p = take(db); w.det.bytes = db;
   w.total = off;
   return w;
 }
@@ -327,7 +345,7 @@ static int layers_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, 
     float* dx1;
     if (i == d->layers - 1) {
       if (i > 0) {
-        TTV_TRY(ttvk_rmsnorm_bwd(l.y2, ydt, dm, nullptr, dx, TTV_F32, dm, nullptr, lw.ffd_post_ln, tmp, TTV_F32, dm, nullptr, 0, lg.ffd_post_ln, Lc, dm, d->eps, s));
+        TTV_TRY(ttvk_rmsnorm_bwd(l.y2, ydt, dm, nullptr, dx, TTV_F32, dm, nullptr, lw.ffd_post_ln, tmp, TTV_F32, dm, nullptr, 0, lg.ffd_post_ln, Lc, dm, d->eps, s, &ws.det));
         // tmp = dy2 ; df (T) = dy2 ; dx1 = alpha * dy2 (into dx)
         TTV_TRY(ttvk_scale_cast(tmp, d->alpha, dx, df, dt, nLc, s));
       } else {
@@ -349,7 +367,7 @@ static int layers_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, 
     // i > 0: dy1 = rmsnorm_bwd(y1, attn_post_ln, dx1) ; do = (T) dy1 ; dx = alpha * dy1      i == 0: do = (T) dx1 ; dx = dx1
     TTV_TRY(ttvk_rmsnorm_bwd_chain(l.x1, dm, ws.g_d2, dm, lw.ffd_norm, lg.ffd_norm, dx1, dm, i > 0 ? l.y1 : nullptr, ydt, dm,
                                    i > 0 ? lw.attn_post_ln : nullptr, i > 0 ? lg.attn_post_ln : nullptr, i > 0 ? d->alpha : 1.f, ws.g_do, dm, Lc,
-                                   dm, d->eps, dt, s));
+                                   dm, d->eps, dt, s, &ws.det));
     TTV_TRY(side_fork(sd, 2, s));          // do is complete
     // dag = do Wo ; dWo += do^T ag
     TTV_TRY(ttvk_gemm(EPI_STORE, gemm_args(dt, ws.g_do, dm, lt.out_proj_t, dm, Lc, dm, dm, ws.g_d2, dm), s));
@@ -388,12 +406,12 @@ static int layers_backward(const ttv_tower_dims* d, const ttv_tower_weights* w, 
     // dx += rmsnorm_bwd(X[i], pre_ln, dxn1) = dL/dX[i]; chained with the head of the layer below: through its feed-forward
     // post-norm (layers >= 1) and the bf16 copy df that its w3 products read
     if (i == 0) {
-      TTV_TRY(ttvk_rmsnorm_bwd(t.X[i], dt, dm, nullptr, ws.g_d2, dt, dm, nullptr, lw.pre_ln, dx, TTV_F32, dm, nullptr, 1, lg.pre_ln, L, dm, d->eps, s));
+      TTV_TRY(ttvk_rmsnorm_bwd(t.X[i], dt, dm, nullptr, ws.g_d2, dt, dm, nullptr, lw.pre_ln, dx, TTV_F32, dm, nullptr, 1, lg.pre_ln, L, dm, d->eps, s, &ws.det));
     } else {
       const bool post = i - 1 > 0;
       TTV_TRY(ttvk_rmsnorm_bwd_chain(t.X[i], dm, ws.g_d2, dm, lw.pre_ln, lg.pre_ln, dx, dm, post ? t.l[i - 1].y2 : nullptr, ydt, dm,
                                      post ? w->layers[i - 1].ffd_post_ln : nullptr, post ? gr->layers[i - 1].ffd_post_ln : nullptr,
-                                     post ? d->alpha : 1.f, g_df[cur ^ 1], dm, L, dm, d->eps, dt, s));   // df of the layer below (da is consumed)
+                                     post ? d->alpha : 1.f, g_df[cur ^ 1], dm, L, dm, d->eps, dt, s, &ws.det));   // df of the layer below (da is consumed)
     }
     cur ^= 1;
     TTV_TRY(side_join(sd, s));             // the caller's stream takes the weight gradients back in; dY operands may be overwritten from here
@@ -474,21 +492,21 @@ int ttv_encoder_backward_ex(const ttv_tower_dims* d, const ttv_tower_weights* w,
   const int L = b->total_rows, dm = d->width, dt = d->dtype, P = b->sum_patches, K = b->sum_tokens, C = d->token_size, pd = patch_dim(d);
   // ---- tail: z = proj_out(n) + b, n = ln_post(X_last[latent rows]) ----
   TTV_TRY(ttvk_rmsnorm(t.X[d->layers], dt, dm, b->latent_rows, ws.g_d, dt, dm, nullptr, w->ln_post, K, dm, d->eps, s));   // n
-  TTV_TRY(ttvk_outer_small(dz, TTV_F32, C, C, ws.g_d, dt, dm, nullptr, gr->proj_out_w, dm, 0, K, dm, s));
-  TTV_TRY(ttvk_colsum(dz, TTV_F32, C, nullptr, K, C, gr->proj_out_b, s));
+  TTV_TRY(ttvk_outer_small(dz, TTV_F32, C, C, ws.g_d, dt, dm, nullptr, gr->proj_out_w, dm, 0, K, dm, s, &ws.det));
+  TTV_TRY(ttvk_colsum(dz, TTV_F32, C, nullptr, K, C, gr->proj_out_b, s, &ws.det));
   TTV_TRY(ttvk_expand_small(dz, TTV_F32, C, C, w->proj_out_w, dt, dm, 1, ws.g_d2, dt, dm, K, dm, s));                      // dn
   (void)hipMemsetAsync(ws.dxa, 0, (size_t)L * dm * sizeof(float), s);
-  TTV_TRY(ttvk_rmsnorm_bwd(t.X[d->layers], dt, dm, b->latent_rows, ws.g_d2, dt, dm, nullptr, w->ln_post, ws.dxa, TTV_F32, dm, b->latent_rows, 0, gr->ln_post, K, dm, d->eps, s));
+  TTV_TRY(ttvk_rmsnorm_bwd(t.X[d->layers], dt, dm, b->latent_rows, ws.g_d2, dt, dm, nullptr, w->ln_post, ws.dxa, TTV_F32, dm, b->latent_rows, 0, gr->ln_post, K, dm, d->eps, s, &ws.det));
   TTV_TRY(layers_backward(d, w, wt, b, t, gr, ws, tape_mode, s));
   // ---- head ----
   // latent rows are the constant vector ln_pre_t(mask_token * 1)
   (void)hipMemsetAsync(ws.colsum, 0, dm * sizeof(float), s);
-  TTV_TRY(ttvk_colsum(ws.dxa, TTV_F32, dm, b->latent_rows, K, dm, ws.colsum, s));
+  TTV_TRY(ttvk_colsum(ws.dxa, TTV_F32, dm, b->latent_rows, K, dm, ws.colsum, s, &ws.det));
   TTV_TRY(ttvk_const_rows_bwd(ws.colsum, w->mask_token, w->ln_pre_t, dt, d->eps, gr->ln_pre_t, gr->mask_token, dm, s));
   // patch rows: X0[patch] = ln_pre_p(pe), pe = proj_in(patches) + bias + mask_token
-  TTV_TRY(ttvk_rmsnorm_bwd(t.pe, dt, dm, nullptr, ws.dxa, TTV_F32, dm, b->patch_rows, w->ln_pre_p, ws.g_d, dt, dm, nullptr, 0, gr->ln_pre_p, P, dm, d->eps, s));  // dpe
-  TTV_TRY(ttvk_sumall(ws.g_d, dt, dm, nullptr, P, dm, nullptr, 1.f, gr->mask_token, s));
-  TTV_TRY(ttvk_colsum(ws.g_d, dt, dm, nullptr, P, dm, gr->proj_in_b, s));
+  TTV_TRY(ttvk_rmsnorm_bwd(t.pe, dt, dm, nullptr, ws.dxa, TTV_F32, dm, b->patch_rows, w->ln_pre_p, ws.g_d, dt, dm, nullptr, 0, gr->ln_pre_p, P, dm, d->eps, s, &ws.det));  // dpe
+  TTV_TRY(ttvk_sumall(ws.g_d, dt, dm, nullptr, P, dm, nullptr, 1.f, gr->mask_token, s, &ws.det));
+  TTV_TRY(ttvk_colsum(ws.g_d, dt, dm, nullptr, P, dm, gr->proj_in_b, s, &ws.det));
   TTV_TRY(ttvk_wgrad(ws.g_d, dm, t.patches, pd, gr->proj_in_w, pd, P, dm, pd, dt, ws.wg_part, ws.wg_part_bytes, s));
   if (dclips) {
     TTV_TRY(ttvk_gemm(EPI_STORE, gemm_args(dt, ws.g_d, dm, wt->proj_in_t, dm, P, pd, dm, ws.g_pd, pd), s));
@@ -538,21 +556,21 @@ int ttv_decoder_backward_ex(const ttv_tower_dims* d, const ttv_tower_weights* w,
   const int L = b->total_rows, dm = d->width, dt = d->dtype, P = b->sum_patches, K = b->sum_tokens, C = d->token_size, pd = patch_dim(d);
   // ---- tail: clips = unpatch(proj_out(pn) + bias), pn = ln_post(X_last[patch rows]) ----
   TTV_TRY(patch_copy_all(false, (void* const*)dclips_out, d, b, ws.g_pd, dt, s));
-  TTV_TRY(ttvk_colsum(ws.g_pd, dt, pd, nullptr, P, pd, gr->proj_out_b, s));
+  TTV_TRY(ttvk_colsum(ws.g_pd, dt, pd, nullptr, P, pd, gr->proj_out_b, s, &ws.det));
   TTV_TRY(ttvk_wgrad(ws.g_pd, pd, t.pn, dm, gr->proj_out_w, dm, P, pd, dm, dt, ws.wg_part, ws.wg_part_bytes, s));
   TTV_TRY(ttvk_gemm(EPI_STORE, gemm_args(dt, ws.g_pd, pd, wt->proj_out_t, pd, P, dm, pd, ws.g_d2, dm), s));   // dpn
   (void)hipMemsetAsync(ws.dxa, 0, (size_t)L * dm * sizeof(float), s);
-  TTV_TRY(ttvk_rmsnorm_bwd(t.X[d->layers], dt, dm, b->patch_rows, ws.g_d2, dt, dm, nullptr, w->ln_post, ws.dxa, TTV_F32, dm, b->patch_rows, 0, gr->ln_post, P, dm, d->eps, s));
+  TTV_TRY(ttvk_rmsnorm_bwd(t.X[d->layers], dt, dm, b->patch_rows, ws.g_d2, dt, dm, nullptr, w->ln_post, ws.dxa, TTV_F32, dm, b->patch_rows, 0, gr->ln_post, P, dm, d->eps, s, &ws.det));
   TTV_TRY(layers_backward(d, w, wt, b, t, gr, ws, tape_mode, s));
   // ---- head ----
   (void)hipMemsetAsync(ws.colsum, 0, dm * sizeof(float), s);
-  TTV_TRY(ttvk_colsum(ws.dxa, TTV_F32, dm, b->patch_rows, P, dm, ws.colsum, s));
+  TTV_TRY(ttvk_colsum(ws.dxa, TTV_F32, dm, b->patch_rows, P, dm, ws.colsum, s, &ws.det));
   TTV_TRY(ttvk_const_rows_bwd(ws.colsum, w->mask_token, w->ln_pre_p, dt, d->eps, gr->ln_pre_p, gr->mask_token, dm, s));
   // latent rows: X0[latent] = ln_pre_t(hpre), hpre = proj_in(codes) + bias + mask_token
-  TTV_TRY(ttvk_rmsnorm_bwd(t.hpre, dt, dm, nullptr, ws.dxa, TTV_F32, dm, b->latent_rows, w->ln_pre_t, ws.small_f32, TTV_F32, dm, nullptr, 0, gr->ln_pre_t, K, dm, d->eps, s));  // dh
-  TTV_TRY(ttvk_sumall(ws.small_f32, TTV_F32, dm, nullptr, K, dm, nullptr, 1.f, gr->mask_token, s));
-  TTV_TRY(ttvk_colsum(ws.small_f32, TTV_F32, dm, nullptr, K, dm, gr->proj_in_b, s));
-  TTV_TRY(ttvk_outer_small(codes, dt, C, C, ws.small_f32, TTV_F32, dm, nullptr, gr->proj_in_w, C, 1, K, dm, s));
+  TTV_TRY(ttvk_rmsnorm_bwd(t.hpre, dt, dm, nullptr, ws.dxa, TTV_F32, dm, b->latent_rows, w->ln_pre_t, ws.small_f32, TTV_F32, dm, nullptr, 0, gr->ln_pre_t, K, dm, d->eps, s, &ws.det));  // dh
+  TTV_TRY(ttvk_sumall(ws.small_f32, TTV_F32, dm, nullptr, K, dm, nullptr, 1.f, gr->mask_token, s, &ws.det));
+  TTV_TRY(ttvk_colsum(ws.small_f32, TTV_F32, dm, nullptr, K, dm, gr->proj_in_b, s, &ws.det));
+  TTV_TRY(ttvk_outer_small(codes, dt, C, C, ws.small_f32, TTV_F32, dm, nullptr, gr->proj_in_w, C, 1, K, dm, s, &ws.det));
   if (dcodes) TTV_TRY(ttvk_reduce_small(ws.small_f32, TTV_F32, dm, nullptr, w->proj_in_w, dt, C, C, dcodes, C, K, dm, s));
   return TTV_OK;
 }
@@ -575,15 +593,45 @@ int ttv_linear_wgrad(const void* dy, int lddy, const void* x, int ldx, float* dw
 int ttv_rmsnorm_backward_chain(const void* x, int ldx, const void* dy, int lddy, const float* gain1, float* dgain1, float* dx, int lddx,
                                const float* y, int ldy, const float* gain2, float* dgain2, float out_scale, void* cast_out, int ldc, int rows,
                                int width, float eps, int dtype, void* stream) {
+  TTV_CHECK_ARG(!ttv_det(), "rmsnorm_backward_chain: deterministic mode is on and this entry point has no scratch for the block partials: call ttv_rmsnorm_backward_chain_det");
   TTV_CHECK_ARG(rows == 0 || (x && dy && gain1 && dx), "rmsnorm_backward_chain: null buffer");
   return ttvk_rmsnorm_bwd_chain(x, ldx, dy, lddy, gain1, dgain1, dx, lddx, y, TTV_F32, ldy, gain2, dgain2, out_scale, cast_out, ldc, rows, width, eps,
-                                dtype, (hipStream_t)stream);
+                                dtype, (hipStream_t)stream, nullptr);      // mode off (checked above): no partials
 }
 
 int ttv_rmsnorm_backward(const void* x, int ldx, const void* dy, int lddy, const float* gain, void* dx, int lddx, float* dgain, int rows,
                          int width, float eps, int dtype, void* stream) {
+  TTV_CHECK_ARG(!ttv_det(), "rmsnorm_backward: deterministic mode is on and this entry point has no scratch for the block partials: call ttv_rmsnorm_backward_det");
   TTV_CHECK_ARG(rows == 0 || (x && dy && gain && dx), "rmsnorm_backward: null buffer");
-  return ttvk_rmsnorm_bwd(x, dtype, ldx, nullptr, dy, dtype, lddy, nullptr, gain, dx, dtype, lddx, nullptr, 0, dgain, rows, width, eps, (hipStream_t)stream);
+  return ttvk_rmsnorm_bwd(x, dtype, ldx, nullptr, dy, dtype, lddy, nullptr, gain, dx, dtype, lddx, nullptr, 0, dgain, rows, width, eps, (hipStream_t)stream,
+                          nullptr);      // mode off (checked above): no partials
+}
+
+int64_t ttv_rmsnorm_backward_det_scratch_bytes(int rows, int width) {
+  if (rows < 0 || width < 4 || width % 4 != 0 || width > 1024) { ttv_set_error("rmsnorm_backward_det_scratch_bytes: %d rows of width %d", rows, width); return -1; }
+  return ttvk_det_rms_bytes(rows, width);
+}
+int64_t ttv_rmsnorm_backward_chain_det_scratch_bytes(int rows, int width) {
+  const int64_t one = ttv_rmsnorm_backward_det_scratch_bytes(rows, width);
+  return one < 0 ? one : 2 * one;
+}
+
+int ttv_rmsnorm_backward_chain_det(const void* x, int ldx, const void* dy, int lddy, const float* gain1, float* dgain1, float* dx, int lddx,
+                                   const float* y, int ldy, const float* gain2, float* dgain2, float out_scale, void* cast_out, int ldc, int rows,
+                                   int width, float eps, int dtype, void* scratch, int64_t scratch_bytes, void* stream) {
+  TTV_CHECK_ARG(rows == 0 || (x && dy && gain1 && dx), "rmsnorm_backward_chain_det: null buffer");
+  const DetScratch det = {scratch, scratch_bytes};
+  return ttvk_rmsnorm_bwd_chain(x, ldx, dy, lddy, gain1, dgain1, dx, lddx, y, TTV_F32, ldy, gain2, dgain2, out_scale, cast_out, ldc, rows, width, eps,
+                                dtype, (hipStream_t)stream, &det);
+}
+
+int ttv_rmsnorm_backward_det(const void* x, int ldx, const void* dy, int lddy, const float* gain, void* dx, int lddx, float* dgain, int rows,
+                             int width, float eps, int dtype, const int32_t* x_rows, const int32_t* dy_rows, const int32_t* dx_rows, void* scratch,
+                             int64_t scratch_bytes, void* stream) {
+  TTV_CHECK_ARG(rows == 0 || (x && dy && gain && dx), "rmsnorm_backward_det: null buffer");
+  const DetScratch det = {scratch, scratch_bytes};
+  return ttvk_rmsnorm_bwd(x, dtype, ldx, x_rows, dy, dtype, lddy, dy_rows, gain, dx, dtype, lddx, dx_rows, 0, dgain, rows, width, eps, (hipStream_t)stream,
+                          &det);
 }
 
 int ttv_attention_backward(const void* qkvg, int ld, const void* o, int ldo, const void* dout, int ldd, const float* lse, float* delta,
@@ -593,6 +641,15 @@ int ttv_attention_backward(const void* qkvg, int ld, const void* o, int ldo, con
   TTV_CHECK_ARG(total_rows == 0 || (qkvg && o && dout && lse && delta && cu_seqlens && blocks64 && dqkvg), "attention_backward: null buffer");
   return ttvk_attention_bwd(qkvg, ld, o, ldo, dout, ldd, lse, delta, cu_seqlens, blocks64, n_blocks64, row_seq, dqkvg, ldg, dkv_scratch,
                             total_rows, q_heads, kv_heads, dtype, rope_cs, (hipStream_t)stream);
+}
+
+int ttv_attention_backward_qlim(const void* qkvg, int ld, const void* o, int ldo, const void* dout, int ldd, const float* lse, float* delta,
+                                const int32_t* cu_seqlens, const int32_t* blocks64, int n_blocks64, const int32_t* row_seq, void* dqkvg,
+                                int ldg, float* dkv_scratch, int total_rows, int q_heads, int kv_heads, int dtype, const float* rope_cs,
+                                const int32_t* clip_desc, void* stream) {
+  TTV_CHECK_ARG(total_rows == 0 || (qkvg && o && dout && lse && delta && cu_seqlens && blocks64 && dqkvg), "attention_backward_qlim: null buffer");
+  return ttvk_attention_bwd(qkvg, ld, o, ldo, dout, ldd, lse, delta, cu_seqlens, blocks64, n_blocks64, row_seq, dqkvg, ldg, dkv_scratch,
+                            total_rows, q_heads, kv_heads, dtype, rope_cs, (hipStream_t)stream, 0, clip_desc);
 }
 
 int ttv_attention_lse(const void* qkvg, int ld, void* out, int ldo, const int32_t* cu_seqlens, const int32_t* qblocks, int n_qblocks,

@@ -278,6 +278,44 @@ __global__ __launch_bounds__(256) void k_vq_lookup_bwd(const T* __restrict__ dco
   atomicAdd(dcb + (size_t)indices[r] * ldc + c, Cvt<T>::to_f(dcodes[(size_t)r * ld + c]));
 }
 
+// Deterministic form: lpe lanes (the power of two >= C) OWN a codebook entry; they walk the token rows in ascending order and add the rows
+// that chose the entry one after the other in fp32, then add the sum onto the entry's gradient (plain load / add / store: the only writer).
+// Every group reads every index (broadcast loads of an array that stays in cache); an entry no row chose is left as it is.
+template <typename T>
+__global__ __launch_bounds__(256) void k_vq_lookup_bwd_det(const T* __restrict__ dcodes, int ld, const int* __restrict__ indices, int rows, int N,
+                                                           int C, int lpe, float* __restrict__ dcb, int ldc) {
+  const int grp = threadIdx.x / lpe, c = threadIdx.x - grp * lpe;
+  const int n = blockIdx.x * (256 / lpe) + grp;
+  if (n >= N || c >= C) return;
+  float s = 0.f;
+  bool any = false;
+  for (int r0 = 0; r0 < rows; r0 += 8) {
+    int k[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) k[u] = indices[r0 + u < rows ? r0 + u : rows - 1];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (r0 + u < rows && k[u] == n) {
+        s += Cvt<T>::to_f(dcodes[(size_t)(r0 + u) * ld + c]);
+        any = true;
+      }
+  }
+  if (any) dcb[(size_t)n * ldc + c] += s;
+}
+
+int ttvk_vq_lookup_bwd_det(const void* dcodes, int dtype, int ld, const int* indices, int rows, int N, int C, float* dcb, int ldc, hipStream_t s) {
+  if (rows == 0 || N == 0) return TTV_OK;
+  TTV_CHECK_ARG(dtype == TTV_BF16 || dtype == TTV_F32, "vq_lookup_backward_det: bad dtype");
+  TTV_CHECK_ARG(N >= 1 && C >= 1 && C <= 256, "vq_lookup_backward_det: %d entries of dim %d", N, C);
+  int lpe = 1;
+  while (lpe < C) lpe <<= 1;
+  dim3 grid((unsigned)ttv_cdiv(N, 256 / lpe));
+  if (dtype == TTV_F32) hipLaunchKernelGGL((k_vq_lookup_bwd_det<float>), grid, dim3(256), 0, s, (const float*)dcodes, ld, indices, rows, N, C, lpe, dcb, ldc);
+  else hipLaunchKernelGGL((k_vq_lookup_bwd_det<bf16_t>), grid, dim3(256), 0, s, (const bf16_t*)dcodes, ld, indices, rows, N, C, lpe, dcb, ldc);
+  TTV_CHECK_LAUNCH("vq_lookup_bwd_det");
+  return TTV_OK;
+}
+
 int ttvk_vq_lookup_bwd(const void* dcodes, int dtype, int ld, const int* indices, int rows, int C, float* dcb, int ldc, hipStream_t s) {
   if (rows == 0) return TTV_OK;
   TTV_CHECK_ARG(dtype == TTV_BF16 || dtype == TTV_F32, "vq_lookup_backward: bad dtype");

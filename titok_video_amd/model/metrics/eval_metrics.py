@@ -101,6 +101,7 @@ class EvalMetrics(nn.Module):
         self._acc = None         # psnr: (sum of squared errors, element count), double
         self._ssim_acc = None    # ssim: (sum of per-frame SSIM, frame count), double
         self._ssim_ws = None     # ssim: per-tile partial sums, grown as needed
+        self._det_scratch = None # psnr in deterministic mode: the block partials, grown as needed
         self._lpips_acc = None   # lpips: (sum of per-frame LPIPS, frame count), double
 
     def _ssim_groups(self, rs, ts):
@@ -133,8 +134,19 @@ class EvalMetrics(nn.Module):
             if self._acc is None or self._acc.device != r0.device:
                 self._acc = torch.zeros(2, dtype=torch.float64, device=r0.device)
             sizes = (C.c_int32 * len(rs))(*[int(t.numel()) for t in rs])
-            rc = _lib.lib().ttv_sq_err_accumulate(_lib.ptr_array(rs), _lib.ptr_array(ts), sizes, len(rs), dt, 1, self._acc.data_ptr(), stream)
-            _lib.check(rc, "ttv_sq_err_accumulate")
+            if _lib.is_deterministic():      # fixed-order sums: the block partials go through a scratch this object keeps
+                need = _lib.lib().ttv_sq_err_accumulate_det_scratch_bytes(sizes, len(rs))
+                if need < 0:
+                    _lib.check(1, "ttv_sq_err_accumulate_det_scratch_bytes")
+                if self._det_scratch is None:
+                    self._det_scratch = _lib.DetScratch()
+                scratch = self._det_scratch.get(need, r0.device)
+                rc = _lib.lib().ttv_sq_err_accumulate_det(_lib.ptr_array(rs), _lib.ptr_array(ts), sizes, len(rs), dt, 1, self._acc.data_ptr(),
+                                                          scratch.data_ptr(), scratch.numel(), stream)
+                _lib.check(rc, "ttv_sq_err_accumulate_det")
+            else:
+                rc = _lib.lib().ttv_sq_err_accumulate(_lib.ptr_array(rs), _lib.ptr_array(ts), sizes, len(rs), dt, 1, self._acc.data_ptr(), stream)
+                _lib.check(rc, "ttv_sq_err_accumulate")
         if groups:
             if self._ssim_acc is None or self._ssim_acc.device != r0.device:
                 self._ssim_acc = torch.zeros(2, dtype=torch.float64, device=r0.device)

@@ -227,6 +227,8 @@ class _CommitFn(torch.autograd.Function):
 class _LookupFn(torch.autograd.Function):
     """codes = codebook[idx] on the HIP path; backward = ttv_vq_lookup_backward (fp32 scatter-add into the codebook gradient)."""
 
+    _det_scratch = None
+
     @staticmethod
     def forward(ctx, vq: "L2Quantizer", idx: torch.Tensor, dtype, codebook: torch.Tensor):
         ctx.idx, ctx.shape, ctx.cb_dtype = idx, tuple(codebook.shape), codebook.dtype
@@ -238,6 +240,20 @@ class _LookupFn(torch.autograd.Function):
         if dcodes.dtype not in (torch.float32, torch.bfloat16):
             dcodes = dcodes.float()
         dcb = torch.zeros(ctx.shape, dtype=torch.float32, device=dcodes.device)
-        _lib.check(_lib.lib().ttv_vq_lookup_backward(dcodes.data_ptr(), _lib.dtype_code(dcodes.dtype), dcodes.shape[1], ctx.idx.data_ptr(), dcodes.shape[0],
-                                                     dcodes.shape[1], dcb.data_ptr(), ctx.shape[1], _lib.stream_ptr(dcodes.device)), "ttv_vq_lookup_backward")
+        if _lib.is_deterministic():      # an owner per codebook entry adds its rows in ascending order
+            need = _lib.lib().ttv_vq_lookup_backward_det_scratch_bytes(dcodes.shape[0], ctx.shape[0], dcodes.shape[1])
+            if need < 0:
+                _lib.check(1, "ttv_vq_lookup_backward_det_scratch_bytes")
+            scratch = None              # the owner form has no partials (need == 0); a form with partials would take them from here
+            if need > 0:
+                if _LookupFn._det_scratch is None:
+                    _LookupFn._det_scratch = _lib.DetScratch()
+                scratch = _LookupFn._det_scratch.get(need, dcodes.device)
+            _lib.check(_lib.lib().ttv_vq_lookup_backward_det(dcodes.data_ptr(), _lib.dtype_code(dcodes.dtype), dcodes.shape[1], ctx.idx.data_ptr(),
+                                                             dcodes.shape[0], ctx.shape[0], dcodes.shape[1], dcb.data_ptr(), ctx.shape[1],
+                                                             _lib.ptr(scratch), need, _lib.stream_ptr(dcodes.device)),
+                       "ttv_vq_lookup_backward_det")
+        else:
+            _lib.check(_lib.lib().ttv_vq_lookup_backward(dcodes.data_ptr(), _lib.dtype_code(dcodes.dtype), dcodes.shape[1], ctx.idx.data_ptr(), dcodes.shape[0],
+                                                         dcodes.shape[1], dcb.data_ptr(), ctx.shape[1], _lib.stream_ptr(dcodes.device)), "ttv_vq_lookup_backward")
         return None, None, None, dcb.to(ctx.cb_dtype)

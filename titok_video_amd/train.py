@@ -26,7 +26,10 @@ from .optim import HipAdamW, use_hip_adamw
 
 
 class _L1LossFn(torch.autograd.Function):
-    """Value and gradient of the L1 term for all clips in one HIP launch (ttv_l1_loss)."""
+    """Value and gradient of the L1 term for all clips in one HIP launch (ttv_l1_loss; in deterministic mode ttv_l1_loss_det with the
+    scratch this class keeps for the block partials)."""
+
+    _det_scratch = None
 
     @staticmethod
     def forward(ctx, n, *tensors):
@@ -38,8 +41,19 @@ class _L1LossFn(torch.autograd.Function):
         loss = torch.zeros((), dtype=torch.float32, device=dev)
         grads = [torch.empty_like(r) for r in recon]
         sizes = (C.c_int32 * n)(*[int(r.numel()) for r in recon])
-        _lib.check(_lib.lib().ttv_l1_loss(_lib.ptr_array(recon), _lib.ptr_array(target), _lib.ptr_array(grads), sizes, n,
-                                          _lib.dtype_code(dt), loss.data_ptr(), _lib.stream_ptr(dev)), "ttv_l1_loss")
+        if _lib.is_deterministic():
+            need = _lib.lib().ttv_l1_loss_det_scratch_bytes(sizes, n)
+            if need < 0:
+                _lib.check(1, "ttv_l1_loss_det_scratch_bytes")
+            if _L1LossFn._det_scratch is None:
+                _L1LossFn._det_scratch = _lib.DetScratch()
+            scratch = _L1LossFn._det_scratch.get(need, dev)
+            _lib.check(_lib.lib().ttv_l1_loss_det(_lib.ptr_array(recon), _lib.ptr_array(target), _lib.ptr_array(grads), sizes, n,
+                                                  _lib.dtype_code(dt), loss.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                                  _lib.stream_ptr(dev)), "ttv_l1_loss_det")
+        else:
+            _lib.check(_lib.lib().ttv_l1_loss(_lib.ptr_array(recon), _lib.ptr_array(target), _lib.ptr_array(grads), sizes, n,
+                                              _lib.dtype_code(dt), loss.data_ptr(), _lib.stream_ptr(dev)), "ttv_l1_loss")
         ctx.grads, ctx.n = grads, n
         return loss
 

@@ -8,7 +8,8 @@ ttv_opt_prepare; three launches per bucket instead of two) - with GRAPH=1 it is 
 --recompute: both towers on the recompute tape (TiTok.set_activation_recompute).  --ab: stored and recompute tape alternating in this
 one process (ROUNDS= rounds of STEPS= timed steps per mode behind one untimed step, default 3; not with GRAPH=1), one JSON line with every round's time per mode
 and torch.cuda.max_memory_allocated() per mode.  SIZE= tower size (default tiny), CLIP=TxHxW (default 16x128x128), K= tokens per clip
-(default 128); B=fit: the largest batch whose STORED tapes and backward workspace (the library's size functions) fill at most 3/4 of
+(default 128); --det-ab: deterministic mode (titok_video_amd.set_deterministic) off and on alternating in this one process, ROUNDS= rounds of
+STEPS= timed steps per setting, one JSON line with every round's time per setting (profiles/deterministic_train_ab.txt); B=fit: the largest batch whose STORED tapes and backward workspace (the library's size functions) fill at most 3/4 of
 the free device memory."""
 import json, os, sys, time
 from types import SimpleNamespace
@@ -18,6 +19,7 @@ from titok_video_amd.model.titok import TiTok
 from titok_video_amd.synthetic import seeded_titok_state, synthetic_clips
 from titok_video_amd.train import freeze_python_gc, limit_host_threads, make_optimizer, training_step
 RECOMPUTE, AB = "--recompute" in sys.argv[1:], "--ab" in sys.argv[1:]
+DET_AB = "--det-ab" in sys.argv[1:]
 SIZE = os.environ.get("SIZE", "tiny")
 CLIP = tuple(int(v) for v in os.environ.get("CLIP", "16x128x128").split("x"))
 K = int(os.environ.get("K", "128"))
@@ -63,6 +65,28 @@ EMA = os.environ.get("EMA", "0") == "1" and not GRAPH
 if EMA:
     from titok_video_amd.ema import WeightEMA
     ema = WeightEMA(m, decay=0.9999)
+if DET_AB:
+    assert not GRAPH, "--det-ab times eager steps"
+    import titok_video_amd
+    rounds = int(os.environ.get("ROUNDS", "3"))
+    times, loss = {False: [], True: []}, {}
+    for r in range(rounds + 1):                # round 0 warms both settings up (the larger workspace is allocated) and is not reported
+        for mode in (False, True):
+            titok_video_amd.set_deterministic(mode)
+            training_step(m, clips, counts, opt)          # not timed
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                loss[mode], gn, _ = training_step(m, clips, counts, opt)
+            torch.cuda.synchronize()
+            if r > 0:
+                times[mode].append(1e3 * (time.perf_counter() - t0) / n)
+    titok_video_amd.set_deterministic(False)
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    print(json.dumps({"size": SIZE, "clip": CLIP, "tokens": K, "batch": B, "steps_per_round": n, "off_ms_per_step": times[False],
+                      "deterministic_ms_per_step": times[True], "off_ms_median": med[False], "deterministic_ms_median": med[True],
+                      "deterministic_over_off": med[True] / med[False], "loss_off": float(loss[False]), "loss_deterministic": float(loss[True])}))
+    sys.exit(0)
 if AB:
     assert not GRAPH, "--ab times eager steps"
     rounds = int(os.environ.get("ROUNDS", "3"))
