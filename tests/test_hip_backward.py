@@ -8,6 +8,7 @@ kernels) against torch autograd through the CPU oracle on the same seeded inputs
   * single kernels (weight-gradient GEMM, RMSNorm backward, attention backward) against torch autograd directly.
 """
 import ctypes as C
+import functools
 import os
 from types import SimpleNamespace
 
@@ -69,6 +70,88 @@ def test_wgrad(dt, shape, workspace):
     assert rel(outs[0], ref) < (2e-3 if dt == "bf16" else 2e-5)
     if workspace and dt == "bf16":     # the fp32 checking kernel accumulates with atomics
         assert torch.equal(outs[0], outs[1])
+
+
+# (N, K) of the layer linears of the wider towers: to_qkv, w12, w3, out_proj of base and large, w12 and w3 of small.  large's w12 is
+# 43 x 8 tiles, its w3 has a 64-wide K edge (2752 = 21 x 128 + 64); at base's w12 (192 tiles) the plan's split count comes from its
+# clamps alone.  L = 175 (the rows of SMALL: 3 splits of 64 tokens, the last one ragged) and L = 1090: at every shape here the plan's
+# first formula and its cap are 0, the `sp < 8` clamp decides, and 8 ranges of 192 tokens cover 1090 rows in 6 splits.
+WIDE_LINEARS = {"base-to_qkv": (2048, 768), "base-w12": (4096, 768), "base-w3": (768, 2048), "base-out_proj": (768, 768),
+                "large-to_qkv": (2560, 1024), "large-w12": (5504, 1024), "large-w3": (1024, 2752), "large-out_proj": (1024, 1024),
+                "small-w12": (2752, 512), "small-w3": (512, 1376)}
+WGRAD_TILE_FACTOR = 8      # the kernel sums a tile as a chain of 64-token steps, up to 8 split partials and a second accumulation
+
+
+@functools.lru_cache(maxsize=4)
+def _wide_wgrad_case(Lr, N, K, dt):
+    """Operands rounded to `dt`, the float64 product of two accumulating calls, and the yardstick: the per-tile error of torch's float32
+    CPU product of the same operands (fp32 accumulation in another order) against float64.  Read only."""
+    from tests.blockwise import tile_errors
+    g = torch.Generator().manual_seed(Lr + N + K)
+    dy = torch.randn(Lr, N, generator=g).to(DT[dt])
+    x = torch.randn(Lr, K, generator=g).to(DT[dt])
+    ref = 2 * (dy.double().T @ x.double())
+    yard = float(tile_errors(2 * (dy.float().T @ x.float()), ref).max())
+    return dy, x, ref, yard
+
+
+def _wide_wgrad(dt, layer, Lr, nbytes, full):
+    """Two runs of two accumulating ttv_linear_wgrad calls with `nbytes` of NaN-filled workspace (`full`: what the plan asks for)."""
+    from tests.blockwise import tile_errors
+    N, K = WIDE_LINEARS[layer]
+    dy, x, ref, yard = _wide_wgrad_case(Lr, N, K, dt)
+    dyd, xd = dy.to(DEV), x.to(DEV)
+    ws = torch.full((max(nbytes, 4) // 4,), float("nan"), device=DEV)
+    outs = []
+    for _ in range(2):
+        dw = torch.zeros(N, K, device=DEV)
+        for _ in range(2):
+            _lib.check(L().ttv_linear_wgrad(dyd.data_ptr(), N, xd.data_ptr(), K, dw.data_ptr(), K, Lr, N, K, _lib.dtype_code(DT[dt]),
+                                            ws.data_ptr() if nbytes else None, nbytes, S()), "wgrad")
+        outs.append(dw.cpu())
+    assert bool(torch.isfinite(outs[0]).all()) and bool(torch.isfinite(outs[1]).all()), "the NaN-filled workspace leaked into dW"
+    err = tile_errors(outs[0], ref)
+    worst, glob = float(err.max()), rel(outs[0], ref)
+    tn, tk = divmod(int(err.argmax()), err.shape[1])
+    bound = max(WGRAD_TILE_FACTOR * yard, 1e-6)
+    print(f"MEASURED wgrad {layer} L {Lr} {dt} workspace {nbytes} of {full}: worst tile {worst:.2e} at ({tn}, {tk}) of {tuple(err.shape)}, "
+          f"float32 CPU product's worst tile {yard:.2e} (bound {bound:.2e}), global {glob:.2e}", flush=True)
+    assert glob < (2e-3 if dt == "bf16" else 2e-5)
+    assert worst <= bound, (layer, Lr, dt, (tn, tk), worst, yard)
+    return outs
+
+
+# First MI355X run, worst tile (the float32 CPU product's worst tile) over the ten shapes, the same with or without a workspace and one
+# tile short of it: bf16 5.5 - 6.2e-8 (8.8 - 9.0e-8) at 175 tokens and 8.6 - 9.6e-8 (1.04 - 1.05e-7) at 1090, 0.61 - 0.93 of the
+# yardstick (the operands' products are exact in fp32); fp32 2.41 - 2.44e-7 at 175 tokens, equal to the yardstick to three digits (one
+# chain of fmaf in token order on both sides), and 5.7e-7 (2.5e-7) at 1090, 2.24 - 2.27 times it (a chain of 1024 where the CPU sums
+# in blocks).  No tile stands out: the worst one sits at another place in every case.
+@pytest.mark.parametrize("workspace", [False, True])
+@pytest.mark.parametrize("dt", ["bf16", "f32"])
+@pytest.mark.parametrize("Lr", [175, 1090])
+@pytest.mark.parametrize("layer", list(WIDE_LINEARS))
+def test_wgrad_at_the_wide_layers_shapes(dt, layer, Lr, workspace):
+    """ttv_linear_wgrad at the (N, K) of the base and large towers' layer linears, which test_wgrad's shapes (N <= 1408, K <= 768,
+    never both wide) do not reach, per 128 x 128 tile: one wrong tile of 344 hides under a global 2e-3.  Reference: float64 product of
+    the dtype-rounded operands.  Both kernels accumulate in fp32, so a tile is held to WGRAD_TILE_FACTOR times the worst tile of
+    torch's float32 CPU product of the same operands (floored at 1e-6); the global bounds of test_wgrad hold as well."""
+    N, K = WIDE_LINEARS[layer]
+    full = int(L().ttv_linear_wgrad_workspace_bytes(Lr, N, K))
+    assert full >= 65536 * (-(-N // 128)) * (-(-K // 128))
+    outs = _wide_wgrad(dt, layer, Lr, full if workspace else 0, full)
+    if workspace and dt == "bf16":      # the split sum has a fixed order (the fp32 checking kernel accumulates with atomics)
+        assert torch.equal(outs[0], outs[1])
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f32"])
+@pytest.mark.parametrize("layer", ["base-w12", "large-w12", "small-w12"])
+def test_wgrad_workspace_one_tile_short(dt, layer):
+    """A workspace exactly one 64 KB partial tile short of ttv_linear_wgrad_workspace_bytes: the bf16 kernel may not write partials
+    (the last one would land past the end) and takes the atomic fall-back.  Same bounds; no bit-equality between runs."""
+    N, K = WIDE_LINEARS[layer]
+    full = int(L().ttv_linear_wgrad_workspace_bytes(1090, N, K))
+    assert full > 65536
+    _wide_wgrad(dt, layer, 1090, full - 65536, full)
 
 
 def _wgrad_call(dy, lddy, x, ldx, dw, lddw, Lr, N, K, dt, workspace):
@@ -140,7 +223,7 @@ def _rms_bwd_ref(x, gain, dy):
 
 @pytest.mark.parametrize("dt", ["bf16", "f32"])
 @pytest.mark.parametrize("second", [False, True])
-@pytest.mark.parametrize("rows,d", [(77, 256), (2051, 256), (33, 512), (9, 1024), (130, 320)])
+@pytest.mark.parametrize("rows,d", [(77, 256), (2051, 256), (33, 512), (9, 1024), (130, 320), (175, 768), (175, 1024)])
 def test_rmsnorm_backward_chain(dt, second, rows, d):
     g = torch.Generator().manual_seed(rows + d)
     x = (torch.randn(rows, d, generator=g) * 2).to(DT[dt])

@@ -21,6 +21,14 @@ Losses are linear with fixed seeded weights (encoder sum(wz * z), decoder sum(W 
 the same on both sides.  Batches: the tiny size at FULL (1152-row sequence, K = 128 / 200 / 5), the small size at SMALL, and the
 reference's training batch - 5 clips of 16x128x128 with K = 128, which runs on half-item attention tables.
 
+The base (12 layers) and large (24 layers) towers run on SMALL as well (test_tower_gradients_bf16_against_the_tape_replay only).  The
+constants below are absolute and were measured at 4 and 8 layers, and the gap grows with depth, so these two cases are held to
+R x the gap of each quantity instead (tests/gap_bounds.py: R and the measured ratios; tests/test_backward_sizes_cpu.py: what that
+check can still see).  Towers, global / gap (ratio), the five cases side by side - first MI355X runs:
+    tiny-full, small, tiny-five   0.64 - 1.12 of the gap (the figures above)
+    base    encoder 1.81e-2 / 2.26e-2 (0.80)    decoder 1.62e-2 / 1.52e-2 (1.07)
+    large   encoder 3.01e-2 / 2.94e-2 (1.03)    decoder 2.68e-2 / 2.30e-2 (1.17)
+
 The A/B switches of the bf16 backward run in child processes (each is read once per process): TTV_WGRAD_BATCHED=0 is bit-identical;
 TTV_GEGLU_BWD_ERF=1 is within the same bounds and not bit-equal; TTV_TAPE_Y_F32=1 and TTV_TRAIN_FUSED_NORMS=1 are within the same
 bounds of the replay with unrounded KEEL sums.  Also: ttv_fsq_backward against the float64 autograd of the straight-through FSQ.
@@ -41,6 +49,7 @@ import torch
 
 from oracle import titok_oracle as O
 from tests import bf16_tape as T
+from tests import gap_bounds as G
 from tests.blockwise import block_errors, check_blockwise, check_tiles, global_error, tile_errors
 from tests.test_hip_backward_shapes import FULL, SMALL, _model, _state, report
 from titok_video_amd import _lib
@@ -52,7 +61,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LEVELS = [7, 5, 5, 5, 5]
 PATCH = (4, 8, 8)
 FIVE = ([(16, 128, 128)] * 5, [128] * 5)          # the reference's 5-clip training batch
-CASES = {"tiny-full": ("tiny", FULL), "small": ("small", SMALL), "tiny-five": ("tiny", FIVE)}
+CASES = {"tiny-full": ("tiny", FULL), "small": ("small", SMALL), "tiny-five": ("tiny", FIVE), "base": ("base", SMALL), "large": ("large", SMALL)}
+GAP_CASES = ("base", "large")    # 12 and 24 layers: held to R x the rounding gap of each quantity (tests/gap_bounds.py), not to the constants below
 
 TILE_TOL = 0.14          # weight matrices, every 128 x 128 tile      (measured worst 7.0e-2)
 W_GLOBAL_TOL = 0.1       # weight matrices, whole                     (4.9e-2)
@@ -103,6 +113,8 @@ def _is_matrix(t):
 
 def check_against_replay(got, case, what, y_bf16=True):
     """Every bound of the module docstring; the failures are collected so that one run reports every value.  Returns the worst figures."""
+    if case in GAP_CASES:
+        return check_against_gaps(got, case, what, y_bf16)
     size, shapes, counts = CASES[case][0], CASES[case][1][0], CASES[case][1][1]
     ref, ref_clips, ref_codes = replay(case, True, y_bf16)
     exact = replay(case, False)[0]
@@ -152,6 +164,53 @@ def check_against_replay(got, case, what, y_bf16=True):
            f"{worst['clips'][1]:.3e}, codes {worst['codes']:.3e}")
     assert not bad, "\n".join(bad)
     return worst
+
+
+def _tower_references(case, tower, y_bf16=True, params=None):
+    """One tower's float64 gradients and input gradients (the clips, or the codes in a one-element list), twice: the rounded replay and
+    the unrounded model.  The large towers' are built here, one tower at a time from `params` (the bf16 state), and not kept (2.3 GB
+    per tower and replay); the others come from the cached replay, under the cache keys of its other callers."""
+    size, shapes, counts, wz, clips, codes, w = _inputs(case)
+    out = []
+    for rounding in (True, False):
+        if params is None:
+            grads, rclips, rcodes = replay(case, True, y_bf16) if rounding else replay(case, False)
+            out += [{n: v for n, v in grads.items() if n.startswith(tower)}, rclips if tower == "encoder." else [rcodes]]
+        elif tower == "encoder.":
+            out += list(T.encoder_grads(params, clips, counts, wz, size, rounding, y_bf16))
+        else:
+            grads, dcodes = T.decoder_grads(params, codes, counts, shapes, w, size, rounding, y_bf16)
+            out += [grads, [dcodes]]
+    return out
+
+
+def check_against_gaps(got, case, what, y_bf16=True):
+    """check_against_replay for the GAP_CASES: every quantity within tests/gap_bounds.R x its own gap.  Reports per tower the global
+    error, the gap and their ratio (the line of check_against_replay), the worst ratio of every class and the worst ratio per layer."""
+    shapes = CASES[case][1][0]
+    bad, out = [], {}
+    params = {k: v.to(torch.bfloat16) for k, v in _state("large").items()} if CASES[case][0] == "large" else None
+    for tower in ("encoder.", "decoder."):
+        ref, ref_in, exact, exact_in = _tower_references(case, tower, y_bf16, params)
+        mine = {n: g for n, g in got["params"].items() if n.startswith(tower)}
+        b, worst, per_layer, (glob, gap) = G.check_tower(mine, ref, exact, f"{what} {tower[:-1]}")
+        bad += b
+        if tower == "encoder.":
+            b, w_in = G.check_clips(got["clips"], ref_in, exact_in, shapes, what)
+        else:
+            b, w_in = G.check_codes(got["codes"], ref_in[0], exact_in[0], what)
+        bad += b
+        del ref, exact
+        report(f"{what} {tower[:-1]}: global error over all parameters {glob:.3e}, gap {gap:.3e} (ratio {glob / gap:.3f})")
+        report(f"{what} {tower[:-1]}: worst figure / gap per class: "
+               + "; ".join(f"{c} {r:.2f} ({f:.3e} / {g:.3e}, {n})" for c, (r, f, g, n) in worst.items() if c != "tower") + "; "
+               + "; ".join(f"{c} {r:.2f} ({f:.3e} / {g:.3e})" for c, (r, f, g) in w_in.items()))
+        report(f"{what} {tower[:-1]}: worst ratio per layer: "
+               + " ".join(f"{'tower' if k is None else k}:{v:.2f}" for k, v in sorted(per_layer.items(), key=lambda kv: -1 if kv[0] is None else kv[0])))
+        out[tower + "global"], out[tower + "gap"] = glob, gap
+        out.update({tower + c: v for c, v in list(worst.items()) + list(w_in.items())})
+    assert not bad, "\n".join(bad)
+    return out
 
 
 @pytest.mark.parametrize("case", list(CASES))

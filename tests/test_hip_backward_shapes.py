@@ -10,6 +10,8 @@ blocks of 128, GQA 2 (tiny), 4 (small) or 3 (base).  tests/test_hip_backward.py 
   * towers: encoder (smooth loss on z) and decoder (fixed codes, smooth loss on the pixels) gradients against the oracle's autograd at
     full-size clips, with latent-only query rows skipped in the encoder's last layer (K = 128 of 1152 rows, K = 200: two latent
     query blocks), at the tiny and the small size; the bf16 encoder with and without that shortcut.
+  * fp32 towers at the base (12 layers, GQA 12:4, inner 2048) and large (24 layers, 16:4, inner 2752) size on SMALL (175 rows)
+    against the float64 model, per parameter and per 128 x 128 tile, within 4 times the fp32 oracle's own distance from it.
 """
 import functools
 import os
@@ -21,7 +23,9 @@ import pytest
 import torch
 
 from oracle import titok_oracle as O
-from tests.blockwise import attention_reference, check_blockwise
+from tests import bf16_tape as T
+from tests.blockwise import attention_reference, check_blockwise, check_tiles, tile_errors
+from tests.gap_bounds import is_matrix, layer_of
 from titok_video_amd import _lib
 from titok_video_amd.plan import BatchPlan
 
@@ -271,25 +275,166 @@ def _check_bf16(got, ref, what):
     assert glob < 0.12, (what, glob)
 
 
-@pytest.mark.parametrize("size,batch", [("tiny", FULL), ("small", SMALL)], ids=["tiny-full", "small"])
+# ------------------------------------------------------------------------------ fp32 towers against a float64 model of themselves
+# The oracle computes its norms, rotary and attention in fp32 whatever it is given, so it is itself an fp32 execution; the reference
+# here is tests/bf16_tape.py with rounding off - the plain float64 autograd of the model - on the fp32 state, with the linear losses
+# of tests/test_hip_backward_bf16.py (dL/d(output) exact on both sides).  The yardstick is the oracle's fp32 CPU autograd under the
+# same losses against that float64 model: the HIP gradient of a parameter may be 4 times as far from float64 as the oracle's (two fp32
+# executions of one model in different summation orders; the margin of tests/test_hip_fid.py::test_network_against_float64), bound
+# floored at 1e-6 and capped at this file's 2e-3; every 128 x 128 tile of a weight matrix within 4 times the oracle's worst tile of
+# that matrix (floored at 1e-6).  Inputs (clips, codes) like a parameter.  The HIP towers run in the fixed-order summation mode.
+F64_FACTOR, F64_FLOOR, F64_CAP = 4.0, 1e-6, 2e-3
+
+
+def _linear_inputs(shapes, counts):
+    """The loss weights and inputs of tests/test_hip_backward_bf16._inputs: wz, clips, codes and pixel weights (bf16 numbers)."""
+    from titok_video_amd.synthetic import synthetic_clips
+    g = torch.Generator().manual_seed(11)
+    wz = torch.randn(sum(counts), 5, generator=g)
+    codes = O.fsq_indices_to_codes(torch.randint(0, 4375, (sum(counts),), generator=g, dtype=torch.int32), LEVELS)
+    w = [torch.randn((3,) + tuple(s), generator=g).to(torch.bfloat16).float() for s in shapes]
+    clips = [c.float() for c in synthetic_clips(shapes, seed=8, dtype=torch.bfloat16)]
+    return wz, clips, codes, w
+
+
+def _tower_grads_linear_loss(tower, size, shapes, counts, how, state):
+    """({parameter: gradient}, [input gradients]) of one tower under its linear loss.  how: "float64" (the model in float64 autograd),
+    "oracle" (the oracle's fp32 CPU autograd) or "hip" (the fp32 HIP towers).  state: _state(size), built once by the caller (the large
+    size takes seconds) and not modified."""
+    wz, clips, codes, w = _linear_inputs(shapes, counts)
+    mine = {k: v for k, v in state.items() if k.startswith(tower + ".")}
+    if how == "float64":
+        state = mine
+        if tower == "encoder":
+            return T.encoder_grads(state, clips, counts, wz, size, rounding=False)
+        grads, dcodes = T.decoder_grads(state, codes, counts, shapes, w, size, rounding=False)
+        return grads, [dcodes]
+    if how == "oracle":
+        sd = {k: v.clone().requires_grad_(True) for k, v in mine.items()}
+        if tower == "encoder":
+            inputs = [c.clone().requires_grad_(True) for c in clips]
+            z = O.encoder_forward(inputs, list(counts), sd, size, (4, 8, 8), prefix="encoder.")
+            (z * wz).sum().backward()
+        else:
+            inputs = [codes.clone().requires_grad_(True)]
+            rec = O.titok_decode(inputs[0], list(counts), [tuple(s) for s in shapes], sd, size)
+            sum((r * wc).sum() for r, wc in zip(rec, w)).backward()
+        return {k: v.grad for k, v in sd.items()}, [c.grad for c in inputs]
+    from titok_video_amd.model.titok import TiTok
+    # fixed-order sums (set_deterministic): with the atomics the figures move by 10 - 25 % from run to run with the order the blocks
+    # finish in, and a bound at 4 times the oracle is then met or missed by chance; in this mode a build gives one number
+    before = _lib.set_deterministic(True)
+    try:
+        model = TiTok(config(size))
+        model.load_state_dict(state, strict=True)
+        model = model.to(DEV, torch.float32).train()
+        if tower == "encoder":
+            inputs = [c.to(DEV).requires_grad_(True) for c in clips]
+            z = model.encoder.forward_z(inputs, list(counts))
+            (z * wz.to(DEV)).sum().backward()
+        else:
+            inputs = [codes.to(DEV).requires_grad_(True)]
+            rec = model.decode(inputs[0], list(counts), [tuple(s) for s in shapes])
+            sum((r.float() * wc.to(DEV)).sum() for r, wc in zip(rec, w)).backward()
+        torch.cuda.synchronize()
+    finally:
+        _lib.set_deterministic(before)
+    return ({f"{tower}.{n}": p.grad.cpu() for n, p in getattr(model, tower).named_parameters()}, [c.grad.cpu() for c in inputs])
+
+
+def _check_against_float64(tower, size, batch):
+    """The bounds of the comment above; failures are collected so that one run reports every figure."""
+    shapes, counts = batch
+    state = _state(size)
+    ref, ref_in = _tower_grads_linear_loss(tower, size, shapes, counts, "float64", state)
+    yard, yard_in = _tower_grads_linear_loss(tower, size, shapes, counts, "oracle", state)
+    got, got_in = _tower_grads_linear_loss(tower, size, shapes, counts, "hip", state)
+    del state
+    assert set(got) == set(ref) == set(yard)
+    what = f"fp32 {tower} {size} against float64"
+    bad, worst, worst_tile, layers = [], (0.0,), (0.0,), {}
+    for n, r in ref.items():
+        assert got[n] is not None and bool(torch.isfinite(got[n]).all()), n
+        e, y = _rel(got[n], r), _rel(yard[n], r)
+        bound = min(max(F64_FACTOR * y, F64_FLOOR), F64_CAP)
+        worst = max(worst, (e / bound, e, y, bound, n))
+        k = layer_of(n)
+        layers[k] = max(layers.get(k, (0.0, 0.0)), (e, y))
+        if not e <= bound:
+            bad.append(f"{what} {n}: {e:.3e} > {bound:.3e} (oracle {y:.3e})")
+        if is_matrix(r):
+            yt = float(tile_errors(yard[n], r).max())
+            tb = max(F64_FACTOR * yt, F64_FLOOR)
+            try:
+                et, _ = check_tiles(got[n], r, tb, F64_CAP, f"{what} {n}")
+            except AssertionError as err:
+                bad.append(f"{err} (oracle's worst tile {yt:.3e})")
+                et = float(tile_errors(got[n], r).max())
+            worst_tile = max(worst_tile, (et / tb, et, yt, tb, n))
+    for i, (g, r, y) in enumerate(zip(got_in, ref_in, yard_in)):
+        e, ye = _rel(g, r), _rel(y, r)
+        bound = min(max(F64_FACTOR * ye, F64_FLOOR), F64_CAP)
+        report(f"{what}: input {i} gradient {e:.2e} (oracle {ye:.2e}, bound {bound:.2e})")
+        if not e <= bound:
+            bad.append(f"{what} input {i}: {e:.3e} > {bound:.3e} (oracle {ye:.3e})")
+    report(f"{what}: worst parameter {worst[1]:.2e} (oracle {worst[2]:.2e}, bound {worst[3]:.2e}, {worst[4]}); "
+           f"worst tile {worst_tile[1]:.2e} (oracle's worst tile of that matrix {worst_tile[2]:.2e}, bound {worst_tile[3]:.2e}, {worst_tile[4]})")
+    report(f"{what}: worst parameter per layer, HIP/oracle: "
+           + " ".join(f"{'tower' if k is None else k}:{e:.1e}/{y:.1e}" for k, (e, y) in sorted(layers.items(), key=lambda kv: -1 if kv[0] is None else kv[0])))
+    assert not bad, "\n".join(bad)
+
+
+FP32_CASES = [("tiny", FULL), ("small", SMALL), ("base", SMALL), ("large", SMALL)]
+FP32_IDS = ["tiny-full", "small", "base", "large"]
+
+
+# MI355X figures of the HIP towers against float64 on SMALL: worst parameter (its bound), worst tile (its bound);
+# worst parameter per layer.  Fixed-order mode: two runs gave these same digits.
+#   base   encoder 4.5e-6 (mask_token; bound 6.8e-6), tile 1.1e-5 (2.0e-5); layers 4.0e-6 (layer 0), 6.3e-6 (layer 1) - 7.5e-6 (layer 9)
+#          decoder 3.4e-6 (5.6e-6), tile 1.8e-5 (2.9e-5, layer 10 to_qkv); layers 2.8 - 3.7e-6
+#   large  encoder 5.5e-6 (9.1e-6), tile 8.3e-6 (1.4e-5); layers 5.6e-6 (layer 0), 8.7e-6 (layer 1) - 1.1e-5 (layer 19)
+#          decoder 4.8e-6 (7.9e-6), tile 2.2e-5 (3.3e-5, layer 16 to_qkv); layers 3.7 - 4.8e-6
+# The figure nearest its bound is at 0.66 of it (a bound is 4 times the oracle's own figure, 1.4 - 2.3e-6 per parameter here).
+# No growth with depth beyond the first layers: the KEEL post-norms keep the residual stream's error level.  HIP's worst tile of a
+# matrix is about twice the oracle's worst tile of it: the fp32 GEMMs here sum K = 768 ... 2752 as one chain where the CPU's sum in
+# blocks (tests/test_hip_backward.py test_wgrad_at_the_wide_layers_shapes: 2.2 times the CPU product's error at 1090 tokens).
+# One matrix stood out when these cases first ran, decoder layer 0's to_qkv at the large size (q rows of heads 4 and 5, 4 - 5 times
+# the oracle).  There 128 of the long sequence's 168 rows are the same mask-token row up to the rotary angle, so the keys share one
+# large component c and dQ = sum_j dS_j k_j carries c * sum_j dS_j, which is zero on paper.  The fp32 attention backward took delta and
+# P from the forward's output and LSE, which leaves sum_j dS_j at ~1e-6 |dP|, and summed dQ in fp32, which rounds at the size of the
+# partial sums; it now forms delta from its own P and dP and sums dQ (and the owner kernel's dK, dV) in float64 (csrc/ttv_bwd.hip,
+# k_attn_delta_f32_consistent, k_attn_bwd_f32).
+# With both the matrix is no longer the tower's worst (layer 16's to_qkv is, at 2.6 times the oracle).
+# The float64 comparison is not added to the tiny and small cases, which were to get it if it cost under a second each: with it the
+# small cases took 2.1 - 2.4 s (three model runs and the tile errors of every matrix, more than half of that), and at tiny on FULL
+# (1661 rows) the float64 model and the oracle alone take 0.85 s on the CPU before the second HIP run and the tiles.
+@pytest.mark.parametrize("size,batch", FP32_CASES, ids=FP32_IDS)
 def test_encoder_gradients_fp32_at_full_size(size, batch):
     """fp32 encoder (k_attn_bwd_f32 with the latent query-row limit, the compact latent_tail backward with patch rows present) against
-    the oracle's autograd: every parameter and the input clips within 2e-3."""
+    the oracle's autograd: every parameter and the input clips within 2e-3 (tiny, small); base and large against the float64 model
+    within 4 times the oracle's own error (the comment above)."""
     shapes, counts = batch
-    ref, ref_clips = _encoder_reference(size, tuple(shapes), tuple(counts))
-    got, clips = _encoder_grads(size, torch.float32, shapes, counts)
-    _check_fp32(got, ref, f"fp32 encoder {size}")
-    for c, rc in zip(clips, ref_clips):
-        assert _rel(c, rc) < 2e-3
+    if size in ("tiny", "small"):
+        ref, ref_clips = _encoder_reference(size, tuple(shapes), tuple(counts))
+        got, clips = _encoder_grads(size, torch.float32, shapes, counts)
+        _check_fp32(got, ref, f"fp32 encoder {size}")
+        for c, rc in zip(clips, ref_clips):
+            assert _rel(c, rc) < 2e-3
+    else:       # tiny and small keep the oracle as their reference (the cost of the float64 comparison there: the comment above)
+        _check_against_float64("encoder", size, batch)
 
 
-@pytest.mark.parametrize("size,batch", [("tiny", FULL), ("small", SMALL)], ids=["tiny-full", "small"])
+@pytest.mark.parametrize("size,batch", FP32_CASES, ids=FP32_IDS)
 def test_decoder_gradients_fp32_at_full_size(size, batch):
+    """As the encoder's."""
     shapes, counts = batch
-    ref, ref_codes = _decoder_reference(size, tuple(shapes), tuple(counts))
-    got, codes = _decoder_grads(size, torch.float32, shapes, counts)
-    _check_fp32(got, ref, f"fp32 decoder {size}")
-    assert _rel(codes, ref_codes) < 2e-3
+    if size in ("tiny", "small"):
+        ref, ref_codes = _decoder_reference(size, tuple(shapes), tuple(counts))
+        got, codes = _decoder_grads(size, torch.float32, shapes, counts)
+        _check_fp32(got, ref, f"fp32 decoder {size}")
+        assert _rel(codes, ref_codes) < 2e-3
+    else:
+        _check_against_float64("decoder", size, batch)
 
 
 @pytest.mark.parametrize("size,batch", [("tiny", FULL), ("small", SMALL)], ids=["tiny-full", "small"])

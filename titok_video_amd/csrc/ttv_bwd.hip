@@ -11,6 +11,7 @@
 //                      ds_read_b64_tr_b16 (hardware transpose read) from row-major LDS tiles; split over token ranges,
 //                      fp32 atomic accumulation into dW (one 256-byte row segment per wave instruction)
 //   k_attn_delta       delta[t,h] = sum_d dO*O
+//   k_attn_delta_f32_consistent   the fp32 checking path's delta = sum_j p_j dP_j / sum_j p_j, from its own P and dP
 //   k_attn_bwd_dq / k_attn_bwd_dkv   flash-style recompute (P from Q,K and the forward's LSE): no atomics - one kernel
 //                      owns query blocks (dQ), the other key blocks (dK, dV); GQA heads of a group are summed in-kernel
 //   *_f32 variants     naive VALU kernels, used only to check gradients tightly in fp32
@@ -1505,6 +1506,41 @@ __device__ __forceinline__ int attn_bwd_query_rows(const int* __restrict__ qlim_
   return lim < S ? lim : S;
 }
 
+// delta of the naive fp32 backward, formed from the very P and dP that backward subtracts it from: one wave per (query row, q-head),
+//   delta[t, h] = sum_j p_j dP_j / sum_j p_j,   p_j = exp(s_j - lse), dP_j = dO . v_j   (the expressions of k_attn_bwd_f32, same order).
+// rowsum(dO * O) is the same number on paper, but it comes from the forward's O, and p_j from the forward's lse: the recomputed scores
+// differ from the forward's in the last bits, so sum_j p_j (dP_j - delta) is not zero but ~1e-6 |dP|.  Where the keys of a sequence
+// share a large common component (decoder layer 0: every patch row is the mask token) dQ = sum_j dS_j k_j multiplies that residue
+// by the common component, which the exact gradient cancels: the to_qkv gradient of that layer was 4 - 5 times as far from float64 as
+// an fp32 autograd of the same model, against 2 times everywhere else.  Rows attn_bwd_query_rows leaves out are not written.
+__global__ __launch_bounds__(256) void k_attn_delta_f32_consistent(const float* __restrict__ qkvg, int ld, const float* __restrict__ dout, int ldd,
+                                                                   const float* __restrict__ lse, float* __restrict__ delta,
+                                                                   const int* __restrict__ cu, const int* __restrict__ row_seq,
+                                                                   int total_rows, int hq, int hkv, float scale, const int* __restrict__ qlim_desc) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int idx = blockIdx.x * 4 + wave;
+  if (idx >= total_rows * hq) return;
+  const int t = idx / hq, h = idx % hq;
+  const int d_model = hq * 64, gqa = hkv * 64, kvh = h / (hq / hkv);
+  const int seq = row_seq[t];
+  const int s0 = cu[seq], s1 = cu[seq + 1];
+  if (qlim_desc && t - s0 >= attn_bwd_query_rows(qlim_desc, seq, s0, s1 - s0)) return;
+  const float q = qkvg[(size_t)t * ld + h * 64 + lane];
+  const float dov = dout[(size_t)t * ldd + h * 64 + lane];
+  const float l = lse[(size_t)t * hq + h];
+  double sp = 0.0, spd = 0.0;       // float64 sums of the fp32 terms: delta is then the rounding of the exact ratio of what the backward adds
+  for (int j = s0; j < s1; ++j) {
+    const float kv = qkvg[(size_t)j * ld + 2 * d_model + kvh * 64 + lane];
+    const float vv = qkvg[(size_t)j * ld + 2 * d_model + gqa + kvh * 64 + lane];
+    const float sdot = wave_sum(q * kv) * scale;
+    const float p = expf(sdot - l);
+    const float dp = wave_sum(dov * vv);
+    sp += (double)p;
+    spd += (double)p * (double)dp;
+  }
+  if (lane == 0) delta[(size_t)t * hq + h] = (float)(spd / sp);
+}
+
 // naive fp32 backward: one wave per (query row, q-head); lane = head dim.  dk/dv accumulate with fp32 atomics into
 // [L, g] scratch (zeroed by the caller), dq is written directly.  ATOMIC_DKV = false (deterministic mode): dq only, the same
 // arithmetic; dk / dv then come from k_attn_bwd_f32_dkv below.
@@ -1528,7 +1564,9 @@ __global__ __launch_bounds__(256) void k_attn_bwd_f32(const float* __restrict__ 
   const float q = qkvg[(size_t)t * ld + h * 64 + lane];
   const float dov = dout[(size_t)t * ldd + h * 64 + lane];
   const float l = lse[(size_t)t * hq + h], dl = delta[(size_t)t * hq + h];
-  float dq = 0.f;
+  // dq in float64: sum_j ds_j is zero on paper, so where the keys share a large common component the running fp32 sum of ds_j k_j
+  // carried that component times the partial sums of ds and rounded at their size, not at the size of the result
+  double dq = 0.0;
   for (int j = s0; j < s1; ++j) {
     const float kv = qkvg[(size_t)j * ld + 2 * d_model + kvh * 64 + lane];
     const float vv = qkvg[(size_t)j * ld + 2 * d_model + gqa + kvh * 64 + lane];
@@ -1536,13 +1574,13 @@ __global__ __launch_bounds__(256) void k_attn_bwd_f32(const float* __restrict__ 
     const float p = expf(sdot - l);
     const float dp = wave_sum(dov * vv);
     const float ds = p * (dp - dl) * scale;
-    dq += ds * kv;
+    dq += (double)ds * (double)kv;
     if (ATOMIC_DKV) {
       atomicAdd(dkv + (size_t)j * 2 * gqa + kvh * 64 + lane, ds * q);
       atomicAdd(dkv + (size_t)j * 2 * gqa + gqa + kvh * 64 + lane, p * dov);
     }
   }
-  dqkvg[(size_t)t * ldg + h * 64 + lane] = dq;
+  dqkvg[(size_t)t * ldg + h * 64 + lane] = (float)dq;
 }
 
 // Deterministic dk / dv of the naive fp32 backward: one wave OWNS a (key row, kv-head) and adds the terms of the kernel above in a fixed
@@ -1563,7 +1601,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_f32_dkv(const float* __restric
   const int nq = attn_bwd_query_rows(qlim_desc, seq, s0, S);
   const float kv = qkvg[(size_t)j * ld + 2 * d_model + kvh * 64 + lane];
   const float vv = qkvg[(size_t)j * ld + 2 * d_model + gqa + kvh * 64 + lane];
-  float dk = 0.f, dv = 0.f;
+  double dk = 0.0, dv = 0.0;        // as dq above: the query rows share a common component too
   for (int t = s0; t < s0 + nq; ++t)
     for (int h = kvh * rep; h < (kvh + 1) * rep; ++h) {
       const float q = qkvg[(size_t)t * ld + h * 64 + lane];
@@ -1573,11 +1611,11 @@ __global__ __launch_bounds__(256) void k_attn_bwd_f32_dkv(const float* __restric
       const float p = expf(sdot - l);
       const float dp = wave_sum(dov * vv);
       const float ds = p * (dp - dl) * scale;
-      dk += ds * q;
-      dv += p * dov;
+      dk += (double)ds * (double)q;
+      dv += (double)p * (double)dov;
     }
-  dkv[(size_t)j * 2 * gqa + kvh * 64 + lane] = dk;
-  dkv[(size_t)j * 2 * gqa + gqa + kvh * 64 + lane] = dv;
+  dkv[(size_t)j * 2 * gqa + kvh * 64 + lane] = (float)dk;
+  dkv[(size_t)j * 2 * gqa + gqa + kvh * 64 + lane] = (float)dv;
 }
 
 // ---- bf16 MFMA kernels.  LDS tiles are row-major [64 rows][64 cols] bf16 with 128-byte rows; the 16-byte chunk c of row r
@@ -1974,17 +2012,19 @@ int ttvk_attention_bwd(const void* qkvg, int ld, const void* o, int ldo, const v
   TTV_CHECK_ARG(hq >= 1 && hkv >= 1 && hq % hkv == 0, "attention_bwd: %d q-heads on %d kv-heads", hq, hkv);
   const float scale = 0.125f;
   const int d_model = hq * 64, gqa = hkv * 64;
-  if (delta_ready) {
-    // the caller's gate backward already filled delta (same values: sum of the stored dO times O)
-  } else if (dt == TTV_BF16) hipLaunchKernelGGL((k_attn_delta<bf16_t>), dim3(ttv_cdiv(total_rows * hq, 256)), dim3(256), 0, s, (const bf16_t*)dout, ldd, (const bf16_t*)o, ldo, delta, total_rows, hq);
-  else hipLaunchKernelGGL((k_attn_delta<float>), dim3(ttv_cdiv(total_rows * hq, 256)), dim3(256), 0, s, (const float*)dout, ldd, (const float*)o, ldo, delta, total_rows, hq);
-  TTV_CHECK_LAUNCH("attn_delta");
+  if (dt == TTV_BF16 && !delta_ready) {    // delta_ready: the caller's gate backward already filled delta (same values: sum of the stored dO times O)
+    hipLaunchKernelGGL((k_attn_delta<bf16_t>), dim3(ttv_cdiv(total_rows * hq, 256)), dim3(256), 0, s, (const bf16_t*)dout, ldd, (const bf16_t*)o, ldo, delta, total_rows, hq);
+    TTV_CHECK_LAUNCH("attn_delta");
+  }
   if (dt == TTV_BF16) {
     hipLaunchKernelGGL(k_attn_bwd, dim3(n_blocks64 * (hkv + hq)), dim3(256), 0, s, (const bf16_t*)qkvg, ld, (const bf16_t*)dout, ldd, lse, delta, cu,
                        blocks64, n_blocks64, (bf16_t*)dqkvg, ldg, hq, hkv, scale, rope_cs, qlim_desc);
     TTV_CHECK_LAUNCH("attn_bwd");
   } else {
     TTV_CHECK_ARG(dkv_scratch && row_seq, "attention_bwd: fp32 path needs scratch and row map");
+    // the checking path replaces rowsum(dO * O) by the delta that is consistent with its own P and dP (k_attn_delta_f32_consistent)
+    hipLaunchKernelGGL(k_attn_delta_f32_consistent, dim3(ttv_cdiv(total_rows * hq, 4)), dim3(256), 0, s, (const float*)qkvg, ld, (const float*)dout, ldd, lse, delta, cu, row_seq, total_rows, hq, hkv, scale, qlim_desc);
+    TTV_CHECK_LAUNCH("attn_delta_f32_consistent");
     if (ttv_det()) {
       // dq as ever, dk / dv by an owner per (key row, kv-head): the same [L, 2g] scratch, written whole
       hipLaunchKernelGGL(k_attn_bwd_f32<false>, dim3(ttv_cdiv(total_rows * hq, 4)), dim3(256), 0, s, (const float*)qkvg, ld, (const float*)dout, ldd, lse, delta, cu, row_seq, (float*)dqkvg, ldg, dkv_scratch, total_rows, hq, hkv, scale, qlim_desc);

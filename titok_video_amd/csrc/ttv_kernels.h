@@ -247,6 +247,8 @@ int ttvk_expand_small(const void* a, int a_dt, int lda, int C, const void* w, in
                       int rows, int d, hipStream_t s);
 int ttvk_reduce_small(const void* a, int a_dt, int lda, const int* a_rows, const void* w, int w_dt, int ldw, int C, float* out, int ldo,
                       int rows, int d, hipStream_t s);
+// o / ldo and delta_ready apply to bf16 only (delta = rowsum(dO * O), or the caller's gate backward filled it): the fp32 checking path
+// writes `delta` itself, from its own P and dP (k_attn_delta_f32_consistent), whatever the buffer held.
 int ttvk_attention_bwd(const void* qkvg, int ld, const void* o, int ldo, const void* dout, int ldd, const float* lse, float* delta,
                        const int* cu, const int* blocks64, int n_blocks64, const int* row_seq, void* dqkvg, int ldg, float* dkv_scratch,
                        int total_rows, int hq, int hkv, int dt, const float* rope_cs, hipStream_t s, int delta_ready = 0, const int* qlim_desc = nullptr);
