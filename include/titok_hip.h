@@ -924,6 +924,57 @@ int ttv_clip_resample_u8(void* const* frames_thwc, void* const* clips_cthw, cons
 int ttv_recon_panels_u8(void* const* target, void* const* recon, const int32_t* dims, int n_clips, int dtype, void* const* panels,
                         void* stream);
 
+/* ---- whole videos: overlapped 3-D tiles in, blended uint8 frames out (titok_video_amd/video.py) -----------------------------
+ * A decoded video uint8 [T][H][W][3] is cut into equal tiles that overlap, each tile goes through the tokenizer on its own, and the
+ * reconstructions are blended back into frames.  The plan is the same for both directions.
+ * Timeline: output frame j is source frame frame_stride * j, j = 0 .. T' - 1, T' = ceil(T / frame_stride); axes below are (T', H, W).
+ * Per axis a (length n, tile[a], overlap[a], count[a]): stride = tile - overlap; tile k of the axis starts at k * stride for
+ * k < count - 1 and the last one at max(n - tile, 0), so it ends at the border.  count is 1 when n < tile (the tile is then longer
+ * than the axis: samples beyond n - 1 are edge-clamped on the way in and dropped on the way out) and ceil((n - tile) / stride) + 1
+ * otherwise; a point may lie in up to three tiles of an axis.  Tile index = (kt * count[1] + kh) * count[2] + kw.
+ * Weight of a tile at local coordinate u of an axis: the integer min(u + 1, tile - u, overlap + 1); at an element the product of
+ * the three.  TTV_ERR_INVALID for a plan with T, H, W, frame_stride or a tile below 1, overlap < 0, overlap > tile / 2 on an axis
+ * with more than one tile, a count that is not the rule's (it would put an origin outside the timeline),
+ * (overlap[0] + 1)(overlap[1] + 1)(overlap[2] + 1) >= 2^24, a tile of 2^31 elements or more, or 2^31 tiles or more. */
+typedef struct ttv_video_plan {
+  int32_t T, H, W;          /* the decoded video */
+  int32_t frame_stride;
+  int32_t tile[3];          /* (Tt, Ht, Wt), the effective tile: a multiple of the patch, never more than one patch beyond a short axis */
+  int32_t overlap[3];
+  int32_t count[3];         /* tiles per axis */
+} ttv_video_plan;
+
+/* Gather: tiles [tile_begin, tile_end) of the plan -> `tiles`, one contiguous buffer [tile_end - tile_begin][3][Tt][Ht][Wt] in `dtype`
+ * (TTV_BF16 or TTV_F32), 16-byte aligned.  Element (c, i, y, x) of the tile with origin (t0, h0, w0) is
+ *   frames[frame_stride * min(t0 + i, T' - 1)][min(h0 + y, H - 1)][min(w0 + x, W - 1)][c] / 127.5 - 1
+ * evaluated in fp32 (one division, one subtraction) and rounded once to `dtype`: ttv_clip_from_u8's expression, so the bits are those
+ * ttv_clip_from_u8 gives for the same pixels.  Any H, W >= 1 and any alignment of `frames_thwc`: with Wt % 8 == 0 a thread takes 8
+ * pixels of a tile row with 4-byte loads of the aligned words that hold their 24 bytes and writes three 16-byte (bf16) or six
+ * 16-byte (fp32) vectors; at the ends of the video (words that leave the array, clamped columns) and for other Wt it goes byte by byte.
+ * Every source byte inside a tile is read once per tile that covers it (the aligned words of neighbouring threads share bytes, which
+ * the cache serves).  TTV_ERR_INVALID with nothing launched: a bad dtype, a null pointer, a destination off the 16-byte grid, a tile
+ * range outside [0, tiles of the plan], a bad plan.  An empty range does nothing.  Work is enqueued on `stream` only. */
+int ttv_video_tiles_u8(const void* frames_thwc, const ttv_video_plan* plan, int tile_begin, int tile_end, void* tiles, int dtype,
+                       void* stream);
+
+/* Blend: frames [t0, t1) of the timeline -> frames_out uint8 [t1 - t0][H][W][3] from reconstructed tiles [3][Tt][Ht][Wt] in `dtype`.
+ * tiles: HOST array of the plan's tile count of device pointers in tile order (what the checks read); tiles_dev: the same table in
+ * device memory (what the kernel reads).  A tile that covers no frame of the range may be NULL.
+ * Value of byte (t, y, x, c), from the tiles that cover (t, y, x) in ascending tile index:
+ *   v = the tile's element (c, t - t0_tile, y - h0, x - w0) widened exactly to fp32 and clamped to [-1, 1] (a NaN stays a NaN);
+ *   one covering tile: q = v.  More: num = 0.0f, then num = num + (w * v) per tile with the product and the sum each rounded to fp32
+ *   on their own (no fused multiply-add), w the tile's integer weight at the element; den = the integer sum of the weights,
+ *   converted to fp32 once; q = num / den, correctly rounded;
+ *   t = q + 1.0f; t = t * 127.5f, each rounded on its own; level = round-half-even(t), with t < 0 -> 0, t >= 255 -> 255, NaN -> 0.
+ * A gather per output element, no atomics: identical calls give identical bits.  Any H, W >= 1 and any alignment of frames_out; a
+ * thread owns 4 consecutive pixels of a row, reads each tile that holds them once (one 8- or 16-byte vector per channel where the
+ * four lie in the tile on a vector boundary, single elements otherwise) and stores their 12 bytes as three words where they lie on
+ * the 4-byte grid, byte by byte otherwise and at the end of a row.  Every byte of the range is written once and nothing outside it.
+ * TTV_ERR_INVALID with nothing launched: a bad dtype or plan, a null table or output, t0 < 0, t1 > T', t0 > t1, a covering tile whose
+ * pointer is NULL or not aligned to its element size.  An empty range does nothing.  Work is enqueued on `stream` only. */
+int ttv_video_blend_u8(void* const* tiles, void* const* tiles_dev, const ttv_video_plan* plan, int t0, int t1, int dtype,
+                       void* frames_out, void* stream);
+
 /* PSNR statistic of the evaluation loop (model/metrics/eval_metrics.py:19,32-36: x.clamp(-1, 1), torchmetrics
  * PeakSignalNoiseRatio(data_range=2) = running sum of squared errors + element count): acc[0] += sum (clamp(recon) - target)^2,
  * acc[1] += number of elements, both double, device memory, over the clips of the call (host arrays of device pointers, `dtype`).

@@ -192,6 +192,10 @@ class VjepaWeights(C.Structure):
                 ("pool_fc2_w", vp), ("pool_fc2_b", vp)]
 
 
+class VideoPlan(C.Structure):
+    _fields_ = [("T", i32), ("H", i32), ("W", i32), ("frame_stride", i32), ("tile", i32 * 3), ("overlap", i32 * 3), ("count", i32 * 3)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -314,6 +318,8 @@ SYMBOLS = {
     "ttv_clip_from_u8": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "ttv_clip_resample_u8": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
     "ttv_recon_panels_u8": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp]),
+    "ttv_video_tiles_u8": (C.c_int, [vp, C.POINTER(VideoPlan), C.c_int, C.c_int, vp, C.c_int, vp]),
+    "ttv_video_blend_u8": (C.c_int, [vp, vp, C.POINTER(VideoPlan), C.c_int, C.c_int, C.c_int, vp, vp]),
     "ttv_sq_err_accumulate": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "ttv_ssim_workspace_bytes": (C.c_int64, [vp, C.c_int]),
     "ttv_ssim_accumulate": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int64, vp]),

@@ -46,6 +46,11 @@ template <> struct Cvt<bf16_t> {
 // round a fp32 value through the storage type (what a store+load of T would do)
 template <typename T> __device__ __forceinline__ float round_to(float v) { return Cvt<T>::to_f(Cvt<T>::from_f(v)); }
 
+// A decoded uint8 level as the normalised pixel the towers take: u8 / 127.5 - 1 in fp32, one correctly rounded division and one
+// subtraction (the torch expression of the host loader).  k_clip_from_u8 (ttv_elem.hip) and k_video_tiles (ttv_video.hip) both call
+// this, so a tile cut from a video holds the bits the loader would have produced for the same pixels.
+__device__ __forceinline__ float ttv_unit_from_u8(uint32_t level) { return __fsub_rn(__fdiv_rn((float)level, 127.5f), 1.0f); }
+
 // 4 consecutive elements
 template <typename T> struct Vec4;
 template <> struct Vec4<float> {

@@ -901,12 +901,12 @@ __global__ __launch_bounds__(256) void k_clip_from_u8(const uint8_t* __restrict_
     for (int c = 0; c < 3; ++c) {
       f32x4 v;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = __fsub_rn(__fdiv_rn((float)b[3 * i + c], 127.5f), 1.0f);
+      for (int i = 0; i < 4; ++i) v[i] = ttv_unit_from_u8(b[3 * i + c]);
       Vec4<T>::store(clip + (size_t)c * n_pix + p0, v);
     }
   } else {
     for (long long p = p0; p < n_pix; ++p)
-      for (int c = 0; c < 3; ++c) clip[(size_t)c * n_pix + p] = Cvt<T>::from_f(__fsub_rn(__fdiv_rn((float)frames[p * 3 + c], 127.5f), 1.0f));
+      for (int c = 0; c < 3; ++c) clip[(size_t)c * n_pix + p] = Cvt<T>::from_f(ttv_unit_from_u8(frames[p * 3 + c]));
   }
 }
 

@@ -1,0 +1,354 @@
+// Whole videos in and out (titok_video_amd/video.py): a decoded video uint8 [T][H][W][3] is cut into equal, overlapping 3-D tiles the
+// towers can take, and the reconstructed tiles are blended back into uint8 frames.  include/titok_hip.h states the plan (origins,
+// tile order, weights) and the value of every output element; both kernels are streaming kernels with no atomics.
+//
+// Kernels
+//   k_video_tiles<T>     : grid (blocks per tile x tiles of the range), 1 KiB of LDS (the 256 normalised levels).  Wt % 8 == 0.  A
+//                          thread owns 8 consecutive pixels of one tile row: their 24 source bytes start at any byte offset (rows
+//                          are 3W bytes), so it loads the 7 aligned words that hold them, shifts them into place (v_alignbyte_b32)
+//                          and stores one 16-byte (bf16) or two 16-byte (fp32) vectors into each of the three channel planes.  A
+//                          thread whose words would leave the array, or whose columns are clamped (W shorter than the tile), reads
+//                          its bytes one by one.
+//   k_video_tiles_any<T> : any Wt, a thread per pixel of a tile: 3 byte loads, 3 element stores.
+//   k_video_blend<T>     : a thread owns 4 consecutive pixels of an output row (12 bytes).  It walks the tiles that hold any of them
+//                          in ascending index - up to 3 per axis for a pixel - and reads from each one vector per channel (the four
+//                          pixels inside the tile on a vector boundary) or up to 12 single elements; the 12 bytes go out as three
+//                          words when they lie on the 4-byte grid (always, when 3W % 4 == 0 and the output is aligned; one row in
+//                          four otherwise) and byte by byte elsewhere.
+// Traffic per pixel of the timeline, tile t with overlap o per axis (r = prod t / (t - o), the cover ratio: 1.75 at 16 x 128 x 128
+// with 4 x 16 x 16): the gather reads 3 r bytes and writes 3 r elements; the blend reads 3 r elements and writes 3 bytes.  DESIGN.md
+// has the measured rates beside a device-to-device copy of the same byte count.
+#include <algorithm>
+
+#include "ttv_common.h"
+#include "ttv_kernels.h"
+
+namespace {
+
+struct VideoAxis {
+  int32_t n;          // length on the timeline
+  int32_t tile, stride, count, overlap;
+};
+struct VideoGeo {
+  VideoAxis a[3];
+  int32_t H, W, frame_stride;      // of the source frames
+};
+
+__host__ __device__ __forceinline__ int axis_origin(const VideoAxis& a, int k) {
+  if (k < a.count - 1) return k * a.stride;
+  return a.n > a.tile ? a.n - a.tile : 0;
+}
+__host__ __device__ __forceinline__ int axis_weight(const VideoAxis& a, int u) {
+  int w = u + 1;
+  if (a.tile - u < w) w = a.tile - u;
+  if (a.overlap + 1 < w) w = a.overlap + 1;
+  return w;
+}
+
+// The tiles of an axis that hold any of the points p0 .. p1 (p0 == p1: one point): `regular` consecutive ones from k0 among the
+// tiles 0 .. count - 2 - from the first that holds p0 to the last that holds p1 - then the last tile (index count - 1) when p1
+// reaches it.  Ascending, and however many there are (three at most for one point under the plan's rules).  Whether a tile of a
+// span holds one given point is its local coordinate's business.
+struct Cover {
+  int k0, regular, n;
+};
+__device__ __forceinline__ Cover axis_cover(const VideoAxis& a, int p0, int p1) {
+  Cover c = {0, 0, 0};
+  if (a.count > 1) {
+    const int lo = p0 - a.tile + 1;
+    c.k0 = lo <= 0 ? 0 : (lo + a.stride - 1) / a.stride;
+    const int hi = min(p1 / a.stride, a.count - 2);
+    c.regular = hi >= c.k0 ? hi - c.k0 + 1 : 0;
+  }
+  c.n = c.regular + (p1 >= a.n - a.tile ? 1 : 0);
+  return c;
+}
+__device__ __forceinline__ int cover_tile(const VideoAxis& a, const Cover& c, int j) { return j < c.regular ? c.k0 + j : a.count - 1; }
+
+template <typename T> __device__ __forceinline__ void store8(T* p, const float (&v)[8]);
+template <> __device__ __forceinline__ void store8<float>(float* p, const float (&v)[8]) {
+  *reinterpret_cast<f32x4*>(p) = (f32x4){v[0], v[1], v[2], v[3]};
+  *reinterpret_cast<f32x4*>(p + 4) = (f32x4){v[4], v[5], v[6], v[7]};
+}
+template <> __device__ __forceinline__ void store8<bf16_t>(bf16_t* p, const float (&v)[8]) {
+  bf16x8 b;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) b[e] = (bf16_t)v[e];
+  *reinterpret_cast<bf16x8*>(p) = b;
+}
+
+// ---- gather ---------------------------------------------------------------------------------------------------------------
+struct TileAt {
+  int t0, h0, w0;
+};
+__device__ __forceinline__ TileAt tile_origin(const VideoGeo& g, int tile) {
+  const int kw = tile % g.a[2].count, r = tile / g.a[2].count;
+  return {axis_origin(g.a[0], r / g.a[1].count), axis_origin(g.a[1], r % g.a[1].count), axis_origin(g.a[2], kw)};
+}
+// byte offset of the source row of tile row (i, y): frame frame_stride * min(t0 + i, T' - 1), row min(h0 + y, H - 1)
+__device__ __forceinline__ size_t source_row(const VideoGeo& g, const TileAt& o, int i, int y) {
+  const int ts = g.frame_stride * min(o.t0 + i, g.a[0].n - 1), ys = min(o.h0 + y, g.H - 1);
+  return ((size_t)ts * g.H + ys) * (size_t)g.W * 3;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_video_tiles(const uint8_t* __restrict__ frames, size_t frame_bytes, T* __restrict__ out,
+                                                     const VideoGeo g, int tile_begin, uint32_t groups_per_tile, uint32_t blocks_per_tile) {
+  const uint32_t local = blockIdx.x / blocks_per_tile;
+  const uint32_t gi = (blockIdx.x - local * blocks_per_tile) * 256u + threadIdx.x;      // group of 8 pixels inside the tile
+  // The 256 values a byte can take, each formed by the shared expression (the same bits), then looked up: a correctly rounded
+  // division is some 15 instructions, and 24 of them per thread would make this kernel compute-bound.
+  __shared__ float unit[256];
+  unit[threadIdx.x] = ttv_unit_from_u8(threadIdx.x);
+  __syncthreads();
+  if (gi >= groups_per_tile) return;
+  const int Ht = g.a[1].tile, Wt = g.a[2].tile;
+  const uint32_t per_row = (uint32_t)Wt / 8u;
+  const uint32_t row = gi / per_row, xg = gi - row * per_row;
+  const int i = (int)(row / (uint32_t)Ht), y = (int)(row - (uint32_t)i * (uint32_t)Ht);
+  const TileAt o = tile_origin(g, tile_begin + (int)local);
+  const int x0 = o.w0 + (int)xg * 8;
+  const uint8_t* src = frames + source_row(g, o, i, y);
+  uint32_t d[6];                                                  // the 24 bytes of pixels x0 .. x0 + 7, in place
+  const uintptr_t at = (uintptr_t)(src + (size_t)x0 * 3), lo = at & ~(uintptr_t)3;
+  if (x0 + 8 <= g.W && lo >= (uintptr_t)frames && lo + 28 <= (uintptr_t)frames + frame_bytes) {
+    const uint32_t* wp = reinterpret_cast<const uint32_t*>(lo);
+    uint32_t w[7];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) w[k] = wp[k];
+    const uint32_t sh = (uint32_t)(at & 3);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) d[k] = __builtin_amdgcn_alignbyte(w[k + 1], w[k], sh);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) d[k] = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const uint8_t* px = src + (size_t)min(x0 + e, g.W - 1) * 3;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) d[(3 * e + c) >> 2] |= (uint32_t)px[c] << (8 * ((3 * e + c) & 3));
+    }
+  }
+  const size_t plane = (size_t)g.a[0].tile * Ht * Wt;
+  T* dst = out + (size_t)local * 3 * plane + (size_t)row * Wt + (size_t)xg * 8;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = unit[(d[(3 * e + c) >> 2] >> (8 * ((3 * e + c) & 3))) & 0xFFu];
+    store8<T>(dst + (size_t)c * plane, v);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_video_tiles_any(const uint8_t* __restrict__ frames, T* __restrict__ out, const VideoGeo g,
+                                                         int tile_begin, uint32_t pixels_per_tile, uint32_t blocks_per_tile) {
+  const uint32_t local = blockIdx.x / blocks_per_tile;
+  const uint32_t pi = (blockIdx.x - local * blocks_per_tile) * 256u + threadIdx.x;
+  if (pi >= pixels_per_tile) return;
+  const int Ht = g.a[1].tile, Wt = g.a[2].tile;
+  const uint32_t row = pi / (uint32_t)Wt;
+  const int x = (int)(pi - row * (uint32_t)Wt), i = (int)(row / (uint32_t)Ht), y = (int)(row - (uint32_t)i * (uint32_t)Ht);
+  const TileAt o = tile_origin(g, tile_begin + (int)local);
+  const uint8_t* px = frames + source_row(g, o, i, y) + (size_t)min(o.w0 + x, g.W - 1) * 3;
+  T* dst = out + (size_t)local * 3 * pixels_per_tile + pi;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) dst[(size_t)c * pixels_per_tile] = Cvt<T>::from_f(ttv_unit_from_u8(px[c]));
+}
+
+// ---- blend ----------------------------------------------------------------------------------------------------------------
+// torch's clamp(-1, 1): a NaN stays a NaN
+__device__ __forceinline__ float clamp_unit(float v) { return v < -1.f ? -1.f : (v > 1.f ? 1.f : v); }
+// (q + 1) * 127.5 with each step rounded on its own, then round-half-even; t < 0 -> 0, t >= 255 -> 255, NaN -> 0
+__device__ __forceinline__ uint32_t frame_level(float q) {
+#pragma clang fp contract(off)
+  const float t = __fmul_rn(__fadd_rn(q, 1.0f), 127.5f);
+  if (!(t >= 0.0f)) return 0u;
+  if (t >= 255.0f) return 255u;
+  return (uint32_t)rintf(t);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_video_blend(const T* const* __restrict__ tiles, uint8_t* __restrict__ out, const VideoGeo g,
+                                                     int t_begin, uint32_t groups_per_row, long long total_groups) {
+#pragma clang fp contract(off)
+  const long long gidx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (gidx >= total_groups) return;
+  const long long row = gidx / groups_per_row;                    // (frame of the range, y)
+  const int x0 = (int)(gidx - row * groups_per_row) * 4;
+  const int tl = (int)(row / g.H), y = (int)(row - (long long)tl * g.H);
+  const int npx = min(4, g.W - x0);
+  const VideoAxis &at = g.a[0], &ah = g.a[1], &aw = g.a[2];
+  const int Ht = ah.tile, Wt = aw.tile;
+  const size_t plane = (size_t)at.tile * Ht * Wt;
+  const int t = t_begin + tl;
+  const Cover ct = axis_cover(at, t, t), ch = axis_cover(ah, y, y), cw = axis_cover(aw, x0, x0 + npx - 1);
+  // The thread's four pixels share their t and y tiles and nearly always their x tiles, so a tile is visited once for all four and
+  // its up to 12 elements are loaded together (one vector per channel where the four lie in the tile on a vector boundary): the
+  // loads of a visit are in flight at the same time, and a visit is the unit of the dependent chain pointer -> elements.
+  float num[4][3], only[4][3];
+  int den[4], cnt[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    den[e] = cnt[e] = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) num[e][c] = only[e][c] = 0.0f;
+  }
+  for (int jt = 0; jt < ct.n; ++jt) {
+    const int kt = cover_tile(at, ct, jt), ut = t - axis_origin(at, kt), wt = axis_weight(at, ut);
+    for (int jh = 0; jh < ch.n; ++jh) {
+      const int kh = cover_tile(ah, ch, jh), uh = y - axis_origin(ah, kh), wth = wt * axis_weight(ah, uh);
+      const size_t line = ((size_t)ut * Ht + uh) * Wt;
+      for (int jw = 0; jw < cw.n; ++jw) {
+        const int kw = cover_tile(aw, cw, jw), uw = x0 - axis_origin(aw, kw);       // local x of the first pixel, may be negative
+        const T* p = tiles[((size_t)kt * ah.count + kh) * aw.count + kw];
+        float v[3][4];
+        bool in[4];
+        if (npx == 4 && uw >= 0 && uw + 4 <= Wt && ((uw | Wt) & 3) == 0 && ((uintptr_t)p & (4 * sizeof(T) - 1)) == 0) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const f32x4 q = Vec4<T>::load(p + (size_t)c * plane + line + uw);
+            v[c][0] = q[0]; v[c][1] = q[1]; v[c][2] = q[2]; v[c][3] = q[3];
+          }
+          in[0] = in[1] = in[2] = in[3] = true;
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            in[e] = e < npx && uw + e >= 0 && uw + e < Wt;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c][e] = in[e] ? Cvt<T>::to_f(p[(size_t)c * plane + line + (uw + e)]) : 0.0f;
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          if (!in[e]) continue;
+          const int w = wth * axis_weight(aw, uw + e);
+          den[e] += w;
+          cnt[e] += 1;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            only[e][c] = clamp_unit(v[c][e]);
+            num[e][c] = __fadd_rn(num[e][c], __fmul_rn((float)w, only[e][c]));
+          }
+        }
+      }
+    }
+  }
+  uint32_t level[12];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const bool one = ct.n * ch.n * cnt[e] == 1;
+    const float fden = (float)den[e];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) level[3 * e + c] = e < npx ? frame_level(one ? only[e][c] : __fdiv_rn(num[e][c], fden)) : 0u;
+  }
+  uint8_t* dst = out + ((size_t)row * g.W + x0) * 3;
+  if (npx == 4 && ((uintptr_t)dst & 3) == 0) {
+    uint32_t* dw = reinterpret_cast<uint32_t*>(dst);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dw[k] = level[4 * k] | (level[4 * k + 1] << 8) | (level[4 * k + 2] << 16) | (level[4 * k + 3] << 24);
+  } else {
+#pragma unroll
+    for (int b = 0; b < 12; ++b)
+      if (b < 3 * npx) dst[b] = (uint8_t)level[b];
+  }
+}
+
+// ---- host: the plan's rules ---------------------------------------------------------------------------------------------------
+int plan_geometry(const char* what, const ttv_video_plan* p, VideoGeo* g) {
+  TTV_CHECK_ARG(p != nullptr, "%s: null plan", what);
+  TTV_CHECK_ARG(p->T >= 1 && p->H >= 1 && p->W >= 1 && p->frame_stride >= 1, "%s: video %d x %d x %d with frame stride %d (each at least 1)", what,
+                p->T, p->H, p->W, p->frame_stride);
+  const int n[3] = {(int)(((int64_t)p->T + p->frame_stride - 1) / p->frame_stride), p->H, p->W};
+  int64_t elements = 1, tiles = 1, weight = 1;
+  for (int k = 0; k < 3; ++k) {
+    const int tile = p->tile[k], o = p->overlap[k], count = p->count[k];
+    TTV_CHECK_ARG(tile >= 1 && o >= 0 && count >= 1, "%s: axis %d has tile %d, overlap %d, %d tiles", what, k, tile, o, count);
+    int64_t want = 1;
+    if (n[k] > tile) {
+      TTV_CHECK_ARG(2 * (int64_t)o <= tile, "%s: axis %d: overlap %d is more than half the tile %d", what, k, o, tile);
+      const int64_t stride = tile - o;
+      want = ((int64_t)n[k] - tile + stride - 1) / stride + 1;
+    }
+    TTV_CHECK_ARG(count == want, "%s: axis %d of length %d with tile %d and overlap %d has %lld tiles, not %d: an origin would lie outside the timeline",
+                  what, k, n[k], tile, o, (long long)want, count);
+    g->a[k] = {n[k], tile, tile - o, count, o};
+    elements = std::min<int64_t>(elements * tile, (int64_t)1 << 40);
+    tiles = std::min<int64_t>(tiles * count, (int64_t)1 << 40);
+    weight = std::min<int64_t>(weight * ((int64_t)o + 1), (int64_t)1 << 40);
+  }
+  TTV_CHECK_ARG(elements < ((int64_t)1 << 31) && tiles < ((int64_t)1 << 31), "%s: a tile of %lld elements or %lld tiles (each below 2^31)", what,
+                (long long)elements, (long long)tiles);
+  TTV_CHECK_ARG(weight < ((int64_t)1 << 24), "%s: the largest weight (overlap + 1 over the axes) is %lld, not below 2^24", what, (long long)weight);
+  g->H = p->H; g->W = p->W; g->frame_stride = p->frame_stride;
+  return TTV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ttv_video_tiles_u8(const void* frames_thwc, const ttv_video_plan* plan, int tile_begin, int tile_end, void* tiles, int dtype,
+                       void* stream) {
+  TTV_CHECK_ARG(dtype == TTV_BF16 || dtype == TTV_F32, "video_tiles_u8: dtype %d is neither TTV_BF16 nor TTV_F32", dtype);
+  VideoGeo g;
+  const int rc = plan_geometry("video_tiles_u8", plan, &g);
+  if (rc != TTV_OK) return rc;
+  const int64_t n_tiles = (int64_t)g.a[0].count * g.a[1].count * g.a[2].count;
+  TTV_CHECK_ARG(0 <= tile_begin && tile_begin <= tile_end && tile_end <= n_tiles, "video_tiles_u8: tiles [%d, %d) of %lld", tile_begin, tile_end,
+                (long long)n_tiles);
+  if (tile_begin == tile_end) return TTV_OK;
+  TTV_CHECK_ARG(frames_thwc && tiles, "video_tiles_u8: null pointer");
+  TTV_CHECK_ARG((uintptr_t)tiles % 16 == 0, "video_tiles_u8: the tile buffer is not 16-byte aligned");
+  const int64_t pixels = (int64_t)g.a[0].tile * g.a[1].tile * g.a[2].tile;
+  const bool vec = g.a[2].tile % 8 == 0;
+  const int64_t items = vec ? pixels / 8 : pixels;
+  const int64_t per_tile = (items + 255) / 256, blocks = per_tile * (tile_end - tile_begin);
+  TTV_CHECK_ARG(blocks < ((int64_t)1 << 31), "video_tiles_u8: %lld blocks in one launch (below 2^31: take a shorter tile range)", (long long)blocks);
+  const size_t frame_bytes = (size_t)plan->T * plan->H * plan->W * 3;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)blocks), block(256);
+  const uint8_t* f = (const uint8_t*)frames_thwc;
+  if (dtype == TTV_BF16) {
+    if (vec) hipLaunchKernelGGL((k_video_tiles<bf16_t>), grid, block, 0, s, f, frame_bytes, (bf16_t*)tiles, g, tile_begin, (uint32_t)items, (uint32_t)per_tile);
+    else hipLaunchKernelGGL((k_video_tiles_any<bf16_t>), grid, block, 0, s, f, (bf16_t*)tiles, g, tile_begin, (uint32_t)items, (uint32_t)per_tile);
+  } else {
+    if (vec) hipLaunchKernelGGL((k_video_tiles<float>), grid, block, 0, s, f, frame_bytes, (float*)tiles, g, tile_begin, (uint32_t)items, (uint32_t)per_tile);
+    else hipLaunchKernelGGL((k_video_tiles_any<float>), grid, block, 0, s, f, (float*)tiles, g, tile_begin, (uint32_t)items, (uint32_t)per_tile);
+  }
+  TTV_CHECK_LAUNCH("video_tiles_u8");
+  return TTV_OK;
+}
+
+int ttv_video_blend_u8(void* const* tiles, void* const* tiles_dev, const ttv_video_plan* plan, int t0, int t1, int dtype, void* frames_out,
+                       void* stream) {
+  TTV_CHECK_ARG(dtype == TTV_BF16 || dtype == TTV_F32, "video_blend_u8: dtype %d is neither TTV_BF16 nor TTV_F32", dtype);
+  VideoGeo g;
+  const int rc = plan_geometry("video_blend_u8", plan, &g);
+  if (rc != TTV_OK) return rc;
+  TTV_CHECK_ARG(0 <= t0 && t0 <= t1 && t1 <= g.a[0].n, "video_blend_u8: frames [%d, %d) of a timeline of %d", t0, t1, g.a[0].n);
+  if (t0 == t1) return TTV_OK;
+  TTV_CHECK_ARG(tiles && tiles_dev && frames_out, "video_blend_u8: null table or output");
+  const size_t esz = dtype_bytes(dtype);
+  const int64_t per_layer = (int64_t)g.a[1].count * g.a[2].count;
+  for (int kt = 0; kt < g.a[0].count; ++kt) {
+    const int o = axis_origin(g.a[0], kt);
+    if (o >= t1 || o + g.a[0].tile <= t0) continue;              // the layer holds no frame of the range
+    for (int64_t k = kt * per_layer; k < (kt + 1) * per_layer; ++k)
+      TTV_CHECK_ARG(tiles[k] && (uintptr_t)tiles[k] % esz == 0, "video_blend_u8: tile %lld covers frames [%d, %d) and is %s", (long long)k, t0, t1,
+                    tiles[k] ? "not aligned to its element size" : "NULL");
+  }
+  const uint32_t per_row = ((uint32_t)g.W + 3u) / 4u;
+  const long long groups = (long long)(t1 - t0) * g.H * per_row;
+  const long long blocks = (groups + 255) / 256;
+  TTV_CHECK_ARG(blocks < ((long long)1 << 31), "video_blend_u8: %lld blocks in one launch (below 2^31: take a shorter frame range)", blocks);
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == TTV_BF16)
+    hipLaunchKernelGGL((k_video_blend<bf16_t>), dim3((unsigned)blocks), dim3(256), 0, s, (const bf16_t* const*)tiles_dev, (uint8_t*)frames_out, g, t0, per_row, groups);
+  else
+    hipLaunchKernelGGL((k_video_blend<float>), dim3((unsigned)blocks), dim3(256), 0, s, (const float* const*)tiles_dev, (uint8_t*)frames_out, g, t0, per_row, groups);
+  TTV_CHECK_LAUNCH("video_blend_u8");
+  return TTV_OK;
+}
+
+}  // extern "C"

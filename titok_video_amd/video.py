@@ -1,0 +1,370 @@
+"""Whole videos in and out: overlapped 3-D tiles through the tokenizer, tokens back to uint8 frames.
+
+    vt = VideoTokenizer(model, tile=(16, 128, 128), overlap=(4, 16, 16), tokens_per_tile=128, seq_len=6144,
+                        dtype=torch.bfloat16, depth=2)
+    tok = vt.encode_video(frames_u8, fps=24.0, frame_stride=3)      # frames_u8: uint8 [T,H,W,3] on the GPU -> VideoTokens
+    out = vt.decode_video(tok)                                       # uint8 [T',H,W,3] on the GPU
+    for t0, part in vt.decode_video_iter(tok): ...                   # frame ranges in timeline order, memory of a few tile layers
+    tok.save(path); VideoTokens.load(path); tok.bits_per_pixel
+
+`TilePlan` is the geometry (pure Python, no GPU): where the tiles lie, their order and their blending weights.  The pixel work is two
+HIP kernels (csrc/ttv_video.hip): `gather_tiles` cuts and normalises tiles (`ttv_video_tiles_u8`), `blend_tiles` turns reconstructed
+tiles into frames (`ttv_video_blend_u8`); include/titok_hip.h states both element by element.  Neither has a CPU or eager path: host
+tensors raise.  The token container (`VideoTokens.to_bytes`) is host-side numpy: token streams are tiny.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import math
+import struct
+from typing import Iterator, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+
+MAGIC = b"TTVTOK\r\n"
+VERSION = 1
+MAX_WEIGHT = 1 << 24          # tile weights are integers that fp32 holds exactly
+
+
+def _triple(v, what) -> Tuple[int, int, int]:
+    out = tuple(int(x) for x in v)
+    if len(out) != 3:
+        raise ValueError(f"{what} must have three entries (t, h, w), got {v!r}")
+    return out
+
+
+class TilePlan:
+    """Tiles of a video (T, H, W) of nominal size `tile` overlapping by `overlap`, on the timeline of every `frame_stride`-th frame.
+
+    Timeline: output frame j is source frame frame_stride * j, j < T' = ceil(T / frame_stride); `timeline` = (T', H, W).
+    Per axis of length n: with n < tile there is one tile at 0 of ceil(n / patch) * patch samples (beyond n - 1 the edge repeats on the
+    way in and is dropped on the way out); otherwise tiles of `tile` at k * (tile - overlap), the last one moved back to n - tile, so
+    no padding is ever needed.  All tiles share the effective shape `tile`; index = (kt * n_h + kh) * n_w + kw.  A tile's weight at
+    local coordinate u of an axis is min(u + 1, tile - u, overlap + 1); at an element the product over the axes."""
+
+    def __init__(self, video, tile, overlap, patch, frame_stride: int = 1):
+        self.video, self.nominal_tile = _triple(video, "video"), _triple(tile, "tile")
+        self.overlap, self.patch, self.frame_stride = _triple(overlap, "overlap"), _triple(patch, "patch"), int(frame_stride)
+        if min(self.video) < 1 or min(self.patch) < 1:
+            raise ValueError(f"video {self.video} and patch {self.patch} must be at least 1 on every axis")
+        if self.frame_stride < 1:
+            raise ValueError(f"frame_stride must be at least 1, got {frame_stride}")
+        for t, o, p in zip(self.nominal_tile, self.overlap, self.patch):
+            if t < 1 or t % p:
+                raise ValueError(f"tile {self.nominal_tile} must be a positive multiple of the patch {self.patch}")
+            if o < 0 or 2 * o > t:
+                raise ValueError(f"overlap {self.overlap} must lie in 0 .. tile / 2 of tile {self.nominal_tile}")
+        if math.prod(o + 1 for o in self.overlap) >= MAX_WEIGHT:
+            raise ValueError(f"overlap {self.overlap}: (ot + 1)(oh + 1)(ow + 1) must stay below 2^24")
+        self.timeline = (-(-self.video[0] // self.frame_stride),) + self.video[1:]
+        tiles, origins = [], []
+        for n, t, o, p in zip(self.timeline, self.nominal_tile, self.overlap, self.patch):
+            if n < t:
+                tiles.append(-(-n // p) * p)
+                origins.append([0])
+            else:
+                stride = t - o
+                m = -(-(n - t) // stride) + 1
+                tiles.append(t)
+                origins.append([k * stride for k in range(m - 1)] + [n - t])
+        self.tile: Tuple[int, int, int] = tuple(tiles)
+        self.origins: Tuple[List[int], ...] = tuple(origins)
+        self.counts: Tuple[int, int, int] = tuple(len(o) for o in origins)
+        self.n_tiles = math.prod(self.counts)
+        self.tiles_per_layer = self.counts[1] * self.counts[2]
+
+    def tile_origin(self, index: int) -> Tuple[int, int, int]:
+        if not 0 <= index < self.n_tiles:
+            raise IndexError(f"tile {index} of {self.n_tiles}")
+        kt, r = divmod(index, self.tiles_per_layer)
+        kh, kw = divmod(r, self.counts[2])
+        return self.origins[0][kt], self.origins[1][kh], self.origins[2][kw]
+
+    def axis_weights(self, axis: int) -> List[int]:
+        t, o = self.tile[axis], self.overlap[axis]
+        return [min(u + 1, t - u, o + 1) for u in range(t)]
+
+    @property
+    def patches_per_tile(self) -> int:
+        return math.prod(t // p for t, p in zip(self.tile, self.patch))
+
+    def c_plan(self) -> "_lib.VideoPlan":
+        i3 = _lib.i32 * 3
+        return _lib.VideoPlan(T=self.video[0], H=self.video[1], W=self.video[2], frame_stride=self.frame_stride, tile=i3(*self.tile),
+                              overlap=i3(*self.overlap), count=i3(*self.counts))
+
+    def __repr__(self):
+        return (f"TilePlan(video={self.video}, tile={self.nominal_tile}, overlap={self.overlap}, patch={self.patch}, "
+                f"frame_stride={self.frame_stride}): {self.counts} tiles of {self.tile}")
+
+
+# ---- the two kernels ------------------------------------------------------------------------------------------------------------------
+def gather_tiles(frames_u8: torch.Tensor, plan: TilePlan, begin: int = 0, end: Optional[int] = None,
+                 dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """Tiles [begin, end) of `plan` cut from decoded frames uint8 [T,H,W,3] on the GPU: one buffer [end - begin, 3, Tt, Ht, Wt] in
+    `dtype`, values u8 / 127.5 - 1 (the loader's bits).  One launch on the current stream."""
+    _lib.require_gpu(frames_u8, "gather_tiles")
+    if frames_u8.dtype != torch.uint8 or tuple(frames_u8.shape) != plan.video + (3,) or not frames_u8.is_contiguous():
+        raise ValueError(f"frames must be contiguous uint8 {plan.video + (3,)}, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+    end = plan.n_tiles if end is None else int(end)
+    if not 0 <= begin <= end <= plan.n_tiles:
+        raise ValueError(f"tiles [{begin}, {end}) of {plan.n_tiles}")
+    out = torch.empty((end - begin, 3) + plan.tile, dtype=dtype, device=frames_u8.device)
+    cp = plan.c_plan()
+    _lib.check(_lib.lib().ttv_video_tiles_u8(frames_u8.data_ptr(), C.byref(cp), int(begin), end, out.data_ptr(), _lib.dtype_code(dtype),
+                                             _lib.stream_ptr(frames_u8.device)), "ttv_video_tiles_u8")
+    return out
+
+
+def blend_tiles(tiles: Sequence[Optional[torch.Tensor]], plan: TilePlan, t0: int = 0, t1: Optional[int] = None) -> torch.Tensor:
+    """Frames [t0, t1) of the timeline, uint8 [t1 - t0, H, W, 3] on the GPU, from reconstructed tiles [3,Tt,Ht,Wt] in tile order; an
+    entry may be None when its tile holds no frame of the range.  Overlaps are the weighted mean the header defines; bit-reproducible.
+    One launch on the current stream."""
+    t1 = plan.timeline[0] if t1 is None else int(t1)
+    if len(tiles) != plan.n_tiles:
+        raise ValueError(f"{len(tiles)} tiles for a plan of {plan.n_tiles}")
+    given = [t for t in tiles if t is not None]
+    if not given:
+        raise ValueError("blend_tiles: no tile given")
+    dtype, device = given[0].dtype, given[0].device
+    for t in given:
+        _lib.require_gpu(t, "blend_tiles")
+        if t.dtype != dtype or t.device != device or tuple(t.shape) != (3,) + plan.tile or not t.is_contiguous():
+            raise ValueError(f"tiles must be contiguous {(3,) + plan.tile} of one dtype on one device, got {t.dtype} {tuple(t.shape)}")
+    ptrs = [0 if t is None else t.data_ptr() for t in tiles]
+    host = (_lib.vp * len(ptrs))(*ptrs)
+    table = torch.tensor(ptrs, dtype=torch.int64).to(device)
+    out = torch.empty((max(t1 - t0, 0),) + plan.timeline[1:] + (3,), dtype=torch.uint8, device=device)
+    cp = plan.c_plan()
+    _lib.check(_lib.lib().ttv_video_blend_u8(host, table.data_ptr(), C.byref(cp), int(t0), t1, _lib.dtype_code(dtype), out.data_ptr(),
+                                             _lib.stream_ptr(device)), "ttv_video_blend_u8")
+    return out
+
+
+# ---- the token container ----------------------------------------------------------------------------------------------------------------
+def index_bits(codebook_size: int) -> int:
+    """Bits per stored index: max(1, ceil(log2(codebook_size)))."""
+    return max(1, (int(codebook_size) - 1).bit_length())
+
+
+def pack_indices(indices: np.ndarray, bits: int) -> bytes:
+    """Index i in bits [i * bits, (i + 1) * bits) of the stream, least significant bit first, bytes little-endian."""
+    idx = np.asarray(indices, dtype=np.uint32).reshape(-1)
+    planes = ((idx[:, None] >> np.arange(bits, dtype=np.uint32)) & 1).astype(np.uint8)
+    return np.packbits(planes.reshape(-1), bitorder="little").tobytes()
+
+
+def unpack_indices(data: bytes, n: int, bits: int) -> np.ndarray:
+    planes = np.unpackbits(np.frombuffer(data, dtype=np.uint8), bitorder="little")[:n * bits].reshape(n, bits).astype(np.int64)
+    return (planes << np.arange(bits, dtype=np.int64)).sum(axis=1).astype(np.int32)
+
+
+class VideoTokens:
+    """What `encode_video` returns: `indices` int32 [sum counts] in tile order, `counts` tokens per tile, the plan's parameters
+    (`video`, `tile`, `overlap`, `patch`, `frame_stride`), `fps` of the timeline (source fps / frame_stride, or None), `codebook_size`
+    and `quantizer` ('fsq' or 'l2')."""
+
+    def __init__(self, indices, counts, video, tile, overlap, patch, frame_stride, fps, codebook_size, quantizer):
+        self.indices = indices if isinstance(indices, torch.Tensor) else torch.as_tensor(np.asarray(indices), dtype=torch.int32)
+        self.counts = [int(c) for c in counts]
+        self.video, self.tile, self.overlap, self.patch = _triple(video, "video"), _triple(tile, "tile"), _triple(overlap, "overlap"), _triple(patch, "patch")
+        self.frame_stride, self.fps = int(frame_stride), (None if fps is None else float(fps))
+        self.codebook_size, self.quantizer = int(codebook_size), str(quantizer)
+        if self.indices.dim() != 1 or self.indices.numel() != sum(self.counts):
+            raise ValueError(f"{self.indices.numel()} indices for counts that sum to {sum(self.counts)}")
+
+    def plan(self) -> TilePlan:
+        return TilePlan(self.video, self.tile, self.overlap, self.patch, self.frame_stride)
+
+    def to_bytes(self) -> bytes:
+        """MAGIC (8 bytes) | version uint32 | header length uint32 (both little-endian) | JSON header | the indices packed at
+        max(1, ceil(log2(codebook_size))) bits each, least significant bit first."""
+        bits = index_bits(self.codebook_size)
+        idx = self.indices.detach().to("cpu").numpy().astype(np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= self.codebook_size):
+            raise ValueError(f"indices outside 0 .. {self.codebook_size - 1}")
+        uniform = len(set(self.counts)) <= 1
+        header = json.dumps({"video": self.video, "tile": self.tile, "overlap": self.overlap, "patch": self.patch,
+                             "frame_stride": self.frame_stride, "fps": self.fps, "codebook_size": self.codebook_size,
+                             "quantizer": self.quantizer, "n_tiles": len(self.counts),
+                             "counts": (self.counts[0] if self.counts else 0) if uniform else self.counts,
+                             "n_indices": int(idx.size), "bits": bits}, separators=(",", ":")).encode("utf-8")
+        return MAGIC + struct.pack("<II", VERSION, len(header)) + header + pack_indices(idx, bits)
+
+    @classmethod
+    def from_bytes(cls, data: bytes) -> "VideoTokens":
+        data = bytes(data)
+        if len(data) < 16 or data[:8] != MAGIC:
+            raise ValueError("not a TTVTOK token stream")
+        version, hlen = struct.unpack("<II", data[8:16])
+        if version != VERSION:
+            raise ValueError(f"token stream version {version}, this reader knows {VERSION}")
+        if len(data) < 16 + hlen:
+            raise ValueError("token stream is truncated inside its header")
+        try:
+            h = json.loads(data[16:16 + hlen].decode("utf-8"))
+            n, bits, n_tiles = int(h["n_indices"]), int(h["bits"]), int(h["n_tiles"])
+            counts = [int(h["counts"])] * n_tiles if isinstance(h["counts"], int) else [int(c) for c in h["counts"]]
+            fields = [h[k] for k in ("video", "tile", "overlap", "patch", "frame_stride", "fps", "codebook_size", "quantizer")]
+        except (ValueError, KeyError, TypeError) as e:
+            raise ValueError(f"token stream header is damaged: {e}") from None
+        if bits != index_bits(fields[6]) or len(counts) != n_tiles or sum(counts) != n:
+            raise ValueError("token stream header is inconsistent")
+        body = data[16 + hlen:]
+        if len(body) != (n * bits + 7) // 8:
+            raise ValueError(f"token stream holds {len(body)} bytes of indices, its header promises {(n * bits + 7) // 8}")
+        idx = unpack_indices(body, n, bits)
+        if n and int(idx.max()) >= int(fields[6]):
+            raise ValueError("token stream holds an index outside its codebook")
+        return cls(torch.from_numpy(idx), counts, *fields)
+
+    def save(self, path) -> None:
+        with open(path, "wb") as f:
+            f.write(self.to_bytes())
+
+    @classmethod
+    def load(cls, path) -> "VideoTokens":
+        with open(path, "rb") as f:
+            return cls.from_bytes(f.read())
+
+    @property
+    def bits_per_pixel(self) -> float:
+        """8 * len(to_bytes()) / (T' * H * W): the whole container over the pixels of the timeline."""
+        t = -(-self.video[0] // self.frame_stride)
+        return 8.0 * len(self.to_bytes()) / (t * self.video[1] * self.video[2])
+
+
+# ---- the public surface -----------------------------------------------------------------------------------------------------------------
+def _budget_ranges(rows: Sequence[int], begin: int, end: int, seq_len: int) -> List[Tuple[int, int]]:
+    """Consecutive ranges of [begin, end) under the reference's token budget (data.dynamic_batches): a range is closed when the next
+    tile's rows would take it past seq_len."""
+    out, a, cur = [], begin, 0
+    for i in range(begin, end):
+        if cur + rows[i] > seq_len and i > a:
+            out.append((a, i))
+            a, cur = i, 0
+        cur += rows[i]
+    if end > a:
+        out.append((a, end))
+    return out
+
+
+class VideoTokenizer:
+    """A `TiTok` on the GPU applied to whole decoded videos.  `tile` defaults to `config.training.sampling.max_grid` when the model's
+    config has it; `tokens_per_tile` is one count or one per tile; `seq_len` is the packed-row budget of a batch (rows = patches +
+    tokens, the reference's rule); `dtype` is the compute dtype of the tiles (the model's); `depth` batches are in flight at a time
+    while encoding (`ForwardPipeline`; 1 = everything on the current stream)."""
+
+    def __init__(self, model, tile=None, overlap=(4, 16, 16), tokens_per_tile=128, seq_len: int = 6144,
+                 dtype: torch.dtype = torch.bfloat16, depth: int = 2):
+        self.model = model
+        self.device = next(model.parameters()).device
+        if self.device.type != "cuda":
+            raise RuntimeError("VideoTokenizer needs a GPU model: titok_video_amd runs on MI355X (HIP) only, there is no CPU path")
+        self.patch = _triple(model.config.tokenizer.model.patch_size, "patch_size")
+        if tile is None:
+            sampling = getattr(getattr(model.config, "training", None), "sampling", None)
+            tile = getattr(sampling, "max_grid", None)
+            if tile is None:
+                raise ValueError("tile is required: the model's config has no training.sampling.max_grid")
+        self.tile, self.overlap = _triple(tile, "tile"), _triple(overlap, "overlap")
+        TilePlan(self.tile, self.tile, self.overlap, self.patch)           # refuses a tile off the patch lattice or a bad overlap
+        self.tokens_per_tile = tokens_per_tile if isinstance(tokens_per_tile, int) else [int(k) for k in tokens_per_tile]
+        self.seq_len, self.dtype, self.depth = int(seq_len), dtype, int(depth)
+        _lib.dtype_code(dtype)
+        if self.depth < 1:
+            raise ValueError("depth must be >= 1")
+        self.quantizer = model.quantizer_kind
+        self.codebook_size = int(model.quantize.codebook_size)
+        self._pipe = None
+
+    def _counts(self, n_tiles: int) -> List[int]:
+        k = self.tokens_per_tile
+        counts = [k] * n_tiles if isinstance(k, int) else list(k)
+        if len(counts) != n_tiles or min(counts) < 1:
+            raise ValueError(f"tokens_per_tile: {len(counts)} counts for {n_tiles} tiles (each at least 1)")
+        return counts
+
+    def _ranges(self, plan: TilePlan, counts, begin, end):
+        rows = [plan.patches_per_tile + k for k in counts]
+        if max(rows) > self.seq_len:
+            raise ValueError(f"a tile of {plan.tile} with {max(counts)} tokens is {max(rows)} rows, seq_len is {self.seq_len}")
+        return _budget_ranges(rows, begin, end, self.seq_len)
+
+    def _encode_batch(self, clips, counts):
+        return self.model.encode(clips, counts)[1]["indices"]
+
+    def encode_video(self, frames_u8: torch.Tensor, fps: Optional[float] = None, frame_stride: int = 1) -> VideoTokens:
+        """Decoded frames uint8 [T,H,W,3] on the GPU -> tokens of every `frame_stride`-th frame.  Tiles are gathered in tile order into
+        batches under the token budget and encoded; equal tile shapes mean one cached batch plan per batch size."""
+        _lib.require_gpu(frames_u8, "encode_video")
+        if frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
+            raise ValueError(f"frames must be uint8 [T,H,W,3], got {tuple(frames_u8.shape)}")
+        plan = TilePlan(tuple(frames_u8.shape[:3]), self.tile, self.overlap, self.patch, frame_stride)
+        counts = self._counts(plan.n_tiles)
+        ranges = self._ranges(plan, counts, 0, plan.n_tiles)
+        parts, inflight = [], []
+        if self.depth > 1 and self._pipe is None:
+            from .pipeline import ForwardPipeline
+            self._pipe = ForwardPipeline(self.model, depth=self.depth, device=self.device, fn=self._encode_batch)
+        with torch.no_grad():
+            for a, b in ranges:
+                clips = list(gather_tiles(frames_u8, plan, a, b, self.dtype).unbind(0))      # on the current stream, as the frames are
+                if self.depth == 1:
+                    parts.append(self._encode_batch(clips, counts[a:b]))
+                    continue
+                inflight.append(self._pipe.submit(clips, counts[a:b]))
+                if len(inflight) >= self.depth:                                              # at most `depth` batches of tiles alive
+                    parts.append(self._pipe.result(inflight.pop(0)))
+            parts += [self._pipe.result(t) for t in inflight]
+            indices = torch.cat(parts).to(torch.int32)
+        return VideoTokens(indices, counts, plan.video, self.tile, self.overlap, self.patch, plan.frame_stride,
+                           None if fps is None else float(fps) / plan.frame_stride, self.codebook_size, self.quantizer)
+
+    def _check_tokens(self, tok: VideoTokens) -> TilePlan:
+        if tok.codebook_size != self.codebook_size or tok.quantizer != self.quantizer:
+            raise ValueError(f"tokens of a {tok.quantizer} codebook of {tok.codebook_size}, the model has {self.quantizer} of {self.codebook_size}")
+        if tok.patch != self.patch:
+            raise ValueError(f"tokens of patch {tok.patch}, the model's is {self.patch}")
+        plan = tok.plan()                                                   # refuses a tile that is no multiple of the patch
+        if len(tok.counts) != plan.n_tiles:
+            raise ValueError(f"{len(tok.counts)} token counts for {plan.n_tiles} tiles")
+        return plan
+
+    @torch.no_grad()
+    def _decode_layer(self, plan: TilePlan, tok: VideoTokens, indices, offsets, kt: int):
+        a0, b0 = kt * plan.tiles_per_layer, (kt + 1) * plan.tiles_per_layer
+        out = []
+        for a, b in self._ranges(plan, tok.counts, a0, b0):
+            out += self.model.decode_indices(indices[offsets[a]:offsets[b]], [plan.tile] * (b - a), tok.counts[a:b])
+        return out
+
+    def decode_video_iter(self, tok: VideoTokens) -> Iterator[Tuple[int, torch.Tensor]]:
+        """(t0, frames uint8 [n,H,W,3] on the GPU) in timeline order, gap-free.  The temporal tile layers are decoded in order; a frame
+        range is blended and yielded as soon as every tile that holds it is decoded, and the reconstructions of layers that hold no
+        unfinished frame are dropped: memory is that of a few layers, whatever the video's length."""
+        plan = self._check_tokens(tok)
+        indices = tok.indices.to(self.device)
+        offsets = [0]
+        for k in tok.counts:
+            offsets.append(offsets[-1] + k)
+        per_layer, starts, n_frames = plan.tiles_per_layer, plan.origins[0], plan.timeline[0]
+        live: List[Optional[torch.Tensor]] = [None] * plan.n_tiles
+        first_live, done = 0, 0
+        for kt in range(plan.counts[0]):
+            live[kt * per_layer:(kt + 1) * per_layer] = self._decode_layer(plan, tok, indices, offsets, kt)
+            upto = starts[kt + 1] if kt + 1 < plan.counts[0] else n_frames         # the next layer starts here: frames below are complete
+            if upto > done:
+                yield done, blend_tiles(live, plan, done, upto)
+                done = upto
+            while first_live <= kt and starts[first_live] + plan.tile[0] <= done:  # every frame of the layer is out
+                live[first_live * per_layer:(first_live + 1) * per_layer] = [None] * per_layer
+                first_live += 1
+
+    def decode_video(self, tok: VideoTokens) -> torch.Tensor:
+        """uint8 [T',H,W,3] on the GPU: the ranges of `decode_video_iter`, concatenated."""
+        return torch.cat([part for _, part in self.decode_video_iter(tok)], dim=0)
