@@ -975,6 +975,28 @@ int ttv_video_tiles_u8(const void* frames_thwc, const ttv_video_plan* plan, int 
 int ttv_video_blend_u8(void* const* tiles, void* const* tiles_dev, const ttv_video_plan* plan, int t0, int t1, int dtype,
                        void* frames_out, void* stream);
 
+/* Measured distortion: per tile of [tile_begin, tile_end) the sum of squared level differences between a reconstruction of the tile
+ * and the source pixels it was cut from (video.py: tile_sse, the rate table of VideoTokenizer.rate_distortion).
+ * recon: HOST array of tile_end - tile_begin device pointers (what the checks read), recon_dev: the same table in device memory
+ * (what the kernel reads), the blend's convention; entry j is tile tile_begin + j, [3][Tt][Ht][Wt] in `dtype` (TTV_BF16 or TTV_F32).
+ * sse: device memory, uint64 [tile_end - tile_begin], 8-byte aligned.  For tile j of the range with origin (t0, h0, w0):
+ *   sse[j] = sum over c < 3, i < min(Tt, T' - t0), y < min(Ht, H - h0), x < min(Wt, W - w0) of
+ *            (level(recon_j[c][i][y][x]) - frames[frame_stride * (t0 + i)][h0 + y][w0 + x][c])^2
+ *   level(v): the blend's rule for a pixel that one tile covers: v widened exactly to fp32 and clamped to [-1, 1] (a NaN stays a NaN);
+ *   t = v + 1.0f; t = t * 127.5f, each rounded on its own; round-half-even(t), with t < 0 -> 0, t >= 255 -> 255, NaN -> 0.
+ * Samples a tile holds beyond a short axis (the edge-clamped ones, which the blend drops) are not counted.  sse[j] is written, not
+ * accumulated: the entry point clears the sums on `stream` and the blocks of a tile add their partial sums (each below 2^32) with
+ * one 64-bit atomic per block.  An exact integer, so the same bits in any order of summation, with or without the deterministic mode.
+ * Any H, W >= 1 and any alignment of `frames_thwc`.  With Wt % 8 == 0 a thread takes 8 pixels of a tile row (the gather's geometry
+ * and its source load: aligned words, byte by byte at the array's ends and on clamped columns) and reads one 16-byte (bf16) or two
+ * 16-byte (fp32) vectors per channel plane from a tile on the 16-byte grid, single elements from any other; for other Wt a thread
+ * takes one pixel.  Nothing but sse[0 .. tile_end - tile_begin) is written.  TTV_ERR_INVALID with nothing launched and nothing
+ * written: a bad dtype or plan, a null frames_thwc, table (either) or sse, a tile range outside [0, tiles of the plan], a tile pointer
+ * of the range that is NULL or not aligned to its element size, sse off the 8-byte grid.  An empty range does nothing.  Work is
+ * enqueued on `stream` only. */
+int ttv_video_tile_sse_u8(const void* frames_thwc, const ttv_video_plan* plan, int tile_begin, int tile_end, void* const* recon,
+                          void* const* recon_dev, int dtype, uint64_t* sse, void* stream);
+
 /* PSNR statistic of the evaluation loop (model/metrics/eval_metrics.py:19,32-36: x.clamp(-1, 1), torchmetrics
  * PeakSignalNoiseRatio(data_range=2) = running sum of squared errors + element count): acc[0] += sum (clamp(recon) - target)^2,
  * acc[1] += number of elements, both double, device memory, over the clips of the call (host arrays of device pointers, `dtype`).

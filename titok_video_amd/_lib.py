@@ -320,6 +320,7 @@ SYMBOLS = {
     "ttv_recon_panels_u8": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp]),
     "ttv_video_tiles_u8": (C.c_int, [vp, C.POINTER(VideoPlan), C.c_int, C.c_int, vp, C.c_int, vp]),
     "ttv_video_blend_u8": (C.c_int, [vp, vp, C.POINTER(VideoPlan), C.c_int, C.c_int, C.c_int, vp, vp]),
+    "ttv_video_tile_sse_u8": (C.c_int, [vp, C.POINTER(VideoPlan), C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
     "ttv_sq_err_accumulate": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "ttv_ssim_workspace_bytes": (C.c_int64, [vp, C.c_int]),
     "ttv_ssim_accumulate": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int64, vp]),

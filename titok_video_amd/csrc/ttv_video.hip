@@ -1,6 +1,8 @@
 // Whole videos in and out (titok_video_amd/video.py): a decoded video uint8 [T][H][W][3] is cut into equal, overlapping 3-D tiles the
 // towers can take, and the reconstructed tiles are blended back into uint8 frames.  include/titok_hip.h states the plan (origins,
-// tile order, weights) and the value of every output element; both kernels are streaming kernels with no atomics.
+// tile order, weights) and the value of every output element; both kernels are streaming kernels with no atomics.  A third one
+// measures what a reconstruction costs: per tile the exact integer sum of squared level differences against the source
+// (ttv_video_tile_sse_u8; video.py builds the per-tile token allocation on it).
 //
 // Kernels
 //   k_video_tiles<T>     : grid (blocks per tile x tiles of the range), 1 KiB of LDS (the 256 normalised levels).  Wt % 8 == 0.  A
@@ -15,6 +17,12 @@
 //                          pixels inside the tile on a vector boundary) or up to 12 single elements; the 12 bytes go out as three
 //                          words when they lie on the 4-byte grid (always, when 3W % 4 == 0 and the output is aligned; one row in
 //                          four otherwise) and byte by byte elsewhere.
+//   k_video_tile_sse<T>  : k_video_tiles with the tile read, not written: the same thread geometry and source load, one 16-byte
+//                          (bf16) or two 16-byte (fp32) loads per channel plane; a thread takes 8 such groups of 8 pixels, 256
+//                          groups apart, and keeps a 32-bit partial, summed over the wave by lane exchanges, over the block through
+//                          16 bytes of LDS, and added to the tile's 64-bit sum by one vector atomic per block.
+//                          k_video_tile_sse_any<T>: any Wt, a pixel at a time.  Reads what the gather reads and writes, stores
+//                          8 bytes per tile.
 // Traffic per pixel of the timeline, tile t with overlap o per axis (r = prod t / (t - o), the cover ratio: 1.75 at 16 x 128 x 128
 // with 4 x 16 x 16): the gather reads 3 r bytes and writes 3 r elements; the blend reads 3 r elements and writes 3 bytes.  DESIGN.md
 // has the measured rates beside a device-to-device copy of the same byte count.
@@ -90,6 +98,34 @@ __device__ __forceinline__ size_t source_row(const VideoGeo& g, const TileAt& o,
   const int ts = g.frame_stride * min(o.t0 + i, g.a[0].n - 1), ys = min(o.h0 + y, g.H - 1);
   return ((size_t)ts * g.H + ys) * (size_t)g.W * 3;
 }
+
+// The 24 bytes of pixels x0 .. x0 + 7 of the source row `src`, in place in d (channel c of pixel e is byte 3 e + c): k_video_tiles'
+// source load as a function, for k_video_tile_sse.  The 7 aligned words that hold the bytes, shifted into place; byte by byte, with
+// the columns clamped to W - 1, where the pixels are not all inside the row or a word would leave the array.  (k_video_tiles keeps
+// its own copy of these lines: called from there, the compiler orders the byte-wise path differently, and that kernel's code is
+// held as it was measured.)
+__device__ __forceinline__ void source_px8(const uint8_t* frames, size_t frame_bytes, const uint8_t* src, int x0, int W, uint32_t (&d)[6]) {
+  const uintptr_t at = (uintptr_t)(src + (size_t)x0 * 3), lo = at & ~(uintptr_t)3;
+  if (x0 + 8 <= W && lo >= (uintptr_t)frames && lo + 28 <= (uintptr_t)frames + frame_bytes) {
+    const uint32_t* wp = reinterpret_cast<const uint32_t*>(lo);
+    uint32_t w[7];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) w[k] = wp[k];
+    const uint32_t sh = (uint32_t)(at & 3);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) d[k] = __builtin_amdgcn_alignbyte(w[k + 1], w[k], sh);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) d[k] = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const uint8_t* px = src + (size_t)min(x0 + e, W - 1) * 3;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) d[(3 * e + c) >> 2] |= (uint32_t)px[c] << (8 * ((3 * e + c) & 3));
+    }
+  }
+}
+__device__ __forceinline__ uint32_t px8_byte(const uint32_t (&d)[6], int e, int c) { return (d[(3 * e + c) >> 2] >> (8 * ((3 * e + c) & 3))) & 0xFFu; }
 
 template <typename T>
 __global__ __launch_bounds__(256) void k_video_tiles(const uint8_t* __restrict__ frames, size_t frame_bytes, T* __restrict__ out,
@@ -254,6 +290,162 @@ __global__ __launch_bounds__(256) void k_video_blend(const T* const* __restrict_
   }
 }
 
+// ---- per-tile squared error against the source ------------------------------------------------------------------------------
+// 8 consecutive elements of a reconstructed tile: one (bf16) or two (fp32) 16-byte vectors where the tile lies on the 16-byte grid
+// (rows and planes are multiples of 8 elements), single elements under any other pointer.
+template <typename T> __device__ __forceinline__ void load8(const T* __restrict__ p, bool vec, float (&v)[8]);
+template <> __device__ __forceinline__ void load8<float>(const float* __restrict__ p, bool vec, float (&v)[8]) {
+  if (vec) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
+    v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = p[e];
+  }
+}
+template <> __device__ __forceinline__ void load8<bf16_t>(const bf16_t* __restrict__ p, bool vec, float (&v)[8]) {
+  if (vec) {
+    const bf16x8 b = *reinterpret_cast<const bf16x8*>(p);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (float)b[e];
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (float)p[e];
+  }
+}
+
+// frame_level(clamp_unit(v)) as a float, without a branch: a NaN of any kind is replaced by -1, whose level is 0 (a select, not the
+// NaN rule of min / max: a widened bf16 may be a signalling NaN, which those return as a NaN); everything else is clamped to [-1, 1] as
+// clamp_unit does, and then t lies in [0, 255], where frame_level is round-half-even(t).  (frame_level's three exits are divergent
+// branches per element in a kernel that forms 24 levels per thread.)
+__device__ __forceinline__ float tile_level(float v) {
+#pragma clang fp contract(off)
+  const float w = v != v ? -1.0f : v;
+  const float q = fminf(fmaxf(w, -1.0f), 1.0f);
+  return rintf(__fmul_rn(__fadd_rn(q, 1.0f), 127.5f));
+}
+// acc + (level(recon) - level)^2 in fp32: integers below 2^24 all the way (a thread adds at most 24 x 65025), so exact.
+__device__ __forceinline__ float add_sq_diff(float acc, float recon, uint32_t level) {
+#pragma clang fp contract(off)
+  const float d = __fsub_rn(tile_level(recon), (float)level);
+  return __fmaf_rn(d, d, acc);
+}
+
+// Sum over the 64 lanes, in every lane: the exchanges of wave_sum (ttv_common.h) on integers.
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+  {
+    const auto b = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+    const unsigned b0 = b[0], b1 = b[1];
+    v = b0 + b1;
+  }
+  {
+    const auto a = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+    const unsigned a0 = a[0], a1 = a[1];
+    v = a0 + a1;
+  }
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, true);       // row_ror:8
+  {
+    int r = __builtin_amdgcn_update_dpp(0, (int)v, 0x12C, 0xF, 0x5, false);           // xor 4: see wave_xor_dpp4
+    r = __builtin_amdgcn_update_dpp(r, (int)v, 0x124, 0xF, 0xA, false);
+    v += (uint32_t)r;
+  }
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);        // quad_perm [2,3,0,1]
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);        // quad_perm [1,0,3,2]
+  return v;
+}
+// A thread takes TTV_SSE_ITERS items of its block's span (8 pixels each in k_video_tile_sse, one in the _any kernel), 256 items apart,
+// so a block covers 256 * TTV_SSE_ITERS items of one tile and ends in ONE atomic: all the sums of a call lie in a few cache lines, and
+// atomics on one line are served one after the other (the 64 x 256 x 256 video in bf16 takes 49 us with one
+// item per thread = 5760 atomics, 27 us with four or eight).  8 keeps the block's partial in 32 bits: 256 * 8 * 24 * 65025 < 2^32.
+#ifndef TTV_SSE_ITERS
+#define TTV_SSE_ITERS 8
+#endif
+static_assert(TTV_SSE_ITERS >= 1 && 256ull * TTV_SSE_ITERS * 24 * 65025 < (1ull << 32), "a block's partial sum must fit 32 bits");
+
+// A block's threads (all 256 of them, none may have left) each bring a partial of at most TTV_SSE_ITERS * 24 * 65025; their sum,
+// below 2^32, is added to *dst by one 64-bit atomic of thread 0.  Integer addition: the order of the blocks changes no bit.
+__device__ __forceinline__ void block_add_u64(uint32_t part, unsigned long long* dst) {
+  __shared__ uint32_t wave_part[4];
+  part = wave_sum_u32(part);
+  if ((threadIdx.x & 63u) == 0) wave_part[threadIdx.x >> 6] = part;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t total = wave_part[0] + wave_part[1] + wave_part[2] + wave_part[3];
+    if (total) atomicAdd(dst, (unsigned long long)total);
+  }
+}
+
+// k_video_tile_sse<T>     : k_video_tiles' geometry (Wt % 8 == 0, a thread owns 8 pixels of a tile row at a time, the same source
+//                           load) with the tile read in place of written; rows and columns the tile holds beyond a short axis are
+//                           not counted.
+// k_video_tile_sse_any<T> : any Wt, a pixel of a tile at a time.
+template <typename T>
+__global__ __launch_bounds__(256) void k_video_tile_sse(const uint8_t* __restrict__ frames, size_t frame_bytes, const T* const* __restrict__ recon,
+                                                        const VideoGeo g, int tile_begin, uint32_t groups_per_tile, uint32_t blocks_per_tile,
+                                                        unsigned long long* __restrict__ sse) {
+  const uint32_t local = blockIdx.x / blocks_per_tile;
+  const uint32_t first = (blockIdx.x - local * blocks_per_tile) * (256u * TTV_SSE_ITERS) + threadIdx.x;
+  const int Ht = g.a[1].tile, Wt = g.a[2].tile;
+  const uint32_t per_row = (uint32_t)Wt / 8u;
+  const TileAt o = tile_origin(g, tile_begin + (int)local);
+  const T* p = recon[local];
+  const bool vec = ((uintptr_t)p & 15) == 0;
+  const size_t plane = (size_t)g.a[0].tile * Ht * Wt;
+  uint32_t part = 0;
+#pragma unroll 2
+  for (int it = 0; it < TTV_SSE_ITERS; ++it) {
+    const uint32_t gi = first + (uint32_t)it * 256u;                // group of 8 pixels inside the tile
+    if (gi >= groups_per_tile) break;
+    const uint32_t row = gi / per_row, xg = gi - row * per_row;
+    const int i = (int)(row / (uint32_t)Ht), y = (int)(row - (uint32_t)i * (uint32_t)Ht);
+    const int x0 = o.w0 + (int)xg * 8;
+    if (o.t0 + i >= g.a[0].n || o.h0 + y >= g.H || x0 >= g.W) continue;
+    const T* q = p + (size_t)row * Wt + (size_t)xg * 8;
+    float v[3][8];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) load8<T>(q + (size_t)c * plane, vec, v[c]);
+    uint32_t d[6];
+    source_px8(frames, frame_bytes, frames + source_row(g, o, i, y), x0, g.W, d);
+    const int npx = g.W - x0;                                     // pixels of the eight that the video holds, when below 8
+    float acc = 0.0f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float s = 0.0f;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) s = add_sq_diff(s, v[c][e], px8_byte(d, e, c));
+      acc += e < npx ? s : 0.0f;
+    }
+    part += (uint32_t)acc;
+  }
+  block_add_u64(part, sse + local);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_video_tile_sse_any(const uint8_t* __restrict__ frames, const T* const* __restrict__ recon, const VideoGeo g,
+                                                            int tile_begin, uint32_t pixels_per_tile, uint32_t blocks_per_tile,
+                                                            unsigned long long* __restrict__ sse) {
+  const uint32_t local = blockIdx.x / blocks_per_tile;
+  const uint32_t first = (blockIdx.x - local * blocks_per_tile) * (256u * TTV_SSE_ITERS) + threadIdx.x;
+  const int Ht = g.a[1].tile, Wt = g.a[2].tile;
+  const TileAt o = tile_origin(g, tile_begin + (int)local);
+  const T* p = recon[local];
+  uint32_t part = 0;
+  for (int it = 0; it < TTV_SSE_ITERS; ++it) {
+    const uint32_t pi = first + (uint32_t)it * 256u;
+    if (pi >= pixels_per_tile) break;
+    const uint32_t row = pi / (uint32_t)Wt;
+    const int x = (int)(pi - row * (uint32_t)Wt), i = (int)(row / (uint32_t)Ht), y = (int)(row - (uint32_t)i * (uint32_t)Ht);
+    if (o.t0 + i >= g.a[0].n || o.h0 + y >= g.H || o.w0 + x >= g.W) continue;
+    const uint8_t* px = frames + source_row(g, o, i, y) + (size_t)(o.w0 + x) * 3;
+    const T* q = p + pi;
+    float acc = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc = add_sq_diff(acc, Cvt<T>::to_f(q[(size_t)c * pixels_per_tile]), px[c]);
+    part += (uint32_t)acc;
+  }
+  block_add_u64(part, sse + local);
+}
+
 // ---- host: the plan's rules ---------------------------------------------------------------------------------------------------
 int plan_geometry(const char* what, const ttv_video_plan* p, VideoGeo* g) {
   TTV_CHECK_ARG(p != nullptr, "%s: null plan", what);
@@ -348,6 +540,53 @@ int ttv_video_blend_u8(void* const* tiles, void* const* tiles_dev, const ttv_vid
   else
     hipLaunchKernelGGL((k_video_blend<float>), dim3((unsigned)blocks), dim3(256), 0, s, (const float* const*)tiles_dev, (uint8_t*)frames_out, g, t0, per_row, groups);
   TTV_CHECK_LAUNCH("video_blend_u8");
+  return TTV_OK;
+}
+
+int ttv_video_tile_sse_u8(const void* frames_thwc, const ttv_video_plan* plan, int tile_begin, int tile_end, void* const* recon,
+                          void* const* recon_dev, int dtype, uint64_t* sse, void* stream) {
+  TTV_CHECK_ARG(dtype == TTV_BF16 || dtype == TTV_F32, "video_tile_sse_u8: dtype %d is neither TTV_BF16 nor TTV_F32", dtype);
+  VideoGeo g;
+  const int rc = plan_geometry("video_tile_sse_u8", plan, &g);
+  if (rc != TTV_OK) return rc;
+  const int64_t n_tiles = (int64_t)g.a[0].count * g.a[1].count * g.a[2].count;
+  TTV_CHECK_ARG(0 <= tile_begin && tile_begin <= tile_end && tile_end <= n_tiles, "video_tile_sse_u8: tiles [%d, %d) of %lld", tile_begin, tile_end,
+                (long long)n_tiles);
+  if (tile_begin == tile_end) return TTV_OK;
+  TTV_CHECK_ARG(frames_thwc && recon && recon_dev && sse, "video_tile_sse_u8: null frames, table or sums");
+  TTV_CHECK_ARG((uintptr_t)sse % 8 == 0, "video_tile_sse_u8: the sums are not 8-byte aligned");
+  const size_t esz = dtype_bytes(dtype);
+  const int n = tile_end - tile_begin;
+  for (int j = 0; j < n; ++j)
+    TTV_CHECK_ARG(recon[j] && (uintptr_t)recon[j] % esz == 0, "video_tile_sse_u8: the reconstruction of tile %d is %s", tile_begin + j,
+                  recon[j] ? "not aligned to its element size" : "NULL");
+  const int64_t pixels = (int64_t)g.a[0].tile * g.a[1].tile * g.a[2].tile;
+  const bool vec = g.a[2].tile % 8 == 0;
+  const int64_t items = vec ? pixels / 8 : pixels;
+  const int64_t span = 256 * TTV_SSE_ITERS;                       // items of a tile per block
+  const int64_t per_tile = (items + span - 1) / span, blocks = per_tile * n;
+  TTV_CHECK_ARG(blocks < ((int64_t)1 << 31), "video_tile_sse_u8: %lld blocks in one launch (below 2^31: take a shorter tile range)", (long long)blocks);
+  const size_t frame_bytes = (size_t)plan->T * plan->H * plan->W * 3;
+  hipStream_t s = (hipStream_t)stream;
+  // the blocks of a tile add into its sum, so it starts at zero: written, not accumulated
+  const hipError_t e = hipMemsetAsync(sse, 0, (size_t)n * sizeof(uint64_t), s);
+  if (e != hipSuccess) {
+    ttv_set_error("video_tile_sse_u8: clearing the sums: %s", hipGetErrorString(e));
+    return TTV_ERR_LAUNCH;
+  }
+  const dim3 grid((unsigned)blocks), block(256);
+  const uint8_t* f = (const uint8_t*)frames_thwc;
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(sse);
+  if (dtype == TTV_BF16) {
+    const bf16_t* const* r = (const bf16_t* const*)recon_dev;
+    if (vec) hipLaunchKernelGGL((k_video_tile_sse<bf16_t>), grid, block, 0, s, f, frame_bytes, r, g, tile_begin, (uint32_t)items, (uint32_t)per_tile, out);
+    else hipLaunchKernelGGL((k_video_tile_sse_any<bf16_t>), grid, block, 0, s, f, r, g, tile_begin, (uint32_t)items, (uint32_t)per_tile, out);
+  } else {
+    const float* const* r = (const float* const*)recon_dev;
+    if (vec) hipLaunchKernelGGL((k_video_tile_sse<float>), grid, block, 0, s, f, frame_bytes, r, g, tile_begin, (uint32_t)items, (uint32_t)per_tile, out);
+    else hipLaunchKernelGGL((k_video_tile_sse_any<float>), grid, block, 0, s, f, r, g, tile_begin, (uint32_t)items, (uint32_t)per_tile, out);
+  }
+  TTV_CHECK_LAUNCH("video_tile_sse_u8");
   return TTV_OK;
 }
 

@@ -6,11 +6,16 @@
     out = vt.decode_video(tok)                                       # uint8 [T',H,W,3] on the GPU
     for t0, part in vt.decode_video_iter(tok): ...                   # frame ranges in timeline order, memory of a few tile layers
     tok.save(path); VideoTokens.load(path); tok.bits_per_pixel
+    tok = vt.encode_video(frames_u8, fps=24.0, target_psnr=30.0)     # per-tile token counts from measured distortion: this quality ...
+    tok = vt.encode_video(frames_u8, fps=24.0, total_tokens=4096)    # ... or this many tokens for the whole video
+    table = vt.rate_distortion(frames_u8, (16, 32, 64, 128)); allocate_tokens(table, total_tokens=4096); table.psnr()
 
-`TilePlan` is the geometry (pure Python, no GPU): where the tiles lie, their order and their blending weights.  The pixel work is two
-HIP kernels (csrc/ttv_video.hip): `gather_tiles` cuts and normalises tiles (`ttv_video_tiles_u8`), `blend_tiles` turns reconstructed
-tiles into frames (`ttv_video_blend_u8`); include/titok_hip.h states both element by element.  Neither has a CPU or eager path: host
-tensors raise.  The token container (`VideoTokens.to_bytes`) is host-side numpy: token streams are tiny.
+`TilePlan` is the geometry (pure Python, no GPU): where the tiles lie, their order and their blending weights.  The pixel work is
+three HIP kernels (csrc/ttv_video.hip): `gather_tiles` cuts and normalises tiles (`ttv_video_tiles_u8`), `blend_tiles` turns
+reconstructed tiles into frames (`ttv_video_blend_u8`), `tile_sse` measures reconstructed tiles against the source
+(`ttv_video_tile_sse_u8`); include/titok_hip.h states all three element by element.  None has a CPU or eager path: host tensors raise.
+The token container (`VideoTokens.to_bytes`) is host-side numpy and the allocator (`allocate_tokens`) plain Python on exact integers:
+token streams and rate tables are tiny.
 """
 from __future__ import annotations
 
@@ -84,6 +89,11 @@ class TilePlan:
         kh, kw = divmod(r, self.counts[2])
         return self.origins[0][kt], self.origins[1][kh], self.origins[2][kw]
 
+    def tile_elements(self, index: int) -> int:
+        """Samples of tile `index` that lie inside the video, over the three channels: 3 * prod over the axes of
+        min(tile, n - origin).  What a tile holds beyond a short axis is edge-clamped on the way in and counted nowhere."""
+        return 3 * math.prod(min(t, n - o) for t, n, o in zip(self.tile, self.timeline, self.tile_origin(index)))
+
     def axis_weights(self, axis: int) -> List[int]:
         t, o = self.tile[axis], self.overlap[axis]
         return [min(u + 1, t - u, o + 1) for u in range(t)]
@@ -102,7 +112,7 @@ class TilePlan:
                 f"frame_stride={self.frame_stride}): {self.counts} tiles of {self.tile}")
 
 
-# ---- the two kernels ------------------------------------------------------------------------------------------------------------------
+# ---- the three kernels ----------------------------------------------------------------------------------------------------------------
 def gather_tiles(frames_u8: torch.Tensor, plan: TilePlan, begin: int = 0, end: Optional[int] = None,
                  dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
     """Tiles [begin, end) of `plan` cut from decoded frames uint8 [T,H,W,3] on the GPU: one buffer [end - begin, 3, Tt, Ht, Wt] in
@@ -142,6 +152,41 @@ def blend_tiles(tiles: Sequence[Optional[torch.Tensor]], plan: TilePlan, t0: int
     cp = plan.c_plan()
     _lib.check(_lib.lib().ttv_video_blend_u8(host, table.data_ptr(), C.byref(cp), int(t0), t1, _lib.dtype_code(dtype), out.data_ptr(),
                                              _lib.stream_ptr(device)), "ttv_video_blend_u8")
+    return out
+
+
+def tile_sse(frames_u8: torch.Tensor, plan: TilePlan, recon_tiles: Sequence[torch.Tensor], begin: int = 0,
+             end: Optional[int] = None) -> torch.Tensor:
+    """Per tile of [begin, end) the sum of squared level differences between its reconstruction `recon_tiles[k - begin]`
+    ([3,Tt,Ht,Wt], what the model returns for the tile `gather_tiles` cut) and the source pixels of `frames_u8`: int64 [end - begin] on
+    the GPU, exact integers (`ttv_video_tile_sse_u8`; the header defines the level of an element and which samples count).  One launch
+    on the current stream."""
+    _lib.require_gpu(frames_u8, "tile_sse")
+    if frames_u8.dtype != torch.uint8 or tuple(frames_u8.shape) != plan.video + (3,) or not frames_u8.is_contiguous():
+        raise ValueError(f"frames must be contiguous uint8 {plan.video + (3,)}, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+    end = plan.n_tiles if end is None else int(end)
+    if not 0 <= begin <= end <= plan.n_tiles:
+        raise ValueError(f"tiles [{begin}, {end}) of {plan.n_tiles}")
+    if len(recon_tiles) != end - begin:
+        raise ValueError(f"{len(recon_tiles)} reconstructions for tiles [{begin}, {end})")
+    device = frames_u8.device
+    out = torch.empty((end - begin,), dtype=torch.int64, device=device)
+    if end == begin:
+        return out
+    dtype = recon_tiles[0].dtype
+    for t in recon_tiles:
+        _lib.require_gpu(t, "tile_sse")
+        if t.dtype != dtype or t.device != device or tuple(t.shape) != (3,) + plan.tile or not t.is_contiguous():
+            raise ValueError(f"reconstructions must be contiguous {(3,) + plan.tile} of one dtype on the frames' device, got {t.dtype} "
+                             f"{tuple(t.shape)} on {t.device}")
+    ptrs = [t.data_ptr() for t in recon_tiles]
+    host = (_lib.vp * len(ptrs))(*ptrs)
+    # from pinned memory and without waiting: a pageable upload would hold the host until the stream has run everything queued
+    # before it - the forward that made these tiles - and the next batch of the pipeline could not be queued meanwhile
+    table = torch.tensor(ptrs, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+    cp = plan.c_plan()
+    _lib.check(_lib.lib().ttv_video_tile_sse_u8(frames_u8.data_ptr(), C.byref(cp), int(begin), end, host, table.data_ptr(),
+                                                _lib.dtype_code(dtype), out.data_ptr(), _lib.stream_ptr(device)), "ttv_video_tile_sse_u8")
     return out
 
 
@@ -238,6 +283,117 @@ class VideoTokens:
         return 8.0 * len(self.to_bytes()) / (t * self.video[1] * self.video[2])
 
 
+# ---- rate and distortion ------------------------------------------------------------------------------------------------------------------
+def _check_ladder(ladder) -> Tuple[int, ...]:
+    out = tuple(int(k) for k in ladder)
+    if not out or out[0] < 1 or any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError(f"a ladder is ascending distinct token counts of at least 1, got {tuple(ladder)!r}")
+    return out
+
+
+def default_ladder(tokens_per_tile: int) -> Tuple[int, ...]:
+    """tokens_per_tile / 8, / 4, / 2 and tokens_per_tile itself, rounded up, the distinct ones."""
+    k = int(tokens_per_tile)
+    if k < 1:
+        raise ValueError(f"tokens_per_tile must be at least 1, got {tokens_per_tile}")
+    return tuple(sorted({-(-k // d) for d in (8, 4, 2, 1)}))
+
+
+class RateTable:
+    """What every tile of a video costs at every token count of a ladder (`VideoTokenizer.rate_distortion`).  `ladder`: ascending
+    distinct counts; `sse[tile][level]`: Python ints, the tile's `tile_sse` when coded with `ladder[level]` tokens; `elements[tile]`:
+    the samples that sum runs over (`TilePlan.tile_elements`); `indices[tile][level]`: the int32 indices the probe produced, or None
+    for a table that only feeds `allocate_tokens`."""
+
+    def __init__(self, ladder, sse, elements, indices=None):
+        self.ladder = _check_ladder(ladder)
+        self.sse = [[int(v) for v in row] for row in sse]
+        self.elements = [int(e) for e in elements]
+        self.indices = indices
+        if len(self.elements) != len(self.sse) or any(len(row) != len(self.ladder) for row in self.sse):
+            raise ValueError(f"sse must be [n_tiles][{len(self.ladder)}] with one element count per tile")
+        if any(v < 0 for row in self.sse for v in row) or any(e < 1 for e in self.elements):
+            raise ValueError("sums of squares are at least 0 and element counts at least 1")
+        if indices is not None and (len(indices) != len(self.sse) or any(len(row) != len(self.ladder) for row in indices)):
+            raise ValueError(f"indices must be [n_tiles][{len(self.ladder)}]")
+
+    @property
+    def n_tiles(self) -> int:
+        return len(self.sse)
+
+    def psnr(self) -> List[List[float]]:
+        """[tile][level] 10 log10(65025 elements / sse) in float64 (levels 0 .. 255), inf where the sum is 0."""
+        return [[math.inf if v == 0 else 10.0 * math.log10(65025 * e / v) for v in row] for row, e in zip(self.sse, self.elements)]
+
+
+def _hull_levels(ladder: Sequence[int], row: Sequence[int]) -> List[int]:
+    """Levels of the lower convex hull of the points (ladder[l], row[l]) from level 0 on, as far as it falls: each step of it lowers
+    the sum, and the drop per token shrinks from step to step.  Integer cross-multiplication, no division."""
+    hull = [0]
+    for l in range(1, len(ladder)):
+        while len(hull) >= 2:
+            a, b = hull[-2], hull[-1]
+            # b stays only when it lies strictly below the chord a -> l
+            if (row[b] - row[a]) * (ladder[l] - ladder[a]) >= (row[l] - row[a]) * (ladder[b] - ladder[a]):
+                hull.pop()
+            else:
+                break
+        hull.append(l)
+    keep = [0]
+    for l in hull[1:]:
+        if row[l] >= row[keep[-1]]:
+            break
+        keep.append(l)
+    return keep
+
+
+def allocate_tokens(table: RateTable, target_psnr: Optional[float] = None, total_tokens: Optional[int] = None) -> List[int]:
+    """One ladder count per tile from measured distortion; exactly one of the two arguments.  Pure Python on the table's exact
+    integers, and nothing assumes that a tile's sum falls as its count grows.
+
+    target_psnr: per tile the smallest count whose `RateTable.psnr` reaches the target; where none does, the count of the least sum
+    (the smaller count on a tie).
+    total_tokens: every tile starts at ladder[0] (ValueError when the budget is below n_tiles * ladder[0]).  Each tile's candidates
+    are the steps of its lower convex hull from ladder[0] on, as far as the hull falls.  Among the tiles' next steps that still fit
+    what is left of the budget, the one with the largest drop of the sum per token is taken (the lower tile index on a tie), until
+    no step fits.  If a uniform ladder count that fits the budget has a lower total than the result, the best such count is returned
+    for every tile (the smaller count on a tie): the result is never worse than uniform at the same budget."""
+    if (target_psnr is None) == (total_tokens is None):
+        raise ValueError("allocate_tokens: give exactly one of target_psnr and total_tokens")
+    ladder, sse, n = table.ladder, table.sse, table.n_tiles
+    if target_psnr is not None:
+        target, out = float(target_psnr), []
+        for row, quality in zip(sse, table.psnr()):
+            reached = [l for l, q in enumerate(quality) if q >= target]
+            out.append(ladder[reached[0] if reached else min(range(len(row)), key=lambda l: (row[l], l))])
+        return out
+    budget = int(total_tokens)
+    if budget < n * ladder[0]:
+        raise ValueError(f"total_tokens {budget} is below {n} tiles at the ladder's least count {ladder[0]}")
+    hulls = [_hull_levels(ladder, row) for row in sse]
+    at = [0] * n                                            # position on the tile's hull
+    left = budget - n * ladder[0]
+    while True:
+        best = None                                         # (drop, tokens, tile)
+        for j in range(n):
+            if at[j] + 1 == len(hulls[j]):
+                continue
+            a, b = hulls[j][at[j]], hulls[j][at[j] + 1]
+            tokens, drop = ladder[b] - ladder[a], sse[j][a] - sse[j][b]
+            if tokens <= left and (best is None or drop * best[1] > best[0] * tokens):
+                best = (drop, tokens, j)
+        if best is None:
+            break
+        at[best[2]] += 1
+        left -= best[1]
+    levels = [hulls[j][at[j]] for j in range(n)]
+    total = sum(sse[j][levels[j]] for j in range(n))
+    uniform = [(sum(row[l] for row in sse), l) for l in range(len(ladder)) if n * ladder[l] <= budget]
+    if uniform and min(uniform)[0] < total:
+        return [ladder[min(uniform)[1]]] * n
+    return [ladder[l] for l in levels]
+
+
 # ---- the public surface -----------------------------------------------------------------------------------------------------------------
 def _budget_ranges(rows: Sequence[int], begin: int, end: int, seq_len: int) -> List[Tuple[int, int]]:
     """Consecutive ranges of [begin, end) under the reference's token budget (data.dynamic_batches): a range is closed when the next
@@ -281,6 +437,7 @@ class VideoTokenizer:
         self.quantizer = model.quantizer_kind
         self.codebook_size = int(model.quantize.codebook_size)
         self._pipe = None
+        self._probe_pipe = None
 
     def _counts(self, n_tiles: int) -> List[int]:
         k = self.tokens_per_tile
@@ -298,13 +455,76 @@ class VideoTokenizer:
     def _encode_batch(self, clips, counts):
         return self.model.encode(clips, counts)[1]["indices"]
 
-    def encode_video(self, frames_u8: torch.Tensor, fps: Optional[float] = None, frame_stride: int = 1) -> VideoTokens:
+    def _probe_batch(self, frames_u8, plan: TilePlan, a: int, b: int, count: int):
+        """Tiles [a, b) coded at `count` tokens each and measured: (sums int64 [b - a], indices int32 [(b - a) * count]), all on the
+        current stream.  The reconstructions are dropped here."""
+        clips = list(gather_tiles(frames_u8, plan, a, b, self.dtype).unbind(0))
+        recon, info = self.model(clips, [count] * (b - a))
+        return tile_sse(frames_u8, plan, recon, a, b), info["indices"].to(torch.int32)
+
+    def rate_distortion(self, frames_u8: torch.Tensor, ladder: Sequence[int], frame_stride: int = 1) -> RateTable:
+        """What every tile costs at every count of `ladder`.  Per count, all tiles are coded at that count, in tile order, in the
+        batches the token budget gives; a batch is gathered, run through the model and measured against the same frames (`tile_sse`)
+        on one stream - a side stream of the pipeline when `depth` > 1 - and only its sums and indices are kept: memory is that of
+        `depth` batches, whatever the video's length.  The table describes these reconstructions, batch for batch."""
+        _lib.require_gpu(frames_u8, "rate_distortion")
+        if frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
+            raise ValueError(f"frames must be uint8 [T,H,W,3], got {tuple(frames_u8.shape)}")
+        ladder = _check_ladder(ladder)
+        plan = TilePlan(tuple(frames_u8.shape[:3]), self.tile, self.overlap, self.patch, frame_stride)
+        n = plan.n_tiles
+        if self.depth > 1 and self._probe_pipe is None:
+            from .pipeline import ForwardPipeline
+            self._probe_pipe = ForwardPipeline(self.model, depth=self.depth, device=self.device, fn=self._probe_batch)
+        sums, indices = [], []
+        with torch.no_grad():
+            for count in ladder:
+                parts, inflight = [], []
+                for a, b in self._ranges(plan, [count] * n, 0, n):
+                    if self.depth == 1:
+                        parts.append(self._probe_batch(frames_u8, plan, a, b, count))
+                        continue
+                    inflight.append(self._probe_pipe.submit(frames_u8, plan, a, b, count))
+                    if len(inflight) >= self.depth:                                          # at most `depth` batches of tiles alive
+                        parts.append(self._probe_pipe.result(inflight.pop(0)))
+                parts += [self._probe_pipe.result(t) for t in inflight]
+                sums.append(torch.cat([p[0] for p in parts]))
+                indices.append(torch.cat([p[1] for p in parts]).view(n, count))
+            sse = torch.stack(sums, dim=1).cpu().tolist()                                    # [n_tiles][len(ladder)], one read
+        return RateTable(ladder, sse, [plan.tile_elements(j) for j in range(n)],
+                         [[level[j] for level in indices] for j in range(n)])
+
+    def encode_video(self, frames_u8: torch.Tensor, fps: Optional[float] = None, frame_stride: int = 1, ladder: Optional[Sequence[int]] = None,
+                     target_psnr: Optional[float] = None, total_tokens: Optional[int] = None) -> VideoTokens:
         """Decoded frames uint8 [T,H,W,3] on the GPU -> tokens of every `frame_stride`-th frame.  Tiles are gathered in tile order into
-        batches under the token budget and encoded; equal tile shapes mean one cached batch plan per batch size."""
+        batches under the token budget and encoded; equal tile shapes mean one cached batch plan per batch size.
+
+        With `target_psnr` (dB per tile, levels 0 .. 255) or `total_tokens` (a budget for the whole video) the count of every tile is
+        chosen from measured distortion: `rate_distortion` over `ladder` (default `default_ladder(tokens_per_tile)`), then
+        `allocate_tokens`.  The tokens are the probe's own indices at the chosen count of each tile - there is no second encoding
+        pass - and `counts` is the allocation.  The table describes the probe's reconstructions, batch for batch: a tile decoded later
+        in another batch goes through the same arithmetic on its own rows, but nothing here decodes it again to check."""
         _lib.require_gpu(frames_u8, "encode_video")
         if frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
             raise ValueError(f"frames must be uint8 [T,H,W,3], got {tuple(frames_u8.shape)}")
         plan = TilePlan(tuple(frames_u8.shape[:3]), self.tile, self.overlap, self.patch, frame_stride)
+        if target_psnr is not None or total_tokens is not None:
+            if ladder is None:
+                if not isinstance(self.tokens_per_tile, int):
+                    raise ValueError("a ladder is required when tokens_per_tile is one count per tile")
+                ladder = default_ladder(self.tokens_per_tile)
+            if (target_psnr is None) == (total_tokens is None):
+                raise ValueError("encode_video: give at most one of target_psnr and total_tokens")
+            ladder = _check_ladder(ladder)
+            if total_tokens is not None and int(total_tokens) < plan.n_tiles * ladder[0]:        # before the probe, not after it
+                raise ValueError(f"total_tokens {total_tokens} is below {plan.n_tiles} tiles at the ladder's least count {ladder[0]}")
+            table = self.rate_distortion(frames_u8, ladder, frame_stride)
+            counts = allocate_tokens(table, target_psnr=target_psnr, total_tokens=total_tokens)
+            indices = torch.cat([table.indices[j][table.ladder.index(k)] for j, k in enumerate(counts)])
+            return VideoTokens(indices, counts, plan.video, self.tile, self.overlap, self.patch, plan.frame_stride,
+                               None if fps is None else float(fps) / plan.frame_stride, self.codebook_size, self.quantizer)
+        if ladder is not None:
+            raise ValueError("encode_video: a ladder needs target_psnr or total_tokens")
         counts = self._counts(plan.n_tiles)
         ranges = self._ranges(plan, counts, 0, plan.n_tiles)
         parts, inflight = [], []
