@@ -192,6 +192,9 @@ int ttv_rmsnorm(const void* in, int in_dtype, int ld_in, const int32_t* src_rows
 /* apply_rotary_emb (model/base/rope.py:19-27) on x [rows, heads, 64] in place; rope_cs fp32 [rows,64] =
  * (cos[32] | sin[32]) per row, entries 30,31 = (1,0) so the last 4 dims of a head stay untouched. */
 int ttv_rope_apply(void* x, int dtype, int ld, int rows, int heads, const float* rope_cs, void* stream);
+/* The inverse rotation (by -theta: the sine half of rope_cs negated), in place: what the fp32 attention backward applies to dq and dk.
+ * Same arguments; ld a multiple of 4 and >= heads * 64, x aligned to 4 elements, else TTV_ERR_INVALID. */
+int ttv_rope_apply_conj(void* x, int dtype, int ld, int rows, int heads, const float* rope_cs, void* stream);
 
 /* y[M,N] = x[M,K] @ w[N,K]^T (+ bias[N]) (+ *add_scalar): nn.Linear (blocks.py:93,166,173; transformer.py:49,55,87,104). */
 int ttv_linear(const void* x, int ldx, const void* w, int ldw, const void* bias, const float* add_scalar, void* y, int ldy,
@@ -252,6 +255,10 @@ int ttv_fill_const_rows(void* x, int dtype, int ld, const int32_t* rows_map, int
  * codes [rows, token_size] (dtype), w [width, token_size], bias [width] (dtype). */
 int ttv_decoder_embed(const void* codes, int token_size, const void* w, const void* bias, const float* mask_token, const float* gain,
                       void* x, int dtype, int ld, const int32_t* rows_map, int rows, int width, float eps, void* stream);
+/* The same, also writing the training tape's pre-norm row hpre [rows, width] (dtype, dense, row i of codes; NULL: not written) =
+ * round_T(round_T(proj_in(codes[i]) + bias) + (T) mask_token): x is bit for bit what ttv_decoder_embed writes. */
+int ttv_decoder_embed_tape(const void* codes, int token_size, const void* w, const void* bias, const float* mask_token, const float* gain,
+                           void* x, int dtype, int ld, const int32_t* rows_map, int rows, int width, float eps, void* hpre, void* stream);
 
 /* flash_attn_varlen_func as called at transformer.py:100, fused with the sigmoid gate of transformer.py:103:
  * qkvg [L, 2d+2g] packed (q | gate | k | v) with RoPE already applied to q,k; out [L,d] = attn * sigmoid(gate).
@@ -711,6 +718,46 @@ int ttv_decoder_backward(const ttv_tower_dims* dims, const ttv_tower_weights* w,
                          void* workspace, int64_t workspace_bytes, void* stream);
 /* Straight-through FSQ backward (fsq.py:48-51,78-90): dz = dcodes * half_l/half_width * (1 - tanh^2(z + shift)). */
 int ttv_fsq_backward(const ttv_fsq_params* p, const float* z, const void* dcodes, int dcodes_dtype, float* dz, int rows, void* stream);
+
+/* The elementwise and small-projection ops of the training tape, one launch each (tests: the towers call the same launchers, so every
+ * check below holds for them too).  T is `dtype` (TTV_BF16 or TTV_F32); arithmetic is fp32 with one rounding to T at the store.  rows == 0
+ * (n == 0) is a no-op that accepts NULL pointers.  The 4-wide ops (gate, geglu, scale_cast, cast_to_f32) move whole 4-element vectors:
+ * the width, every leading dimension (>= the width it spans) and every pointer must be a multiple of 4 elements, n a multiple of 4;
+ * anything else is TTV_ERR_INVALID before any launch. */
+/* ag[r, 0:width] = a * sigmoid(gate) (transformer.py:103; the gate sits inside a q|gate|k|v row).  ag may be a itself (same pointer and
+ * leading dimension): every element is read and written exactly once. */
+int ttv_gate_forward(const void* a, int lda, const void* gate, int ldg, void* ag, int ldo, int rows, int width, int dtype, void* stream);
+/* da = dag * sigmoid(gate), dgate = dag * a * sigmoid(gate) * (1 - sigmoid(gate)).  delta (may be NULL; fp32 [rows, width / 64], needs
+ * width % 64 == 0): the attention backward's delta[r, h] = sum over head h's 64 dims of da * a with da AS STORED (rounded to T), every
+ * element written exactly once. */
+int ttv_gate_backward(const void* dag, int lddag, const void* a, int lda, const void* gate, int ldg, void* da, int ldda, void* dgate,
+                      int lddg, int rows, int width, int dtype, float* delta, void* stream);
+/* h[r, 0:inner] = gelu_erf(u[r, inner:2 inner]) * u[r, 0:inner] (erff() for both dtypes). */
+int ttv_geglu_forward(const void* u, int ldu, void* h, int ldh, int rows, int inner, int dtype, void* stream);
+/* du[:, 0:inner] = dh * gelu(g), du[:, inner:2 inner] = dh * x * gelu'(g) with x | g = u.  fp32: erff() / expf().  bf16: the 8-wide
+ * kernel with the fast Phi of the forward GEMM epilogue (|g Phi - gelu| <= 2.6e-5, |Phi + g phi - gelu'| <= 5.1e-5 for |g| <= 2^20) when
+ * inner and all three leading dimensions are multiples of 8 and all three pointers 16-byte aligned, the 4-wide erff() kernel otherwise
+ * (and always when TTV_GEGLU_BWD_ERF=1, read once per process). */
+int ttv_geglu_backward(const void* u, int ldu, const void* dh, int lddh, void* du, int lddu, int rows, int inner, int dtype, void* stream);
+/* b = alpha * a (fp32, NULL: skipped, may alias a) and c = (T) a (NULL: skipped) over n contiguous fp32 elements. */
+int ttv_scale_cast(const float* a, float alpha, float* b, void* c, int dtype, int64_t n, void* stream);
+/* b = (float) a, or b += (float) a when accumulate != 0, over n contiguous elements of T. */
+int ttv_cast_to_f32(const void* a, int dtype, float* b, int64_t n, int accumulate, void* stream);
+/* out[r, f] = sum_{c < C} a[r, c] * w[c, f] (w_cf = 1) or w[f, c] (w_cf = 0), f < width: the wide side of a width <-> token_size
+ * projection, summed in fp32 in the order of c.  (a, w, out) dtypes: (f32, bf16, bf16), (f32, f32, f32) or (f32, bf16, f32); any other
+ * triple is TTV_ERR_INVALID.  No alignment demands (scalar accesses). */
+int ttv_expand_small(const void* a, int a_dtype, int lda, int C, const void* w, int w_dtype, int ldw, int w_cf, void* out, int out_dtype,
+                     int ldo, int rows, int width, void* stream);
+/* out[r, c] (fp32) = sum_{f < width} a[a_rows ? a_rows[r] : r][f] * w[f, c], c < C: one wave per row, 64 interleaved partial sums and a
+ * 6-step wave sum.  (a, w) dtypes: (bf16, bf16), (f32, f32) or (f32, bf16); any other pair is TTV_ERR_INVALID. */
+int ttv_reduce_small(const void* a, int a_dtype, int lda, const int32_t* a_rows, const void* w, int w_dtype, int ldw, int C, float* out,
+                     int ldo, int rows, int width, void* stream);
+/* Backward of the constant mask-token rows v[f] = m * rsqrt(m^2 + eps) * gain[f], m = (T) mask_token[0] straight through, given
+ * colsum[f] = the sum of the incoming gradient over those rows (all fp32 [width] / [1]): dgain[f] += colsum[f] * m * rsqrt(m^2 + eps),
+ * dmask[0] += sum_f colsum[f] * gain[f] * eps * (m^2 + eps)^-1.5.  dgain and dmask both NULL: a no-op; exactly one NULL:
+ * TTV_ERR_INVALID (the kernel writes both; the towers always pass both or neither). */
+int ttv_const_rows_backward(const float* colsum, const float* mask_token, const float* gain, int dtype, float eps, float* dgain,
+                            float* dmask, int width, void* stream);
 
 /* Optimizer step of the training loop (reference train.py:76-77 clip_gradients + :183-190 optim.AdamW; the arithmetic of
  * torch.nn.utils.clip_grad_norm_ followed by torch.optim.AdamW, fp32 whatever the tensors' dtype) over a list of tensors, in two launches.

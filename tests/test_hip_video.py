@@ -411,6 +411,8 @@ def test_iter_holds_a_few_layers_not_the_video():
     del warm
 
     def peak_of(run):
+        import gc
+        gc.collect()             # cyclic garbage of earlier tests still holds device memory: freed inside `run` it would lower the peak below `base`
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
         base = torch.cuda.memory_allocated()

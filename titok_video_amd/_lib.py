@@ -288,6 +288,18 @@ SYMBOLS = {
     "ttv_decoder_backward_ex": (C.c_int, [C.POINTER(TowerDims), C.POINTER(TowerWeights), C.POINTER(TowerWeightsT), C.POINTER(Batch), vp,
                                           C.POINTER(vp), vp, C.POINTER(TowerGrads), vp, vp, i64, vp, C.c_int]),
     "ttv_fsq_backward": (C.c_int, [C.POINTER(FsqParams), vp, vp, C.c_int, vp, C.c_int, vp]),
+    # the tape's elementwise and small-projection ops one by one (tests only)
+    "ttv_gate_forward": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ttv_gate_backward": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "ttv_geglu_forward": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ttv_geglu_backward": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ttv_scale_cast": (C.c_int, [vp, f32, vp, vp, C.c_int, C.c_int64, vp]),
+    "ttv_cast_to_f32": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.c_int, vp]),
+    "ttv_expand_small": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ttv_reduce_small": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "ttv_const_rows_backward": (C.c_int, [vp, vp, vp, C.c_int, f32, vp, vp, C.c_int, vp]),
+    "ttv_rope_apply_conj": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "ttv_decoder_embed_tape": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, f32, vp, vp]),
     "ttv_rmsnorm_backward_chain": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_float, vp, C.c_int,
                                               C.c_int, C.c_int, C.c_float, C.c_int, vp]),
     "ttv_opt_grad_sumsq": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),

@@ -601,6 +601,11 @@ int ttv_rope_apply(void* x, int dtype, int ld, int rows, int heads, const float*
   return ttvk_rope_apply(x, dtype, ld, rows, heads, rope_cs, (hipStream_t)stream);
 }
 
+int ttv_rope_apply_conj(void* x, int dtype, int ld, int rows, int heads, const float* rope_cs, void* stream) {
+  TTV_CHECK_ARG(rows >= 0, "rope_apply_conj: %d rows", rows);
+  return ttvk_rope_apply_dir(x, dtype, ld, rows, heads, rope_cs, 1, (hipStream_t)stream);
+}
+
 int ttv_linear(const void* x, int ldx, const void* w, int ldw, const void* bias, const float* add_scalar, void* y, int ldy, int M,
                int N, int K, int dtype, void* stream) {
   TTV_CHECK_ARG(M == 0 || (x && w && y), "linear: null buffer");
@@ -685,6 +690,12 @@ int ttv_decoder_embed(const void* codes, int token_size, const void* w, const vo
                       void* x, int dtype, int ld, const int32_t* rows_map, int rows, int width, float eps, void* stream) {
   TTV_CHECK_ARG(rows == 0 || (codes && w && bias && mask_token && gain && x && rows_map), "decoder_embed: null buffer");
   return ttvk_dec_embed(codes, token_size, w, bias, mask_token, gain, x, dtype, ld, rows_map, rows, width, eps, (hipStream_t)stream);
+}
+
+int ttv_decoder_embed_tape(const void* codes, int token_size, const void* w, const void* bias, const float* mask_token, const float* gain,
+                           void* x, int dtype, int ld, const int32_t* rows_map, int rows, int width, float eps, void* hpre, void* stream) {
+  TTV_CHECK_ARG(rows >= 0 && (rows == 0 || (codes && w && bias && mask_token && gain && x && rows_map)), "decoder_embed_tape: null buffer");
+  return ttvk_dec_embed_ex(codes, token_size, w, bias, mask_token, gain, x, dtype, ld, rows_map, rows, width, eps, hpre, (hipStream_t)stream);
 }
 
 int ttv_attention(const void* qkvg, int ld, void* out, int ldo, const int32_t* cu_seqlens, const int32_t* qblocks, int n_qblocks,

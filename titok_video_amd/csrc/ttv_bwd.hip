@@ -522,10 +522,9 @@ int ttvk_sumall(const void* a, int dt, int lda, const int* rows_map, int rows, i
 // ------------------------------------------------------------------------------------------------ elementwise
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + __expf(-v)); }
 
-// ag = a * sigmoid(gate)
+// ag = a * sigmoid(gate).  ag may be a itself (no __restrict__ on the two): every vector is loaded and stored by one thread, once.
 template <typename T>
-__global__ __launch_bounds__(256) void k_gate_fwd(const T* __restrict__ a, int lda, const T* __restrict__ gate, int ldg, T* __restrict__ ag,
-                                                  int ldo, int rows, int d) {
+__global__ __launch_bounds__(256) void k_gate_fwd(const T* a, int lda, const T* __restrict__ gate, int ldg, T* ag, int ldo, int rows, int d) {
   const long total = (long)rows * (d / 4);
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const long r = i / (d / 4);
@@ -660,9 +659,17 @@ static inline int ew_blocks(long total) {
   long b = (total + 255) / 256;
   return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
 }
+// The kernels above move whole 4-element vectors of T: the width, every leading dimension and every pointer in units of 4 elements
+// (16 bytes in fp32, 8 in bf16).  Checked here so the tower paths and the stand-alone entry points are refused alike, before any launch.
+static inline bool ew_dtype_ok(int dt) { return dt == TTV_BF16 || dt == TTV_F32; }
+static inline bool ew_ptr_ok(const void* p, int dt) { return p && (uintptr_t)p % (dt == TTV_BF16 ? 8 : 16) == 0; }
+static inline bool ew_ld_ok(int ld, int width) { return ld >= width && ld % 4 == 0; }
 
 int ttvk_gate_fwd(const void* a, int lda, const void* gate, int ldg, void* ag, int ldo, int rows, int d, int dt, hipStream_t s) {
   if (rows == 0) return TTV_OK;
+  TTV_CHECK_ARG(ew_dtype_ok(dt) && rows > 0 && d > 0 && d % 4 == 0, "gate_fwd: dtype %d, %d rows, width %d (a positive multiple of 4)", dt, rows, d);
+  TTV_CHECK_ARG(ew_ld_ok(lda, d) && ew_ld_ok(ldg, d) && ew_ld_ok(ldo, d), "gate_fwd: leading dimensions %d %d %d (>= %d, multiples of 4)", lda, ldg, ldo, d);
+  TTV_CHECK_ARG(ew_ptr_ok(a, dt) && ew_ptr_ok(gate, dt) && ew_ptr_ok(ag, dt), "gate_fwd: null or not 4-element aligned pointer");
   const int nb = ew_blocks((long)rows * d / 4);
   if (dt == TTV_BF16) hipLaunchKernelGGL((k_gate_fwd<bf16_t>), dim3(nb), dim3(256), 0, s, (const bf16_t*)a, lda, (const bf16_t*)gate, ldg, (bf16_t*)ag, ldo, rows, d);
   else hipLaunchKernelGGL((k_gate_fwd<float>), dim3(nb), dim3(256), 0, s, (const float*)a, lda, (const float*)gate, ldg, (float*)ag, ldo, rows, d);
@@ -672,7 +679,12 @@ int ttvk_gate_fwd(const void* a, int lda, const void* gate, int ldg, void* ag, i
 int ttvk_gate_bwd(const void* dag, int ldd, const void* a, int lda, const void* gate, int ldg, void* da, int ldda, void* dgate, int lddg,
                   int rows, int d, int dt, float* delta, hipStream_t s) {
   if (rows == 0) return TTV_OK;
+  TTV_CHECK_ARG(ew_dtype_ok(dt) && rows > 0 && d > 0 && d % 4 == 0, "gate_bwd: dtype %d, %d rows, width %d (a positive multiple of 4)", dt, rows, d);
   TTV_CHECK_ARG(!delta || d % 64 == 0, "gate_bwd: delta needs whole 64-wide heads");
+  TTV_CHECK_ARG(ew_ld_ok(ldd, d) && ew_ld_ok(lda, d) && ew_ld_ok(ldg, d) && ew_ld_ok(ldda, d) && ew_ld_ok(lddg, d),
+                "gate_bwd: leading dimensions %d %d %d %d %d (>= %d, multiples of 4)", ldd, lda, ldg, ldda, lddg, d);
+  TTV_CHECK_ARG(ew_ptr_ok(dag, dt) && ew_ptr_ok(a, dt) && ew_ptr_ok(gate, dt) && ew_ptr_ok(da, dt) && ew_ptr_ok(dgate, dt),
+                "gate_bwd: null or not 4-element aligned pointer");
   const int nb = ew_blocks((long)rows * d / 4);
   if (dt == TTV_BF16) hipLaunchKernelGGL((k_gate_bwd<bf16_t>), dim3(nb), dim3(256), 0, s, (const bf16_t*)dag, ldd, (const bf16_t*)a, lda, (const bf16_t*)gate, ldg, (bf16_t*)da, ldda, (bf16_t*)dgate, lddg, rows, d, delta);
   else hipLaunchKernelGGL((k_gate_bwd<float>), dim3(nb), dim3(256), 0, s, (const float*)dag, ldd, (const float*)a, lda, (const float*)gate, ldg, (float*)da, ldda, (float*)dgate, lddg, rows, d, delta);
@@ -681,6 +693,9 @@ int ttvk_gate_bwd(const void* dag, int ldd, const void* a, int lda, const void* 
 }
 int ttvk_geglu_fwd(const void* u, int ldu, void* h, int ldh, int rows, int I, int dt, hipStream_t s) {
   if (rows == 0) return TTV_OK;
+  TTV_CHECK_ARG(ew_dtype_ok(dt) && rows > 0 && I > 0 && I % 4 == 0, "geglu_fwd: dtype %d, %d rows, inner %d (a positive multiple of 4)", dt, rows, I);
+  TTV_CHECK_ARG(ew_ld_ok(ldu, 2 * I) && ew_ld_ok(ldh, I), "geglu_fwd: leading dimensions %d (>= %d) %d (>= %d), multiples of 4", ldu, 2 * I, ldh, I);
+  TTV_CHECK_ARG(ew_ptr_ok(u, dt) && ew_ptr_ok(h, dt), "geglu_fwd: null or not 4-element aligned pointer");
   const int nb = ew_blocks((long)rows * I / 4);
   if (dt == TTV_BF16) hipLaunchKernelGGL((k_geglu_fwd<bf16_t>), dim3(nb), dim3(256), 0, s, (const bf16_t*)u, ldu, (bf16_t*)h, ldh, rows, I);
   else hipLaunchKernelGGL((k_geglu_fwd<float>), dim3(nb), dim3(256), 0, s, (const float*)u, ldu, (float*)h, ldh, rows, I);
@@ -689,6 +704,10 @@ int ttvk_geglu_fwd(const void* u, int ldu, void* h, int ldh, int rows, int I, in
 }
 int ttvk_geglu_bwd(const void* u, int ldu, const void* dh, int lddh, void* du, int lddu, int rows, int I, int dt, hipStream_t s) {
   if (rows == 0) return TTV_OK;
+  TTV_CHECK_ARG(ew_dtype_ok(dt) && rows > 0 && I > 0 && I % 4 == 0, "geglu_bwd: dtype %d, %d rows, inner %d (a positive multiple of 4)", dt, rows, I);
+  TTV_CHECK_ARG(ew_ld_ok(ldu, 2 * I) && ew_ld_ok(lddh, I) && ew_ld_ok(lddu, 2 * I),
+                "geglu_bwd: leading dimensions %d %d %d (u, du >= %d, dh >= %d, multiples of 4)", ldu, lddh, lddu, 2 * I, I);
+  TTV_CHECK_ARG(ew_ptr_ok(u, dt) && ew_ptr_ok(dh, dt) && ew_ptr_ok(du, dt), "geglu_bwd: null or not 4-element aligned pointer");
   const int nb = ew_blocks((long)rows * I / 4);
   static const bool exact = ttv_env_flag("TTV_GEGLU_BWD_ERF", false);      // A/B: the erff() form
   const bool v8 = !exact && I % 8 == 0 && ldu % 8 == 0 && lddh % 8 == 0 && lddu % 8 == 0 && ((uintptr_t)u % 16 == 0) && ((uintptr_t)dh % 16 == 0) && ((uintptr_t)du % 16 == 0);
@@ -700,6 +719,9 @@ int ttvk_geglu_bwd(const void* u, int ldu, const void* dh, int lddh, void* du, i
 }
 int ttvk_scale_cast(const float* a, float alpha, float* b, void* c, int dt, long n, hipStream_t s) {
   if (n == 0) return TTV_OK;
+  // the kernel walks n / 4 vectors: a tail of n % 4 elements would be left unwritten without a word
+  TTV_CHECK_ARG(ew_dtype_ok(dt) && n > 0 && n % 4 == 0, "scale_cast: dtype %d, %ld elements (a positive multiple of 4)", dt, n);
+  TTV_CHECK_ARG(ew_ptr_ok(a, TTV_F32) && (!b || ew_ptr_ok(b, TTV_F32)) && (!c || ew_ptr_ok(c, dt)), "scale_cast: null or not 4-element aligned pointer");
   const int nb = ew_blocks(n / 4);
   if (dt == TTV_BF16) hipLaunchKernelGGL((k_scale_cast<bf16_t>), dim3(nb), dim3(256), 0, s, a, alpha, b, (bf16_t*)c, n / 4);
   else hipLaunchKernelGGL((k_scale_cast<float>), dim3(nb), dim3(256), 0, s, a, alpha, b, (float*)c, n / 4);
@@ -708,6 +730,8 @@ int ttvk_scale_cast(const float* a, float alpha, float* b, void* c, int dt, long
 }
 int ttvk_to_f32(const void* a, int dt, float* b, long n, int accumulate, hipStream_t s) {
   if (n == 0) return TTV_OK;
+  TTV_CHECK_ARG(ew_dtype_ok(dt) && n > 0 && n % 4 == 0, "to_f32: dtype %d, %ld elements (a positive multiple of 4)", dt, n);
+  TTV_CHECK_ARG(ew_ptr_ok(a, dt) && ew_ptr_ok(b, TTV_F32), "to_f32: null or not 4-element aligned pointer");
   const int nb = ew_blocks(n / 4);
   if (dt == TTV_BF16) hipLaunchKernelGGL((k_to_f32<bf16_t>), dim3(nb), dim3(256), 0, s, (const bf16_t*)a, b, n / 4, accumulate);
   else hipLaunchKernelGGL((k_to_f32<float>), dim3(nb), dim3(256), 0, s, (const float*)a, b, n / 4, accumulate);
@@ -1454,6 +1478,8 @@ __global__ __launch_bounds__(256) void k_reduce_small(const TA* __restrict__ a, 
 int ttvk_expand_small(const void* a, int a_dt, int lda, int C, const void* w, int w_dt, int ldw, int w_cf, void* out, int o_dt, int ldo,
                       int rows, int d, hipStream_t s) {
   if (rows == 0) return TTV_OK;
+  TTV_CHECK_ARG(rows > 0 && C >= 1 && d >= 1 && lda >= C && ldo >= d && ldw >= (w_cf ? d : C) && a && w && out,
+                "expand_small: %d rows, C %d, d %d, leading dimensions %d %d %d", rows, C, d, lda, ldw, ldo);
   const int nb = ew_blocks((long)rows * d);
 #define ES(TA, TW, TO) hipLaunchKernelGGL((k_expand_small<TA, TW, TO>), dim3(nb), dim3(256), 0, s, (const TA*)a, lda, C, (const TW*)w, ldw, w_cf, (TO*)out, ldo, rows, d)
   if (a_dt == TTV_F32 && w_dt == TTV_BF16 && o_dt == TTV_BF16) ES(float, bf16_t, bf16_t);
@@ -1467,6 +1493,8 @@ int ttvk_expand_small(const void* a, int a_dt, int lda, int C, const void* w, in
 int ttvk_reduce_small(const void* a, int a_dt, int lda, const int* a_rows, const void* w, int w_dt, int ldw, int C, float* out, int ldo,
                       int rows, int d, hipStream_t s) {
   if (rows == 0) return TTV_OK;
+  TTV_CHECK_ARG(rows > 0 && C >= 1 && d >= 1 && ldw >= C && ldo >= C && (a_rows || lda >= d) && a && w && out,
+                "reduce_small: %d rows, C %d, d %d, leading dimensions %d %d %d", rows, C, d, lda, ldw, ldo);
   dim3 grid(ttv_cdiv(rows, 4));
 #define RS(TA, TW) hipLaunchKernelGGL((k_reduce_small<TA, TW>), grid, dim3(256), 0, s, (const TA*)a, lda, a_rows, (const TW*)w, ldw, C, out, ldo, rows, d)
   if (a_dt == TTV_BF16 && w_dt == TTV_BF16) RS(bf16_t, bf16_t);

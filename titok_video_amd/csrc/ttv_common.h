@@ -254,9 +254,11 @@ __device__ __forceinline__ void cubic_taps(int dst, int n_in, int n_out, int (&i
   }
 }
 // bf16 path: gelu(g) * x without erff().  Phi(g) = sigmoid(p(g)), p odd of degree 5 (minimax fit, g clamped to +-8 so the
-// negative g^5 coefficient never takes over): max |g*Phi - gelu_erf(g)| = 2.6e-5 over all g - 1/10 of a bf16 half-ulp at
-// 0.06 - and 12 VALU issue slots per element (v_exp_f32 / v_rcp_f32 count 2 each) against 18 for an erf polynomial of
-// the same accuracy; single-lane ops on purpose: v_pk_*_f32 beside MFMAs costs more than the two scalar ops it replaces
+// negative g^5 coefficient never takes over): max |g*Phi - gelu_erf(g)| = 2.6e-5 over every finite bf16 g with |g| <= 2^20
+// (tests/test_tape_ops_cpu.py evaluates all of them) - 1/10 of a bf16 half-ulp at 0.06.  Not over all g: for g < -8 the clamp
+// freezes Phi at 1.01e-12, so g*Phi is -1.01e-12 |g| where gelu is 0, and passes 2.6e-5 beyond |g| = 2.6e7.  The gradient form
+// of k_geglu_bwd_bf16, Phi + g phi: max error 5.04e-5 against gelu' on the same domain.  12 VALU issue slots per element
+// (v_exp_f32 / v_rcp_f32 count 2 each) against 18 for an erf polynomial of the same accuracy; single-lane ops on purpose: v_pk_*_f32 beside MFMAs costs more than the two scalar ops it replaces
 // (measured: the packed form of this epilogue ran 1.4x longer).  The fp32 parity path uses erff().
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float geglu_fast(float g, float x) {

@@ -509,6 +509,7 @@ int ttvk_dec_embed_ex(const void* codes, int C, const void* w, const void* bias,
   if (rows == 0) return TTV_OK;
   TTV_CHECK_ARG(C >= 1 && C <= TTV_MAX_TOKEN, "dec_embed: token_size %d out of range", C);
   TTV_CHECK_ARG(d % 4 == 0 && d <= 1024, "dec_embed: width");
+  TTV_CHECK_ARG((dtype == TTV_BF16 || dtype == TTV_F32) && rows > 0 && d > 0 && ld >= d && ld % 4 == 0, "dec_embed: dtype %d, %d rows, leading dim %d", dtype, rows, ld);
   dim3 grid(ttv_cdiv(rows, ROWS_PER_BLOCK));
   if (dtype == TTV_BF16)
     hipLaunchKernelGGL((k_dec_embed<bf16_t>), grid, dim3(256), 0, s, (const bf16_t*)codes, C, (const bf16_t*)w, (const bf16_t*)bias, mask_token, gain, (bf16_t*)x, ld, rows_map, rows, d, eps, (bf16_t*)hpre);
@@ -777,6 +778,8 @@ int ttvk_rope_apply(void* x, int dtype, int ld, int rows, int heads, const float
 
 int ttvk_rope_apply_dir(void* x, int dtype, int ld, int rows, int heads, const float* cs, int conj, hipStream_t s) {
   if (rows == 0) return TTV_OK;
+  TTV_CHECK_ARG((dtype == TTV_BF16 || dtype == TTV_F32) && rows > 0 && heads >= 1 && ld % 4 == 0 && ld >= heads * 64 && x && cs &&
+                (uintptr_t)x % (dtype == TTV_BF16 ? 8 : 16) == 0, "rope_apply: dtype %d, %d rows, %d heads, leading dim %d, or a null / unaligned buffer", dtype, rows, heads, ld);
   const float sgn = conj ? -1.f : 1.f;
   const long total = (long)rows * heads * 16;
   int blocks = (int)((total + 255) / 256);
@@ -832,6 +835,11 @@ __global__ __launch_bounds__(256) void k_const_rows_bwd(const float* __restrict_
 int ttvk_const_rows_bwd(const float* colsum, const float* mask_token, const float* gain, int dt, float eps, float* dgain, float* dmask,
                         int d, hipStream_t s) {
   if (!dgain && !dmask) return TTV_OK;
+  // the kernel adds into both unconditionally: with exactly one of them NULL it would be launched on a bad address.  Refused here rather
+  // than guarded in the kernel: both tower callers pass both or neither (the two sit in one ttv_tower_grads), so a lone NULL is a caller's
+  // mistake to report, not a mode to serve, and the kernel keeps its two branch-free atomics.
+  TTV_CHECK_ARG(dgain && dmask, "const_rows_bwd: dgain and dmask come together (both or neither NULL)");
+  TTV_CHECK_ARG((dt == TTV_BF16 || dt == TTV_F32) && d >= 1 && colsum && mask_token && gain, "const_rows_bwd: dtype %d, width %d, or a null input", dt, d);
   if (dt == TTV_BF16) hipLaunchKernelGGL((k_const_rows_bwd<bf16_t>), dim3(1), dim3(256), 0, s, colsum, mask_token, gain, eps, dgain, dmask, d);
   else hipLaunchKernelGGL((k_const_rows_bwd<float>), dim3(1), dim3(256), 0, s, colsum, mask_token, gain, eps, dgain, dmask, d);
   TTV_CHECK_LAUNCH("const_rows_bwd");

@@ -448,6 +448,47 @@ int ttv_fsq_backward(const ttv_fsq_params* p, const float* z, const void* dcodes
   return ttvk_fsq_bwd(p, z, dcodes, dcodes_dtype, dz, rows, (hipStream_t)stream);
 }
 
+// The tape's elementwise and small-projection ops one by one (tests): each is the launcher the towers call, argument checks included.
+int ttv_gate_forward(const void* a, int lda, const void* gate, int ldg, void* ag, int ldo, int rows, int width, int dtype, void* stream) {
+  TTV_CHECK_ARG(rows >= 0, "gate_forward: %d rows", rows);
+  return ttvk_gate_fwd(a, lda, gate, ldg, ag, ldo, rows, width, dtype, (hipStream_t)stream);
+}
+int ttv_gate_backward(const void* dag, int lddag, const void* a, int lda, const void* gate, int ldg, void* da, int ldda, void* dgate,
+                      int lddg, int rows, int width, int dtype, float* delta, void* stream) {
+  TTV_CHECK_ARG(rows >= 0, "gate_backward: %d rows", rows);
+  return ttvk_gate_bwd(dag, lddag, a, lda, gate, ldg, da, ldda, dgate, lddg, rows, width, dtype, delta, (hipStream_t)stream);
+}
+int ttv_geglu_forward(const void* u, int ldu, void* h, int ldh, int rows, int inner, int dtype, void* stream) {
+  TTV_CHECK_ARG(rows >= 0, "geglu_forward: %d rows", rows);
+  return ttvk_geglu_fwd(u, ldu, h, ldh, rows, inner, dtype, (hipStream_t)stream);
+}
+int ttv_geglu_backward(const void* u, int ldu, const void* dh, int lddh, void* du, int lddu, int rows, int inner, int dtype, void* stream) {
+  TTV_CHECK_ARG(rows >= 0, "geglu_backward: %d rows", rows);
+  return ttvk_geglu_bwd(u, ldu, dh, lddh, du, lddu, rows, inner, dtype, (hipStream_t)stream);
+}
+int ttv_scale_cast(const float* a, float alpha, float* b, void* c, int dtype, int64_t n, void* stream) {
+  TTV_CHECK_ARG(n >= 0, "scale_cast: %lld elements", (long long)n);
+  return ttvk_scale_cast(a, alpha, b, c, dtype, (long)n, (hipStream_t)stream);
+}
+int ttv_cast_to_f32(const void* a, int dtype, float* b, int64_t n, int accumulate, void* stream) {
+  TTV_CHECK_ARG(n >= 0, "cast_to_f32: %lld elements", (long long)n);
+  return ttvk_to_f32(a, dtype, b, (long)n, accumulate, (hipStream_t)stream);
+}
+int ttv_expand_small(const void* a, int a_dtype, int lda, int C, const void* w, int w_dtype, int ldw, int w_cf, void* out, int out_dtype,
+                     int ldo, int rows, int width, void* stream) {
+  TTV_CHECK_ARG(rows >= 0, "expand_small: %d rows", rows);
+  return ttvk_expand_small(a, a_dtype, lda, C, w, w_dtype, ldw, w_cf, out, out_dtype, ldo, rows, width, (hipStream_t)stream);
+}
+int ttv_reduce_small(const void* a, int a_dtype, int lda, const int32_t* a_rows, const void* w, int w_dtype, int ldw, int C, float* out,
+                     int ldo, int rows, int width, void* stream) {
+  TTV_CHECK_ARG(rows >= 0, "reduce_small: %d rows", rows);
+  return ttvk_reduce_small(a, a_dtype, lda, a_rows, w, w_dtype, ldw, C, out, ldo, rows, width, (hipStream_t)stream);
+}
+int ttv_const_rows_backward(const float* colsum, const float* mask_token, const float* gain, int dtype, float eps, float* dgain,
+                            float* dmask, int width, void* stream) {
+  return ttvk_const_rows_bwd(colsum, mask_token, gain, dtype, eps, dgain, dmask, width, (hipStream_t)stream);
+}
+
 int ttv_encoder_forward_train_ex(const ttv_tower_dims* d, const ttv_tower_weights* w, const ttv_batch* b, const void* const* clips, float* z,
                                  void* tape, int64_t tape_bytes, void* stream, int tape_mode) {
   TTV_TRY(check(d, b, tape_mode));
