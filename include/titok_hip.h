@@ -1044,6 +1044,67 @@ int ttv_video_blend_u8(void* const* tiles, void* const* tiles_dev, const ttv_vid
 int ttv_video_tile_sse_u8(const void* frames_thwc, const ttv_video_plan* plan, int tile_begin, int tile_end, void* const* recon,
                           void* const* recon_dev, int dtype, uint64_t* sse, void* stream);
 
+/* ---- whole videos: Y'CbCr 4:2:0 frames in and out (I420, NV12, NV21; video.py: YUV420Frames) -------------------------------------
+ * The three entry points above with 8-bit 4:2:0 planes in place of packed RGB: what video decoders hand out and encoders take.  A frame
+ * of H x W has a luma plane of H x W and chroma planes of Hc x Wc, Hc = ceil(H / 2), Wc = ceil(W / 2).  Any H, W >= 1, any pointer
+ * alignment, any pitch at or above the minimum.  TTV_ERR_INVALID, nothing launched and nothing written: a null description or plane,
+ * c_step not 1 or 2, an enum out of range, y_pitch < W, c_pitch < c_step * Wc, y_frame < (H - 1) * y_pitch + W,
+ * c_frame < (Hc - 1) * c_pitch + c_step * (Wc - 1) + 1 (a frame's samples end before the next frame's begin).
+ *
+ * Everything is integer arithmetic up to the last two fp32 operations.  Every integer coefficient is round-half-up of the real value.
+ * (Kr, Kb) = (0.299, 0.114) for BT.601 and (0.2126, 0.0722) for BT.709, Kg = 1 - Kr - Kb; limited range: sy = 255/219, sc = 255/224,
+ * ys = 219/255, cs = 224/255, y0 = 16; full range: all four scales 1, y0 = 0.
+ *   to RGB, at 2^-12:    ky = sy 4096; rv = 2 (1 - Kr) sc 4096; bu = 2 (1 - Kb) sc 4096;
+ *                        gu = -round(2 (1 - Kb) Kb / Kg sc 4096); gv = -round(2 (1 - Kr) Kr / Kg sc 4096)
+ *   from RGB, at 2^-16:  ytot = ys 65536; yr = Kr ys 65536; yb = Kb ys 65536; yg = ytot - yr - yb;
+ *                        ub = vr = cs 32768; ur = -round(Kr / (2 (1 - Kb)) cs 65536); ug = -(ur + ub);
+ *                        vb = -round(Kb / (2 (1 - Kr)) cs 65536); vg = -(vr + vb)      (so every grey has chroma exactly 128)
+ * Chroma at a luma position (y, x): row y reads chroma rows j - 1 and j with weights 1 and 3 when y is even, j and j + 1 with weights
+ * 3 and 1 when y is odd, j = y >> 1.  Column x under TTV_YUV_CENTER follows the same rule; under TTV_YUV_LEFT an even x reads column
+ * x >> 1 with weight 4, an odd x columns x >> 1 and (x >> 1) + 1 with weights 2 and 2.  Indices are clamped to the plane.
+ * C16 = sum of row weight * column weight * sample (the weights sum to 16: 0 <= C16 <= 4080).
+ * Source pixel: Yc = 16 ky (Y - y0), u = U16 - 2048, v = V16 - 2048; N_R = Yc + rv v, N_G = Yc + gu u + gv v, N_B = Yc + bu u, each
+ * clamped to [0, 255 * 65536] (below 2^24: exact in fp32; the intermediates fit int32).  Source level of channel c: (N_c + 32768) >> 16. */
+enum { TTV_YUV_BT601 = 0, TTV_YUV_BT709 = 1 };
+enum { TTV_YUV_LIMITED = 0, TTV_YUV_FULL = 1 };
+enum { TTV_YUV_LEFT = 0, TTV_YUV_CENTER = 1 };
+typedef struct ttv_yuv420 {
+  void* y; void* u; void* v;       /* first byte of each plane's first sample; NV12: v = u + 1, NV21: u = v + 1 */
+  int64_t y_frame, c_frame;        /* bytes between frames of the luma / chroma planes */
+  int32_t y_pitch, c_pitch;        /* bytes between rows; y_pitch >= W, c_pitch >= c_step * Wc */
+  int32_t c_step;                  /* bytes between chroma samples of a row: 1 planar, 2 interleaved */
+  int32_t matrix;                  /* TTV_YUV_BT601 | TTV_YUV_BT709 */
+  int32_t range;                   /* TTV_YUV_LIMITED | TTV_YUV_FULL */
+  int32_t siting;                  /* TTV_YUV_LEFT (horizontally co-sited, H.264/HEVC default) | TTV_YUV_CENTER */
+} ttv_yuv420;
+
+/* Gather: ttv_video_tiles_u8 with `frames` (plan->T frames of plan->H x plan->W) in place of frames_thwc: the same plan, tile order,
+ * edge clamping on all three axes, frame stride, destination [n][3][Tt][Ht][Wt], dtypes and refusals.  Element (c, i, y, x) of the tile
+ * with origin (t0, h0, w0) is
+ *   float(N_c) / 8355840.0f - 1.0f      (one correctly rounded division, one subtraction, rounded once to `dtype`)
+ * with N of the pixel (frame_stride * min(t0 + i, T' - 1), min(h0 + y, H - 1), min(w0 + x, W - 1)): the coordinates are clamped
+ * before the chroma rule is applied, so a clamped column repeats the edge pixel's value.  N is not rounded to 8 bits first.
+ * The description is checked even for an empty tile range. */
+int ttv_video_tiles_yuv420(const ttv_yuv420* frames, const ttv_video_plan* plan, int tile_begin, int tile_end, void* tiles, int dtype,
+                           void* stream);
+
+/* Blend: frames [t0, t1) of the timeline into the planes of `frames_out`, whose plane pointers address frame t0.  Per pixel the RGB
+ * levels L_R, L_G, L_B are exactly the bytes ttv_video_blend_u8 defines (the same clamp, weighted mean in ascending tile index,
+ * rounding).  Y = y0 + ((yr L_R + yg L_G + yb L_B + 32768) >> 16).  Chroma sample (j, i): S_c = the sum of L_c over rows 2j, 2j + 1
+ * and, under TTV_YUV_CENTER, columns 2i, 2i + 1 (D = 4); under TTV_YUV_LEFT columns 2i - 1, 2i, 2i + 1 with weights 1, 2, 1 (D = 8);
+ * rows and columns clamped to the picture.  U = 128 + floor((ur S_R + ug S_G + ub S_B + D 32768) / (D 65536)), V likewise with
+ * vr, vg, vb.  Limited range clamps Y to [16, 235] and U, V to [16, 240]; full range clamps all to [0, 255].
+ * One launch, no RGB frame in memory, no atomics: identical calls give identical bits.  Every plane byte of the range inside the
+ * picture is written once; pitch padding and everything else is left alone.  The tables and the refusals are ttv_video_blend_u8's. */
+int ttv_video_blend_yuv420(void* const* tiles, void* const* tiles_dev, const ttv_video_plan* plan, int t0, int t1, int dtype,
+                           const ttv_yuv420* frames_out, void* stream);
+
+/* Measured distortion: ttv_video_tile_sse_u8 with the source level (N_c + 32768) >> 16 of pixel (frame_stride * (t0 + i), h0 + y,
+ * w0 + x) in place of the source byte; level(recon), the samples that count, the exact 64-bit integer (written, not accumulated, the
+ * same bits in every order of summation) and the refusals are as there. */
+int ttv_video_tile_sse_yuv420(const ttv_yuv420* frames, const ttv_video_plan* plan, int tile_begin, int tile_end, void* const* recon,
+                              void* const* recon_dev, int dtype, uint64_t* sse, void* stream);
+
 /* PSNR statistic of the evaluation loop (model/metrics/eval_metrics.py:19,32-36: x.clamp(-1, 1), torchmetrics
  * PeakSignalNoiseRatio(data_range=2) = running sum of squared errors + element count): acc[0] += sum (clamp(recon) - target)^2,
  * acc[1] += number of elements, both double, device memory, over the clips of the call (host arrays of device pointers, `dtype`).

@@ -196,6 +196,15 @@ class VideoPlan(C.Structure):
     _fields_ = [("T", i32), ("H", i32), ("W", i32), ("frame_stride", i32), ("tile", i32 * 3), ("overlap", i32 * 3), ("count", i32 * 3)]
 
 
+class Yuv420(C.Structure):
+    _fields_ = [("y", vp), ("u", vp), ("v", vp), ("y_frame", i64), ("c_frame", i64), ("y_pitch", i32), ("c_pitch", i32), ("c_step", i32),
+                ("matrix", i32), ("range", i32), ("siting", i32)]
+
+
+YUV_MATRIX = {"bt601": 0, "bt709": 1}             # TTV_YUV_BT601, TTV_YUV_BT709
+YUV_RANGE = {"limited": 0, "full": 1}             # TTV_YUV_LIMITED, TTV_YUV_FULL
+YUV_SITING = {"left": 0, "center": 1}             # TTV_YUV_LEFT, TTV_YUV_CENTER
+
 _lib = None
 _lock = threading.Lock()
 
@@ -333,6 +342,9 @@ SYMBOLS = {
     "ttv_video_tiles_u8": (C.c_int, [vp, C.POINTER(VideoPlan), C.c_int, C.c_int, vp, C.c_int, vp]),
     "ttv_video_blend_u8": (C.c_int, [vp, vp, C.POINTER(VideoPlan), C.c_int, C.c_int, C.c_int, vp, vp]),
     "ttv_video_tile_sse_u8": (C.c_int, [vp, C.POINTER(VideoPlan), C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
+    "ttv_video_tiles_yuv420": (C.c_int, [C.POINTER(Yuv420), C.POINTER(VideoPlan), C.c_int, C.c_int, vp, C.c_int, vp]),
+    "ttv_video_blend_yuv420": (C.c_int, [vp, vp, C.POINTER(VideoPlan), C.c_int, C.c_int, C.c_int, C.POINTER(Yuv420), vp]),
+    "ttv_video_tile_sse_yuv420": (C.c_int, [C.POINTER(Yuv420), C.POINTER(VideoPlan), C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
     "ttv_sq_err_accumulate": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "ttv_ssim_workspace_bytes": (C.c_int64, [vp, C.c_int]),
     "ttv_ssim_accumulate": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int64, vp]),

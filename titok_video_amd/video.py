@@ -16,6 +16,12 @@ reconstructed tiles into frames (`ttv_video_blend_u8`), `tile_sse` measures reco
 (`ttv_video_tile_sse_u8`); include/titok_hip.h states all three element by element.  None has a CPU or eager path: host tensors raise.
 The token container (`VideoTokens.to_bytes`) is host-side numpy and the allocator (`allocate_tokens`) plain Python on exact integers:
 token streams and rate tables are tiny.
+
+Decoders hand out Y'CbCr 4:2:0 and encoders take it: `YUV420Frames` wraps such planes (I420, NV12, NV21; pitched decoder surfaces as
+views, no copy) and goes wherever the uint8 RGB frames go - `gather_tiles`, `tile_sse`, `encode_video`, `rate_distortion` - and
+`blend_tiles(out=...)`, `decode_video(output=...)` and `decode_video_iter(output=...)` write planes instead of RGB
+(`ttv_video_tiles_yuv420`, `ttv_video_blend_yuv420`, `ttv_video_tile_sse_yuv420`: the colour conversion is defined on integers in the
+header and fused into the three kernels, there is no RGB frame in between).
 """
 from __future__ import annotations
 
@@ -112,11 +118,137 @@ class TilePlan:
                 f"frame_stride={self.frame_stride}): {self.counts} tiles of {self.tile}")
 
 
+# ---- Y'CbCr 4:2:0 frames -----------------------------------------------------------------------------------------------------------------
+YUV_LAYOUTS = ("i420", "nv12", "nv21")
+
+
+class YUV420Frames:
+    """8-bit Y'CbCr 4:2:0 frames on the GPU, as decoders hand them out: `y` uint8 [T,H,W] and chroma of Hc = ceil(H / 2) by
+    Wc = ceil(W / 2), either planar `u` and `v` [T,Hc,Wc] (I420) or interleaved `uv` [T,Hc,Wc,2] (NV12; `vu` for NV21).  The tensors may
+    be views with row and frame strides - a pitched decoder surface wrapped without a copy - as long as samples of a row are adjacent
+    (innermost stride 1; 2 between the pairs of an interleaved plane) and `u` and `v` share their strides.  `matrix` 'bt601' | 'bt709',
+    `range` 'limited' | 'full', `siting` 'left' (chroma horizontally co-sited with even luma columns, the H.264 / HEVC default) |
+    'center'.  include/titok_hip.h defines every value computed from or into such frames."""
+
+    def __init__(self, y, u=None, v=None, uv=None, matrix: str = "bt709", range: str = "limited", siting: str = "left", vu=None):
+        given = [k for k, t in (("u", u), ("v", v), ("uv", uv), ("vu", vu)) if t is not None]
+        if given not in (["u", "v"], ["uv"], ["vu"]):
+            raise ValueError(f"YUV420Frames: give u and v, or uv, or vu; got {given or 'no chroma'}")
+        for name, table, value in (("matrix", _lib.YUV_MATRIX, matrix), ("range", _lib.YUV_RANGE, range), ("siting", _lib.YUV_SITING, siting)):
+            if value not in table:
+                raise ValueError(f"YUV420Frames: {name} must be one of {sorted(table)}, got {value!r}")
+        if not isinstance(y, torch.Tensor) or y.dtype != torch.uint8 or y.dim() != 3 or min(y.shape) < 1:
+            raise ValueError(f"YUV420Frames: y must be uint8 [T,H,W], got {getattr(y, 'dtype', type(y))} {tuple(getattr(y, 'shape', ()))}")
+        T, H, W = (int(n) for n in y.shape)
+        Hc, Wc = (H + 1) // 2, (W + 1) // 2
+        pair = uv if uv is not None else vu
+        if pair is not None:
+            if not isinstance(pair, torch.Tensor) or pair.dtype != torch.uint8 or tuple(pair.shape) != (T, Hc, Wc, 2):
+                raise ValueError(f"YUV420Frames: interleaved chroma must be uint8 {(T, Hc, Wc, 2)}, got {getattr(pair, 'dtype', type(pair))} "
+                                 f"{tuple(getattr(pair, 'shape', ()))}")
+            if pair.stride(3) != 1 or (Wc > 1 and pair.stride(2) != 2):
+                raise ValueError(f"YUV420Frames: the pairs of interleaved chroma must be adjacent bytes (strides 2, 1), got {pair.stride()[2:]}")
+            first, second = pair[..., 0], pair[..., 1]
+            u, v = (first, second) if uv is not None else (second, first)
+            self.layout, step = ("nv12" if uv is not None else "nv21"), 2
+        else:
+            for name, t in (("u", u), ("v", v)):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or tuple(t.shape) != (T, Hc, Wc):
+                    raise ValueError(f"YUV420Frames: {name} must be uint8 {(T, Hc, Wc)}, got {getattr(t, 'dtype', type(t))} "
+                                     f"{tuple(getattr(t, 'shape', ()))}")
+            if Wc > 1 and (u.stride(2) != 1 or v.stride(2) != 1):
+                raise ValueError(f"YUV420Frames: the samples of a chroma row must be adjacent bytes, got strides {u.stride(2)} and {v.stride(2)}")
+            if (Hc > 1 and u.stride(1) != v.stride(1)) or (T > 1 and u.stride(0) != v.stride(0)):
+                raise ValueError(f"YUV420Frames: u and v must share their row and frame strides, got {u.stride()} and {v.stride()}")
+            self.layout, step = "i420", 1
+        if W > 1 and y.stride(2) != 1:
+            raise ValueError(f"YUV420Frames: the samples of a luma row must be adjacent bytes, got stride {y.stride(2)}")
+        c_row = step * (Wc - 1) + 1
+        self.y_pitch = int(y.stride(1)) if H > 1 else W
+        self.c_pitch = int(u.stride(1)) if Hc > 1 else step * Wc
+        y_min, c_min = (H - 1) * self.y_pitch + W, (Hc - 1) * self.c_pitch + c_row
+        self.y_frame = int(y.stride(0)) if T > 1 else y_min
+        self.c_frame = int(u.stride(0)) if T > 1 else c_min
+        if self.y_pitch < W or self.c_pitch < step * Wc or self.y_frame < y_min or self.c_frame < c_min:
+            raise ValueError(f"YUV420Frames: rows or frames overlap: luma strides {y.stride()} for {(T, H, W)}, chroma strides {u.stride()} "
+                             f"for {(T, Hc, Wc)} at {step} byte(s) per sample")
+        if self.y_pitch >= 1 << 31 or self.c_pitch >= 1 << 31:
+            raise ValueError("YUV420Frames: a row pitch of 2^31 bytes or more")
+        if not (y.device == u.device == v.device):
+            raise ValueError(f"YUV420Frames: planes on different devices: {y.device}, {u.device}, {v.device}")
+        _lib.require_gpu(y, "YUV420Frames")
+        self.y, self.u, self.v, self.c_step = y, u, v, step
+        self.matrix, self.range, self.siting = matrix, range, siting
+        self.shape: Tuple[int, int, int] = (T, H, W)
+        self.device = y.device
+
+    @classmethod
+    def empty(cls, T: int, H: int, W: int, layout: str = "i420", device="cuda", matrix: str = "bt709", range: str = "limited",
+              siting: str = "left") -> "YUV420Frames":
+        """Uninitialised planes for T frames of H x W: 'i420' (planar u, v), 'nv12' (interleaved uv) or 'nv21' (interleaved vu)."""
+        if layout not in YUV_LAYOUTS:
+            raise ValueError(f"YUV420Frames.empty: layout must be one of {YUV_LAYOUTS}, got {layout!r}")
+        T, H, W = int(T), int(H), int(W)
+        if min(T, H, W) < 1:
+            raise ValueError(f"YUV420Frames.empty: {(T, H, W)} must be at least 1 on every axis")
+        Hc, Wc = (H + 1) // 2, (W + 1) // 2
+        y = torch.empty((T, H, W), dtype=torch.uint8, device=device)
+        kw = dict(matrix=matrix, range=range, siting=siting)
+        if layout == "i420":
+            return cls(y, u=torch.empty((T, Hc, Wc), dtype=torch.uint8, device=device), v=torch.empty((T, Hc, Wc), dtype=torch.uint8, device=device), **kw)
+        pair = torch.empty((T, Hc, Wc, 2), dtype=torch.uint8, device=device)
+        return cls(y, uv=pair, **kw) if layout == "nv12" else cls(y, vu=pair, **kw)
+
+    def frames(self, t0: int, t1: int) -> "YUV420Frames":
+        """Frames [t0, t1) as views of the same planes."""
+        if not 0 <= t0 < t1 <= self.shape[0]:
+            raise ValueError(f"frames [{t0}, {t1}) of {self.shape[0]}")
+        out = object.__new__(YUV420Frames)
+        out.__dict__.update(self.__dict__)
+        out.y, out.u, out.v = self.y[t0:t1], self.u[t0:t1], self.v[t0:t1]
+        out.shape = (t1 - t0,) + self.shape[1:]
+        return out
+
+    def like(self, T: int) -> "YUV420Frames":
+        """New planes for T frames of this picture size, layout and colour description."""
+        return YUV420Frames.empty(T, self.shape[1], self.shape[2], self.layout, self.device, self.matrix, self.range, self.siting)
+
+    def c_frames(self) -> "_lib.Yuv420":
+        return _lib.Yuv420(y=self.y.data_ptr(), u=self.u.data_ptr(), v=self.v.data_ptr(), y_frame=self.y_frame, c_frame=self.c_frame,
+                           y_pitch=self.y_pitch, c_pitch=self.c_pitch, c_step=self.c_step, matrix=_lib.YUV_MATRIX[self.matrix],
+                           range=_lib.YUV_RANGE[self.range], siting=_lib.YUV_SITING[self.siting])
+
+    def __repr__(self):
+        return f"YUV420Frames({self.shape}, {self.layout}, {self.matrix}, {self.range}, {self.siting})"
+
+
+def _frames_shape(frames, what: str) -> Tuple[int, int, int]:
+    """(T, H, W) of uint8 [T,H,W,3] frames or of a `YUV420Frames`, which is on the GPU."""
+    if isinstance(frames, YUV420Frames):
+        return frames.shape
+    _lib.require_gpu(frames, what)
+    if frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError(f"frames must be uint8 [T,H,W,3] or YUV420Frames, got {tuple(frames.shape)}")
+    return tuple(frames.shape[:3])
+
+
 # ---- the three kernels ----------------------------------------------------------------------------------------------------------------
 def gather_tiles(frames_u8: torch.Tensor, plan: TilePlan, begin: int = 0, end: Optional[int] = None,
                  dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
     """Tiles [begin, end) of `plan` cut from decoded frames uint8 [T,H,W,3] on the GPU: one buffer [end - begin, 3, Tt, Ht, Wt] in
-    `dtype`, values u8 / 127.5 - 1 (the loader's bits).  One launch on the current stream."""
+    `dtype`, values u8 / 127.5 - 1 (the loader's bits).  One launch on the current stream.  `frames_u8` may be a `YUV420Frames`: the
+    values are then the header's N / 8355840 - 1 of the converted pixels, not rounded to 8 bits on the way (`ttv_video_tiles_yuv420`)."""
+    if isinstance(frames_u8, YUV420Frames):
+        if frames_u8.shape != plan.video:
+            raise ValueError(f"frames must be YUV420Frames of {plan.video}, got {frames_u8.shape}")
+        end = plan.n_tiles if end is None else int(end)
+        if not 0 <= begin <= end <= plan.n_tiles:
+            raise ValueError(f"tiles [{begin}, {end}) of {plan.n_tiles}")
+        out = torch.empty((end - begin, 3) + plan.tile, dtype=dtype, device=frames_u8.device)
+        cp, cf = plan.c_plan(), frames_u8.c_frames()
+        _lib.check(_lib.lib().ttv_video_tiles_yuv420(C.byref(cf), C.byref(cp), int(begin), end, out.data_ptr(), _lib.dtype_code(dtype),
+                                                     _lib.stream_ptr(frames_u8.device)), "ttv_video_tiles_yuv420")
+        return out
     _lib.require_gpu(frames_u8, "gather_tiles")
     if frames_u8.dtype != torch.uint8 or tuple(frames_u8.shape) != plan.video + (3,) or not frames_u8.is_contiguous():
         raise ValueError(f"frames must be contiguous uint8 {plan.video + (3,)}, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
@@ -130,10 +262,12 @@ def gather_tiles(frames_u8: torch.Tensor, plan: TilePlan, begin: int = 0, end: O
     return out
 
 
-def blend_tiles(tiles: Sequence[Optional[torch.Tensor]], plan: TilePlan, t0: int = 0, t1: Optional[int] = None) -> torch.Tensor:
+def blend_tiles(tiles: Sequence[Optional[torch.Tensor]], plan: TilePlan, t0: int = 0, t1: Optional[int] = None, out=None):
     """Frames [t0, t1) of the timeline, uint8 [t1 - t0, H, W, 3] on the GPU, from reconstructed tiles [3,Tt,Ht,Wt] in tile order; an
     entry may be None when its tile holds no frame of the range.  Overlaps are the weighted mean the header defines; bit-reproducible.
-    One launch on the current stream."""
+    One launch on the current stream.  `out`: None for RGB; 'i420' | 'nv12' | 'nv21' for new `YUV420Frames` (BT.709, limited range,
+    left-sited); or a `YUV420Frames` of (t1 - t0, H, W) whose planes are written and which is returned (`ttv_video_blend_yuv420`: the
+    same blended levels, converted in the same launch)."""
     t1 = plan.timeline[0] if t1 is None else int(t1)
     if len(tiles) != plan.n_tiles:
         raise ValueError(f"{len(tiles)} tiles for a plan of {plan.n_tiles}")
@@ -148,8 +282,19 @@ def blend_tiles(tiles: Sequence[Optional[torch.Tensor]], plan: TilePlan, t0: int
     ptrs = [0 if t is None else t.data_ptr() for t in tiles]
     host = (_lib.vp * len(ptrs))(*ptrs)
     table = torch.tensor(ptrs, dtype=torch.int64).to(device)
-    out = torch.empty((max(t1 - t0, 0),) + plan.timeline[1:] + (3,), dtype=torch.uint8, device=device)
     cp = plan.c_plan()
+    if out is not None:
+        if isinstance(out, str):
+            if t1 <= t0:
+                raise ValueError(f"blend_tiles: no frame in [{t0}, {t1}) to make {out} planes for")
+            out = YUV420Frames.empty(t1 - t0, plan.timeline[1], plan.timeline[2], out, device)
+        if not isinstance(out, YUV420Frames) or out.shape != (t1 - t0,) + plan.timeline[1:] or out.device != device:
+            raise ValueError(f"out must be a layout name or YUV420Frames of {(t1 - t0,) + plan.timeline[1:]} on {device}, got {out!r}")
+        cf = out.c_frames()
+        _lib.check(_lib.lib().ttv_video_blend_yuv420(host, table.data_ptr(), C.byref(cp), int(t0), t1, _lib.dtype_code(dtype), C.byref(cf),
+                                                     _lib.stream_ptr(device)), "ttv_video_blend_yuv420")
+        return out
+    out = torch.empty((max(t1 - t0, 0),) + plan.timeline[1:] + (3,), dtype=torch.uint8, device=device)
     _lib.check(_lib.lib().ttv_video_blend_u8(host, table.data_ptr(), C.byref(cp), int(t0), t1, _lib.dtype_code(dtype), out.data_ptr(),
                                              _lib.stream_ptr(device)), "ttv_video_blend_u8")
     return out
@@ -160,10 +305,15 @@ def tile_sse(frames_u8: torch.Tensor, plan: TilePlan, recon_tiles: Sequence[torc
     """Per tile of [begin, end) the sum of squared level differences between its reconstruction `recon_tiles[k - begin]`
     ([3,Tt,Ht,Wt], what the model returns for the tile `gather_tiles` cut) and the source pixels of `frames_u8`: int64 [end - begin] on
     the GPU, exact integers (`ttv_video_tile_sse_u8`; the header defines the level of an element and which samples count).  One launch
-    on the current stream."""
-    _lib.require_gpu(frames_u8, "tile_sse")
-    if frames_u8.dtype != torch.uint8 or tuple(frames_u8.shape) != plan.video + (3,) or not frames_u8.is_contiguous():
-        raise ValueError(f"frames must be contiguous uint8 {plan.video + (3,)}, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+    on the current stream.  With `YUV420Frames` the source level is the header's (N + 32768) >> 16 (`ttv_video_tile_sse_yuv420`)."""
+    yuv = isinstance(frames_u8, YUV420Frames)
+    if yuv:
+        if frames_u8.shape != plan.video:
+            raise ValueError(f"frames must be YUV420Frames of {plan.video}, got {frames_u8.shape}")
+    else:
+        _lib.require_gpu(frames_u8, "tile_sse")
+        if frames_u8.dtype != torch.uint8 or tuple(frames_u8.shape) != plan.video + (3,) or not frames_u8.is_contiguous():
+            raise ValueError(f"frames must be contiguous uint8 {plan.video + (3,)}, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
     end = plan.n_tiles if end is None else int(end)
     if not 0 <= begin <= end <= plan.n_tiles:
         raise ValueError(f"tiles [{begin}, {end}) of {plan.n_tiles}")
@@ -185,6 +335,11 @@ def tile_sse(frames_u8: torch.Tensor, plan: TilePlan, recon_tiles: Sequence[torc
     # before it - the forward that made these tiles - and the next batch of the pipeline could not be queued meanwhile
     table = torch.tensor(ptrs, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
     cp = plan.c_plan()
+    if yuv:
+        cf = frames_u8.c_frames()
+        _lib.check(_lib.lib().ttv_video_tile_sse_yuv420(C.byref(cf), C.byref(cp), int(begin), end, host, table.data_ptr(),
+                                                        _lib.dtype_code(dtype), out.data_ptr(), _lib.stream_ptr(device)), "ttv_video_tile_sse_yuv420")
+        return out
     _lib.check(_lib.lib().ttv_video_tile_sse_u8(frames_u8.data_ptr(), C.byref(cp), int(begin), end, host, table.data_ptr(),
                                                 _lib.dtype_code(dtype), out.data_ptr(), _lib.stream_ptr(device)), "ttv_video_tile_sse_u8")
     return out
@@ -462,16 +617,14 @@ class VideoTokenizer:
         recon, info = self.model(clips, [count] * (b - a))
         return tile_sse(frames_u8, plan, recon, a, b), info["indices"].to(torch.int32)
 
-    def rate_distortion(self, frames_u8: torch.Tensor, ladder: Sequence[int], frame_stride: int = 1) -> RateTable:
+    def rate_distortion(self, frames_u8, ladder: Sequence[int], frame_stride: int = 1) -> RateTable:
         """What every tile costs at every count of `ladder`.  Per count, all tiles are coded at that count, in tile order, in the
         batches the token budget gives; a batch is gathered, run through the model and measured against the same frames (`tile_sse`)
         on one stream - a side stream of the pipeline when `depth` > 1 - and only its sums and indices are kept: memory is that of
         `depth` batches, whatever the video's length.  The table describes these reconstructions, batch for batch."""
-        _lib.require_gpu(frames_u8, "rate_distortion")
-        if frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
-            raise ValueError(f"frames must be uint8 [T,H,W,3], got {tuple(frames_u8.shape)}")
+        video = _frames_shape(frames_u8, "rate_distortion")
         ladder = _check_ladder(ladder)
-        plan = TilePlan(tuple(frames_u8.shape[:3]), self.tile, self.overlap, self.patch, frame_stride)
+        plan = TilePlan(video, self.tile, self.overlap, self.patch, frame_stride)
         n = plan.n_tiles
         if self.depth > 1 and self._probe_pipe is None:
             from .pipeline import ForwardPipeline
@@ -494,9 +647,9 @@ class VideoTokenizer:
         return RateTable(ladder, sse, [plan.tile_elements(j) for j in range(n)],
                          [[level[j] for level in indices] for j in range(n)])
 
-    def encode_video(self, frames_u8: torch.Tensor, fps: Optional[float] = None, frame_stride: int = 1, ladder: Optional[Sequence[int]] = None,
+    def encode_video(self, frames_u8, fps: Optional[float] = None, frame_stride: int = 1, ladder: Optional[Sequence[int]] = None,
                      target_psnr: Optional[float] = None, total_tokens: Optional[int] = None) -> VideoTokens:
-        """Decoded frames uint8 [T,H,W,3] on the GPU -> tokens of every `frame_stride`-th frame.  Tiles are gathered in tile order into
+        """Decoded frames uint8 [T,H,W,3] on the GPU, or `YUV420Frames`, -> tokens of every `frame_stride`-th frame.  Tiles are gathered in tile order into
         batches under the token budget and encoded; equal tile shapes mean one cached batch plan per batch size.
 
         With `target_psnr` (dB per tile, levels 0 .. 255) or `total_tokens` (a budget for the whole video) the count of every tile is
@@ -504,10 +657,7 @@ class VideoTokenizer:
         `allocate_tokens`.  The tokens are the probe's own indices at the chosen count of each tile - there is no second encoding
         pass - and `counts` is the allocation.  The table describes the probe's reconstructions, batch for batch: a tile decoded later
         in another batch goes through the same arithmetic on its own rows, but nothing here decodes it again to check."""
-        _lib.require_gpu(frames_u8, "encode_video")
-        if frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
-            raise ValueError(f"frames must be uint8 [T,H,W,3], got {tuple(frames_u8.shape)}")
-        plan = TilePlan(tuple(frames_u8.shape[:3]), self.tile, self.overlap, self.patch, frame_stride)
+        plan = TilePlan(_frames_shape(frames_u8, "encode_video"), self.tile, self.overlap, self.patch, frame_stride)
         if target_psnr is not None or total_tokens is not None:
             if ladder is None:
                 if not isinstance(self.tokens_per_tile, int):
@@ -563,11 +713,17 @@ class VideoTokenizer:
             out += self.model.decode_indices(indices[offsets[a]:offsets[b]], [plan.tile] * (b - a), tok.counts[a:b])
         return out
 
-    def decode_video_iter(self, tok: VideoTokens) -> Iterator[Tuple[int, torch.Tensor]]:
-        """(t0, frames uint8 [n,H,W,3] on the GPU) in timeline order, gap-free.  The temporal tile layers are decoded in order; a frame
+    def decode_video_iter(self, tok: VideoTokens, output=None) -> Iterator[Tuple[int, torch.Tensor]]:
+        """(t0, frames uint8 [n,H,W,3] on the GPU) in timeline order, gap-free.  `output`: None for RGB; 'i420' | 'nv12' | 'nv21' for
+        new `YUV420Frames` per range (BT.709, limited range, left-sited); or a `YUV420Frames` of the whole timeline, whose planes are
+        written and of which each range is yielded as a view.  The temporal tile layers are decoded in order; a frame
         range is blended and yielded as soon as every tile that holds it is decoded, and the reconstructions of layers that hold no
         unfinished frame are dropped: memory is that of a few layers, whatever the video's length."""
         plan = self._check_tokens(tok)
+        if output is not None and not isinstance(output, YUV420Frames) and output not in YUV_LAYOUTS:
+            raise ValueError(f"output must be None, one of {YUV_LAYOUTS} or YUV420Frames, got {output!r}")
+        if isinstance(output, YUV420Frames) and output.shape != plan.timeline:
+            raise ValueError(f"output must hold the timeline {plan.timeline}, got {output.shape}")
         indices = tok.indices.to(self.device)
         offsets = [0]
         for k in tok.counts:
@@ -579,12 +735,23 @@ class VideoTokenizer:
             live[kt * per_layer:(kt + 1) * per_layer] = self._decode_layer(plan, tok, indices, offsets, kt)
             upto = starts[kt + 1] if kt + 1 < plan.counts[0] else n_frames         # the next layer starts here: frames below are complete
             if upto > done:
-                yield done, blend_tiles(live, plan, done, upto)
+                yield done, blend_tiles(live, plan, done, upto, output.frames(done, upto) if isinstance(output, YUV420Frames) else output)
                 done = upto
             while first_live <= kt and starts[first_live] + plan.tile[0] <= done:  # every frame of the layer is out
                 live[first_live * per_layer:(first_live + 1) * per_layer] = [None] * per_layer
                 first_live += 1
 
-    def decode_video(self, tok: VideoTokens) -> torch.Tensor:
-        """uint8 [T',H,W,3] on the GPU: the ranges of `decode_video_iter`, concatenated."""
-        return torch.cat([part for _, part in self.decode_video_iter(tok)], dim=0)
+    def decode_video(self, tok: VideoTokens, output=None):
+        """uint8 [T',H,W,3] on the GPU: the ranges of `decode_video_iter`, concatenated.  With `output` (a layout name or a
+        `YUV420Frames` of the timeline, as for `decode_video_iter`) the ranges are blended into the planes of one `YUV420Frames`, which
+        is returned."""
+        if output is None:
+            return torch.cat([part for _, part in self.decode_video_iter(tok)], dim=0)
+        if not isinstance(output, YUV420Frames):
+            if output not in YUV_LAYOUTS:
+                raise ValueError(f"output must be None, one of {YUV_LAYOUTS} or YUV420Frames, got {output!r}")
+            t, h, w = tok.plan().timeline
+            output = YUV420Frames.empty(t, h, w, output, self.device)
+        for _ in self.decode_video_iter(tok, output):
+            pass
+        return output

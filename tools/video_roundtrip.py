@@ -9,7 +9,11 @@ seeded tiny / tiny tokenizer in bf16, 128 tokens per tile.
   the yardstick   a device-to-device copy_ that moves the same byte count (half read, half written), in the same run, same rotation;
   the round trip  encode_video + decode_video, host clock around work that ends in a synchronise, and the two kernels' share of it.
 
-Reported, not gated.  GPU box only; writes what it prints to the file given as the first argument, if any."""
+With --yuv as the first argument: the three Y'CbCr 4:2:0 entry points (ttv_video_tiles_yuv420, ttv_video_blend_yuv420,
+ttv_video_tile_sse_yuv420; NV12, BT.709 limited range, left-sited and centred chroma) beside their three RGB siblings and a copy_ of the
+YUV kernel's byte count, all in the same run, from HBM and cache-warm (profiles/video_yuv.txt).
+
+Reported, not gated.  GPU box only; writes what it prints to the file given as the first argument (after --yuv), if any."""
 import ctypes as C
 import os
 import sys
@@ -141,7 +145,92 @@ def bench_round_trip(gather_us, blend_us):
             f"(one launch each, cache-warm) are {100 * (gather_us + blend_us) / total:.2f} % of it")
 
 
+def bench_yuv(dtype):
+    """gather, blend and tile_sse: YUV (both sitings) and RGB, and a copy_ of the YUV kernel's byte count, same run and rotation."""
+    plan = V.TilePlan(VIDEO, TILE, OVERLAP, PATCH)
+    esz = torch.empty(0, dtype=dtype).element_size()
+    tile_px = plan.n_tiles * plan.tile[0] * plan.tile[1] * plan.tile[2]
+    video_px = VIDEO[0] * VIDEO[1] * VIDEO[2]
+    lib, stream, code, cp = _lib.lib(), _lib.stream_ptr(torch.device(DEV)), _lib.dtype_code(dtype), plan.c_plan()
+    name = "bf16" if dtype == torch.bfloat16 else "fp32"
+    sets = max(2, -(-(2 * 256 * 2 ** 20) // (video_px * 3 // 2 + tile_px * 3 * esz)))
+    say(f"{plan!r}: {plan.n_tiles} tiles, cover ratio {tile_px / video_px:.2f}, {name}, {sets} working sets")
+
+    def yuv_frames(siting, _fill):
+        y = torch.randint(0, 256, VIDEO, dtype=torch.uint8, device=DEV)
+        uv = torch.randint(0, 256, (VIDEO[0], VIDEO[1] // 2, VIDEO[2] // 2, 2), dtype=torch.uint8, device=DEV)
+        return V.YUV420Frames(y, uv=uv, siting=siting)
+
+    def tiles_and_table():
+        tiles = (torch.rand((plan.n_tiles, 3) + plan.tile, device=DEV) * 2.4 - 1.2).to(dtype)
+        ptrs = [t.data_ptr() for t in tiles.unbind(0)]
+        return tiles, (C.c_void_p * len(ptrs))(*ptrs), torch.tensor(ptrs, dtype=torch.int64).to(DEV)
+
+    def gather(siting):
+        def make(_k):
+            out = torch.empty((plan.n_tiles, 3) + plan.tile, dtype=dtype, device=DEV)
+            if siting is None:
+                frames = torch.randint(0, 256, VIDEO + (3,), dtype=torch.uint8, device=DEV)
+                return lambda: _lib.check(lib.ttv_video_tiles_u8(frames.data_ptr(), C.byref(cp), 0, plan.n_tiles, out.data_ptr(), code, stream), "tiles")
+            f = yuv_frames(siting, True)
+            cf = f.c_frames()
+            return lambda: (f, _lib.check(lib.ttv_video_tiles_yuv420(C.byref(cf), C.byref(cp), 0, plan.n_tiles, out.data_ptr(), code, stream), "tiles_yuv"))
+        return make
+
+    def blend(siting):
+        def make(_k):
+            tiles, host, table = tiles_and_table()
+            if siting is None:
+                out = torch.empty(VIDEO + (3,), dtype=torch.uint8, device=DEV)
+                return lambda: (tiles, _lib.check(lib.ttv_video_blend_u8(host, table.data_ptr(), C.byref(cp), 0, VIDEO[0], code, out.data_ptr(), stream), "blend"))
+            f = yuv_frames(siting, False)
+            cf = f.c_frames()
+            return lambda: (tiles, f, _lib.check(lib.ttv_video_blend_yuv420(host, table.data_ptr(), C.byref(cp), 0, VIDEO[0], code, C.byref(cf), stream), "blend_yuv"))
+        return make
+
+    def sse(siting):
+        def make(_k):
+            tiles, host, table = tiles_and_table()
+            out = torch.empty((plan.n_tiles,), dtype=torch.int64, device=DEV)
+            if siting is None:
+                frames = torch.randint(0, 256, VIDEO + (3,), dtype=torch.uint8, device=DEV)
+                return lambda: (tiles, _lib.check(lib.ttv_video_tile_sse_u8(frames.data_ptr(), C.byref(cp), 0, plan.n_tiles, host, table.data_ptr(), code,
+                                                                            out.data_ptr(), stream), "sse"))
+            f = yuv_frames(siting, True)
+            cf = f.c_frames()
+            return lambda: (tiles, f, _lib.check(lib.ttv_video_tile_sse_yuv420(C.byref(cf), C.byref(cp), 0, plan.n_tiles, host, table.data_ptr(), code,
+                                                                               out.data_ptr(), stream), "sse_yuv"))
+        return make
+
+    tile_bytes = tile_px * 3 * esz
+    for what, maker, yuv_bytes, rgb_bytes in (("gather", gather, tile_px * 3 // 2 + tile_bytes, tile_px * 3 + tile_bytes),
+                                              ("blend", blend, tile_bytes + video_px * 3 // 2, tile_bytes + video_px * 3),
+                                              ("tile_sse", sse, tile_px * 3 // 2 + tile_bytes, tile_px * 3 + tile_bytes)):
+        rows = []
+        for label, siting, nbytes in (("yuv420 left", "left", yuv_bytes), ("yuv420 center", "center", yuv_bytes), ("rgb", None, rgb_bytes)):
+            fn = rotating(maker(siting), sets)
+            rows.append((label, nbytes, events(lambda: fn(True)), events(lambda: fn(False))))
+            del fn
+            torch.cuda.empty_cache()
+        c_hbm, c_warm = copy_yardstick(yuv_bytes, sets)
+        for label, nbytes, hbm, warm in rows:
+            say(f"  {what:8s} {label:13s} {nbytes / 1e6:7.1f} MB asked for: {hbm:7.1f} us = {nbytes / hbm / 1e3:6.0f} GB/s from HBM, {warm:7.1f} us = "
+                f"{nbytes / warm / 1e3:6.0f} GB/s cache-warm")
+        say(f"  {what:8s} {'copy_':13s} {yuv_bytes / 1e6:7.1f} MB moved:     {c_hbm:7.1f} us = {yuv_bytes / c_hbm / 1e3:6.0f} GB/s from HBM, {c_warm:7.1f} us = "
+            f"{yuv_bytes / c_warm / 1e3:6.0f} GB/s cache-warm")
+        torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--yuv":
+        say(f"device: {torch.cuda.get_device_name(0)}; kernel times by HIP events over {ITERS} launches after {WARMUP}")
+        bench_yuv(torch.float32)
+        bench_yuv(torch.bfloat16)
+        if len(sys.argv) > 2:
+            os.makedirs(os.path.dirname(os.path.abspath(sys.argv[2])), exist_ok=True)
+            with open(sys.argv[2], "w") as f:
+                f.write("\n".join(LINES) + "\n")
+        sys.exit(0)
     say(f"device: {torch.cuda.get_device_name(0)}; kernel times by HIP events over {ITERS} launches after {WARMUP}; round trips over {TRIPS} after 2")
     bench_kernels(torch.float32)
     g, b = bench_kernels(torch.bfloat16)
