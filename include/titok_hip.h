@@ -1105,6 +1105,49 @@ int ttv_video_blend_yuv420(void* const* tiles, void* const* tiles_dev, const ttv
 int ttv_video_tile_sse_yuv420(const ttv_yuv420* frames, const ttv_video_plan* plan, int tile_begin, int tile_end, void* const* recon,
                               void* const* recon_dev, int dtype, uint64_t* sse, void* stream);
 
+/* ---- whole videos: per-frame quality of what comes back (video.py: frame_sse, frame_ssim, VideoQuality) ---------------------------------
+ * `a` holds the n pictures under test, frame j at index j; `b` is the yardstick: frame j of `a` is compared with frame j * b_stride of
+ * `b`, b_stride >= 1.  Both pointers (plane descriptions) address the first compared frame, and the caller guarantees that `b` holds
+ * (n - 1) * b_stride + 1 frames.
+ *   RGB:   a_thwc, b_thwc uint8 [.][H][W][3], any alignment.  Components 0, 1, 2 = R, G, B, each of H x W samples.
+ *   4:2:0: two ttv_yuv420; layouts, pitches and frame strides may differ between `a` and `b`.  Components 0, 1, 2 = Y (H x W), U, V
+ *          (Hc x Wc, Hc = ceil(H / 2), Wc = ceil(W / 2)); the planes are compared sample by sample.  matrix, range and siting are not
+ *          read (video.py refuses a mismatch).
+ * Pitch padding and the bytes between the samples of an interleaved chroma plane never count.
+ * TTV_ERR_INVALID with nothing launched and nothing written, for all four entry points: a null pointer or description, n < 0,
+ * b_stride < 1, H or W below the minimum, a ttv_yuv420 that fails the checks above for the frames its side holds (a null plane, c_step,
+ * pitches, frame strides), an output off the 8-byte grid, a workspace that is too small or off the 8-byte grid.  n == 0 passes the
+ * same checks and does nothing.  Work is enqueued on `stream` only.
+ *
+ * Squared error.  sse: device memory, uint64 [n][3], 8-byte aligned.
+ *   sse[j][c] = sum over the samples (y, x) of component c of (a_j[c][y][x] - b_{j * b_stride}[c][y][x])^2
+ * written, not accumulated: the entry point clears the sums on `stream`, a block's partial sum stays below 2^32 and is added with one
+ * 64-bit atomic per block and component.  An exact integer, so the same bits in any order of summation, with or without the
+ * deterministic mode.  Any H, W >= 1.  RGB: a thread takes 12 bytes (4 pixels) of a frame from the 4 aligned words that hold them on
+ * each side; 4:2:0: 8 samples of a plane row from 3 aligned words (5 for interleaved chroma).  The ends of the arrays (words that
+ * would leave them), the last, shorter group of a frame or a row go byte by byte; rows off the word grid are shifted into place.
+ * Nothing but sse[0 .. n)[0 .. 3) is written. */
+int ttv_video_frame_sse_u8(const void* a_thwc, const void* b_thwc, int n, int b_stride, int H, int W, uint64_t* sse, void* stream);
+int ttv_video_frame_sse_yuv420(const ttv_yuv420* a, const ttv_yuv420* b, int n, int b_stride, int H, int W, uint64_t* sse, void* stream);
+
+/* SSIM.  ssim: device memory, double [n][3], 8-byte aligned, written.  For component c of h x w samples,
+ *   ssim[j][c] = mean over the (h - 10)(w - 10) windows wholly inside the plane of
+ *                ((2 mx my + C1)(2 sxy + C2)) / ((mx^2 + my^2 + C1)(sx^2 + sy^2 + C2))
+ * on the levels 0 .. 255: C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2; window = the 11-tap Gaussian, sigma 1.5, normalised to sum 1, in
+ * both directions; mx, my the windowed means of a and b, sx^2 = max(E[x^2] - mx^2, 0), sy^2 likewise, sxy = E[xy] - mx my.  This is
+ * torchmetrics' StructuralSimilarityIndexMeasure(data_range=255) per plane, restricted to the windows its reflect-pad and crop keeps
+ * (the rule of ttv_ssim_accumulate below).  Every compared plane needs h, w >= 11: H, W >= 11 for RGB, H, W >= 21 for 4:2:0.
+ * fp32 arithmetic after subtracting one sample of the block's tile from each plane (exact for integer levels; E[x^2] - mx^2 then
+ * cancels on the local spread, not on the value).  One double per 32 x 32 tile of a plane's valid region goes into the caller-owned
+ * workspace (ttv_video_frame_ssim_workspace_bytes(n, H, W, yuv420) bytes - yuv420 != 0 for the 4:2:0 entry point -, 8-byte aligned;
+ * -1 with the error set for n < 0 or H, W below the minimum), and a second launch adds each plane's tiles in tile order: no
+ * floating-point atomics, identical calls give identical bits. */
+int64_t ttv_video_frame_ssim_workspace_bytes(int n, int H, int W, int yuv420);
+int ttv_video_frame_ssim_u8(const void* a_thwc, const void* b_thwc, int n, int b_stride, int H, int W, double* ssim, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+int ttv_video_frame_ssim_yuv420(const ttv_yuv420* a, const ttv_yuv420* b, int n, int b_stride, int H, int W, double* ssim, void* workspace,
+                                int64_t workspace_bytes, void* stream);
+
 /* PSNR statistic of the evaluation loop (model/metrics/eval_metrics.py:19,32-36: x.clamp(-1, 1), torchmetrics
  * PeakSignalNoiseRatio(data_range=2) = running sum of squared errors + element count): acc[0] += sum (clamp(recon) - target)^2,
  * acc[1] += number of elements, both double, device memory, over the clips of the call (host arrays of device pointers, `dtype`).

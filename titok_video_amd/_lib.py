@@ -345,6 +345,12 @@ SYMBOLS = {
     "ttv_video_tiles_yuv420": (C.c_int, [C.POINTER(Yuv420), C.POINTER(VideoPlan), C.c_int, C.c_int, vp, C.c_int, vp]),
     "ttv_video_blend_yuv420": (C.c_int, [vp, vp, C.POINTER(VideoPlan), C.c_int, C.c_int, C.c_int, C.POINTER(Yuv420), vp]),
     "ttv_video_tile_sse_yuv420": (C.c_int, [C.POINTER(Yuv420), C.POINTER(VideoPlan), C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
+    "ttv_video_frame_sse_u8": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "ttv_video_frame_sse_yuv420": (C.c_int, [C.POINTER(Yuv420), C.POINTER(Yuv420), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "ttv_video_frame_ssim_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ttv_video_frame_ssim_u8": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int64, vp]),
+    "ttv_video_frame_ssim_yuv420": (C.c_int, [C.POINTER(Yuv420), C.POINTER(Yuv420), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int64,
+                                              vp]),
     "ttv_sq_err_accumulate": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "ttv_ssim_workspace_bytes": (C.c_int64, [vp, C.c_int]),
     "ttv_ssim_accumulate": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int64, vp]),

@@ -12,7 +12,7 @@ export FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=on -fno-s
 # host-only C++ (no HIP call, no kernel): the float64 rotary table must round as written, so no contraction
 HOST_FLAGS="-O2 -std=c++17 -fPIC -ffp-contract=off -Wall"
 # every object of the library, named once: compiled by the two loops, linked in this order
-HIP_SRCS="ttv_elem ttv_gemm ttv_patch_embed ttv_attn ttv_attn_swp ttv_attn64 ttv_attn_pv8 ttv_mlp ttv_bwd ttv_train ttv_optim ttv_vq ttv_vq_train ttv_metrics ttv_lpips ttv_i3d ttv_inception ttv_vjepa ttv_resample ttv_crops ttv_disc ttv_panels ttv_video ttv_plan ttv_api"
+HIP_SRCS="ttv_elem ttv_gemm ttv_patch_embed ttv_attn ttv_attn_swp ttv_attn64 ttv_attn_pv8 ttv_mlp ttv_bwd ttv_train ttv_optim ttv_vq ttv_vq_train ttv_metrics ttv_lpips ttv_i3d ttv_inception ttv_vjepa ttv_resample ttv_crops ttv_disc ttv_panels ttv_video ttv_video_quality ttv_plan ttv_api"
 HOST_SRCS="ttv_plan_host"
 VARIANT=; UNITS=
 if [ "$1" = --variant ]; then

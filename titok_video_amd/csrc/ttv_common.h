@@ -112,6 +112,29 @@ __device__ __forceinline__ float wave_sum(float v) {
   v += wave_xor_dpp1(v);
   return v;
 }
+// Sum over the 64 lanes, in every lane: the exchanges of wave_sum on integers (the exact sums of ttv_video.hip and
+// ttv_video_quality.hip).
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+  {
+    const auto b = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+    const unsigned b0 = b[0], b1 = b[1];
+    v = b0 + b1;
+  }
+  {
+    const auto a = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+    const unsigned a0 = a[0], a1 = a[1];
+    v = a0 + a1;
+  }
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, true);       // row_ror:8
+  {
+    int r = __builtin_amdgcn_update_dpp(0, (int)v, 0x12C, 0xF, 0x5, false);           // xor 4: see wave_xor_dpp4
+    r = __builtin_amdgcn_update_dpp(r, (int)v, 0x124, 0xF, 0xA, false);
+    v += (uint32_t)r;
+  }
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);        // quad_perm [2,3,0,1]
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);        // quad_perm [1,0,3,2]
+  return v;
+}
 __device__ __forceinline__ float wave_max(float v) {
   {
     const unsigned u = __float_as_uint(v);

@@ -332,28 +332,6 @@ __device__ __forceinline__ float add_sq_diff(float acc, float recon, uint32_t le
   return __fmaf_rn(d, d, acc);
 }
 
-// Sum over the 64 lanes, in every lane: the exchanges of wave_sum (ttv_common.h) on integers.
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-  {
-    const auto b = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    const unsigned b0 = b[0], b1 = b[1];
-    v = b0 + b1;
-  }
-  {
-    const auto a = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-    const unsigned a0 = a[0], a1 = a[1];
-    v = a0 + a1;
-  }
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, true);       // row_ror:8
-  {
-    int r = __builtin_amdgcn_update_dpp(0, (int)v, 0x12C, 0xF, 0x5, false);           // xor 4: see wave_xor_dpp4
-    r = __builtin_amdgcn_update_dpp(r, (int)v, 0x124, 0xF, 0xA, false);
-    v += (uint32_t)r;
-  }
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);        // quad_perm [2,3,0,1]
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);        // quad_perm [1,0,3,2]
-  return v;
-}
 // A thread takes TTV_SSE_ITERS items of its block's span (8 pixels each in k_video_tile_sse, one in the _any kernel), 256 items apart,
 // so a block covers 256 * TTV_SSE_ITERS items of one tile and ends in ONE atomic: all the sums of a call lie in a few cache lines, and
 // atomics on one line are served one after the other (the 64 x 256 x 256 video in bf16 takes 49 us with one

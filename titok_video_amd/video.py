@@ -22,6 +22,11 @@ views, no copy) and goes wherever the uint8 RGB frames go - `gather_tiles`, `til
 `blend_tiles(out=...)`, `decode_video(output=...)` and `decode_video_iter(output=...)` write planes instead of RGB
 (`ttv_video_tiles_yuv420`, `ttv_video_blend_yuv420`, `ttv_video_tile_sse_yuv420`: the colour conversion is defined on integers in the
 header and fused into the three kernels, there is no RGB frame in between).
+
+What the frames that come back are worth: `vt.quality(frames, tok)` decodes range by range and measures every frame against the
+source, per component (R, G, B or Y, U, V) - `VideoQuality` with per-frame `sse`, `psnr()`, `ssim` and their summaries.  The
+measurements are `frame_sse` and `frame_ssim` on uint8 frames or `YUV420Frames` (csrc/ttv_video_quality.hip:
+`ttv_video_frame_sse_u8 / _yuv420`, `ttv_video_frame_ssim_u8 / _yuv420`), GPU only like the rest.
 """
 from __future__ import annotations
 
@@ -345,6 +350,192 @@ def tile_sse(frames_u8: torch.Tensor, plan: TilePlan, recon_tiles: Sequence[torc
     return out
 
 
+# ---- per-frame quality of what comes back ---------------------------------------------------------------------------------------------
+def _frame_pair(a, b, b_stride: int, what: str, min_rgb: int, min_yuv: int):
+    """The checks `frame_sse` and `frame_ssim` share: (yuv, n, H, W, device).  Shapes and kinds are judged before the device, so a
+    malformed call is a ValueError wherever its tensors live."""
+    b_stride = int(b_stride)
+    if b_stride < 1:
+        raise ValueError(f"{what}: b_stride must be at least 1, got {b_stride}")
+    yuv = isinstance(a, YUV420Frames)
+    if yuv != isinstance(b, YUV420Frames):
+        raise ValueError(f"{what}: a and b must both be uint8 [.,H,W,3] tensors or both YUV420Frames, got {type(a).__name__} and "
+                         f"{type(b).__name__}")
+    if yuv:
+        sa, sb = a.shape, b.shape
+        if (a.matrix, a.range, a.siting) != (b.matrix, b.range, b.siting):
+            raise ValueError(f"{what}: planes of different colour descriptions are not comparable sample by sample: "
+                             f"{(a.matrix, a.range, a.siting)} and {(b.matrix, b.range, b.siting)}")
+    else:
+        for name, t in (("a", a), ("b", b)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3 or not t.is_contiguous():
+                raise ValueError(f"{what}: {name} must be contiguous uint8 [.,H,W,3], got {getattr(t, 'dtype', type(t))} "
+                                 f"{tuple(getattr(t, 'shape', ()))}")
+        sa, sb = tuple(a.shape[:3]), tuple(b.shape[:3])
+    if sa[1:] != sb[1:]:
+        raise ValueError(f"{what}: frames of {sa[1:]} against frames of {sb[1:]}")
+    n, least = sa[0], min_yuv if yuv else min_rgb
+    if min(sa[1:]) < least:
+        raise ValueError(f"{what}: frames of {sa[1:]}; H and W must be at least {least}")
+    if n > 0 and sb[0] < (n - 1) * b_stride + 1:
+        raise ValueError(f"{what}: b holds {sb[0]} frames, {n} frames at b_stride {b_stride} need {(n - 1) * b_stride + 1}")
+    if not yuv:
+        _lib.require_gpu(a, what)
+        _lib.require_gpu(b, what)
+    if a.device != b.device:
+        raise ValueError(f"{what}: a on {a.device}, b on {b.device}")
+    return yuv, n, sa[1], sa[2], a.device
+
+
+def frame_sse(a, b, b_stride: int = 1) -> torch.Tensor:
+    """Per frame and component the sum of squared level differences between frame j of `a` and frame j * b_stride of `b`: int64 [n, 3]
+    on the GPU, exact integers.  `a`, `b`: both contiguous uint8 [.,H,W,3] on the GPU (components R, G, B) or both `YUV420Frames` of
+    one colour description (Y of H x W, U and V of ceil(H / 2) x ceil(W / 2); layouts and pitches may differ).  One call into the
+    library on the current stream (`ttv_video_frame_sse_u8` / `ttv_video_frame_sse_yuv420`)."""
+    yuv, n, H, W, device = _frame_pair(a, b, b_stride, "frame_sse", 1, 1)
+    out = torch.empty((n, 3), dtype=torch.int64, device=device)
+    if n == 0:
+        return out
+    if yuv:
+        ca, cb = a.c_frames(), b.c_frames()
+        _lib.check(_lib.lib().ttv_video_frame_sse_yuv420(C.byref(ca), C.byref(cb), n, int(b_stride), H, W, out.data_ptr(),
+                                                         _lib.stream_ptr(device)), "ttv_video_frame_sse_yuv420")
+    else:
+        _lib.check(_lib.lib().ttv_video_frame_sse_u8(a.data_ptr(), b.data_ptr(), n, int(b_stride), H, W, out.data_ptr(),
+                                                     _lib.stream_ptr(device)), "ttv_video_frame_sse_u8")
+    return out
+
+
+def frame_ssim(a, b, b_stride: int = 1) -> torch.Tensor:
+    """Per frame and component the SSIM between frame j of `a` and frame j * b_stride of `b`: float64 [n, 3] on the GPU.  The
+    arguments are `frame_sse`'s; include/titok_hip.h has the definition (levels 0 .. 255, the 11-tap Gaussian, the windows wholly
+    inside a plane), so H and W must be at least 11, and at least 21 for `YUV420Frames`, whose chroma planes are half the size.
+    One call into the library on the current stream (`ttv_video_frame_ssim_u8` / `ttv_video_frame_ssim_yuv420`)."""
+    yuv, n, H, W, device = _frame_pair(a, b, b_stride, "frame_ssim", 11, 21)
+    out = torch.empty((n, 3), dtype=torch.float64, device=device)
+    if n == 0:
+        return out
+    h = _lib.lib()
+    need = int(h.ttv_video_frame_ssim_workspace_bytes(n, H, W, int(yuv)))
+    if need < 0:
+        _lib.check(1, "ttv_video_frame_ssim_workspace_bytes")
+    work = torch.empty((need // 8,), dtype=torch.float64, device=device)
+    if yuv:
+        ca, cb = a.c_frames(), b.c_frames()
+        _lib.check(h.ttv_video_frame_ssim_yuv420(C.byref(ca), C.byref(cb), n, int(b_stride), H, W, out.data_ptr(), work.data_ptr(), need,
+                                                 _lib.stream_ptr(device)), "ttv_video_frame_ssim_yuv420")
+    else:
+        _lib.check(h.ttv_video_frame_ssim_u8(a.data_ptr(), b.data_ptr(), n, int(b_stride), H, W, out.data_ptr(), work.data_ptr(), need,
+                                             _lib.stream_ptr(device)), "ttv_video_frame_ssim_u8")
+    return out
+
+
+class VideoQuality:
+    """Per-frame PSNR and SSIM per component of a video against its source, from `frame_sse` and `frame_ssim`.
+
+    `components` is ('r', 'g', 'b') or ('y', 'u', 'v'); `elements[c]` the samples of component c in a frame (H W, and
+    ceil(H / 2) ceil(W / 2) for 4:2:0 chroma).  `update` queues the measurement of a frame range and keeps its results on the GPU;
+    `finish` reads everything back once.  After it `sse[frame][c]` holds Python ints and `ssim[frame][c]` floats (`ssim` is None when
+    no range was measured with it); frame 0 is timeline frame `t0`, the start of the first range."""
+
+    def __init__(self, height: int, width: int, yuv420: bool = False):
+        H, W = int(height), int(width)
+        if min(H, W) < 1:
+            raise ValueError(f"VideoQuality: frames of {(H, W)}")
+        self.yuv420 = bool(yuv420)
+        self.components = ("y", "u", "v") if self.yuv420 else ("r", "g", "b")
+        chroma = ((H + 1) // 2) * ((W + 1) // 2)
+        self.elements = (H * W, chroma, chroma) if self.yuv420 else (H * W,) * 3
+        self.shape = (H, W)
+        self.t0 = 0
+        self.sse: Optional[List[List[int]]] = None
+        self.ssim: Optional[List[List[float]]] = None
+        self._parts: List[Tuple[int, torch.Tensor, Optional[torch.Tensor]]] = []
+
+    def update(self, decoded, source, t0: int, frame_stride: int = 1, ssim: bool = True) -> None:
+        """Queue `decoded` - the frames of a range of the timeline that starts at frame `t0` - against `source[frame_stride * (t0 + j)]`
+        on the current stream.  Every range of one object is measured with or without SSIM, as the first one was."""
+        t0, frame_stride = int(t0), int(frame_stride)
+        if t0 < 0 or frame_stride < 1:
+            raise ValueError(f"VideoQuality.update: t0 {t0}, frame_stride {frame_stride}")
+        kind = "YUV420Frames" if self.yuv420 else "uint8 [T,H,W,3]"
+        if not isinstance(source, (YUV420Frames, torch.Tensor)) or isinstance(source, YUV420Frames) != self.yuv420:
+            raise ValueError(f"VideoQuality.update: the source must be {kind} of {self.shape}, got {type(source).__name__}")
+        shape = tuple(source.shape[:3])
+        if len(shape) != 3 or shape[1:] != self.shape:
+            raise ValueError(f"VideoQuality.update: the source must be {kind} of {self.shape}, got {tuple(source.shape)}")
+        first = frame_stride * t0
+        if first >= shape[0]:
+            raise ValueError(f"VideoQuality.update: timeline frame {t0} at frame_stride {frame_stride} is source frame {first} of {shape[0]}")
+        if self._parts and (self._parts[0][2] is not None) != bool(ssim):
+            raise ValueError("VideoQuality.update: every range is measured with SSIM or none is")
+        yardstick = source.frames(first, shape[0]) if self.yuv420 else source[first:]
+        self._parts.append((t0, frame_sse(decoded, yardstick, frame_stride), frame_ssim(decoded, yardstick, frame_stride) if ssim else None))
+
+    def finish(self) -> "VideoQuality":
+        """Read the queued results back (one transfer) and order them by frame.  The ranges must follow each other without a gap."""
+        if not self._parts:
+            raise ValueError("VideoQuality.finish: nothing was measured")
+        parts = sorted(self._parts, key=lambda p: p[0])
+        at = parts[0][0]
+        for t0, sse, _ in parts:
+            if t0 != at:
+                raise ValueError(f"VideoQuality.finish: a range starts at frame {t0}, the one before it ends at {at}")
+            at += sse.shape[0]
+        with_ssim = parts[0][2] is not None
+        flat = [p[1].reshape(-1) for p in parts] + ([p[2].view(torch.int64).reshape(-1) for p in parts] if with_ssim else [])
+        host = torch.cat(flat).cpu()
+        n = at - parts[0][0]
+        self.t0 = parts[0][0]
+        self.sse = host[:3 * n].view(n, 3).tolist()
+        self.ssim = host[3 * n:].view(torch.float64).view(n, 3).tolist() if with_ssim else None
+        self._parts = []
+        return self
+
+    def _done(self) -> List[List[int]]:
+        if self.sse is None:
+            raise ValueError("VideoQuality: call finish() first")
+        return self.sse
+
+    @staticmethod
+    def _db(sse: int, elements: int) -> float:
+        return math.inf if sse == 0 else 10.0 * math.log10(65025 * elements / sse)
+
+    def psnr(self) -> List[List[float]]:
+        """[frame][c] 10 log10(65025 elements[c] / sse) in float64 (levels 0 .. 255), inf where the sum is 0."""
+        return [[self._db(v, e) for v, e in zip(row, self.elements)] for row in self._done()]
+
+    def psnr_overall(self) -> List[float]:
+        """Per component, from the sums over all frames."""
+        sse = self._done()
+        return [self._db(sum(row[c] for row in sse), len(sse) * self.elements[c]) for c in range(3)]
+
+    def psnr_pooled(self) -> float:
+        """All three components together: summed sums over summed sample counts.  For 4:2:0 this weights Y : U : V as 4 : 1 : 1 (by
+        their sample counts), the usual single-number PSNR of a 4:2:0 codec comparison."""
+        sse = self._done()
+        return self._db(sum(sum(row) for row in sse), len(sse) * sum(self.elements))
+
+    def ssim_mean(self) -> Optional[List[float]]:
+        """Per component the mean over the frames, or None without SSIM."""
+        self._done()
+        return None if self.ssim is None else [sum(row[c] for row in self.ssim) / len(self.ssim) for c in range(3)]
+
+    def worst_frame(self, c: int = 0) -> int:
+        """The timeline frame whose component `c` has the largest sum of squares (the lowest PSNR); the first of equals."""
+        sse = self._done()
+        return self.t0 + max(range(len(sse)), key=lambda j: (sse[j][c], -j))
+
+    def as_dict(self) -> dict:
+        """Everything as plain lists and numbers (`json.dumps` takes it); an infinite PSNR is None."""
+        def fin(v):
+            return None if math.isinf(v) else v
+        return {"components": list(self.components), "elements": list(self.elements), "t0": self.t0, "frames": len(self._done()),
+                "sse": [list(row) for row in self.sse], "ssim": None if self.ssim is None else [list(row) for row in self.ssim],
+                "psnr": [[fin(v) for v in row] for row in self.psnr()], "psnr_overall": [fin(v) for v in self.psnr_overall()],
+                "psnr_pooled": fin(self.psnr_pooled()), "ssim_mean": self.ssim_mean(), "worst_frame": [self.worst_frame(c) for c in range(3)]}
+
+
 # ---- the token container ----------------------------------------------------------------------------------------------------------------
 def index_bits(codebook_size: int) -> int:
     """Bits per stored index: max(1, ceil(log2(codebook_size)))."""
@@ -656,7 +847,8 @@ class VideoTokenizer:
         chosen from measured distortion: `rate_distortion` over `ladder` (default `default_ladder(tokens_per_tile)`), then
         `allocate_tokens`.  The tokens are the probe's own indices at the chosen count of each tile - there is no second encoding
         pass - and `counts` is the allocation.  The table describes the probe's reconstructions, batch for batch: a tile decoded later
-        in another batch goes through the same arithmetic on its own rows, but nothing here decodes it again to check."""
+        in another batch goes through the same arithmetic on its own rows, but nothing here decodes it again to check (`quality` does,
+frame by frame, after the blend)."""
         plan = TilePlan(_frames_shape(frames_u8, "encode_video"), self.tile, self.overlap, self.patch, frame_stride)
         if target_psnr is not None or total_tokens is not None:
             if ladder is None:
@@ -724,6 +916,11 @@ class VideoTokenizer:
             raise ValueError(f"output must be None, one of {YUV_LAYOUTS} or YUV420Frames, got {output!r}")
         if isinstance(output, YUV420Frames) and output.shape != plan.timeline:
             raise ValueError(f"output must hold the timeline {plan.timeline}, got {output.shape}")
+        yield from self._decode_ranges(plan, tok, lambda a, b: output.frames(a, b) if isinstance(output, YUV420Frames) else output)
+
+    def _decode_ranges(self, plan: TilePlan, tok: VideoTokens, out_for):
+        """The streaming decode behind `decode_video_iter` and `quality`: (t0, blended frames [t0, t1)) in timeline order, with
+        `out_for(t0, t1)` as the `out` of each range's `blend_tiles`.  Holds the reconstructions of a few layers and nothing else."""
         indices = tok.indices.to(self.device)
         offsets = [0]
         for k in tok.counts:
@@ -735,7 +932,7 @@ class VideoTokenizer:
             live[kt * per_layer:(kt + 1) * per_layer] = self._decode_layer(plan, tok, indices, offsets, kt)
             upto = starts[kt + 1] if kt + 1 < plan.counts[0] else n_frames         # the next layer starts here: frames below are complete
             if upto > done:
-                yield done, blend_tiles(live, plan, done, upto, output.frames(done, upto) if isinstance(output, YUV420Frames) else output)
+                yield done, blend_tiles(live, plan, done, upto, out_for(done, upto))
                 done = upto
             while first_live <= kt and starts[first_live] + plan.tile[0] <= done:  # every frame of the layer is out
                 live[first_live * per_layer:(first_live + 1) * per_layer] = [None] * per_layer
@@ -755,3 +952,19 @@ class VideoTokenizer:
         for _ in self.decode_video_iter(tok, output):
             pass
         return output
+
+    def quality(self, frames, tok: VideoTokens, ssim: bool = True) -> "VideoQuality":
+        """What `decode_video(tok)` is worth against the video it was made from: the finished `VideoQuality` of every timeline frame
+        against `frames[tok.frame_stride * t]`.  `frames` is the source, uint8 [T,H,W,3] on the GPU (decoded to RGB) or `YUV420Frames`
+        (decoded into planes of the source's own layout, matrix, range and siting, compared plane by plane).  The ranges of the
+        streaming decode are measured and dropped one by one: beyond the source, memory is that of a few tile layers, whatever the
+        video's length; the sums stay on the GPU until one read at the end."""
+        plan = self._check_tokens(tok)
+        if _frames_shape(frames, "quality") != plan.video:
+            raise ValueError(f"frames must be the video {plan.video} of the tokens, got {_frames_shape(frames, 'quality')}")
+        yuv = isinstance(frames, YUV420Frames)
+        q = VideoQuality(plan.video[1], plan.video[2], yuv420=yuv)
+        for t0, part in self._decode_ranges(plan, tok, (lambda a, b: frames.like(b - a)) if yuv else (lambda a, b: None)):
+            q.update(part, frames, t0, plan.frame_stride, ssim)
+            del part
+        return q.finish()
